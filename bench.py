@@ -2,6 +2,12 @@
 """bench.py — env-steps/s of the batched AtcGym.step() hot path on MI355X.
 
   python bench.py [--gpus N] [--steps K] [--warmup W]          (N > 1: run under torch.distributed.run, one rank per GPU)
+                  [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times K steps (one block: --steps is the number of timed steps) and prints the line.  --full adds
+everything else this script measures or checks: the parity gates, the one-rank RCCL check and the exchange's cost, the side records
+(fused rollout, store-only reference, without the held-action hint, two streams, beyond the Infinity Cache, C2 / C3 / C4), the
+single-env protocol and the CPU baselines.  --dump-outputs DIR writes what the last timed step returned to its caller as DIR/<name>.npy.
 
 One "step" = one pass of the hot path (one atc_step launch) over this GPU's batch: 65 536 envs x 16 aircraft, the
 configuration BASELINE.json's metric is quoted on ("env-steps/sec aggregate @16 aircraft/env, 64k envs").  Weak scaling:
@@ -511,6 +517,25 @@ def single_env_protocol(n_steps=100000):
     return out
 
 
+DUMP_BYTES = 64 << 20   # --dump-outputs: at most this many bytes in all
+
+
+def dump_outputs(path, arrays, limit=DUMP_BYTES, seed=0):
+    """--dump-outputs: `arrays` (name -> [envs, ...] tensor) as path/<name>.npy in float32 (the integer outputs are exact in it).
+    Above `limit` bytes in all, every array keeps the same seeded sample of envs, whose indices go to env_index.npy (float64)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    host = {k: v.detach().cpu().numpy().astype(np.float32) for k, v in arrays.items()}
+    B = len(next(iter(host.values())))
+    per_env = sum(a.nbytes for a in host.values()) // B
+    if per_env * B > limit:
+        rows = np.sort(np.random.default_rng(seed).choice(B, limit // (per_env + 8), replace=False))
+        host = {k: a[rows] for k, a in host.items()}
+        host["env_index"] = rows.astype(np.float64)
+    for k, a in host.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+
+
 def _sync(dev):
     """torch.cuda.synchronize on a GPU; nothing to drain for the CPU stub flow (--stub-env)."""
     if dev.type == "cuda":
@@ -653,7 +678,7 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-parity-gate", action="store_true", help="developer knob: skip the pre-timing correctness gate")
     ap.add_argument("--no-single-env", action="store_true", help="skip the single-env compute-performance.py protocol")
-    ap.add_argument("--repeats", type=int, default=5, help="timed blocks of --steps steps; value = the median block")
+    ap.add_argument("--repeats", type=int, default=1, help="timed blocks of --steps steps; value = the median block")
     ap.add_argument("--grid-cell", default="auto", help="cell size [nm] of the MVA lookup grid (default: by batch size, "
                     "atc_hip.vec_env.auto_grid_cell)")
     ap.add_argument("--no-held-hint", action="store_true", help="do not tell atc_step that launches 2..%d of an action block "
@@ -677,6 +702,11 @@ def main():
                     "stand-in env that steps nothing (StubEnv); needs ATC_DIST_BACKEND=gloo.  The line says \"data\": \"stub\"")
     ap.add_argument("--graph", action="store_true", help="replay the %d-step action-hold block as one captured HIP graph "
                     "(removes per-launch host overhead; matters for the small launch-bound configs)" % HOLD)
+    ap.add_argument("--full", action="store_true", help="also run what the headline does not need: parity gates, the one-rank RCCL "
+                    "check and the exchange's cost, the side records, the single-env protocol and the CPU baselines (the --no-* "
+                    "options switch parts of it off)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one returned "
+                    "(obs, reward, done, flags, ep_return, ep_length; float32; a seeded sample of envs above 64 MB) as DIR/<name>.npy")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -714,7 +744,7 @@ def main():
     rank, ws, local = D.init()
     assert ws == args.gpus, "WORLD_SIZE (%d) != --gpus (%d)" % (ws, args.gpus)
     collective = {"world_size": ws, "backend": D.backend_name()}
-    if ws == 1 and not args.no_collective:
+    if ws == 1 and args.full and not args.no_collective:
         # One GPU: create a world of ONE rank on the real backend (RCCL) all the same, so that the exact calls of the multi-GPU
         # path — init_process_group("nccl", device_id=...), all_gather_into_tensor / all_reduce on device tensors — run on
         # this box; the collective is issued once, untimed, below.  A failure is recorded, never fatal at N = 1.
@@ -830,7 +860,7 @@ def main():
         return torch.cat([e.ep_return for e in subs]), torch.cat([e.ep_length for e in subs])
 
     gate = None
-    if rank == 0 and not args.no_parity_gate and not stub:
+    if rank == 0 and args.full and not args.no_parity_gate and not stub:
         gate = parity_gate(scn, N, args.grid_cell, args.sep_nm, local, held_hint=held_launchers is not None)   # raises if results are wrong
 
     # Untimed: bring every rank's GPU to its working clocks and the envs into their steady episode mix before the W warm-up
@@ -849,7 +879,7 @@ def main():
                                "all_reduce_max": D.max_over_ranks(1.5, dev, force=True), "all_reduce_sum": D.sum_over_ranks(2.5, dev, force=True)})
         except Exception as exc:
             collective["error"] = "%s: %s" % (type(exc).__name__, str(exc)[:300])
-    if (ws > 1 or forced) and "error" not in collective:
+    if args.full and (ws > 1 or forced) and "error" not in collective:
         # What the exchange costs on THIS group (untimed; the real backend: RCCL on a GPU box, one rank here or eight on the
         # driver's node), so that the line says what a blocking report would have added to a timed block and what the
         # asynchronous one does add (round-3 review, next #1).
@@ -901,6 +931,16 @@ def main():
     _sync(dev)
     returns, lengths = xch.wait()        # the last rollout's report
     _sync(dev)
+    if rank == 0 and args.dump_outputs:
+        # what the caller of the timed path holds after its last step (this rank's envs), before anything else steps them
+        if stub:
+            outs = {}
+        elif args.rollout:
+            outs = {k: roll_out[k][-1] for k in ("obs", "reward", "done", "flags")}
+        else:
+            outs = {k: torch.cat([getattr(e, k) for e in subs]) for k in ("obs", "reward", "done", "flags")}
+        outs["ep_return"], outs["ep_length"] = stats()
+        dump_outputs(args.dump_outputs, outs)
     rank_seeds = D.all_gather_stats(torch.tensor([D.rank_seed(0, rank) & 0x7fffffffffffffff], dtype=torch.int64, device=dev))[0]
     order = sorted(range(len(blocks)), key=lambda i: blocks[i][0])
     elapsed, kernel_ms_total, elapsed_with_barrier = blocks[order[len(order) // 2]]   # the median block
@@ -979,7 +1019,7 @@ def main():
             line["config"]["stub_report"] = {"first_return_of_each_rank": [float(v) for v in returns[:, 0].tolist()],
                                              "first_length_of_each_rank": [int(v) for v in lengths[:, 0].tolist()],
                                              "launches_rank0": subs[0].launches}
-        if ws == 1 and not args.no_single_env and not args.rollout and S == 1 and graph is None:
+        if args.full and ws == 1 and not args.no_single_env and not args.rollout and S == 1 and graph is None:
             # the same envs with 20 steps fused per launch (atc_rollout_hold, the action held like in the timed loop): a
             # side record, not `value` — the headline stays one launch per step, what env.step() costs
             Tf = HOLD
@@ -1071,8 +1111,8 @@ def main():
                                                  "parity_gate": ms_gate}
                 for e in halves:
                     e.close()
-        if (ws == 1 and not args.no_baseline_configs and N == AIRCRAFT and B == ENVS_PER_GPU and not args.rollout and S == 1
-                and graph is None):
+        if (args.full and ws == 1 and not args.no_baseline_configs and N == AIRCRAFT and B == ENVS_PER_GPU and not args.rollout
+                and S == 1 and graph is None):
             # The headline kernel on a working set beyond the 256 MiB Infinity Cache (4 x the envs: 366 MB per launch): what
             # the same code does when the bytes provably come from and go to DRAM (round-3 review, next #7).  Same kernel
             # instantiation and the same 0.25 nm grid as the gated headline; a side record, never `value`.
@@ -1102,7 +1142,7 @@ def main():
                                            "traffic": traffic_entry(Bl, N, 0, not args.no_held_hint)[0]}
             big.close()
             del big, ring_b, fb, rb
-        if (ws == 1 and not args.no_baseline_configs and not args.no_parity_gate and N == AIRCRAFT and B == ENVS_PER_GPU
+        if (args.full and ws == 1 and not args.no_baseline_configs and not args.no_parity_gate and N == AIRCRAFT and B == ENVS_PER_GPU
                 and not args.rollout and S == 1 and graph is None):
             # BASELINE.json's other single-GPU configurations, each gated on its own first 256 envs (side records: `value`
             # stays the headline configuration)
@@ -1114,7 +1154,7 @@ def main():
                             args.sep_nm, local, hh, cpu=not args.no_cpu_baseline),
                 side_config("C4: 4 096 envs x 64 aircraft, multi-polygon MVA + noise-abatement areas", 4096, 64,
                             scenarios.LOWWDense(), args.sep_nm, local, hh, cpu=not args.no_cpu_baseline)]
-        if ws == 1 and not args.no_single_env:
+        if args.full and ws == 1 and not args.no_single_env:
             se = single_env_protocol()
             if not args.no_cpu_baseline:
                 # the compiled-CPU counterpart on 1 host core, same protocol: a one-env step is a launch-latency path on a
@@ -1126,7 +1166,7 @@ def main():
                                          "1 core; the GPU-backed drop-in is %.2fx of it: one env's step is two crossings of the host link and one wavefront's serial chain"
                                          % (se["steps_per_s"] / co["f32"]))
             line["config"]["single_env"] = se
-        if ws == 1 and not args.no_cpu_baseline:
+        if args.full and ws == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(N)
         os.write(json_fd, (json.dumps(line) + "\n").encode())
     for e in subs:

@@ -88,7 +88,7 @@ def test_bench_eight_rank_flow_on_cpu():
     env = dict(os.environ, ATC_DIST_BACKEND="gloo", MASTER_PORT="29547")
     env.pop("WORLD_SIZE", None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "40", "--warmup", "20", "--envs", "512",
-                        "--repeats", "3", "--stub-env", "--no-cpu-baseline", "--no-single-env"],
+                        "--repeats", "3", "--stub-env", "--full", "--no-cpu-baseline", "--no-single-env"],
                        env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -113,3 +113,51 @@ def test_bench_eight_rank_flow_on_cpu():
     assert c["stub_report"]["first_return_of_each_rank"] == [1000.0 * r_ for r_ in range(8)]
     assert c["stub_report"]["first_length_of_each_rank"] == [7 * r_ for r_ in range(8)]
     assert c["stub_report"]["launches_rank0"] >= 20 + 3 * 40
+
+
+def test_plain_run_times_its_steps_and_dumps_what_they_returned(tmp_path):
+    """A plain run (no --full) does what its headline needs and no more: the warm-up, ONE block of exactly --steps timed launches
+    and the line — no parity gate, no one-rank group, no side record, no CPU baseline.  --dump-outputs writes the last timed step's
+    per-env outputs (here the stand-in env's episode statistics, which encode the env index) as float32 .npy files."""
+    import subprocess
+    import numpy as np
+    env = dict(os.environ, ATC_DIST_BACKEND="gloo", MASTER_PORT="29548")
+    env.pop("WORLD_SIZE", None)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "40", "--warmup", "20", "--envs", "512",
+                        "--stub-env", "--dump-outputs", str(tmp_path)], env=env, capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    line = json.loads(lines[0])
+    assert line["steps"] == 40 and line["warmup"] == 20 and line["ms_per_step"] > 0
+    assert abs(line["value"] - 512 / (line["ms_per_step"] * 1e-3)) <= 1e-6 * line["value"]
+    c = line["config"]
+    assert c["stub_report"]["launches_rank0"] == 20 + 40 and len(c["timed_blocks_ms_per_step"]) == 1
+    assert c["parity_gate"] is None and "us" not in c["collective"] and c["collective"]["backend"] is None
+    for key in ("fused_rollout", "without_held_hint", "two_streams", "beyond_l3", "baseline_configs", "single_env"):
+        assert key not in c, key
+    assert "cpu_baseline" not in line
+    assert sorted(os.listdir(tmp_path)) == ["ep_length.npy", "ep_return.npy"]
+    ret, length = np.load(tmp_path / "ep_return.npy"), np.load(tmp_path / "ep_length.npy")
+    assert ret.dtype == length.dtype == np.float32
+    assert np.array_equal(ret, np.arange(512, dtype=np.float32)) and np.array_equal(length, np.arange(512, dtype=np.float32))
+
+
+def test_dump_outputs_keeps_one_seeded_sample_of_envs_above_the_limit(tmp_path):
+    import numpy as np
+    import torch
+    b = _bench()
+    arrays = {"obs": torch.arange(1000 * 10, dtype=torch.float32).reshape(1000, 10), "done": torch.arange(1000).to(torch.uint8)}
+    b.dump_outputs(str(tmp_path / "all"), arrays, limit=1 << 20)
+    assert sorted(os.listdir(tmp_path / "all")) == ["done.npy", "obs.npy"]
+    assert np.array_equal(np.load(tmp_path / "all" / "obs.npy"), arrays["obs"].numpy())
+    assert np.load(tmp_path / "all" / "done.npy").dtype == np.float32
+    for run in ("s1", "s2"):
+        b.dump_outputs(str(tmp_path / run), arrays, limit=4000)
+        got = {k[:-4]: np.load(tmp_path / run / k) for k in os.listdir(tmp_path / run)}
+        assert sorted(got) == ["done", "env_index", "obs"] and sum(a.nbytes for a in got.values()) <= 4000
+        rows = got["env_index"].astype(np.int64)
+        assert got["env_index"].dtype == np.float64 and len(rows) > 50 and np.all(np.diff(rows) > 0)
+        assert np.array_equal(got["obs"], arrays["obs"].numpy()[rows])
+        assert np.array_equal(got["done"], arrays["done"].numpy()[rows].astype(np.float32))
+    assert np.array_equal(np.load(tmp_path / "s1" / "env_index.npy"), np.load(tmp_path / "s2" / "env_index.npy"))

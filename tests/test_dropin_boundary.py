@@ -142,7 +142,7 @@ def test_bench_two_ranks_on_one_device():
     gloo (ATC_DIST_BACKEND=gloo); with 8 GPUs the same code path runs RCCL over xGMI."""
     env = dict(os.environ, ATC_DIST_BACKEND="gloo", MASTER_PORT="29541")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "60", "--warmup", "20",
-                        "--envs", "4096", "--repeats", "2", "--no-cpu-baseline", "--no-single-env"],
+                        "--envs", "4096", "--repeats", "2", "--full", "--no-cpu-baseline", "--no-single-env"],
                        env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])

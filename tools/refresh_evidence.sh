@@ -12,7 +12,7 @@ timeout 1200 python -m pytest tests -m gpu -q -x > $O/${TAG}_pytest_gpu.log 2>&1
 tail -3 $O/${TAG}_pytest_gpu.log
 bash tools/pmc_traffic_all.sh ${TAG} > $O/${TAG}_traffic.log 2>&1
 cp $O/pmc_traffic_${TAG}.json $O/${TAG}_pmc_traffic.json
-python bench.py > $O/${TAG}_bench_default.json 2> $O/${TAG}_bench_default.err
+python bench.py --full > $O/${TAG}_bench_default.json 2> $O/${TAG}_bench_default.err
 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/${TAG}_bench_driver.json 2> $O/${TAG}_bench_driver.err
 B="python $GRAFT_REPO_ROOT/bench.py --steps 400 --warmup 40 --repeats 1 --no-cpu-baseline --no-single-env --no-parity-gate --no-collective --no-baseline-configs"
 for cfg in "n16_65536 --aircraft 16 --envs 65536" "n1_65536 --aircraft 1 --envs 65536" "n16_8192 --aircraft 16 --envs 8192" "n64_4096 --aircraft 64 --envs 4096"; do
