@@ -1006,8 +1006,8 @@ def compile_sector(mvas, runway, entrypoints, noise=(), grid_cell=None, grid_gua
             assert -2 ** 31 < phi_fix < 2 ** 31 - 1
             phi32 = f32(f32(phi_fix) * f32(2.0 ** -L.PHI_FIX_SHIFT) + f32(L.PHI_FIX_OFFSET))   # phi_real (exact for these values)
             x32, y32 = f32(px0 + fix[0] * 2.0 ** -pk), f32(py0 + fix[1] * 2.0 ** -pk)       # pos_to_real: one rounding
-            tfx = f32(f32(min(max(faf_fix[0] - fix[0], -2 ** 31), 2 ** 31 - 1)) * pos_inv)
-            tfy = f32(f32(min(max(faf_fix[1] - fix[1], -2 ** 31), 2 ** 31 - 1)) * pos_inv)
+            tfx = f32(f32(faf_fix[0] - fix[0]) * pos_inv)      # pos_to_faf: the exact difference (33 bits), one rounding
+            tfy = f32(f32(faf_fix[1] - fix[1]) * pos_inv)
             d_faf = f32(math.hypot(float(tfx), float(tfy)))
             phi_rel_faf = f32(math.degrees(math.atan2(float(tfy), float(tfx))))
             on_gp = f32(float(f32(318.4)) * float(d_faf) + float(f32(f32(faf_mva) - f32(200.0))))

@@ -635,8 +635,14 @@ __device__ __forceinline__ int pos_spawn(const float* __restrict__ K, int axis, 
     c = fminf(fmaxf(c, -2147483648.0f), 2147483520.0f);
     return (int)rintf(c);
 }
-// faf - position (atc_gym.py:289-297): exact integer difference on the grid -> fp32 relative precision near the FAF
-__device__ __forceinline__ float pos_to_faf(int faf, float pos_inv, int p) { return (float)sat_sub(faf, p) * pos_inv; }
+// faf - position (atc_gym.py:289-297): exact integer difference on the grid -> fp32 relative precision near the FAF.  The
+// difference of two 32-bit counts needs 33 bits, its magnitude only 32: |faf - p| = max - min in unsigned 32-bit arithmetic (exact),
+// converted with ONE rounding and signed — (float)(faf - p) of the exact 64-bit difference, bit for bit, and never saturating
+// (a 32-bit saturating difference froze the vector to the FAF 2^(31-k) nm from it while the position was still on the grid)
+__device__ __forceinline__ float pos_to_faf(int faf, float pos_inv, int p) {
+    const float m = (float)((uint32_t)max(faf, p) - (uint32_t)min(faf, p)) * pos_inv;
+    return p > faf ? -m : m;
+}
 
 struct Aircraft {
     int x, y;         // position grid counts

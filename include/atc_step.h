@@ -222,11 +222,16 @@ typedef struct atc_params {
  *   - the fp32 position every formula of the reference sees is  (float)(origin + fix * 2^-k)  — ONE rounding (evaluated
  *     in float64, exact before the final conversion);
  *   - differences of positions are exact integers: the vector to the FAF (atc_gym.py:289-297) is
- *     (float)(faf_fix - fix) * 2^-k, accurate to fp32 RELATIVE precision however close the aircraft is to the FAF.
+ *     (float)(faf_fix - fix) * 2^-k, the exact (33-bit, never saturating) difference rounded once — accurate to fp32 RELATIVE
+ *     precision however close the aircraft is to the FAF, and as far from it as the grid reaches.
  * Accumulated rounding over a 6 000-step episode: <= 1.04e-6 nm measured against the float64 reference (dithered rounding, below);
- * half the bytes of a float64 pair.  An aircraft that is flown on, without reset, beyond the grid range (>= 24 nm outside
- * the LOWW bounding box) is pinned at the range limit: it stays "outside the airspace" exactly like the reference's
- * (model.py:289), only its x / y observation stops growing.
+ * half the bytes of a float64 pair.  The grid covers origin +- 2^(31-k) nm per axis (LOWW: +-64 nm around (36, 42), x in
+ * [-28, 100), y in [-22, 106)).  An aircraft flown on without reset (the reference's FPS protocol,
+ * learning/atc-gym-compute-performance.py) follows the reference up to that edge — within it, the vector to the FAF and with it
+ * observation words 6-8 and the shaping reward too — and beyond it is pinned at the range limit (INT32_MIN / INT32_MAX counts):
+ * from the step it crosses, the pinned x / y stop growing, and observation words 6-8 and the shaping reward, evaluated at the
+ * pinned position, leave the reference's values, while the flags (it stays "outside the airspace" like the reference's, model.py:289), `done`, the time-out and the action counters stay
+ * exact (tests/golden/g14: the protocol replayed for 10 000 steps per episode).
  *
  * Speed and heading (model.py:35-37, 60-129) on the fp32 path — ABI 18; unbounded heading: ABI 19.
  * The reference holds v, phi and the decoded action targets in float64.  As fp32 values they carry the rounding of the

@@ -35,7 +35,8 @@
  *   float64 instantiation: Python floats, x += d  — the reference as it is.
  *   float32 instantiation: the fp32 spec of include/atc_step.h ("Aircraft positions"): 32-bit fixed point on the sector's
  *   position grid, saturating; the fp32 value the reference's formulas see is (float)(origin + fix * 2^-k); the vector
- *   to the FAF is an exact integer difference.  The HIP kernels implement the same spec, so their positions are
+ *   to the FAF is an exact 64-bit integer difference, rounded once (it does not saturate: the FAF is on the grid, the
+ *   difference of two counts needs 33 bits).  The HIP kernels implement the same spec, so their positions are
  *   bit-identical to this instantiation's. */
 #if ORC_FIXED_POS
 typedef int32_t FN(pos_t);
@@ -55,7 +56,7 @@ static int32_t FN(pos_advance)(const REAL* S, int32_t p, REAL d) {
 }
 static REAL FN(pos_to_faf)(const REAL* S, int axis, int32_t p) {
     int64_t faf = (int64_t)S[ATC_C_FAF_FIX + 2 * axis] * 65536 + (int64_t)S[ATC_C_FAF_FIX + 2 * axis + 1];
-    return (REAL)FN(sat32)(faf - (int64_t)p) * S[ATC_C_POS_INV];
+    return (REAL)(faf - (int64_t)p) * S[ATC_C_POS_INV]; /* the exact 33-bit difference, rounded once: never saturates */
 }
 /* Speed and heading state of the fp32 spec (include/atc_step.h, ABI 18): 32-bit fixed point,
  *   kt = v_fix 2^-23 (unsigned),  deg = 180 + phi_fix 2^-23 (signed);  targets, rate limits and the action discriminator are

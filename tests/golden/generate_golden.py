@@ -32,6 +32,11 @@ inputs + expected outputs of the AtcGym.step() hot path as small fixtures:
   g11_unbounded.npz   actions outside the action space, replayed by the reference: sustained a_phi up to +-3 (heading to 720 / -360
                       deg), headings wound to +-5 500 deg and back, un-clipped random actions, discrete heading indices beyond 360,
                       G9's winning intercepts flown at heading + 360 k, altitude targets within an fp32 action step of the MVA; the compact form of g9
+  g14_no_reset.npz    the reference's FPS protocol (learning/atc-gym-compute-performance.py): reset() once, ONE action held, no reset,
+                      10 000 steps per episode whatever `done` says — LOWW (= gym.make('AtcEnv-v0')) / LOWW_random / Simple / UnitTest,
+                      dt 0.1 / 1 / 5, one discrete and one unshaped un-normalised episode; fixed actions and seeded float32 Box draws,
+                      headings that fly through the window where the vector to the FAF exceeds the 32-bit grid range while the
+                      position is still on the grid, then off the position grid (compact format of g9, stride 16)
   model_test_known_answers.json  the 8 known answers of the reference's own envs/atc/model_test.py
 
 Usage:
@@ -563,8 +568,9 @@ class WideRecorder:
     """Compact recorder: every step keeps flags / done / actions_taken / reward, every `stride`-th step and the last step of
     an episode also keep the observation and the float64 state."""
 
-    def __init__(self, stride=16):
+    def __init__(self, stride=16, sample_done=True):
         self.stride = stride
+        self.sample_done = sample_done     # False: a step past `done` is sampled like any other (stride / last step only)
         self.ep = []
         self.flags, self.done, self.acts, self.reward = [], [], [], []
         self.samp_rows, self.obs, self.state = [], [], []
@@ -615,7 +621,7 @@ class WideRecorder:
             if done and after < 0:
                 after = extra_after_done
             last = (after == 0)
-            if n % self.stride == 0 or done or last:
+            if n % self.stride == 0 or (done and (self.sample_done or after == extra_after_done)) or last:
                 self.samp_rows.append(row)
                 self.obs.append(np.asarray(obs, dtype=np.float32))
                 self.state.append([ap.x, ap.y, ap.h, ap.phi, ap.v])
@@ -1023,8 +1029,85 @@ def gen_g13():
     return rec
 
 
+def position_range(env):
+    """The fixed-point position grid of the fp32 path as include/atc_step.h ("Aircraft positions") defines it, from the reference
+    scenario: integer-valued origin at the centre of the airspace bounding box, FAF, IAF, corridor corners, runway and entry points,
+    k the largest exponent <= 27 whose range 2^(31-k) nm covers 1.5 x the half extent.  Returns (x0, y0, range_nm)."""
+    c = env._runway.corridor
+    pts = [env._airspace.get_bounding_box()[:2], env._airspace.get_bounding_box()[2:], c.faf.ravel(), c.iaf.ravel(),
+           c.corner1.ravel(), c.corner2.ravel(), (env._runway.x, env._runway.y)]
+    pts += [(e.x, e.y) for e in env._scenario.entrypoints]
+    pts = np.asarray([[float(v) for v in q] for q in pts])
+    x0 = float(np.rint(0.5 * (pts[:, 0].min() + pts[:, 0].max())))
+    y0 = float(np.rint(0.5 * (pts[:, 1].min() + pts[:, 1].max())))
+    half = float(np.abs(pts - np.array([x0, y0])).max())
+    k = int(min(27, np.floor(31 - np.log2(1.5 * half))))
+    return x0, y0, 2.0 ** (31 - k)
+
+
+G14_STEPS = 10000
+
+
+def gen_g14():
+    """The reference's own benchmark protocol, learning/atc-gym-compute-performance.py: reset() once, one action (there:
+    action_space.sample()) held, step on without reset.  The aircraft leaves the airspace, stays `done`, and flies on for
+    10 000 steps — off the fp32 path's 32-bit position grid (include/atc_step.h).  On the way out most headings cross the window
+    where |FAF - x| or |FAF - y| exceeds the grid range while x, y are still on it: the vector to the FAF must not saturate there."""
+    rec = WideRecorder(stride=16, sample_done=False)
+    box = lambda seed: f32(np.random.default_rng(seed).uniform(-1, 1, 3))   # noqa: E731  (action_space.sample(), float32 Box)
+    plan = [  # (scen, dt, shaping, normalize, discrete, action)
+        ("LOWW", 1, True, True, False, [0.0, 0.0, 0.0]),
+        ("LOWW", 1, True, True, False, [1.0, 1.0, 0.5]),
+        ("LOWW", 1, True, True, False, [-1.0, -1.0, -1.0]),
+        ("LOWW", 1, True, True, False, box(14001)),
+        ("LOWW", 1, True, True, False, box(14002)),
+        ("LOWW", 1, True, True, False, box(14003)),
+        ("LOWW", 1, True, True, False, box(14004)),
+        ("LOWW", 1, True, True, False, f32([0.5, 0.2, 0.75])),          # north-west: both axes
+        ("LOWW", 1, True, True, False, f32([0.0, 0.5, 1.0])),           # north (360 deg)
+        ("LOWW", 1, True, True, False, box(14006)),
+        ("LOWW", 1, True, True, False, box(14007)),
+        ("LOWW", 1, True, True, False, box(14008)),
+        ("LOWW", 1, True, True, False, box(14009)),
+        ("LOWW", 1, True, True, False, f32([-0.5, -0.2, 0.6667])),      # 300 deg
+        ("LOWW", 1, True, True, False, f32([0.3, 0.8, 0.8333])),        # 330 deg
+        ("LOWW", 1, True, True, False, f32([-0.8, 0.0, 0.3333])),       # 240 deg
+        ("LOWW_random", 1, True, True, False, [1.0, 1.0, 0.5]),
+        ("LOWW_random", 1, True, True, False, f32([-0.3, 0.1, 0.9])),
+        ("LOWW_random", 1, False, False, False, f32([0.9, 0.3, 0.6])),
+        ("Simple", 1, True, True, False, [1.0, 1.0, 0.5]),
+        ("Simple", 1, True, True, False, f32([0.2, -0.4, 1.0])),
+        ("UnitTest", 1, True, True, False, [1.0, 1.0, 0.5]),
+        ("UnitTest", 1, True, True, False, [-1.0, -1.0, -1.0]),
+        ("LOWW", 0.1, True, True, False, [1.0, 1.0, 0.5]),
+        ("Simple", 0.1, True, True, False, f32([0.5, 0.0, -1.0])),
+        ("LOWW", 5, True, True, False, [-1.0, -1.0, -1.0]),
+        ("LOWW_random", 5, True, True, False, box(14005)),
+        ("LOWW", 1, True, True, True, [15.0, 200.0, 300.0]),            # discrete: 250 kt, FL200, 300 deg
+    ]
+    random.seed(14)
+    crossing = 0
+    for scen, dt, shaping, normalize, discrete, a in plan:
+        env = make_env(scen, dt=dt, shaping=shaping, normalize=normalize, discrete=discrete)
+        start = len(rec.flags)
+        n = rec.run(env, np.tile(np.asarray(a, dtype=np.float64), (G14_STEPS, 1)), scen, dt, shaping, normalize, discrete,
+                    extra_after_done=2 * G14_STEPS)
+        assert n == G14_STEPS
+        x0, y0, rng_nm = position_range(env)
+        faf = env._runway.corridor.faf.ravel()
+        rows = [i for i, r in enumerate(rec.samp_rows) if r >= start]
+        st = np.asarray(rec.state)[rows]
+        on = (np.abs(st[:, 0] - x0) < rng_nm - 1e-3) & (np.abs(st[:, 1] - y0) < rng_nm - 1e-3)
+        window = on & ((np.abs(faf[0] - st[:, 0]) > rng_nm) | (np.abs(faf[1] - st[:, 1]) > rng_nm))
+        crossing += bool(window.any())
+        rec.ep[-1]["window_rows"] = int(window.sum())
+    assert crossing >= 8, crossing
+    rec.save(os.path.join(HERE, "g14_no_reset.npz"))
+    return rec, crossing
+
+
 if __name__ == "__main__":
-    which = sys.argv[1:] or ["g1", "g2", "g3", "g4", "g5", "g6", "g7", "mt", "g8", "g9", "g10", "g11", "g12", "g13"]
+    which = sys.argv[1:] or ["g1", "g2", "g3", "g4", "g5", "g6", "g7", "mt", "g8", "g9", "g10", "g11", "g12", "g13", "g14"]
     if "g1" in which:
         gen_g1()
     if "mt" in which:
@@ -1078,6 +1161,13 @@ if __name__ == "__main__":
         r = gen_g13()
         fl, dn = np.asarray(r.flags), np.asarray(r.done)
         print("g13 episodes", len(r.ep), "steps", len(fl), "sampled rows", len(r.samp_rows), "timesteps", sorted(set(e["dt"] for e in r.ep)))
+        for name, bit in (("below", 1), ("outside", 2), ("won", 4), ("timeout", 8), ("inv_v", 16), ("inv_h", 32)):
+            print(name, int(((fl & bit) != 0).sum()), "terminal:", int((((fl & bit) != 0) & (dn != 0)).sum()))
+    if "g14" in which:
+        r, crossing = gen_g14()
+        fl, dn = np.asarray(r.flags), np.asarray(r.done)
+        print("g14 episodes", len(r.ep), "steps", len(fl), "sampled rows", len(r.samp_rows), "episodes through the window", crossing,
+              "window rows", [e["window_rows"] for e in r.ep])
         for name, bit in (("below", 1), ("outside", 2), ("won", 4), ("timeout", 8), ("inv_v", 16), ("inv_h", 32)):
             print(name, int(((fl & bit) != 0).sum()), "terminal:", int((((fl & bit) != 0) & (dn != 0)).sum()))
     print("done")

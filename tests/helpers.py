@@ -145,7 +145,41 @@ def obs_close(obs, gold, tol, normalize):
     return np.all(d <= tol)
 
 
-def replay_wide(fx, make_backend, obs_tol, state_tol, rew_tol, max_envs=4096):
+def grid_range(comp):
+    """(lo, hi): the fp32 path's position grid of a compiled sector per axis, origin +- 2^(31-k) nm (include/atc_step.h, "Aircraft
+    positions"); hi is the largest position on it, INT32_MAX counts."""
+    org = np.asarray(comp.pos_origin, dtype=np.float64)
+    r = 2.0 ** (31 - comp.pos_k)
+    return org - r, org + r - 2.0 ** -comp.pos_k
+
+
+def grid_prefix(fx):
+    """The no-reset fixture (g14) against the fp32 path's position grid.  Per episode, its ON-GRID PREFIX: the rows up to the last
+    sampled row whose float64 reference position lies inside the compiled sector's grid range on both axes — where the fp32 path
+    must follow the reference at the plain bars.  Past it the path pins the position at the range limit (documented).  Asserts
+    that a sampled row once off the grid stays off.  Returns (prefix[row] bool, sampled rows in the prefix, sampled rows in the
+    SATURATION WINDOW: on the grid with |faf - x| or |faf - y| beyond the range 2^(31-k) nm — where a 32-bit to-FAF difference
+    saturated, episodes with window rows)."""
+    prefix = np.zeros(len(fx.flags), bool)
+    n_on = n_win = eps_win = 0
+    for ep in fx.episodes:
+        comp = compiled(ep["scen"])
+        lo, hi = grid_range(comp)
+        faf = np.asarray(comp.corridor["faf"], dtype=np.float64)
+        s0, s1 = ep["start"], ep["start"] + ep["steps"]
+        rows = fx.samp_rows[(fx.samp_rows >= s0) & (fx.samp_rows < s1)]
+        st = fx.state[fx.samp_index[rows]]
+        on = np.all((st[:, :2] >= lo) & (st[:, :2] <= hi), axis=1)
+        k = int(np.argmin(on)) if not on.all() else len(on)
+        assert on[:k].all() and not on[k:].any(), (ep["scen"], ep["start"], "a sample back on the grid")
+        if k:
+            prefix[s0:rows[k - 1] + 1] = True
+        win = np.any(np.abs(faf - st[:k, :2]) > 2.0 ** (31 - comp.pos_k), axis=1)
+        n_on, n_win, eps_win = n_on + k, n_win + int(win.sum()), eps_win + bool(win.any())
+    return prefix, n_on, n_win, eps_win
+
+
+def replay_wide(fx, make_backend, obs_tol, state_tol, rew_tol, max_envs=4096, prefix=None):
     """Runs every episode of the wide fixture through a lock-step backend (the episodes of one configuration side by
     side as the envs of one batch).  make_backend(scen, dt, shaping, normalize, discrete, B) returns an object with
     place(b, init_state, init_timesteps, init_last_action) and step(actions[B,1,3]) -> (obs[B,10], reward[B], done[B],
@@ -155,10 +189,15 @@ def replay_wide(fx, make_backend, obs_tol, state_tol, rew_tol, max_envs=4096):
     of obs[8] inside 0.25 nm of the FAF (the bearing to it is ill-conditioned there and fp32 speed / heading state put the
     position ~2e-6 nm off the float64 reference); since ABI 18 speed and heading are 32-bit fixed point and the displacement
     is float64 with dithered rounding (include/atc_step.h) — positions stay within ~1e-6 nm over 6 000 steps, 2e-7 typically —
-    and the exception is retired.  Returns the number of steps compared."""
+    and the exception is retired.
+
+    prefix (bool per row, grid_prefix): values — rewards, sampled observations and states — are compared on these rows only; on
+    every sampled row past them the backend's position must be pinned at the grid limit (x or y on it) and the reference's
+    flags say OUTSIDE.  Integer outputs stay exact on every row.  Returns the number of steps compared."""
     total = 0
     for (scen, dt, shaping, normalize, discrete), eps in fx.groups().items():
         half = 0.5 * compiled(scen).norm_max.astype(np.float64)
+        g_lo, g_hi = grid_range(compiled(scen))
         for lo in range(0, len(eps), max_envs):
             ge = eps[lo:lo + max_envs]
             B = len(ge)
@@ -177,11 +216,17 @@ def replay_wide(fx, make_backend, obs_tol, state_tol, rew_tol, max_envs=4096):
                 assert np.array_equal(np.asarray(acts)[live], fx.actions_taken[lr]), (scen, t)
                 gw = fx.reward[lr]
                 st = np.asarray(state, dtype=np.float64)[live]
+                val = np.ones(len(lr), bool) if prefix is None else prefix[lr]
                 # the fixture stores rewards as float32 (6e-8 relative)
-                assert np.all(np.abs(np.asarray(rew, dtype=np.float64)[live] - gw)
-                              <= (rew_tol + 1e-7) * np.maximum(1.0, np.abs(gw))), (scen, t)
+                assert np.all((np.abs(np.asarray(rew, dtype=np.float64)[live] - gw)
+                               <= (rew_tol + 1e-7) * np.maximum(1.0, np.abs(gw)))[val]), (scen, t)
                 si = fx.samp_index[lr]
-                has = si >= 0
+                if prefix is not None:
+                    off = (si >= 0) & ~val
+                    if off.any():
+                        pinned = np.any((st[off][:, :2] == g_lo) | (st[off][:, :2] == g_hi), axis=1)
+                        assert pinned.all() and np.all(fx.flags[lr[off]] & F_OUTSIDE), (scen, t, st[off][~pinned])
+                has = (si >= 0) & val
                 if has.any():
                     go = fx.obs[si[has]].astype(np.float64)
                     tol = (obs_tol if normalize else obs_tol * half) * np.ones((int(has.sum()), 10))
@@ -194,7 +239,7 @@ def replay_wide(fx, make_backend, obs_tol, state_tol, rew_tol, max_envs=4096):
     return total
 
 
-def replay_wide_interleaved(fx, make_backend, N, obs_tol, state_tol, rew_tol, max_envs=1024, chunk=1):
+def replay_wide_interleaved(fx, make_backend, N, obs_tol, state_tol, rew_tol, max_envs=1024, chunk=1, prefix=None):
     """The reference pins MULTI-aircraft envs too, where the extension's own rules are switched off: with a separation minimum of 0
     nobody is ever in conflict, and with the reference's episode rule (ATC_M_KEEP_ACTIVE: no hand-over, any terminal aircraft ends the
     episode) an env of N aircraft IS N reference episodes flown side by side on one clock.  So N episodes of the wide fixture — same
@@ -208,10 +253,12 @@ def replay_wide_interleaved(fx, make_backend, N, obs_tol, state_tol, rew_tol, ma
     set_timesteps(b, t) and step(actions[B, N, 3]) -> (obs[B, N, 10], reward[B], done[B], flags[B, N], actions_taken[B],
     state[B, N, 5]).  chunk > 1: the backend's rollout(actions[chunk, B, N, 3]) flies `chunk` steps per call (a multi-step launch)
     and returns the same tuple with a leading step axis, counters and state as they are after the LAST step of the chunk.
+    prefix: as in replay_wide, per aircraft (the env's reward is compared where all of its aircraft are inside their prefix).
     Returns (aircraft-steps compared, envs flown)."""
     total = envs = 0
     for (scen, dt, shaping, normalize, discrete), eps in fx.groups().items():
         half = 0.5 * compiled(scen).norm_max.astype(np.float64)
+        g_lo, g_hi = grid_range(compiled(scen))
         by_t0 = {}
         for ep in eps:
             by_t0.setdefault(ep["init_timesteps"], []).append(ep)
@@ -238,16 +285,21 @@ def replay_wide_interleaved(fx, make_backend, N, obs_tol, state_tol, rew_tol, ma
                 assert np.array_equal(np.asarray(flags)[live].astype(np.uint8), fx.flags[lr]), (scen, N, t)
                 assert np.array_equal(np.asarray(done)[live].astype(bool), fx.done[lr].astype(bool).any(axis=1)), (scen, N, t)
                 gw = fx.reward[lr]
-                assert np.all(np.abs(np.asarray(rew, dtype=np.float64)[live] - gw.sum(axis=1))
-                              <= (rew_tol + 1e-7) * np.maximum(1.0, np.abs(gw)).sum(axis=1)), (scen, N, t)
+                val = np.ones(lr.shape, bool) if prefix is None else prefix[lr]                # [L, N]
+                assert np.all((np.abs(np.asarray(rew, dtype=np.float64)[live] - gw.sum(axis=1))
+                               <= (rew_tol + 1e-7) * np.maximum(1.0, np.abs(gw)).sum(axis=1))[val.all(axis=1)]), (scen, N, t)
                 si = fx.samp_index[lr]
-                has = si >= 0
+                has = (si >= 0) & val
                 if has.any():
                     go = fx.obs[si[has]].astype(np.float64)
                     tol = (obs_tol if normalize else obs_tol * half) * np.ones((int(has.sum()), 10))
                     assert obs_close(np.asarray(obs, dtype=np.float64)[live][has], go, tol, normalize), (scen, N, t)
                 if acts is not None:
                     assert np.array_equal(np.asarray(acts)[live], fx.actions_taken[lr].sum(axis=1)), (scen, N, t)
+                    off = (si >= 0) & ~val
+                    if off.any():
+                        sto = np.asarray(state, dtype=np.float64)[live][off][:, :2]
+                        assert np.all(np.any((sto == g_lo) | (sto == g_hi), axis=1)) and np.all(fx.flags[lr[off]] & F_OUTSIDE), (scen, N, t)
                     if has.any():
                         gs = fx.state[si[has]]
                         assert np.all(np.abs(np.asarray(state, dtype=np.float64)[live][has] - gs) <= state_tol * np.maximum(1.0, np.abs(gs))), (scen, N, t)

@@ -1,6 +1,7 @@
 """Randomised differential test of the HIP step path against the fp32 oracle: random batch shapes, aircraft counts,
 sectors, lookup-grid cells, modes (dt, discrete, shaping, normalisation, spawn, timeout limit, separation minimum),
-kernel variant (fast / full) and launch form (single steps / fused rollout / fused rollout with held action blocks).  ATC_FUZZ_CASES sets the number of cases
+kernel variant (fast / full), launch form (single steps / fused rollout / fused rollout with held action blocks) and, one case in 50,
+no reset at all.  ATC_FUZZ_CASES sets the number of cases
 (default: a short pass), ATC_FUZZ_SEED the first seed; every case is reproducible from its seed
 (tests/fuzz_debug.py <seed> replays one and prints the first deviation with its context).
 
@@ -76,6 +77,15 @@ def _case(seed):
     # LDS-resident table (k_step<1, ..., LDSG>; tests/test_lds_table.py)
     if N == 1 and kw["use_rollout"] and int(rng.integers(2)) == 0:
         kw["B"] = 256 * int(rng.integers(1, 3))
+    # drawn last: one case in 50 never resets (the reference's FPS protocol, learning/atc-gym-compute-performance.py) — 500 to 5 000
+    # steps with actions held for hundreds of steps, long enough to fly off the position grid (include/atc_step.h); B x N <= 2 048
+    if int(rng.integers(50)) == 0:
+        kw["auto_reset"] = False
+        kw["hold"] = int(rng.choice([200, 400, 1000]))       # (multiples of every rollout_hold)
+        kw["steps"] = int(rng.choice([500, 1000, 2000, 5000]))
+        kw["B"] = min(kw["B"], max(1, 2048 // N))
+        if kw["use_rollout"]:
+            kw["steps"] = -(-kw["steps"] // kw["use_rollout"]) * kw["use_rollout"]
     return scn, comp, kw
 
 

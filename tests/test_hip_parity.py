@@ -328,6 +328,25 @@ class _HipLockstep:
         self.env.close()
 
 
+class _HipLockstepHeld(_HipLockstep):
+    """_HipLockstep whose steps after the first carry the held-action hint (ATC_M_ACTIONS_HELD): for fixtures whose every episode
+    holds ONE action (g14), with check_held verifying the promise."""
+
+    def __init__(self, *a):
+        super().__init__(*a)
+        self.env._check_held = True
+        self.n = 0
+
+    def step(self, actions):
+        held, self.n = self.n > 0, self.n + 1
+        e = self.env
+        obs, rew, done, info = e.step(actions, held=held)
+        pack = e.torch.cat([obs.double(), rew.double()[:, None], done.double()[:, None], info["flags"].double(),
+                            e.actions_taken.double()[:, None], e.x[:, None], e.y[:, None], e.h.double()[:, None],
+                            e.phi.double()[:, None], e.v.double()[:, None]], dim=1).cpu().numpy()
+        return pack[:, :10], pack[:, 10], pack[:, 11], pack[:, 12], pack[:, 13].astype(np.int64), pack[:, 14:19]
+
+
 class _HipInterleaved:
     def __init__(self, scen, dt, shaping, normalize, discrete, B, N):
         from atc_hip.vec_env import AtcVecEnv
@@ -370,15 +389,17 @@ class _HipInterleaved:
 @pytest.mark.parametrize("N,chunk,fixture", [(16, 1, "g9_wide.npz"), (64, 1, "g9_wide.npz"), (5, 1, "g9_wide.npz"), (16, 10, "g9_wide.npz"),
                                               (64, 10, "g9_wide.npz"), (32, 5, "g9_wide.npz"), (8, 1, "g11_unbounded.npz"), (8, 10, "g11_unbounded.npz"),
                                               (8, 1, "g12_timesteps.npz"), (8, 10, "g12_timesteps.npz"), (16, 5, "g12_timesteps.npz"),
-                                              (5, 1, "g13_timestep_sweep.npz"), (5, 10, "g13_timestep_sweep.npz")])
+                                              (5, 1, "g13_timestep_sweep.npz"), (5, 10, "g13_timestep_sweep.npz"), (8, 1, "g14_no_reset.npz"),
+                                              (8, 10, "g14_no_reset.npz")])
 def test_reference_episodes_as_the_aircraft_of_one_env(N, chunk, fixture):
     """helpers.replay_wide_interleaved through the batched kernels: N reference episodes of g9 are the N aircraft of one env
     (separation minimum 0, the reference's episode rule), single steps and multi-step launches (the 32- / 64-aircraft ones under the
     separation-scan horizon) — the multi-aircraft step checked against the REFERENCE over whole episodes."""
     _torch()
     fx = H.WideFixture(fixture)   # (g11: actions outside the action space, WIDE headings in several aircraft of one env)
-    n, envs = H.replay_wide_interleaved(fx, _HipInterleaved, N, obs_tol=1e-5, state_tol=1e-5, rew_tol=1e-5, chunk=chunk)
-    least = {"g9_wide.npz": (8, 100000), "g13_timestep_sweep.npz": (30, 10000)}.get(fixture, (10, 20000))
+    prefix = H.grid_prefix(fx)[0] if fixture == "g14_no_reset.npz" else None     # g14: values on the on-grid prefix (fp32 spec)
+    n, envs = H.replay_wide_interleaved(fx, _HipInterleaved, N, obs_tol=1e-5, state_tol=1e-5, rew_tol=1e-5, chunk=chunk, prefix=prefix)
+    least = {"g9_wide.npz": (8, 100000), "g13_timestep_sweep.npz": (30, 10000), "g14_no_reset.npz": (2, 159999)}.get(fixture, (10, 20000))
     assert envs >= least[0] and n > least[1], (n, envs)
 
 
@@ -422,6 +443,111 @@ def test_timestep_fixture_batched():
     H.WRAP_ROWS[0] = 0
     n = H.replay_wide(fx, _HipLockstep, obs_tol=1e-5, state_tol=1e-5, rew_tol=1e-5)
     assert n == len(fx.flags) > 370000 and H.WRAP_ROWS[0] <= 40
+
+
+@pytest.mark.parametrize("held", [False, True])
+def test_no_reset_fixture_batched(held):
+    """G14: the reference's FPS protocol — reset() once, one action held, 10 000 steps with no reset — through the batched kernel
+    in single steps (held=True: every step after the first with the held-action hint), at the rules of the fp32 CPU test
+    (tests/test_oracle_golden.py::test_no_reset_fixture): integer outputs exact on every row, values at the 1e-5 bars on each
+    episode's on-grid prefix — the saturation window next to the grid edge included —, the position pinned at the grid limit past it."""
+    fx = H.WideFixture("g14_no_reset.npz")
+    prefix, n_on, n_win, eps_win = H.grid_prefix(fx)
+    assert n_win >= 250 and eps_win >= 8
+    H.WRAP_ROWS[0] = 0
+    n = H.replay_wide(fx, _HipLockstepHeld if held else _HipLockstep, obs_tol=1e-5, state_tol=1e-5, rew_tol=1e-5, prefix=prefix)
+    assert n == len(fx.flags) >= 280000 and H.WRAP_ROWS[0] <= 10
+
+
+def test_no_reset_fixture_rollout_hold():
+    """G14 through atc_rollout_hold: the episodes of a configuration as one-aircraft envs, padded (episodes repeated) to a whole number
+    of 256-env workgroups so that the launch answers the MVA lookup from the sector's LDS-resident table (k_step<1, ..., LDSG>), each
+    episode's one action held for 1 000 steps per launch.  Flags / done exact on every step, the action counter and the position at
+    every launch boundary; values on the on-grid prefix; past it the position at the grid limit."""
+    torch = _torch()
+    from atc_hip.vec_env import AtcVecEnv
+    from envs.atc import model
+    fx = H.WideFixture("g14_no_reset.npz")
+    prefix = H.grid_prefix(fx)[0]
+    chunk, total = 1000, 0
+    for (scen, dt, shaping, normalize, discrete), eps in fx.groups().items():
+        half = 0.5 * H.compiled(scen).norm_max.astype(np.float64)
+        g_lo, g_hi = H.grid_range(H.compiled(scen))
+        B = 256 * ((len(eps) + 255) // 256)
+        ge = [eps[b % len(eps)] for b in range(B)]
+        sp = model.SimParameters(dt, reward_shaping=shaping, normalize_state=normalize, discrete_action_space=discrete)
+        env = AtcVecEnv(B, 1, sim_parameters=sp, scenario=H.make_scenario(scen), auto_reset=False, spawn="lattice", keep_active=True)
+        assert env.sector.has_lds_table, scen      # (the lookup grid of a sector without noise areas fits the LDS)
+        for b, ep in enumerate(ge):
+            env.set_state(b, 0, *ep["init_state"])
+            env.timesteps[b] = ep["init_timesteps"]
+            env.set_last_action(b, 0, ep["init_last_action"])
+        starts = np.array([ep["start"] for ep in ge])
+        steps = ge[0]["steps"]
+        assert all(ep["steps"] == steps for ep in ge) and steps % chunk == 0
+        act = torch.as_tensor(fx.action[starts].astype(np.float32).reshape(1, B, 1, 3))
+        assert all(np.array_equal(fx.action[s0:s0 + steps], np.repeat(fx.action[s0][None], steps, 0)) for s0 in starts)
+        for t0 in range(0, steps, chunk):
+            out = env.rollout(act, hold=chunk)
+            fl, dn = out["flags"].cpu().numpy()[:, :, 0], out["done"].cpu().numpy()
+            ob, rw = out["obs"].cpu().numpy(), out["reward"].cpu().numpy().astype(np.float64)
+            for c in range(chunk):
+                rows = starts + t0 + c
+                assert np.array_equal(fl[c].astype(np.uint8), fx.flags[rows]) and np.array_equal(dn[c], fx.done[rows]), (scen, t0 + c)
+                val = prefix[rows]
+                gw = fx.reward[rows]
+                assert np.all((np.abs(rw[c] - gw) <= (1e-5 + 1e-7) * np.maximum(1.0, np.abs(gw)))[val]), (scen, t0 + c)
+                si = fx.samp_index[rows]
+                has = (si >= 0) & val
+                if has.any():
+                    tol = (1e-5 if normalize else 1e-5 * half) * np.ones((int(has.sum()), 10))
+                    assert H.obs_close(ob[c][has].astype(np.float64), fx.obs[si[has]].astype(np.float64), tol, normalize), (scen, t0 + c)
+            rows = starts + t0 + chunk - 1
+            assert np.array_equal(env.actions_taken.cpu().numpy(), fx.actions_taken[rows])
+            st = np.stack([env.x.cpu().numpy(), env.y.cpu().numpy()], 1)
+            si = fx.samp_index[rows]
+            on, off = (si >= 0) & prefix[rows], (si >= 0) & ~prefix[rows]
+            assert np.all(np.abs(st[on] - fx.state[si[on]][:, :2]) <= 1e-5 * np.maximum(1.0, np.abs(fx.state[si[on]][:, :2])))
+            assert np.all(np.any((st[off] == g_lo) | (st[off] == g_hi), axis=1))
+            total += B * chunk
+        env.close()
+    assert total >= 280000
+
+
+@pytest.mark.parametrize("persistent", [None, False])
+def test_no_reset_fixture_single_env(persistent):
+    """G14 through the drop-in AtcGym as the reference's benchmark runs it (learning/atc-gym-compute-performance.py): reset() once,
+    ONE action, 10 000 steps without reset — persistent=None: the step server (a resident kernel polling a mailbox), persistent=False:
+    one launch per step — on LOWW and Simple.  done / action counter exact on every step, reward and observation on the on-grid
+    prefix at 1e-5, the aircraft at the grid limit past it."""
+    from envs.atc import atc_gym, model
+    fx = H.WideFixture("g14_no_reset.npz")
+    prefix = H.grid_prefix(fx)[0]
+    n_eps = 0
+    for scen in ("LOWW", "Simple"):
+        eps = [ep for ep in fx.episodes if ep["scen"] == scen and ep["dt"] == 1.0 and ep["shaping"] and ep["normalize"]
+               and not ep["discrete"]][:2]
+        g_lo, g_hi = H.grid_range(H.compiled(scen))
+        for ep in eps:
+            env = atc_gym.AtcGym(sim_parameters=model.SimParameters(1), scenario=H.make_scenario(scen), persistent=persistent)
+            env.reset()
+            ap = env._airplane
+            assert np.allclose([ap.x, ap.y, ap.h, ap.phi, ap.v], ep["init_state"], rtol=0, atol=1e-6), (scen, ep["init_state"])
+            a = fx.action[ep["start"]].astype(np.float32)
+            for t in range(ep["steps"]):
+                row = ep["start"] + t
+                obs, rew, done, info = env.step(a)
+                assert bool(done) == bool(fx.done[row]) and env.actions_taken == fx.actions_taken[row], (scen, row, t)
+                si = fx.samp_index[row]
+                if prefix[row]:
+                    assert abs(rew - fx.reward[row]) <= (1e-5 + 1e-7) * max(1.0, abs(fx.reward[row])), (scen, row, t)
+                    if si >= 0:
+                        assert H.obs_close(obs[None], fx.obs[si][None].astype(np.float64), 1e-5, True), (scen, row, t, obs, fx.obs[si])
+            # (the aircraft's state is read once, after the episode: a read mid-episode would end the step server's lease)
+            assert not prefix[row] and (ap.x in (g_lo[0], g_hi[0]) or ap.y in (g_lo[1], g_hi[1])), (scen, ap.x, ap.y)
+            n_eps += 1
+            env.close()
+    assert n_eps == 4
 
 
 def test_timestep_fixture_single_env():
@@ -541,7 +667,7 @@ def test_atcgym_keeps_flying_after_a_win():
 # ------------------------------------------------------------------------------------------------ batched vs fp32 oracle
 def _run_vs_oracle(scen_obj, comp, B, N, steps, seed, dt=1.0, discrete=False, spawn="lattice", hold=20, grid_cell=0.5,
                    use_rollout=0, timestep_limit=6000, full=True, shaping=True, normalize=True, sep_nm=3.0,
-                   keep_active=False, held_hint=False, rollout_hold=1, wild=0.0):
+                   keep_active=False, held_hint=False, rollout_hold=1, wild=0.0, auto_reset=True):
     """full=False drives the fast kernel variant (obs / reward / done / flags only), full=True the one with every optional
     output; everything the variant produces is compared with the fp32 oracle.  held_hint: single steps that repeat the
     previous step's action array are launched with ATC_M_ACTIONS_HELD (must change nothing).
@@ -550,16 +676,17 @@ def _run_vs_oracle(scen_obj, comp, B, N, steps, seed, dt=1.0, discrete=False, sp
     inside the kernel; the oracle is stepped once per step with the block's actions.
     wild > 0: that fraction of the drawn action COMPONENTS lies outside the action space — U(-4, 4) (a tenth of those a further
     factor 50 out): the reference enforces no Box (atc_gym.py:128-141); speed / altitude targets beyond their limits are refused,
-    heading targets are never validated and headings leave the state format's 32-bit range (include/atc_step.h, ABI 19)."""
+    heading targets are never validated and headings leave the state format's 32-bit range (include/atc_step.h, ABI 19).
+    auto_reset=False: no env is ever reset — the reference's FPS protocol; held long enough, aircraft fly off the position grid."""
     torch = _torch()
     from atc_hip.vec_env import AtcVecEnv
     from envs.atc import model
     from oracle import oracle as O
     sp = model.SimParameters(dt, discrete_action_space=discrete, reward_shaping=shaping, normalize_state=normalize)
-    env = AtcVecEnv(B, N, sim_parameters=sp, scenario=scen_obj, auto_reset=True, spawn=spawn, seed=seed,
+    env = AtcVecEnv(B, N, sim_parameters=sp, scenario=scen_obj, auto_reset=auto_reset, spawn=spawn, seed=seed,
                     grid_cell=grid_cell, want_raw_obs=full, want_ac_reward=full, want_min_sep=full, want_term_obs=full,
                     timestep_limit=timestep_limit, sep_nm=sep_nm, keep_active=keep_active)
-    p = O.make_params(dt=dt, discrete=discrete, auto_reset=True, random_entry=(spawn == "random"), seed=seed,
+    p = O.make_params(dt=dt, discrete=discrete, auto_reset=auto_reset, random_entry=(spawn == "random"), seed=seed,
                       timestep_limit=timestep_limit, shaping=shaping, normalize=normalize, sep_nm=sep_nm,
                       keep_active=keep_active)
     orc = O.OracleEnv(comp, B, N, p, np.float32)
@@ -744,33 +871,72 @@ def test_actions_outside_the_action_space_vs_oracle(N, B, kw):
     assert n_done > 0 and (seen & H.F_INVALID_V) and (seen & H.F_INVALID_H)
 
 
-def test_flying_on_beyond_the_position_grid():
-    """Documented limit of the fixed-point position grid (include/atc_step.h): an aircraft that is flown on without reset
-    beyond the grid range is pinned at the range limit — it stays OUTSIDE the airspace like the reference's, its x / y
-    observation stops growing, and HIP and the fp32 oracle still agree bit for bit."""
+@pytest.mark.parametrize("grid_cell", [None, 0.125, 0.5])
+@pytest.mark.parametrize("form", ["step", "rollout", "rollout_hold", "ldsg", "n16"])
+def test_flying_on_beyond_the_position_grid(form, grid_cell):
+    """Documented limit of the fixed-point position grid (include/atc_step.h): an aircraft flown on without reset beyond the grid
+    range is pinned at the range limit — INT32_MIN / INT32_MAX counts, origin +- 2^(31-k) nm — and stays OUTSIDE the airspace like
+    the reference's.  Eight compass directions, so the diagonals pin both axes at once (the clamped cell / sub-cell indices of both
+    MVA lookups at every border and corner); launch forms: single steps, fused rollout, rollout_hold, rollout_hold on whole 256-env
+    workgroups (the LDS-resident table, k_step<1, ..., LDSG>), and 16 aircraft per env with a 3 nm separation minimum, where the two
+    aircraft of a diagonal pair meet in the same corner and must report the conflict the oracle reports.  Flags / done exact on every
+    step, positions bit-identical to the fp32 oracle's (every step / every launch boundary), obs and rewards within 1e-5."""
     torch = _torch()
     from atc_hip.vec_env import AtcVecEnv
     from envs.atc import scenarios
     from oracle import oracle as O
-    scn = scenarios.LOWW()
-    comp = H.compiled("LOWW", 0.5)
-    env = AtcVecEnv(4, 1, scenario=scn, auto_reset=False, keep_active=True)
-    orc = O.OracleEnv(comp, 4, 1, O.make_params(keep_active=True), np.float32)
-    a = np.zeros((4, 1, 3), np.float32)
-    a[:, 0, 0] = 1.0                                   # 300 kt
-    a[:, 0, 2] = [-1.0, -0.5, 0.0, 0.5]                 # headings 0 / 90 / 180 / 270: one aircraft per compass direction
-    lim_lo = np.array(comp.pos_origin) - 2.0 ** (31 - comp.pos_k)
-    lim_hi = np.array(comp.pos_origin) + 2.0 ** (31 - comp.pos_k)
-    for t in range(1400):                               # 1400 s x 300 kt = 117 nm: well past the +-64 nm grid
-        obs, rew, done, info = env.step(a)
-        orc.step(a)
-        if t % 50 == 0 or t > 1350:
-            assert np.array_equal(env.ac[:, 0].cpu().numpy(), orc.px) and np.array_equal(env.ac[:, 1].cpu().numpy(), orc.py)
-            assert np.array_equal(info["flags"].cpu().numpy().astype(np.uint16), orc.flags)
-    assert bool((info["flags"][:, 0] & H.F_OUTSIDE).all()) and bool(done.all())
-    x, y = env.x.cpu().numpy(), env.y.cpu().numpy()
-    assert y[0] == lim_hi[1] - 2.0 ** -comp.pos_k and x[1] == lim_hi[0] - 2.0 ** -comp.pos_k      # INT32_MAX counts
-    assert y[2] == lim_lo[1] and x[3] == lim_lo[0]                                                  # INT32_MIN counts
+    B, N = {"ldsg": (256, 1), "n16": (4, 16)}.get(form, (32, 1))
+    chunk = 1 if form == "step" else 100
+    steps = 1400                                        # 1400 s x 300 kt = 117 nm: past the +-64 nm grid on every heading
+    comp = H.compiled("LOWW", grid_cell)
+    env = AtcVecEnv(B, N, scenario=scenarios.LOWW(), grid_cell=grid_cell, auto_reset=False, keep_active=True, sep_nm=3.0)
+    assert env.sector.has_lds_table == (form == "ldsg" and grid_cell is not None)
+    orc = O.OracleEnv(comp, B, N, O.make_params(keep_active=True, sep_nm=3.0), np.float32)
+    lo, hi = H.grid_range(comp)
+    a = np.zeros((B, N, 3), np.float32)
+    dirs = np.zeros((B, N))
+    for b in range(B):
+        for k in range(N):
+            d = 45.0 * ((b + k) % 8)
+            alt = 9000.0 + 1500.0 * ((b + k) % 8)      # (n16: 1 500 ft between the direction pairs, the two of a pair level)
+            off = 5.0 if k >= 8 else 0.0                # (n16: the second of a pair 5 nm to the side of the first's track)
+            x = 36.0 + 0.7 * (b % 5) + off * np.cos(np.radians(d))
+            y = 42.0 - 0.3 * (b % 7) - off * np.sin(np.radians(d))
+            env.set_state(b, k, x, y, alt, d, 300.0)
+            orc.set_state(b, k, x, y, alt, d, 300.0)
+            a[b, k] = (1.0, alt / 19000.0 - 1.0, d / 180.0 - 1.0)
+            dirs[b, k] = d
+    half = 0.5 * comp.norm_max.astype(np.float64)
+    for t0 in range(0, steps, chunk):
+        if form == "step":
+            o, r, d_, info = env.step(a)
+            res = [(o, r, d_, info["flags"])]
+        elif form == "rollout":
+            out = env.rollout(torch.as_tensor(np.repeat(a[None], chunk, 0)))
+            res = [(out["obs"][c], out["reward"][c], out["done"][c], out["flags"][c]) for c in range(chunk)]
+        else:
+            out = env.rollout(torch.as_tensor(a[None]), hold=chunk)
+            res = [(out["obs"][c], out["reward"][c], out["done"][c], out["flags"][c]) for c in range(chunk)]
+        for c in range(chunk):
+            orc.step(a)
+            o, r, d_, fl = res[c]
+            assert np.array_equal(fl.cpu().numpy().astype(np.uint32).reshape(B, N), orc.flags), (form, t0 + c)
+            assert np.array_equal(d_.cpu().numpy(), orc.done), (form, t0 + c)
+            assert np.all(np.abs(o.cpu().numpy().reshape(B, N, 10) - orc.obs) <= 1e-5 * np.maximum(1.0, np.abs(orc.obs))), (form, t0 + c)
+            rr = r.cpu().numpy()
+            assert np.all(np.abs(rr - orc.reward) <= 1e-5 * np.maximum(1.0, np.abs(orc.reward)) + 6e-8 * N * np.abs(orc.ac_reward).sum(1)), t0 + c
+        assert np.array_equal(env.ac[:, 0].cpu().numpy(), orc.px) and np.array_equal(env.ac[:, 1].cpu().numpy(), orc.py), (form, t0)
+    assert np.all(orc.flags & H.F_OUTSIDE)           # (the device's flags are the oracle's, checked above)
+    x, y = env.x.cpu().numpy().reshape(B, N), env.y.cpu().numpy().reshape(B, N)
+    ex = np.where(np.isin(dirs, (45, 90, 135)), hi[0], np.where(np.isin(dirs, (225, 270, 315)), lo[0], np.nan))
+    ey = np.where(np.isin(dirs, (315, 0, 45)), hi[1], np.where(np.isin(dirs, (135, 180, 225)), lo[1], np.nan))
+    assert np.array_equal(x[~np.isnan(ex)], ex[~np.isnan(ex)]) and np.array_equal(y[~np.isnan(ey)], ey[~np.isnan(ey)])
+    assert np.all(((x > lo[0]) & (x < hi[0]))[np.isnan(ex)]) and np.all(((y > lo[1]) & (y < hi[1]))[np.isnan(ey)])
+    assert set(np.unique(env.ac[:, :2].cpu().numpy()[np.isin(dirs.ravel(), (45, 135, 225, 315))])) <= {-2 ** 31, 2 ** 31 - 1}
+    if form == "n16":   # the two aircraft of a diagonal pair share a corner: in conflict, like the oracle says; the others are not
+        diag = np.isin(dirs, (45, 135, 225, 315))
+        conf = (orc.flags & H.F_CONFLICT) != 0
+        assert conf[diag].all() and not conf[~diag].any()
     env.close()
 
 
