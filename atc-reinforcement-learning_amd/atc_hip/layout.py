@@ -2,7 +2,7 @@
 
 tests/test_abi.py parses the header and checks that every constant here matches it.
 """
-ABI_VERSION = 21
+ABI_VERSION = 22
 BLOB_VERSION = 1014.0
 
 H_VERSION, H_NWORDS, H_N_MVA, H_N_NOISE, H_N_ENTRY, H_OFF_POLY, H_OFF_VERT, H_OFF_ENTRY, H_OFF_GRID, H_N_VERTW = range(10)
@@ -64,3 +64,7 @@ LDS_MAGIC = 0x3154444C
  LDS_H_N_LINE, LDS_H_OFF_HTS, LDS_H_SUB, LDS_H_OFF_RESID, LDS_H_N_RESID, LDS_H_LDS_BYTES, LDS_H_OFF_POOL, LDS_H_N_REC) = range(19)
 LDS_HDR_WORDS = 24
 LDS_CLEAN, LDS_LINE, LDS_SUB, LDS_RESID = 0, 1, 2, 3
+# launch record (include/atc_step.h, ABI 22: atc_launch_counts): slot = log2(W) * LF_FORMS + form, LAUNCH_SERVE for server starts
+LF_FULL_ONE, LF_FULL_MULTI, LF_GEN_ONE, LF_ALLV_ONE, LF_GEN_MULTI, LF_ALLV_MULTI, LF_LAT, LF_LDSG, LF_FORMS = range(9)
+LAUNCH_SERVE, LAUNCH_SLOTS = 56, 57
+LF_NAMES = ("full-one", "full-multi", "gen-one", "allv-one", "gen-multi", "allv-multi", "lat", "ldsg")

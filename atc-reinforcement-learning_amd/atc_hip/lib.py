@@ -48,7 +48,7 @@ class AtcStepCall(C.Structure):
                 ("out", C.POINTER(AtcOut)), ("p", C.POINTER(AtcParams)), ("stream", C.c_void_p)]
 
 
-EXPORTS = ("atc_abi_version", "atc_last_error", "atc_host_mapped_ptr", "atc_scenario_create", "atc_scenario_destroy",
+EXPORTS = ("atc_abi_version", "atc_last_error", "atc_launch_counts", "atc_host_mapped_ptr", "atc_scenario_create", "atc_scenario_destroy",
            "atc_scenario_attach_lds_table", "atc_query_mva", "atc_query_mva_lds",
            "atc_query_mva_index", "atc_query_corridor", "atc_query_shaping", "atc_reset", "atc_observe", "atc_step",
            "atc_step_multi", "atc_step_packet", "atc_rollout", "atc_rollout_hold", "atc_serve_start", "atc_serve_step", "atc_serve_stop")
@@ -66,6 +66,7 @@ def load():
     vp, ci = C.c_void_p, C.c_int
     lib.atc_abi_version.restype = ci
     lib.atc_last_error.restype = C.c_char_p
+    lib.atc_launch_counts.argtypes = [C.POINTER(C.c_uint64), ci]
     lib.atc_host_mapped_ptr.argtypes = [vp, C.POINTER(vp)]
     lib.atc_scenario_create.argtypes = [vp, C.c_size_t, ci, C.POINTER(vp)]
     lib.atc_scenario_destroy.argtypes = [vp]
@@ -99,6 +100,21 @@ def check(rc):
         raise RuntimeError("libatcstep: %s (code %d)" % (load().atc_last_error().decode(), rc))
 
 
+def launch_name(slot):
+    """Readable name of a launch-record slot (include/atc_step.h, ABI 22): "<W>/<form>" for the step kernel's instantiations."""
+    if slot == L.LAUNCH_SERVE:
+        return "serve"
+    return "%d/%s" % (1 << (slot // L.LF_FORMS), L.LF_NAMES[slot % L.LF_FORMS])
+
+
+def launch_counts():
+    """Launches made by the calling thread so far, per kernel instantiation: {"16/allv-multi": n, ..., "serve": n}, names with a
+    count of zero left out.  The counters only grow; take the difference of two calls around a block of code."""
+    buf = (C.c_uint64 * L.LAUNCH_SLOTS)()
+    check(load().atc_launch_counts(buf, L.LAUNCH_SLOTS))
+    return {launch_name(i): int(v) for i, v in enumerate(buf) if v}
+
+
 def mapped_ptr(tensor):
     """Device address of a pinned (hipHostMalloc) CPU tensor: kernels access it zero-copy over the host link."""
     dev = C.c_void_p()
@@ -127,6 +143,9 @@ def make_params(dt=1.0, shaping=True, normalize=True, discrete=False, auto_reset
                      0.0, 0)
 
 
+LDS_TOO_LARGE = "larger than the device's LDS per workgroup"   # atc_scenario_attach_lds_table's one refusal that is not an error
+
+
 class Scenario:
     """Device-resident sector (opaque atc_scenario_t handle) + batched geometry queries."""
 
@@ -148,14 +167,21 @@ class Scenario:
             self.attach_lds_table()
 
     def attach_lds_table(self):
-        """Builds (once per CompiledSector) and attaches the LDS-resident lookup table; a sector without one — no lookup grid, noise-
-        abatement areas, too large for the device's LDS — simply keeps stepping from the grid.  Returns has_lds_table."""
+        """Builds (once per CompiledSector) and attaches the LDS-resident lookup table.  Where the table does not apply — a sector
+        without a lookup grid, with noise-abatement areas or otherwise without a table (CompiledSector.lds_table), or a table larger
+        than the device's LDS per workgroup — the sector simply keeps stepping from the grid: returns has_lds_table = False.  Any
+        other refusal by atc_scenario_attach_lds_table (a malformed table, a HIP error) raises with atc_last_error(): a table that
+        should have been attached is never dropped quietly."""
         torch = _torch_cuda()
+        self.has_lds_table = False
         tab = self.compiled.lds_table() if self.compiled.has_grid else None
         if tab is not None:
             t = np.ascontiguousarray(tab)
             with torch.cuda.device(self.device):
-                self.has_lds_table = self._lib.atc_scenario_attach_lds_table(self._h, t.ctypes.data_as(C.c_void_p), t.nbytes) == 0
+                rc = self._lib.atc_scenario_attach_lds_table(self._h, t.ctypes.data_as(C.c_void_p), t.nbytes)
+            if rc != 0 and LDS_TOO_LARGE not in self._lib.atc_last_error().decode():
+                check(rc)
+            self.has_lds_table = rc == 0
         return self.has_lds_table
 
     def query_mva_lds(self, x, y):

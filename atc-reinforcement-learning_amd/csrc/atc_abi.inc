@@ -5,6 +5,12 @@
 extern "C" {
 
 int atc_abi_version(void) { return ATC_ABI_VERSION; }
+
+int atc_launch_counts(uint64_t* out, int n) {
+    if (!out || n < 0) return fail_arg("null pointer");
+    for (int i = 0; i < n && i < ATC_LAUNCH_SLOTS; ++i) out[i] = t_launches[i];
+    return ATC_OK;
+}
 const char* atc_last_error(void) { return g_err; }
 
 int atc_host_mapped_ptr(const void* host, void** dev) {
@@ -306,6 +312,7 @@ int atc_serve_start(const atc_scenario_t* s, const atc_state_t* st, const atc_ou
     hipLaunchKernelGGL(k_serve, dim3(1), dim3(64), lds_bytes(s, false, true), (hipStream_t)stream, s->d_blob, s->off_grid, *st, *out, *p,
                        derive(*p, s, 0), mb_dev, seq, (unsigned long long)lease_us * 100ull);
     HIP_TRY(hipGetLastError());
+    ++t_launches[ATC_LAUNCH_SERVE];
     return ATC_OK;
 }
 

@@ -1540,6 +1540,10 @@ static size_t lds_bytes(const atc_scenario*, bool pair_scan, bool step_kernel = 
     return w * sizeof(float);
 }
 
+// the launch record (include/atc_step.h: atc_launch_counts): launches of each k_step instantiation and k_serve starts made by the
+// calling thread — a plain thread-local counter that nothing in the library reads back
+static thread_local uint64_t t_launches[ATC_LAUNCH_SLOTS] = {0};
+
 template <int W, bool FULL, bool ONE, bool ALLV, bool LAT = false, bool LDSG = false>
 static int launch_step2(const atc_scenario* s, int B, int N, int T, int hold, const atc_state_t* st, const float* actions,
                         const atc_out_t* out, const atc_params_t* p, hipStream_t stream) {
@@ -1558,6 +1562,9 @@ static int launch_step2(const atc_scenario* s, int B, int N, int T, int hold, co
     if (!LDSG) lt.src = nullptr;
     hipLaunchKernelGGL((k_step<W, FULL, ONE, ALLV, LAT, LDSG>), dim3(grid), dim3(kBlock), lds, stream, s->d_blob, s->off_grid, B, N, T, hold, *st, actions, *out, *p, derive(*p, s, scan_horizon<W, FULL, ONE>()), inline_action(), lt);
     HIP_TRY(hipGetLastError());
+    constexpr int form = LDSG ? ATC_LF_LDSG : LAT ? ATC_LF_LAT : FULL ? (ONE ? ATC_LF_FULL_ONE : ATC_LF_FULL_MULTI)
+                         : ONE ? (ALLV ? ATC_LF_ALLV_ONE : ATC_LF_GEN_ONE) : (ALLV ? ATC_LF_ALLV_MULTI : ATC_LF_GEN_MULTI);
+    ++t_launches[__builtin_ctz(W) * ATC_LF_FORMS + form];
     return ATC_OK;
 }
 template <int W>

@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define ATC_ABI_VERSION 21
+#define ATC_ABI_VERSION 22
 
 /* ---------------------------------------------------------------------------------------------
  * Scenario blob: one flat array of 32-bit floats (device copy) compiled on the host from the sector
@@ -420,6 +420,27 @@ typedef struct atc_scenario atc_scenario_t;
 /* -- lifecycle -------------------------------------------------------------------------------- */
 int atc_abi_version(void);
 const char* atc_last_error(void);
+
+/* Launch record (ABI 22).  The step kernel is one template compiled once per lane-group width W (1, 2, 4, ..., 64: the aircraft
+ * count rounded up to a power of two) and FORM; the library picks one per launch from B, N, T, the optional outputs, the device's
+ * CU count and whether an LDS table is attached.  Every thread counts its own launches: slot = log2(W) * ATC_LF_FORMS + form for
+ * the step kernel, ATC_LAUNCH_SERVE for starts of the step server.  Host side only — nothing that is launched depends on it. */
+enum {
+    ATC_LF_FULL_ONE = 0,    /* T = 1, an optional output or a packet requested */
+    ATC_LF_FULL_MULTI = 1,  /* T > 1, an optional output requested */
+    ATC_LF_GEN_ONE = 2,     /* T = 1, required outputs only, idle lanes possible */
+    ATC_LF_ALLV_ONE = 3,    /* T = 1, required outputs only, N == W and B * W a multiple of 256: every lane is an aircraft */
+    ATC_LF_GEN_MULTI = 4,   /* T > 1, required outputs only, idle lanes possible */
+    ATC_LF_ALLV_MULTI = 5,  /* T > 1, every lane an aircraft, more than 2 wavefronts per SIMD of the device */
+    ATC_LF_LAT = 6,         /* T > 1, every lane an aircraft, at most 2 wavefronts per SIMD (8 per CU) */
+    ATC_LF_LDSG = 7,        /* LAT with W = 1, an LDS table attached and B <= 256 * CUs (exists for W = 1 only) */
+    ATC_LF_FORMS = 8,
+    ATC_LAUNCH_SERVE = 56,  /* atc_serve_start */
+    ATC_LAUNCH_SLOTS = 57
+};
+/* Copies the calling thread's first min(n, ATC_LAUNCH_SLOTS) counters to out (launches since the thread started; they only grow,
+ * a failed launch is not counted).  atc_step_multi and atc_step_packet count once per launch they make. */
+int atc_launch_counts(uint64_t* out, int n);
 
 /* Uploads a compiled scenario blob (host pointer, n_words floats) to `device`.
  * Replaces: AtcGym.__init__ scenario unpacking, atc_gym.py:45-58. */

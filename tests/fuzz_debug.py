@@ -67,4 +67,6 @@ for t in range(kw["steps"]):
         print(" state hip", env.get_state(int(b), int(k)), "\n state orc", [orc.x.reshape(B, N)[b, k], orc.y.reshape(B, N)[b, k],
               orc.h.reshape(B, N)[b, k]])
         break
+from atc_hip import lib
+print("launched", lib.launch_counts())
 print("done")

@@ -1,4 +1,5 @@
 """Shared test helpers: golden loading, scenario factory, episode replay against any env adapter."""
+import contextlib
 import json
 import os
 
@@ -9,6 +10,23 @@ GOLDEN = os.path.join(HERE, "golden")
 
 F_BELOW_MVA, F_OUTSIDE, F_WON, F_TIMEOUT, F_INVALID_V, F_INVALID_H, F_CONFLICT, F_NOISE, F_INACTIVE = \
     1, 2, 4, 8, 16, 32, 64, 128, 256
+
+
+@contextlib.contextmanager
+def launches():
+    """Yields a dict that, once the block has ended, holds what the library's launch record (atc_hip.lib.launch_counts: the calling
+    thread's launches per kernel instantiation) gained inside the block: {"16/allv-multi": 3, ...}; nothing else is in it."""
+    from atc_hip import lib
+    before, gained = lib.launch_counts(), {}
+    yield gained
+    for name, n in lib.launch_counts().items():
+        if n != before.get(name, 0):
+            gained[name] = n - before.get(name, 0)
+
+
+def lane_width(N):
+    """W of k_step<W, ...>: the aircraft count rounded up to a power of two."""
+    return 1 << max(0, (int(N) - 1).bit_length())
 
 
 def golden_json(name):

@@ -1,7 +1,8 @@
 """Randomised differential test of the HIP step path against the fp32 oracle: random batch shapes, aircraft counts,
 sectors, lookup-grid cells, modes (dt, discrete, shaping, normalisation, spawn, timeout limit, separation minimum),
-kernel variant (fast / full), launch form (single steps / fused rollout / fused rollout with held action blocks) and, one case in 50,
-no reset at all.  ATC_FUZZ_CASES sets the number of cases
+kernel variant (fast / full), launch form (single steps / fused rollout / fused rollout with held action blocks), one case in 50
+no reset at all and, one in 25 of those with a power-of-two aircraft count, a batch just above the latency-bound limit of the device.
+Every case prints the kernel instantiations it launched (the library's launch record).  ATC_FUZZ_CASES sets the number of cases
 (default: a short pass), ATC_FUZZ_SEED the first seed; every case is reproducible from its seed
 (tests/fuzz_debug.py <seed> replays one and prints the first deviation with its context).
 
@@ -21,7 +22,13 @@ from test_hip_parity import _run_vs_oracle
 pytestmark = pytest.mark.gpu
 
 
-def _case(seed):
+def _n_cu():
+    """CUs of the device the case will run on (256, MI355X's, where there is none: tools that only list the cases)."""
+    import torch
+    return torch.cuda.get_device_properties(0).multi_processor_count if torch.cuda.is_available() else 256
+
+
+def _case(seed, n_cu=None):
     from envs.atc import scenarios
     rng = np.random.default_rng(seed)
     N = int(rng.choice([1, 1, 2, 3, 5, 8, 9, 15, 16, 16, 17, 24, 32, 33, 48, 63, 64]))
@@ -86,6 +93,13 @@ def _case(seed):
         kw["B"] = min(kw["B"], max(1, 2048 // N))
         if kw["use_rollout"]:
             kw["steps"] = -(-kw["steps"] // kw["use_rollout"]) * kw["use_rollout"]
+    # drawn last: one case in 25 whose aircraft count is a power of two flies a fast multi-step launch of whole workgroups just above
+    # the latency-bound limit (2 wavefronts per SIMD of the device at hand), i.e. the all-valid THROUGHPUT instantiation
+    # (k_step<W, false, false, true>) under whatever modes the case drew; two launches, so that the oracle's 131 072 aircraft stay cheap
+    if int(rng.integers(25)) == 0 and (N & (N - 1)) == 0:
+        n_cu = n_cu or _n_cu()
+        T = kw["use_rollout"] or 4
+        kw.update(B=(512 * n_cu + 256 * int(rng.integers(1, 4))) // N, full=False, use_rollout=T, steps=2 * T)
     return scn, comp, kw
 
 
@@ -94,4 +108,8 @@ def _case(seed):
 def test_random_configuration_matches_oracle(seed):
     scn, comp, kw = _case(seed)
     print("fuzz case", seed, type(scn).__name__, kw)
-    _run_vs_oracle(scn, comp, **kw)
+    with H.launches() as got:
+        _run_vs_oracle(scn, comp, **kw)
+    print("fuzz case", seed, "launched", got)
+    W = H.lane_width(kw["N"])
+    assert got and all(name.startswith("%d/" % W) for name in got), got

@@ -258,10 +258,17 @@ def test_fast_and_full_kernel_variants_agree(N):
             ("obs", (B, N * 10), torch.float32), ("reward", (B,), torch.float32), ("done", (B,), torch.uint8),
             ("flags", (B, N), torch.int16), ("raw_obs", (B, N * 10), torch.float32), ("ac_reward", (B, N), torch.float32),
             ("min_sep", (B,), torch.float32), ("term_obs", (B, N * 10), torch.float32))}
-        roll.rollout(acts, out=out)
+        with H.launches() as got:
+            roll.rollout(acts, out=out)
+        assert got == {"%d/full-multi" % N: 1}, got
         for t in range(T):
-            o1, r1, d1, i1 = fast.step(acts[t])
-            o2, r2, d2, i2 = full.step(acts[t])
+            with H.launches() as got:
+                o1, r1, d1, i1 = fast.step(acts[t])
+            # (300 envs x 64 lanes are 75 whole workgroups: the fast step of that batch is the all-valid one)
+            assert got == {"%d/%s" % (N, "allv-one" if N == 64 else "gen-one"): 1}, got
+            with H.launches() as got:
+                o2, r2, d2, i2 = full.step(acts[t])
+            assert got == {"%d/full-one" % N: 1}, got
             assert torch.equal(o1, o2) and torch.equal(r1, r2) and torch.equal(d1, d2) and torch.equal(i1["flags"], i2["flags"])
             assert torch.equal(out["obs"][t], o2) and torch.equal(out["reward"][t], r2) and torch.equal(out["flags"][t], i2["flags"])
             assert torch.equal(out["raw_obs"][t], i2["original_state"]) and torch.equal(out["ac_reward"][t], i2["aircraft_reward"])
@@ -621,18 +628,32 @@ def test_all_valid_instantiation_equals_general_kernels(N):
     envs = [AtcVecEnv(B, N, scenario=scn, seed=9), AtcVecEnv(B + 1, N, scenario=scn, seed=9),
             AtcVecEnv(B, N, scenario=scn, seed=9, want_raw_obs=True)]
     g = torch.Generator(device="cpu").manual_seed(N)
+    ran = [{}, {}, {}]      # the launch record (atc_hip.lib.launch_counts) of each env's launches
+
+    def counted(i, call):
+        with H.launches() as got:
+            res = call()
+        for name, n in got.items():
+            ran[i][name] = ran[i].get(name, 0) + n
+        return res
     for t in range(120):
         if t % 20 == 0:
             a = (torch.rand((B + 1, N, 3), generator=g) * 2 - 1).cuda()
-        res = [e.step(a[:e.B].contiguous(), held=t % 20 != 0) for e in envs]
+        res = [counted(i, lambda: e.step(a[:e.B].contiguous(), held=t % 20 != 0)) for i, e in enumerate(envs)]
         for o, r, d, info in res[1:]:
             assert torch.equal(res[0][0], o[:B]) and torch.equal(res[0][1], r[:B]) and torch.equal(res[0][2], d[:B])
             assert torch.equal(res[0][3]["flags"], info["flags"][:B])
     for j in range(3):
         blocks = (torch.rand((1, B + 1, N, 3), generator=g) * 2 - 1).cuda()
-        outs = [e.rollout(blocks[:, :e.B].contiguous(), hold=20) for e in envs[:2]]
+        outs = [counted(i, lambda: e.rollout(blocks[:, :e.B].contiguous(), hold=20)) for i, e in enumerate(envs[:2])]
         for k in ("obs", "reward", "done", "flags"):
             assert torch.equal(outs[0][k], outs[1][k][:, :B]), k
+    # what the library says it launched: the all-valid instantiations for the whole-workgroup batch (its few wavefronts make the
+    # multi-step launches latency-bound), the general ones for one env more, the full single step for the optional output
+    # (one-aircraft envs in whole workgroups get the sector's LDS table from AtcVecEnv: their latency-bound launch is the LDSG one)
+    assert ran[0] == {"%d/allv-one" % N: 120, ("1/ldsg" if N == 1 else "%d/lat" % N): 3}, ran[0]
+    assert ran[1] == {"%d/gen-one" % N: 120, "%d/gen-multi" % N: 3}, ran[1]
+    assert ran[2] == {"%d/full-one" % N: 120}, ran[2]
     for name in ("ac", "alt", "last_act"):
         assert torch.equal(getattr(envs[0], name), getattr(envs[1], name)[:B * N]), name
     assert torch.equal(envs[0].env, envs[1].env[:B]) and torch.equal(envs[0].stats, envs[1].stats[:B])
@@ -656,6 +677,11 @@ def test_latency_bound_instantiation_equals_the_throughput_kernels(N, big):
     W = 1 << max(0, (N - 1).bit_length())
     assert (big * W + 63) // 64 > 2 * 4 * n_cu >= (small * W + 63) // 64, "batch sizes no longer straddle the LAT threshold"
     envs = [AtcVecEnv(small, N, scenario=scn, seed=5), AtcVecEnv(big, N, scenario=scn, seed=5), AtcVecEnv(big + 1, N, scenario=scn, seed=5)]
+    forms = ["lat", "allv-multi", "gen-multi"]
+    if N == 1:   # AtcVecEnv attaches the LDS table to such a batch: its small launch is the LDSG form of LAT; a fourth env flies plain LAT
+        forms[0] = "ldsg"
+        envs.append(AtcVecEnv(small, N, scenario=scn, seed=5, lds_table=False))
+        forms.append("lat")
     g = torch.Generator(device="cpu").manual_seed(N)
     # every 7th aircraft of the shared envs starts at 430 deg and is told to turn on to 720 (a_phi = 3) for the whole run: its heading
     # leaves the 32-bit field in the second step and stays WIDE (ABI 19) — in all three kernel families
@@ -669,10 +695,16 @@ def test_latency_bound_instantiation_equals_the_throughput_kernels(N, big):
         blocks[..., 2] *= torch.where(torch.rand((2, big + 1, N), generator=g) < 0.1, 6.0, 1.0)
         blocks.reshape(2, -1, 3)[:, turner, 2] = 3.0
         blocks = blocks.cuda()
-        outs = [e.rollout(blocks[:, :e.B].contiguous(), hold=10) for e in envs]
+        outs = []
+        for e, form in zip(envs, forms):
+            with H.launches() as got:
+                outs.append(e.rollout(blocks[:, :e.B].contiguous(), hold=10))
+            assert got == {"%d/%s" % (N, form): 1}, (form, got)   # the family this batch is here for, as the library reports it
         for k in ("obs", "reward", "done", "flags"):
             assert torch.equal(outs[0][k], outs[1][k][:, :small]), (k, "latency-bound vs throughput")
             assert torch.equal(outs[1][k], outs[2][k][:, :big]), (k, "throughput vs general")
+            if N == 1:
+                assert torch.equal(outs[0][k], outs[3][k]), (k, "LDS table vs plain latency-bound")
         # (observation word 3 of a turner beyond 436 deg: normalised (phi - 180) / 180 > 1.4223 — only a WIDE heading gets there)
         # (steps that ended an episode return the RAW reset observation instead: masked out)
         o3 = outs[1]["obs"][:, :small].reshape(-1, small, N, 10)[..., 3]

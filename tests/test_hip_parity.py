@@ -718,12 +718,19 @@ def _run_vs_oracle(scen_obj, comp, B, N, steps, seed, dt=1.0, discrete=False, sp
                         out_of_space = np.floor(out_of_space * np.array([20, 380, 360]))
                     act = np.where(rng.uniform(size=(B, N, 3)) < wild, out_of_space, act).astype(np.float32)
             acts.append(act)
-        if use_rollout and rollout_hold > 1:
-            assert all(acts[c] is acts[c - c % rollout_hold] for c in range(chunk))   # blocks are constant by construction
-            out = env.rollout(torch.as_tensor(np.stack(acts[::rollout_hold])), hold=rollout_hold)
-            res = [(out["obs"][c], out["reward"][c], out["done"][c], out["flags"][c]) for c in range(chunk)]
-        elif use_rollout:
-            out = env.rollout(torch.as_tensor(np.stack(acts)))
+        if use_rollout:
+            step = 1
+            if rollout_hold > 1:
+                assert all(acts[c] is acts[c - c % rollout_hold] for c in range(chunk))   # blocks are constant by construction
+                step = rollout_hold
+            # full=True: the launch gets [T, ...] buffers for every optional output — without them AtcVecEnv.rollout asks for the
+            # required four only and the library launches a fast form whatever the env was built with.  (Zeroed: term_obs is written
+            # for envs that were auto-reset only, and the oracle's stays zero elsewhere — so must the launch's.)
+            bufs = None if not full else {k: torch.zeros((chunk,) + shape, dtype=dt, device=env.device) for k, shape, dt in (
+                ("obs", (B, N * 10), torch.float32), ("reward", (B,), torch.float32), ("done", (B,), torch.uint8),
+                ("flags", (B, N), torch.int16), ("raw_obs", (B, N * 10), torch.float32), ("ac_reward", (B, N), torch.float32),
+                ("min_sep", (B,), torch.float32), ("term_obs", (B, N * 10), torch.float32))}
+            out = env.rollout(torch.as_tensor(np.stack(acts[::step])), out=bufs, hold=step)
             res = [(out["obs"][c], out["reward"][c], out["done"][c], out["flags"][c]) for c in range(chunk)]
         else:
             o, r, d, info = env.step(acts[0], held=held_hint and repeated)
@@ -748,26 +755,29 @@ def _run_vs_oracle(scen_obj, comp, B, N, steps, seed, dt=1.0, discrete=False, sp
             assert np.all(np.abs(rr - orc.reward) <= rtol), ("rew", t + c, np.abs(rr - orc.reward).max())
             n_done += int(orc.done.sum())
             seen |= int(np.bitwise_or.reduce(orc.flags.ravel()))
-        if not use_rollout and full:
-            # optional outputs and persistent state
-            # heading arithmetic is exact in both implementations -> relative_angle (raw[9]) must be bit-identical
-            # (checks the division-free Python-modulo of csrc/atc_device.h against the fmodf-based oracle)
-            assert np.array_equal(info["original_state"].cpu().numpy().reshape(B, N, 10)[..., 9], orc.raw_obs[..., 9]), t
-            assert np.array_equal(info["original_state"].cpu().numpy().reshape(B, N, 10)[..., 3], orc.raw_obs[..., 3]), t
-            # raw (un-normalised) values: 1e-5 of each component's normalisation half-range (= 1e-5 in obs units)
-            assert np.all(np.abs(info["original_state"].cpu().numpy().reshape(B, N, 10) - orc.raw_obs)
-                          <= 1e-5 * half_range), t
-            assert np.all(np.abs(info["aircraft_reward"].cpu().numpy() - orc.ac_reward)
-                          <= 1e-5 * np.maximum(1.0, np.abs(orc.ac_reward))), t
-            # positions are bit-identical and d^2 is the same fma on both sides: the minimum separation is too
-            assert np.array_equal(info["min_separation"].cpu().numpy(), orc.min_sep), t
-            dn = orc.done.astype(bool)
-            if dn.any():
-                tob = info["terminal_observation"].cpu().numpy().reshape(B, N, 10)
-                tscale = np.maximum(1.0, np.abs(orc.term_obs[dn]))
-                if not normalize:
-                    tscale = np.maximum(tscale, half_range.astype(np.float32))
-                assert np.all(np.abs(tob[dn] - orc.term_obs[dn]) <= 1e-5 * tscale), t
+            if full:
+                # optional outputs (of the single step, or row c of the multi-step launch's buffers)
+                if use_rollout:
+                    raw, acr, msep, tob = (out[k][c].cpu().numpy() for k in ("raw_obs", "ac_reward", "min_sep", "term_obs"))
+                else:
+                    raw, acr, msep, tob = (info[k].cpu().numpy() for k in ("original_state", "aircraft_reward", "min_separation",
+                                                                           "terminal_observation"))
+                raw, tob = raw.reshape(B, N, 10), tob.reshape(B, N, 10)
+                # heading arithmetic is exact in both implementations -> relative_angle (raw[9]) must be bit-identical
+                # (checks the division-free Python-modulo of csrc/atc_device.h against the fmodf-based oracle)
+                assert np.array_equal(raw[..., 9], orc.raw_obs[..., 9]), t + c
+                assert np.array_equal(raw[..., 3], orc.raw_obs[..., 3]), t + c
+                # raw (un-normalised) values: 1e-5 of each component's normalisation half-range (= 1e-5 in obs units)
+                assert np.all(np.abs(raw - orc.raw_obs) <= 1e-5 * half_range), t + c
+                assert np.all(np.abs(acr - orc.ac_reward) <= 1e-5 * np.maximum(1.0, np.abs(orc.ac_reward))), t + c
+                # positions are bit-identical and d^2 is the same fma on both sides: the minimum separation is too
+                assert np.array_equal(msep, orc.min_sep), t + c
+                dn = orc.done.astype(bool)
+                if dn.any():
+                    tscale = np.maximum(1.0, np.abs(orc.term_obs[dn]))
+                    if not normalize:
+                        tscale = np.maximum(tscale, half_range.astype(np.float32))
+                    assert np.all(np.abs(tob[dn] - orc.term_obs[dn]) <= 1e-5 * tscale), t + c
         t += chunk
     # persistent state after the run: integer state exact, float state within tolerance
     assert np.array_equal(env.timesteps.cpu().numpy(), orc.timesteps)
@@ -1161,12 +1171,18 @@ def test_full_size_rollout_hold(B, N):
     g = torch.Generator(device="cpu").manual_seed(7 * B + N)
     blocks = [(torch.rand((1, B, N, 3), generator=g) * 2 - 1).cuda() for _ in range(launches)]
 
+    n_cu = torch.cuda.get_device_properties(0).multi_processor_count
+
     def run(nb):
         env = AtcVecEnv(nb, N, scenario=scn, auto_reset=True, seed=3)
         outs = []
-        for j in range(launches):
-            o = env.rollout(blocks[j][:, :nb].contiguous(), hold=T)
-            outs.append({k: v.clone() for k, v in o.items()})
+        with H.launches() as got:
+            for j in range(launches):
+                o = env.rollout(blocks[j][:, :nb].contiguous(), hold=T)
+                outs.append({k: v.clone() for k, v in o.items()})
+        # the form the dispatch rule of csrc/atc_step.hip gives this batch on this device, as the library's launch record names it
+        form = "allv-multi" if nb * N > 512 * n_cu else "ldsg" if N == 1 and nb <= 256 * n_cu else "lat"
+        assert got == {"%d/%s" % (N, form): launches}, (nb, got)
         state = (env.ac.clone(), env.alt.clone(), env.last_act.clone(), env.env.clone())
         env.close()
         return outs, state

@@ -216,9 +216,13 @@ def test_rollouts_identical_with_and_without_the_table(B, scen, dt):
         env = AtcVecEnv(B, 1, sim_parameters=model.SimParameters(dt), scenario=scn, auto_reset=True, seed=5, lds_table=lds)
         assert env.sector.has_lds_table == lds
         outs = []
-        for blk in blocks:
-            o = env.rollout(blk.cuda(), hold=T // 2)
-            outs.append({k: v.clone() for k, v in o.items()})
+        with H.launches() as got:
+            for blk in blocks:
+                o = env.rollout(blk.cuda(), hold=T // 2)
+                outs.append({k: v.clone() for k, v in o.items()})
+        # the library's own record of what it launched: the table on -> the LDSG instantiation, off -> the plain latency-bound one
+        assert B <= 256 * torch.cuda.get_device_properties(0).multi_processor_count
+        assert got == {"1/ldsg" if lds else "1/lat": launches}, (lds, got)
         state = (env.ac.clone(), env.alt.clone(), env.last_act.clone(), env.env.clone(), env.stats.clone())
         env.close()
         return outs, state
@@ -271,7 +275,9 @@ def test_table_rollouts_on_random_sectors_against_the_oracle(seed, n_poly, dt):
     for j in range(10):
         blocks = torch.rand((T // hold, B, 1, 3), generator=g) * 2 - 1
         blocks[:, ::2, :, 1] = -0.95      # half of the envs descend into the floors
-        out = env.rollout(blocks, hold=hold)
+        with H.launches() as got:
+            out = env.rollout(blocks, hold=hold)
+        assert got == {"1/ldsg": 1}, got
         for t in range(T):
             orc.step(blocks[t // hold].numpy())
             fl = out["flags"][t].cpu().numpy().astype(np.uint16).reshape(B, 1)
@@ -287,3 +293,62 @@ def test_table_rollouts_on_random_sectors_against_the_oracle(seed, n_poly, dt):
     assert np.array_equal(env.alt.cpu().numpy(), np.asarray(orc.h, dtype=np.float64).ravel())
     assert np.array_equal(env.actions_taken.cpu().numpy(), orc.actions_taken)
     env.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("k", [1, 3])
+def test_default_env_reaches_the_lds_instantiation(k):
+    """A default AtcVecEnv of 256 k one-aircraft envs on LOWW attaches the table by itself and its rollout runs k_step<1, ..., LDSG>,
+    as the library's launch record says: a table dropped on the way (attach refused, dispatch rule moved) is seen here."""
+    import torch
+    from atc_hip.vec_env import AtcVecEnv
+    env = AtcVecEnv(256 * k, 1, scenario=H.make_scenario("LOWW"), auto_reset=True, seed=1)
+    assert env.sector.has_lds_table
+    with H.launches() as got:
+        env.rollout(torch.zeros((2, 256 * k, 1, 3)), hold=5)
+        env.rollout(torch.zeros((4, 256 * k, 1, 3)))
+    assert got == {"1/ldsg": 2}, got
+    with H.launches() as got:
+        env.step(torch.zeros((256 * k, 1, 3)))
+    assert got == {"1/allv-one": 1}, got
+    env.close()
+
+
+@pytest.mark.gpu
+def test_attach_is_quiet_only_where_the_table_does_not_apply():
+    """Scenario.attach_lds_table returns False without a word for the documented cases — no lookup grid, noise-abatement areas, a
+    table beyond the device's LDS — and raises with the library's message for any other refusal."""
+    from atc_hip import lib
+    from envs.atc import scenarios
+    no_grid = lib.Scenario(H.compiled("LOWW"), lds_table=True)
+    assert not no_grid.has_lds_table and no_grid.attach_lds_table() is False
+    no_grid.close()
+    dense = scenarios.LOWWDense()
+    assert dense.noise_areas
+    noise = lib.Scenario(scenarios.compile_scenario(dense, grid_cell=0.5), lds_table=True)
+    assert not noise.has_lds_table
+    noise.close()
+    comp = scenarios.compile_scenario(H.make_scenario("LOWW"), grid_cell=0.5)
+    good = np.array(comp.lds_table(), copy=True)
+    sc = lib.Scenario(comp)
+    try:
+        # a well-formed table whose LDS part (padded with unused bytes in front of the record pool) exceeds any LDS: quiet False
+        hdr = good[:4 * L.LDS_HDR_WORDS].view(np.uint32)
+        lds_part, off_pool, grown = int(hdr[L.LDS_H_LDS_BYTES]), int(hdr[L.LDS_H_OFF_POOL]), 1 << 20
+        big = np.concatenate([good[:lds_part], np.zeros(grown - lds_part, np.uint8), good[off_pool:]])
+        bh = big[:4 * L.LDS_HDR_WORDS].view(np.uint32)
+        bh[L.LDS_H_LDS_BYTES], bh[L.LDS_H_OFF_POOL], bh[L.LDS_H_BYTES] = grown, grown, len(big)
+        comp.__dict__["_lds_table"] = big
+        assert sc.attach_lds_table() is False and not sc.has_lds_table
+        assert lib.LDS_TOO_LARGE in lib.load().atc_last_error().decode()
+        bad = good.copy()
+        bad[:4 * L.LDS_HDR_WORDS].view(np.uint32)[L.LDS_H_MAGIC] ^= 1
+        comp.__dict__["_lds_table"] = bad
+        with pytest.raises(RuntimeError, match="not an LDS lookup table"):
+            sc.attach_lds_table()
+        assert not sc.has_lds_table
+        comp.__dict__["_lds_table"] = good
+        assert sc.attach_lds_table() is True and sc.has_lds_table
+    finally:
+        comp.__dict__["_lds_table"] = good
+        sc.close()
