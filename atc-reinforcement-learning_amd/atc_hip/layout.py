@@ -68,3 +68,5 @@ LDS_CLEAN, LDS_LINE, LDS_SUB, LDS_RESID = 0, 1, 2, 3
 LF_FULL_ONE, LF_FULL_MULTI, LF_GEN_ONE, LF_ALLV_ONE, LF_GEN_MULTI, LF_ALLV_MULTI, LF_LAT, LF_LDSG, LF_FORMS = range(9)
 LAUNCH_SERVE, LAUNCH_SLOTS = 56, 57
 LF_NAMES = ("full-one", "full-multi", "gen-one", "allv-one", "gen-multi", "allv-multi", "lat", "ldsg")
+# frame skip (include/atc_step.h: atc_step_skip): largest block length; its own launch record, slot = log2(W)
+SKIP_MAX, SKIP_LAUNCH_SLOTS = 255, 7

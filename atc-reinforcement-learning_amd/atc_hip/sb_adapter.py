@@ -34,7 +34,10 @@ _Base = _vecenv_base()
 
 class AtcSBVecEnv(_Base):
     def __init__(self, num_envs, num_aircraft=1, sim_parameters=None, scenario=None, device=0, seed=0, sparse_infos=None,
-                 host_mapped=None, **kw):
+                 host_mapped=None, frame_skip=1, **kw):
+        """frame_skip > 1: every step() holds its actions for up to `frame_skip` env steps (AtcVecEnv.step_skip: one launch; an env
+        stops at its first done) and returns one transition per env — the summed reward, the last observation; infos carry
+        "frame_steps", the env steps the transition covers.  Monitor's episode["l"] keeps counting ENV steps.  1: a plain step."""
         try:   # gym's own space classes where gym is there (stable-baselines' policies type-check them; gym is its dependency)
             from gym.spaces import Box, MultiDiscrete
         except ImportError:
@@ -44,6 +47,9 @@ class AtcSBVecEnv(_Base):
         # in place — no device-to-host copy.  Large batches stay in HBM and cross PCIe once per step.
         if host_mapped is None:
             host_mapped = int(num_envs) * int(num_aircraft) <= 256
+        self.frame_skip = int(frame_skip)
+        if not 1 <= self.frame_skip <= L.SKIP_MAX:   # (before anything is built on the device)
+            raise ValueError("1 <= frame_skip <= %d" % L.SKIP_MAX)
         self.vec = AtcVecEnv(num_envs, num_aircraft, sim_parameters=sim_parameters, scenario=scenario, device=device,
                              auto_reset=True, seed=seed, want_raw_obs=True, want_term_obs=True, host_mapped=host_mapped,
                              **kw)
@@ -87,7 +93,8 @@ class AtcSBVecEnv(_Base):
 
     def step_wait(self):
         vec = self.vec
-        obs, rew, done, info = vec.step(self._actions)
+        skip = self.frame_skip > 1
+        obs, rew, done, info = vec.step_skip(self._actions, self.frame_skip) if skip else vec.step(self._actions)
         torch = vec.torch
         d = vec.obs_dim
         if vec.host_mapped:   # results are host memory already (the step ended with a stream synchronisation)
@@ -96,13 +103,16 @@ class AtcSBVecEnv(_Base):
             rew_h, done_h = rew.numpy().copy(), done.numpy() != 0
             # (host_mapped="io" keeps the state and the episode records in HBM: those two come over with a copy)
             ep_r, ep_l = vec.ep_return.cpu().numpy().copy(), vec.ep_length.cpu().numpy().copy()
+            n_h = info["frame_steps"].numpy().copy() if skip else None
         else:
             pack = torch.cat([obs, info["original_state"], info["terminal_observation"],
                               rew[:, None], done[:, None].to(torch.float32), vec.ep_return[:, None],
-                              vec.ep_length[:, None].to(torch.float32)], dim=1).cpu().numpy()   # one device->host hop
+                              vec.ep_length[:, None].to(torch.float32)] +
+                             ([info["frame_steps"][:, None].to(torch.float32)] if skip else []), dim=1).cpu().numpy()   # one device->host hop
             obs_h, raw_h, term_h = pack[:, :d], pack[:, d:2 * d], pack[:, 2 * d:3 * d]
             rew_h, done_h = pack[:, 3 * d], pack[:, 3 * d + 1] != 0
             ep_r, ep_l = pack[:, 3 * d + 2], pack[:, 3 * d + 3]
+            n_h = pack[:, 3 * d + 4] if skip else None
         now = round(time.time() - self._t0, 6)
         self.original_state = raw_h
         if self.sparse_infos:
@@ -110,10 +120,14 @@ class AtcSBVecEnv(_Base):
             for b in np.nonzero(done_h)[0]:
                 infos[b] = {"original_state": raw_h[b], "terminal_observation": term_h[b],
                             "episode": {"r": float(ep_r[b]), "l": int(ep_l[b]), "t": now}}
+                if skip:
+                    infos[b]["frame_steps"] = int(n_h[b])
         else:
             infos = []
             for b in range(self.num_envs):
                 item = {"original_state": raw_h[b]}
+                if skip:
+                    item["frame_steps"] = int(n_h[b])
                 if done_h[b]:
                     item["terminal_observation"] = term_h[b]
                     item["episode"] = {"r": float(ep_r[b]), "l": int(ep_l[b]), "t": now}

@@ -105,6 +105,8 @@ class AtcVecEnv:
         # host_mapped="io": only what crosses the host link every step (actions in, results out) lives in mapped host memory;
         # the state stays in HBM, so the kernel's state loads and stores do not pay the link's round trip
         zs = (lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)) if host_mapped == "io" else z  # noqa: E731
+        self._new_output = z
+        self.frame_steps = None   # [B] uint8: steps each env took in the last step_skip (allocated by the first one)
         f32, i32 = torch.float32, torch.int32
         # persistent state (atc_state_t): packed records, see include/atc_step.h
         self.ac = zs((BN, L.AC_WORDS), i32)    # x, y (position-grid counts), phi (heading counts), v (speed counts, unsigned)
@@ -195,6 +197,7 @@ class AtcVecEnv:
         self._params_held_ref = C.byref(self._params_held)
         self._n_act = self.B * self.N * L.ACT_DIM
         self._info_cache = self._info()
+        self._info_skip = None
 
     def _finish(self):
         if self.host_mapped:  # results live in host memory: valid only once the stream has drained
@@ -293,6 +296,41 @@ class AtcVecEnv:
         self._keep = a
         self._finish()
         return self.obs, self.reward, self.done, self._info_cache
+
+    def step_skip(self, actions, skip):
+        """Frame skip (atc_step_skip; the reference's demo loop, learning/atc-gym-demo.py:14-22): every env repeats `actions` until
+        it reports done or has taken `skip` steps (1 .. 255) — ONE launch, one transition per env.  Returns (obs, reward, done,
+        info) in this env's own output tensors like step(): the observation after the env's last executed step, the float32 sum
+        of the executed steps' rewards (in step order), done if the episode ended inside the block; info["flags"] is the OR of the
+        executed steps' flag words, info["frame_steps"] the [B] uint8 tensor of executed steps.  An env that ends early is not
+        stepped again in the call (with auto_reset it waits in its fresh spawn state), so a transition never spans two episodes.
+        Bit for bit what a host loop over step() computes; step_skip(a, 1) is step(a)."""
+        torch = self.torch
+        skip = int(skip)
+        if not 1 <= skip <= L.SKIP_MAX:
+            raise ValueError("1 <= skip <= %d" % L.SKIP_MAX)
+        if self.frame_steps is None:
+            self.frame_steps = self._new_output(self.B, torch.uint8)
+            self._frame_steps_ptr = self._ptr(self.frame_steps)
+        if self._info_skip is None:
+            self._info_skip = dict(self._info_cache, frame_steps=self.frame_steps)
+        self._prev_actions = None   # (check_held: the block's last step is not a step() call to repeat)
+        if (torch.is_tensor(actions) and actions.is_cuda and actions.dtype is torch.float32 and actions.is_contiguous()
+                and actions.numel() == self._n_act and actions.device == self.device
+                and torch.cuda.current_device() == self.device.index and not self.host_mapped):
+            rc = self._lib.atc_step_skip(self.sector.handle, self.B, self.N, skip, self._state_ref, actions.data_ptr(), self._out_ref,
+                                         self._frame_steps_ptr, self._params_ref, torch.cuda.current_stream().cuda_stream)
+            if rc:
+                _lib.check(rc)
+            self._keep = actions
+            return self.obs, self.reward, self.done, self._info_skip
+        a = self._as_actions(actions)
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.atc_step_skip(self.sector.handle, self.B, self.N, skip, C.byref(self._state), self._ptr(a),
+                                               C.byref(self._out), self._frame_steps_ptr, C.byref(self.params), self._stream()))
+        self._keep = a
+        self._finish()
+        return self.obs, self.reward, self.done, self._info_skip
 
     def make_launcher(self, actions, stream=None, held=False):
         """Pre-bound `atc_step` call for FIXED buffers (this env's state / outputs, the given device action tensor, the

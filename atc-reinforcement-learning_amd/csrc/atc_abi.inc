@@ -11,6 +11,11 @@ int atc_launch_counts(uint64_t* out, int n) {
     for (int i = 0; i < n && i < ATC_LAUNCH_SLOTS; ++i) out[i] = t_launches[i];
     return ATC_OK;
 }
+int atc_skip_launch_counts(uint64_t* out, int n) {
+    if (!out || n < 0) return fail_arg("null pointer");
+    for (int i = 0; i < n && i < ATC_SKIP_LAUNCH_SLOTS; ++i) out[i] = t_skip_launches[i];
+    return ATC_OK;
+}
 const char* atc_last_error(void) { return g_err; }
 
 int atc_host_mapped_ptr(const void* host, void** dev) {
@@ -380,6 +385,11 @@ int atc_rollout(const atc_scenario_t* s, int B, int N, int T, const atc_state_t*
 int atc_rollout_hold(const atc_scenario_t* s, int B, int N, int T, int hold, const atc_state_t* st, const float* actions,
                      const atc_out_t* out, const atc_params_t* p, void* stream) {
     return step_common(s, B, N, T, hold, st, actions, out, p, stream);
+}
+
+int atc_step_skip(const atc_scenario_t* s, int B, int N, int K, const atc_state_t* st, const float* actions, const atc_out_t* out,
+                  uint8_t* n_steps, const atc_params_t* p, void* stream) {
+    return skip_common(s, B, N, K, st, actions, out, n_steps, p, stream);
 }
 
 }  // extern "C"

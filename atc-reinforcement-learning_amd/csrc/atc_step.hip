@@ -739,6 +739,42 @@ __device__ __forceinline__ uint32_t noise_areas(const float* __restrict__ K, con
     return bits;
 }
 
+// The observation store of step_part_b (see there: a full wavefront transposes its 64 x 10 block through LDS and writes 16-byte
+// pieces, other lanes store their own row) as a function, for the frame-skip kernel's one store per block.  step_part_b keeps its
+// inline copy — calling this from there changed the generated code of two existing kernels —, so the two must be kept in step
+// by hand until the existing kernels' machine code is next allowed to move and they can be merged.
+__device__ __forceinline__ void store_obs_rows(float* obs, const LaneIds& d, const float* o, float* obs_stage) {
+    if (ATC_USUAL(d.wave_full)) {
+        // addresses from threadIdx itself, not from the lane ids a multi-step launch re-derives through an opaque zero: the
+        // compiler then knows the ranges (lane < 64: two of the three row tests fold away, 24-bit multiplies suffice) — with
+        // the opaque copies it emitted a quarter-rate 64-bit multiply-add per LDS read
+        const uint32_t ln = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+        float* tb = obs_stage + __umul24(wv, 64u * ATC_OBS_DIM);
+        float2* tb2 = reinterpret_cast<float2*>(tb) + __umul24(ln, ATC_OBS_DIM / 2);   // rows are 40 B: 8-byte aligned
+#pragma unroll
+        for (int c = 0; c < ATC_OBS_DIM / 2; ++c) tb2[c] = make_float2(o[2 * c], o[2 * c + 1]);
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        // first aircraft of this wavefront (N == W): wave-uniform, so the multiply runs on the scalar unit
+        const uint32_t wave_off = (d.slot0 + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x & ~63u))) * 40u;
+        const float4* src = reinterpret_cast<const float4*>(tb);
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            const uint32_t idx = (uint32_t)j * 64u + ln;
+            if (idx < 64u * ATC_OBS_DIM / 4u) {
+                const float4 v = src[idx];
+                float* d4 = at<float>(obs, wave_off + idx * 16u);
+                typedef float v4f __attribute__((ext_vector_type(4)));
+                __builtin_nontemporal_store(v4f{v.x, v.y, v.z, v.w}, reinterpret_cast<v4f*>(d4));
+            }
+        }
+        __builtin_amdgcn_wave_barrier();
+    } else if (d.lane_valid) {
+        store_obs(at<float>(obs, times40(d.i)), o);
+    }
+}
+
 // ---- second half: separation scan, win/timeout, observation, shaping, reductions, outputs, auto-reset --------------
 // A by-value kernel argument group where it is needed: the single-step kernel names the argument (the compiler places its
 // kernarg load), a multi-step launch re-reads it from the kernarg segment through this step's opaque zero — a scalar load
@@ -757,13 +793,25 @@ constexpr int scan_horizon() {
 }
 constexpr float kScanHMax = 131072.0f;   // |altitude| below which an altitude step rounds by less than 2^-7 ft (scan_horizon_limits)
 
-template <int W, bool FULL, bool ONE, bool LAT, bool LDSG = false>
+// SKIP — the step as the frame-skip kernel (k_skip) runs it: the same arithmetic, state update and auto-reset, but what atc_step
+// stores every step (observation, raw observation, flag word, rewards, done, minimum separation) is handed back in registers —
+// that kernel accumulates over the block and stores once.  Only the terminal observation is still written here, by the step that
+// ends the episode, exactly as atc_step writes it.  FULL means what it means for k_step: an optional output is requested.
+struct StepVals {
+    float o[ATC_OBS_DIM];      // the observation of this step as atc_step stores it (the raw reset observation on the auto-reset path)
+    float zraw[ATC_OBS_DIM];   // FULL: the raw observation (where so.raw_obs is set; zeros otherwise)
+    float r, env_r;            // the aircraft's and the env's reward
+    float min_d2;              // the env's minimum squared distance (FULL), 1e30 without a pair
+    uint32_t fl;
+    bool done;
+};
+template <int W, bool FULL, bool ONE, bool LAT, bool LDSG = false, bool SKIP = false>
 __device__ __forceinline__ bool step_part_b(const float* __restrict__ K, const float* __restrict__ grid,
                                             const atc_params_t& p, const StepDerived& q, const QScan& qs, int zk, int N,
                                             const LaneIds& d, const Mid& m, LaneState& ls,
                                             EnvState& es, const StepOut& so, int32_t* stp, double* wide_named, float4* pos, float* obs_stage,
                                             const float* act_next, Float3& a_next, QRates& qr_next, int& scan_skip, uint32_t& scan_mask,
-                                            const char* ltab = nullptr, const LdsTab* lt = nullptr) {
+                                            const char* ltab = nullptr, const LdsTab* lt = nullptr, StepVals* sv = nullptr) {
     Aircraft& a = ls.a;
     const bool active = m.active;
     const float x32 = m.x32, y32 = m.y32;
@@ -805,7 +853,7 @@ __device__ __forceinline__ bool step_part_b(const float* __restrict__ K, const f
     // and notes which partner batches hold a pair inside them (`flagged`); for the next kHorizon steps (scan_skip > 0) only those
     // batches can hold a pair that lost its separation — they alone are scanned, with the exact minima, and nothing at all when
     // none was flagged.
-    constexpr int kHorizon = scan_horizon<W, FULL, ONE>();
+    constexpr int kHorizon = SKIP ? 0 : scan_horizon<W, FULL, ONE>();   // (the frame-skip kernel scans in full every step)
     constexpr bool kHZ = kHorizon > 0;
     const ScanLimits lim = {qs.sep2, qs.sep_ft, kHZ ? qs.sep2_h : qs.sep2, kHZ ? qs.sep_ft_h : qs.sep_ft};
     const bool in_horizon = kHZ && scan_skip > 0;             // wave-uniform
@@ -1050,10 +1098,14 @@ __device__ __forceinline__ bool step_part_b(const float* __restrict__ K, const f
                 if ((fl >> (16 + q)) & 1u) r -= (K + (int)K[ATC_H_OFF_POLY] + ((int)K[ATC_H_N_MVA] + q) * ATC_P_WORDS)[ATC_P_PENALTY];
             fl &= 0xffffu;
         }
-        if (FULL) {
+        if (FULL && !SKIP) {
 #pragma unroll
             for (int c = 0; c < ATC_OBS_DIM; ++c) zraw[c] = active ? ob.o[c] : 0.0f;  // zeros for handed-over aircraft
             if (so.raw_obs && d.lane_valid) store_obs(at<float>(so.raw_obs, times40(i)), zraw);
+        }
+        if (FULL && SKIP) {
+#pragma unroll
+            for (int c = 0; c < ATC_OBS_DIM; ++c) zraw[c] = (so.raw_obs && active) ? ob.o[c] : 0.0f;
         }
         // atc_gym.py:187-189: (s - min - max/2) / (max/2) as one fma; the identity (1, -0) without ATC_M_NORMALIZE (derive())
 #pragma unroll
@@ -1106,7 +1158,8 @@ __device__ __forceinline__ bool step_part_b(const float* __restrict__ K, const f
         for (int c = 0; c < ATC_PKT_CHUNKS; ++c)
             store16_system(pk + c, __float_as_uint(w[3 * c]), __float_as_uint(w[3 * c + 1]), __float_as_uint(w[3 * c + 2]), tag);
     }
-    if (FULL && so.min_sep) {
+    if (SKIP) sv->min_d2 = (FULL && W > 1) ? group_min<W>(min_d2) : 1e30f;
+    if (FULL && !SKIP && so.min_sep) {
         const float m2 = (W > 1) ? group_min<W>(min_d2) : 1e30f;
         if (d.env_valid && k == 0) *at<float>(so.min_sep, (uint32_t)e * 4u) = (m2 >= 1e30f) ? 1e30f : sqrtf(m2);
     }
@@ -1156,9 +1209,19 @@ __device__ __forceinline__ bool step_part_b(const float* __restrict__ K, const f
     // decode at the top of EVERY step waits for every earlier vector-memory operation — one counter, in order — i.e. for the
     // previous step's observation stores to complete.  By now the load has long arrived.
     if (ATC_RARE(act_next != nullptr)) asm volatile("" : "+v"(a_next.a), "+v"(a_next.b), "+v"(a_next.c));
+    if (SKIP) {   // nothing is stored per step: the values go back to k_skip
+#pragma unroll
+        for (int c = 0; c < ATC_OBS_DIM; ++c) { sv->o[c] = o[c]; sv->zraw[c] = FULL ? zraw[c] : 0.0f; }
+        sv->r = r;
+        sv->env_r = env_r;
+        sv->fl = fl;
+        sv->done = done;
+        return quiet;
+    }
     // ---- observation store: [aircraft][10] rows are 40 B apart, so per-lane stores would scatter 8-byte pieces over 20
     //      cache lines per instruction; a full wavefront instead transposes its 64 x 10 block through LDS and writes 2 560
     //      contiguous bytes as 16-byte stores.
+    //      (store_obs_rows above is a second copy of this block, for k_skip: a change here belongs there too)
     if (ATC_USUAL(d.wave_full)) {
         // addresses from threadIdx itself, not from the lane ids a multi-step launch re-derives through an opaque zero: the
         // compiler then knows the ranges (lane < 64: two of the three row tests fold away, 24-bit multiplies suffice) — with
@@ -1445,6 +1508,161 @@ k_step(const float* __restrict__ blob, int off_grid, int B, int N, int T, int ho
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+// Frame skip (include/atc_step.h: atc_step_skip): up to K steps with ONE held action block in one launch, ONE set of outputs.
+// Per env: step until the step reports done or K steps are taken; outputs = the last executed step's observation, the float32 sums
+// of the executed steps' rewards in step order, the OR of their flag words, the minimum of their separations, done, n.
+//   State is loaded once and kept in registers like in the multi-step k_step; every step runs step_part_a / step_part_b<SKIP> — the
+//   arithmetic of atc_step with the per-step stores taken out — and four accumulators are carried across the loop.  An env STORES
+//   its outputs and its state at the end of its last executed step (`fin`), inside the loop: a wavefront whose envs all run K steps
+//   — almost every one — stores once, behind the last step, with the observation on the transposed 16-byte path; a wavefront in
+//   which an env ends early stores that env's rows then and the others' later.  Nothing of the kept observation lives across a step.
+//   A STOPPED env has no further effect, because from the step after its last
+//     * its lanes run with env_valid = lane_valid = false in that step's LaneIds: `done` is `d.env_valid && ...`, so no second
+//       reset and no write of the per-episode record; the side records of WIDE headings and the terminal observation are
+//       written under lane_valid only;
+//     * its bit in `live` is cleared, and outputs and state are stored under `fin`, a subset of `live`: what its lanes go on
+//       computing on their stale registers is never stored, added to anything that is, or read by another env (group reductions
+//       and the separation scan stay inside the W lanes of an env; wave-uniform shortcuts — plain, quiet, all_active — only choose
+//       between forms that evaluate the same expressions per lane).
+//   The loop ends when no env of the wavefront is live.  Steps after the first repeat the block's actions on envs that were not
+//   reset in between (a reset env is stopped): `repeated`, the structural form of ATC_M_ACTIONS_HELD.
+//   The argument list is k_step's up to `q` (StepArgs): step_part_a / step_part_b re-read state pointers and derived constants from
+//   the kernarg segment by those offsets.  The separation-scan horizon is left off (full scan in every step).
+//   FULL: an optional output (raw_obs, ac_reward, min_sep, term_obs) is requested — as in k_step the fast form compiles them out
+//   (no raw observation in registers, the conflict-only scan); which of them is present is a run-time null test in the full form.
+//   Registers, launch bound: DESIGN.md, frame skip.
+// ---------------------------------------------------------------------------------------------------------------
+struct SkipArgs {
+    const float* blob;
+    int off_grid, B, N, K, pad;
+    atc_state_t st;
+    const float* actions;
+    atc_out_t out;
+    atc_params_t p;
+    StepDerived q;
+    uint8_t* n_steps;
+};
+static_assert(offsetof(SkipArgs, st) == offsetof(StepArgs, st) && offsetof(SkipArgs, q) == offsetof(StepArgs, q),
+              "k_skip's kernel arguments must lie where k_step's do: the step re-reads them by StepArgs offsets");
+// wavefronts per SIMD k_skip is register-budgeted for (<= 96 VGPRs).  Measured against 4 (no spills, slower) and against 6 for the
+// fast form of 16-aircraft envs (k_step's rule for its loop forms: no faster here): DESIGN.md, frame skip.  -DATC_SKIP_WAVES=n: A/B builds.
+#ifndef ATC_SKIP_WAVES
+#define ATC_SKIP_WAVES 5
+#endif
+template <int W, bool FULL>
+__global__ void __launch_bounds__(kBlock, ATC_SKIP_WAVES)
+k_skip(const float* __restrict__ blob, int off_grid, int B, int N, int K_steps, int pad, atc_state_t st,
+       const float* __restrict__ actions, atc_out_t out, atc_params_t p, StepDerived q, uint8_t* n_steps) {
+    constexpr bool ONE = false, LAT = false;   // (QGET: the multi-step form — kernarg re-reads inside the step)
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    float4* pos = reinterpret_cast<float4*>(smem);                    // [2 kBlock] pair-scan staging (W >= 32)
+    float* obs_stage = smem + (W >= 32 ? 2 * kBlock * 4 : 0);  // [4 waves][64 x 10] obs transpose
+    const float* __restrict__ K = blob;
+    const float* __restrict__ grid = off_grid ? blob + off_grid : nullptr;
+    const LaneIds d = make_ids<W, false>(blockIdx.x * kBlock, B, N);
+
+    const int4 e0 = *at<int4>(st.env, (uint32_t)d.e * (ATC_ENV_WORDS * 4u));
+    const uint32_t hi0 = (W == 64) ? *at<uint32_t>(st.stats, (uint32_t)d.e * (ATC_STAT_WORDS * 4u) + ATC_STAT_MASK_HI * 4u) : 0u;
+    EnvState es = {e0.x, e0.y, __int_as_float(e0.z), (uint64_t)(uint32_t)e0.w | ((uint64_t)hi0 << 32)};
+    const int4 ps = *at<int4>(st.ac, d.i * 16u);
+    const double h0 = *at<double>(st.alt, d.i * 8u);
+    const Float3 act = *at<Float3>(actions, times12(d.i));   // the block's action: one 12-byte load per lane
+    const int4 la0 = *at<int4>(st.last_act, d.i * 16u);      // (the block's first step carries a fresh decision: the record is live)
+    LaneState ls = {{ps.x, ps.y, h0, ps.z, (uint32_t)ps.w}, (uint32_t)la0.x, __hiloint2double(la0.w, la0.z), la0.y, false};
+
+    Targets tg = {0u, 0.0f, 0};
+    uint64_t refused_blk = 0ull;
+    bool refused_known = false;
+    bool all_active = false, mask_dirty = true;
+    QRates qr_next;
+    {
+        int zn;
+        asm volatile("s_mov_b32 %0, 0" : "=s"(zn));
+        qr_next = kernarg_reread<QRates>(offsetof(StepArgs, q) + offsetof(StepDerived, r), zn);
+    }
+    {   // the state loads are waited for before the loop (see k_step)
+        asm volatile("" : "+v"(ls.a.x), "+v"(ls.a.y), "+v"(ls.a.h), "+v"(ls.a.phi), "+v"(ls.a.v));
+        asm volatile("" : "+v"(ls.la_v), "+v"(ls.la_h), "+v"(ls.la_p), "+v"(es.t), "+v"(es.n_actions), "+v"(es.total_reward));
+        uint32_t m_lo = (uint32_t)es.amask, m_hi = (uint32_t)(es.amask >> 32);
+        asm volatile("" : "+v"(m_lo), "+v"(m_hi));
+        es.amask = (uint64_t)m_lo | ((uint64_t)m_hi << 32);
+    }
+    // accumulated over the executed steps, in step order: plain float32 additions (the library is built with -ffp-contract=off)
+    float sum_r = 0.0f, sum_env = 0.0f, min_d2 = 1e30f;
+    uint32_t or_fl = 0u;
+    uint64_t live = __builtin_amdgcn_ballot_w64(d.env_valid);   // lanes of envs that have not taken their last step (uniform per env)
+    for (int step = 0; live != 0ull; ++step) {
+        LaneIds dl = d;
+        const bool lane_live = ((live >> d.lane) & 1ull) != 0ull;
+        dl.env_valid = lane_live;
+        dl.lane_valid = d.lane_valid && lane_live;
+        atc_params_t pl = p;
+        int zk;   // this step's opaque zero (see k_step)
+        asm volatile("s_mov_b32 %0, 0" : "=s"(zk));
+        pl.mode += (uint32_t)zk;
+        const atc_out_t outl = out;
+        const StepOut so = {outl.obs, outl.flags, outl.reward, outl.done, FULL ? outl.raw_obs : nullptr, FULL ? outl.ac_reward : nullptr,
+                            FULL ? outl.min_sep : nullptr, FULL ? outl.term_obs : nullptr, nullptr
+#if ATC_TRACE
+                            , nullptr
+#endif
+        };
+        const QRates qr = qr_next;
+        const QScan qs = QGET(s);
+        if (ATC_RARE(step == 0)) tg = decode_targets(qr, act);
+        const bool repeated = step != 0;
+        if (ATC_RARE(mask_dirty)) {
+            all_active = (__builtin_amdgcn_ballot_w64(!(dl.lane_valid && ((dl.k < 32 ? ((uint32_t)es.amask >> dl.k) : ((uint32_t)(es.amask >> 32) >> (dl.k - 32))) & 1u))) |
+                          __builtin_amdgcn_ballot_w64(max(ls.a.phi, ls.la_p) == INT32_MAX) | __builtin_amdgcn_ballot_w64(min(ls.a.phi, ls.la_p) == INT32_MIN)) == 0ull;
+            mask_dirty = false;
+        }
+        const Mid m = step_part_a<false, false>(grid, qr, QGET(k), QGET(g), dl, tg.v, altitude_target(qr, tg.ah), tg.p, act.c, ls, es, repeated, all_active,
+                                                st.phi_wide, zk, refused_blk, refused_known ATC_TRACE_PASS(nullptr));
+        refused_known = true;
+        StepVals sv;
+        Float3 nxt = act;
+        int scan_skip = 0;
+        uint32_t scan_mask = 0u;
+        const bool quiet = step_part_b<W, FULL, false, false, false, true>(K, grid, pl, q, qs, zk, N, dl, m, ls, es, so, st.stats, st.phi_wide, pos, obs_stage,
+                                                                            nullptr, nxt, qr_next, scan_skip, scan_mask, nullptr, nullptr, &sv);
+        if (ATC_RARE(!quiet)) mask_dirty = true;
+        // acc = r1; acc = acc + r2; ...  (the first step assigns: 0 + r would turn a -0 into +0)
+        sum_r = repeated ? sum_r + sv.r : sv.r;
+        sum_env = repeated ? sum_env + sv.env_r : sv.env_r;
+        or_fl |= sv.fl;
+        if (FULL) min_d2 = fminf(min_d2, sv.min_d2);   // (sqrt is monotonic: the minimum of the roots is the root of the minimum)
+        // envs that have just taken their last step: done, or the block's K-th
+        const uint64_t fin = (step + 1 >= K_steps) ? live : (live & __builtin_amdgcn_ballot_w64(sv.done));
+        if (fin != 0ull) {
+            LaneIds df = d;
+            const bool mine = ((fin >> d.lane) & 1ull) != 0ull;
+            df.env_valid = mine;
+            df.lane_valid = d.lane_valid && mine;
+            df.wave_full = d.wave_full && fin == ~0ull;
+            int zs;
+            asm volatile("s_mov_b32 %0, 0" : "=s"(zs));
+            const atc_state_t st_end = kernarg_reread<atc_state_t>(offsetof(StepArgs, st), zs);
+            const atc_out_t o_end = kernarg_reread<atc_out_t>(offsetof(StepArgs, out), zs);
+            store_obs_rows(o_end.obs, df, sv.o, obs_stage);
+            if (df.lane_valid) {
+                if (FULL && o_end.raw_obs) store_obs(at<float>(o_end.raw_obs, times40(d.i)), sv.zraw);
+                stream_store(at<uint16_t>(o_end.flags, d.i * 2u), (uint16_t)or_fl);
+                if (FULL && o_end.ac_reward) *at<float>(o_end.ac_reward, d.i * 4u) = sum_r;
+            }
+            if (mine && d.k == 0) {
+                *at<float>(o_end.reward, (uint32_t)d.e * 4u) = sum_env;
+                *at<uint8_t>(o_end.done, (uint32_t)d.e) = sv.done ? 1 : 0;
+                if (FULL && o_end.min_sep) *at<float>(o_end.min_sep, (uint32_t)d.e * 4u) = (min_d2 >= 1e30f) ? 1e30f : sqrtf(min_d2);
+                if (n_steps) *at<uint8_t>(n_steps, (uint32_t)d.e) = (uint8_t)(step + 1);
+            }
+            store_lane_state(st_end, df, ls, true);
+            store_env_state<W>(st_end, df, es, hi0);
+            live &= ~fin;
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
 // Persistent step server of ONE env x ONE aircraft (the drop-in AtcGym, atc_gym.py:128-192; include/atc_step.h: atc_serve_*).
 // One resident wavefront keeps the env's state in registers and polls a mailbox in pinned mapped host memory: the host writes
 // {action, sequence number} with ONE 16-byte store, the wavefront runs the single-step body (the same step_part_a / step_part_b
@@ -1605,6 +1823,15 @@ static int check_env_args(const atc_scenario_t* s, int B, int N, const atc_state
     return ATC_OK;
 }
 
+// the step's time increment against the fixed-point formats of include/atc_step.h: a step's displacement (<= 512 kt) must stay below
+// 2^30 position-grid counts and the speed's rate limit below 2^31 speed counts — dt up to 51 s for any sector (the reference uses 1 s)
+static int check_dt(const atc_scenario_t* s, const atc_params_t* p) {
+    if (!(p->dt > 0.0)) return fail_arg("dt must be > 0");
+    if (!(0.1423 * p->dt * (double)s->consts[ATC_C_POS_SCALE] < 1073741824.0) || !((double)kAMax * p->dt < 255.9))
+        return fail_arg("dt too large for the fixed-point state formats (see include/atc_step.h)");
+    return ATC_OK;
+}
+
 static int step_common(const atc_scenario_t* s, int B, int N, int T, int hold, const atc_state_t* st, const float* actions,
                        const atc_out_t* out, const atc_params_t* p, void* stream) {
     if (!actions || !out) return fail_arg("null pointer");
@@ -1614,11 +1841,7 @@ static int step_common(const atc_scenario_t* s, int B, int N, int T, int hold, c
     if (T % hold != 0) return fail_arg("T must be a multiple of hold (actions holds T / hold blocks)");
     if (!out->obs || !out->reward || !out->done || !out->flags) return fail_arg("obs/reward/done/flags are required");
     if (out->packet && (N != 1 || T != 1)) return fail_arg("atc_out_t.packet is for single steps of single-aircraft envs");
-    if (!(p->dt > 0.0)) return fail_arg("dt must be > 0");
-    // the fixed-point formats of include/atc_step.h: a step's displacement (<= 512 kt) must stay below 2^30 position-grid
-    // counts and the speed's rate limit below 2^31 speed counts — dt up to 51 s for any sector (the reference uses 1 s)
-    if (!(0.1423 * p->dt * (double)s->consts[ATC_C_POS_SCALE] < 1073741824.0) || !((double)kAMax * p->dt < 255.9))
-        return fail_arg("dt too large for the fixed-point state formats (see include/atc_step.h)");
+    if (const int rc = check_dt(s, p)) return rc;
     hipStream_t q = (hipStream_t)stream;
     if (N == 1) return launch_step<1>(s, B, N, T, hold, st, actions, out, p, q);
     if (N == 2) return launch_step<2>(s, B, N, T, hold, st, actions, out, p, q);
@@ -1627,6 +1850,45 @@ static int step_common(const atc_scenario_t* s, int B, int N, int T, int hold, c
     if (N <= 16) return launch_step<16>(s, B, N, T, hold, st, actions, out, p, q);
     if (N <= 32) return launch_step<32>(s, B, N, T, hold, st, actions, out, p, q);
     return launch_step<64>(s, B, N, T, hold, st, actions, out, p, q);
+}
+
+// ---- frame skip (include/atc_step.h: atc_step_skip) ------------------------------------------------------------------------------
+// its own launch record (atc_skip_launch_counts): slot = log2(W); the step kernel's record and its slots stay as they are
+static thread_local uint64_t t_skip_launches[ATC_SKIP_LAUNCH_SLOTS] = {0};
+
+template <int W>
+static int launch_skip(const atc_scenario* s, int B, int N, int K, const atc_state_t* st, const float* actions, const atc_out_t* out,
+                       uint8_t* n_steps, const atc_params_t* p, hipStream_t stream) {
+    const size_t lds = lds_bytes(s, W >= 32, true);
+    const long long slots = (long long)B * W;
+    const int grid = (int)((slots + kBlock - 1) / kBlock);  // one workgroup per 256 slots, like k_step
+    const StepDerived& q = derive(*p, s, 0);
+    // as for k_step: a launch that asks for no optional output runs the form that has them compiled out
+    if (out->raw_obs || out->ac_reward || out->min_sep || out->term_obs) hipLaunchKernelGGL((k_skip<W, true>), dim3(grid), dim3(kBlock), lds, stream, s->d_blob, s->off_grid, B, N, K, 0, *st, actions, *out, *p, q, n_steps);
+    else hipLaunchKernelGGL((k_skip<W, false>), dim3(grid), dim3(kBlock), lds, stream, s->d_blob, s->off_grid, B, N, K, 0, *st, actions, *out, *p, q, n_steps);
+    HIP_TRY(hipGetLastError());
+    ++t_skip_launches[__builtin_ctz(W)];
+    return ATC_OK;
+}
+
+static int skip_common(const atc_scenario_t* s, int B, int N, int K, const atc_state_t* st, const float* actions, const atc_out_t* out,
+                       uint8_t* n_steps, const atc_params_t* p, void* stream) {
+    // K first, before any pointer is looked at
+    if (K < 1 || K > ATC_SKIP_MAX) return fail_arg("K (the frame-skip length) must be 1 .. 255");
+    if (!actions || !out) return fail_arg("null pointer");
+    if (const int rc = check_env_args(s, B, N, st, p)) return rc;
+    if (!out->obs || !out->reward || !out->done || !out->flags) return fail_arg("obs/reward/done/flags are required");
+    if (out->packet) return fail_arg("atc_out_t.packet must be NULL for atc_step_skip (the packet is a single step's result)");
+    if (p->mode & ATC_M_ACTIONS_HELD) return fail_arg("ATC_M_ACTIONS_HELD is for atc_step only: a frame-skip call's first step carries a fresh decision");
+    if (const int rc = check_dt(s, p)) return rc;
+    hipStream_t q = (hipStream_t)stream;
+    if (N == 1) return launch_skip<1>(s, B, N, K, st, actions, out, n_steps, p, q);
+    if (N == 2) return launch_skip<2>(s, B, N, K, st, actions, out, n_steps, p, q);
+    if (N <= 4) return launch_skip<4>(s, B, N, K, st, actions, out, n_steps, p, q);
+    if (N <= 8) return launch_skip<8>(s, B, N, K, st, actions, out, n_steps, p, q);
+    if (N <= 16) return launch_skip<16>(s, B, N, K, st, actions, out, n_steps, p, q);
+    if (N <= 32) return launch_skip<32>(s, B, N, K, st, actions, out, n_steps, p, q);
+    return launch_skip<64>(s, B, N, K, st, actions, out, n_steps, p, q);
 }
 
 #include "atc_abi.inc"   // the extern "C" entry points (host side)

@@ -441,6 +441,13 @@ enum {
 /* Copies the calling thread's first min(n, ATC_LAUNCH_SLOTS) counters to out (launches since the thread started; they only grow,
  * a failed launch is not counted).  atc_step_multi and atc_step_packet count once per launch they make. */
 int atc_launch_counts(uint64_t* out, int n);
+/* The frame-skip kernel (atc_step_skip) keeps a record of its own, so that the one above stays as it is: slot = log2(W), one per
+ * lane-group width.  Same rules: per calling thread, only grows, a refused or failed call is not counted. */
+enum {
+    ATC_SKIP_MAX = 255,          /* largest frame-skip length K (n_steps is a byte) */
+    ATC_SKIP_LAUNCH_SLOTS = 7
+};
+int atc_skip_launch_counts(uint64_t* out, int n);
 
 /* Uploads a compiled scenario blob (host pointer, n_words floats) to `device`.
  * Replaces: AtcGym.__init__ scenario unpacking, atc_gym.py:45-58. */
@@ -572,6 +579,37 @@ int atc_rollout(const atc_scenario_t* s, int B, int N, int T, const atc_state_t*
  * HBM traffic shrink by that factor. */
 int atc_rollout_hold(const atc_scenario_t* s, int B, int N, int T, int hold, const atc_state_t* st, const float* actions,
                      const atc_out_t* out, const atc_params_t* p, void* stream);
+
+/* FRAME SKIP: one decision, up to K steps, ONE transition — the loop of the reference's demo (learning/atc-gym-demo.py:14-22: a
+ * sampled action is applied for 20 steps) as a vectorised env's `frame_skip` knob.  1 <= K <= ATC_SKIP_MAX.  Defined per env as
+ *
+ *     n = 0
+ *     repeat: atc_step the env once with `actions` (the same [N][3] block every time); n += 1
+ *     until that step reported done, or n == K
+ *
+ * and everything returned or left behind follows from the atc_step results of the n executed steps, in step order:
+ *   obs, raw_obs      those of the LAST executed step (under ATC_M_AUTO_RESET and done: the raw reset observation, exactly as
+ *                     atc_step returns it in that step)
+ *   reward, ac_reward float32 sum of the executed steps' values, accumulated sequentially in step order (acc = r1; acc = acc + r2;
+ *                     ... — plain float32 additions, never fused: reproducible bit for bit by a host loop over atc_step)
+ *   done              1 iff the last executed step reported done
+ *   flags             bitwise OR of the executed steps' flag words
+ *   min_sep           minimum over the executed steps
+ *   term_obs          as atc_step writes it in the terminating step (envs auto-reset in this call); untouched otherwise
+ *   n_steps           [B] bytes (may be NULL): n
+ *   out->packet       must be NULL
+ * STATE afterwards (all of atc_state_t, the per-episode record included) is bit for bit what n atc_step calls leave: an env that
+ * ended at step n < K is NOT stepped again in this call — a transition never spans two episodes.  Without ATC_M_AUTO_RESET it sits
+ * in its terminal state, with it in its fresh spawn state with timesteps == 0.  The last-action record and actions_taken behave as
+ * n single steps with the same actions do: the first step may count actions, the repeats cannot.  Envs are independent: an env's
+ * result does not depend on whether its neighbours stopped early.  K == 1 is atc_step, outputs and state, bit for bit.
+ * ATC_ERR_ARG (atc_last_error() says which): K outside 1 .. 255 — checked first, before any pointer —, the argument errors of
+ * atc_step, out->packet != NULL, ATC_M_ACTIONS_HELD in p->mode (that bit is atc_step's; the first step of a skip call always
+ * carries a fresh decision).
+ * One launch: the state is read and written once and one set of outputs is stored, where K atc_step calls stream both K times and
+ * atc_rollout_hold(T = K, hold = K) stores [K][...] outputs and steps THROUGH resets.  Counted by atc_skip_launch_counts only. */
+int atc_step_skip(const atc_scenario_t* s, int B, int N, int K, const atc_state_t* st, const float* actions /* [B*N*3] */,
+                  const atc_out_t* out, uint8_t* n_steps /* nullable [B] */, const atc_params_t* p, void* stream);
 
 #ifdef __cplusplus
 }
