@@ -23,6 +23,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
+#include <type_traits>
 
 #include "atc_device.h"
 
@@ -440,6 +441,14 @@ __device__ __forceinline__ T kernarg_reread(size_t byte_off, int opaque_zero) {
 #endif
 }
 
+// a zero the compiler cannot see through: what depends on it (a kernarg re-read, an address) is evaluated where it stands, not
+// hoisted out of the step loop
+__device__ __forceinline__ int opaque_zero() {
+    int z;
+    asm volatile("s_mov_b32 %0, 0" : "=s"(z));
+    return z;
+}
+
 // base of atc_state_t.phi_wide on the rare paths that need it: the named argument in single-step launches, a kernarg re-read in
 // multi-step ones (like the per-episode record's base: nothing about it is carried across the step loop)
 template <bool ONE>
@@ -498,7 +507,7 @@ struct StepOut {        // per-step output bases (uniform pointers)
     float *raw_obs, *ac_reward, *min_sep, *term_obs;
     uint32_t* packet;
 #if ATC_TRACE
-    unsigned long long* trace;
+    unsigned long long* trace;   // this step's row of stamps (k_step only: the other kernels leave it out of their initialiser, i.e. null)
 #endif
 };
 
@@ -739,10 +748,9 @@ __device__ __forceinline__ uint32_t noise_areas(const float* __restrict__ K, con
     return bits;
 }
 
-// The observation store of step_part_b (see there: a full wavefront transposes its 64 x 10 block through LDS and writes 16-byte
-// pieces, other lanes store their own row) as a function, for the frame-skip kernel's one store per block.  step_part_b keeps its
-// inline copy — calling this from there changed the generated code of two existing kernels —, so the two must be kept in step
-// by hand until the existing kernels' machine code is next allowed to move and they can be merged.
+// ---- observation store (the end of step_part_b, and k_skip's one store per block): [aircraft][10] rows are 40 B apart, so per-lane
+//      stores would scatter 8-byte pieces over 20 cache lines per instruction; a full wavefront instead transposes its 64 x 10
+//      block through LDS and writes 2 560 contiguous bytes as 16-byte stores.  Other lanes store their own row.
 __device__ __forceinline__ void store_obs_rows(float* obs, const LaneIds& d, const float* o, float* obs_stage) {
     if (ATC_USUAL(d.wave_full)) {
         // addresses from threadIdx itself, not from the lane ids a multi-step launch re-derives through an opaque zero: the
@@ -1199,11 +1207,7 @@ __device__ __forceinline__ bool step_part_b(const float* __restrict__ K, const f
     ATC_STAMP_END(so.trace, 4);
     // Multi-step launches: the NEXT step's rate group is requested here, with the observation store still ahead — requested at
     // the top of the step that uses it, its latency was a stall before the first instruction of the kinematics.
-    if (!ONE && !LAT) {
-        int zn;
-        asm volatile("s_mov_b32 %0, 0" : "=s"(zn));
-        qr_next = kernarg_reread<QRates>(offsetof(StepArgs, q) + offsetof(StepDerived, r), zn);
-    }
+    if (!ONE && !LAT) qr_next = kernarg_reread<QRates>(offsetof(StepArgs, q) + offsetof(StepDerived, r), opaque_zero());
     // The next block's action (requested above, behind the MVA gathers) is WAITED FOR here, in the step that requested it and ahead
     // of this step's stores: left pending across the loop's back edge, "the action may be in flight" reaches the loop header, and the
     // decode at the top of EVERY step waits for every earlier vector-memory operation — one counter, in order — i.e. for the
@@ -1218,39 +1222,7 @@ __device__ __forceinline__ bool step_part_b(const float* __restrict__ K, const f
         sv->done = done;
         return quiet;
     }
-    // ---- observation store: [aircraft][10] rows are 40 B apart, so per-lane stores would scatter 8-byte pieces over 20
-    //      cache lines per instruction; a full wavefront instead transposes its 64 x 10 block through LDS and writes 2 560
-    //      contiguous bytes as 16-byte stores.
-    //      (store_obs_rows above is a second copy of this block, for k_skip: a change here belongs there too)
-    if (ATC_USUAL(d.wave_full)) {
-        // addresses from threadIdx itself, not from the lane ids a multi-step launch re-derives through an opaque zero: the
-        // compiler then knows the ranges (lane < 64: two of the three row tests fold away, 24-bit multiplies suffice) — with
-        // the opaque copies it emitted a quarter-rate 64-bit multiply-add per LDS read
-        const uint32_t ln = threadIdx.x & 63u, wv = threadIdx.x >> 6;
-        float* tb = obs_stage + __umul24(wv, 64u * ATC_OBS_DIM);
-        float2* tb2 = reinterpret_cast<float2*>(tb) + __umul24(ln, ATC_OBS_DIM / 2);   // rows are 40 B: 8-byte aligned
-#pragma unroll
-        for (int c = 0; c < ATC_OBS_DIM / 2; ++c) tb2[c] = make_float2(o[2 * c], o[2 * c + 1]);
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        // first aircraft of this wavefront (N == W): wave-uniform, so the multiply runs on the scalar unit
-        const uint32_t wave_off = (d.slot0 + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x & ~63u))) * 40u;
-        const float4* src = reinterpret_cast<const float4*>(tb);
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            const uint32_t idx = (uint32_t)j * 64u + ln;
-            if (idx < 64u * ATC_OBS_DIM / 4u) {
-                const float4 v = src[idx];
-                float* d4 = at<float>(so.obs, wave_off + idx * 16u);
-                typedef float v4f __attribute__((ext_vector_type(4)));
-                __builtin_nontemporal_store(v4f{v.x, v.y, v.z, v.w}, reinterpret_cast<v4f*>(d4));
-            }
-        }
-        __builtin_amdgcn_wave_barrier();
-    } else if (d.lane_valid) {
-        store_obs(at<float>(so.obs, times40(i)), o);
-    }
+    store_obs_rows(so.obs, d, o, obs_stage);
     ATC_STAMP_END(so.trace, 5);
     // ---- flag word, reward, done: last.  The compiler guards the observation's staging registers with a wait for ALL vector
     //      memory operations (one counter for loads and stores; the auto-reset path's loads merge in above) — issued before the
@@ -1285,6 +1257,17 @@ __device__ __forceinline__ void store_env_state(const atc_state_t& st, const Lan
         if (W == 64 && (uint32_t)(es.amask >> 32) != hi0)
             *at<uint32_t>(st.stats, (uint32_t)d.e * (ATC_STAT_WORDS * 4u) + ATC_STAT_MASK_HI * 4u) = (uint32_t)(es.amask >> 32);
     }
+}
+
+// Multi-step kernels WAIT for their state loads here, before the step loop.  Left pending, "a state register may still be in flight"
+// is merged into the loop header from the pre-header, and the compiler guards the first use of each in the loop body with a wait
+// that — one counter for loads and stores, in order — also waits for the PREVIOUS step's stores in every later step.
+__device__ __forceinline__ void settle_state(LaneState& ls, EnvState& es) {
+    asm volatile("" : "+v"(ls.a.x), "+v"(ls.a.y), "+v"(ls.a.h), "+v"(ls.a.phi), "+v"(ls.a.v));
+    asm volatile("" : "+v"(ls.la_v), "+v"(ls.la_h), "+v"(ls.la_p), "+v"(es.t), "+v"(es.n_actions), "+v"(es.total_reward));
+    uint32_t m_lo = (uint32_t)es.amask, m_hi = (uint32_t)(es.amask >> 32);
+    asm volatile("" : "+v"(m_lo), "+v"(m_hi));
+    es.amask = (uint64_t)m_lo | ((uint64_t)m_hi << 32);
 }
 
 #define ATC_LAT_WAVES 2   // wavefronts per SIMD the latency-bound instantiation is register-budgeted for (<= 256 VGPRs)
@@ -1366,11 +1349,7 @@ k_step(const float* __restrict__ blob, int off_grid, int B, int N, int T, int ho
     int scan_skip = 0;          // wave-uniform: steps left in the separation scan's horizon (step_part_b) ...
     uint32_t scan_mask = 0u;    // ... and the partner batches that have to be scanned inside it
     QRates qr_next = q.r;   // the rate group of the coming step (multi-step launches fetch it one step ahead, see step_part_b)
-    if (!ONE && !LAT) {
-        int zn;
-        asm volatile("s_mov_b32 %0, 0" : "=s"(zn));
-        qr_next = kernarg_reread<QRates>(offsetof(StepArgs, q) + offsetof(StepDerived, r), zn);
-    }
+    if (!ONE && !LAT) qr_next = kernarg_reread<QRates>(offsetof(StepArgs, q) + offsetof(StepDerived, r), opaque_zero());
     // LDSG: stage the lookup table — 28 sixteen-byte pieces per lane in flight at a time (ONE round trip for LOWW's 112 KB), behind
     // the state loads issued above; the terms a step reads with the table go to vector registers like the other uniform terms (LAT)
     LdsTab ltv = lt_arg;
@@ -1403,16 +1382,7 @@ k_step(const float* __restrict__ blob, int off_grid, int B, int N, int T, int ho
         ltv.off_l1 = vg(lt_arg.off_l1); ltv.off_sub = vg(lt_arg.off_sub); ltv.off_line = vg(lt_arg.off_line); ltv.off_hts = vg(lt_arg.off_hts);
         ltv.off_resid = vg(lt_arg.off_resid);
     }
-    if (!ONE) {
-        // The state loads are WAITED FOR here, before the step loop.  Left pending, "a state register may still be in flight" is
-        // merged into the loop header from the pre-header, and the compiler guards the first use of each in the loop body with a
-        // wait that — one counter for loads and stores, in order — also waits for the PREVIOUS step's stores in every later step.
-        asm volatile("" : "+v"(ls.a.x), "+v"(ls.a.y), "+v"(ls.a.h), "+v"(ls.a.phi), "+v"(ls.a.v));
-        asm volatile("" : "+v"(ls.la_v), "+v"(ls.la_h), "+v"(ls.la_p), "+v"(es.t), "+v"(es.n_actions), "+v"(es.total_reward));
-        uint32_t m_lo = (uint32_t)es.amask, m_hi = (uint32_t)(es.amask >> 32);
-        asm volatile("" : "+v"(m_lo), "+v"(m_hi));
-        es.amask = (uint64_t)m_lo | ((uint64_t)m_hi << 32);
-    }
+    if (!ONE) settle_state(ls, es);
     for (int step = 0; step < n_steps; ++step) {
 #if ATC_TRACE
         unsigned long long* trow = trace ? trace + ((size_t)(blockIdx.x * (kBlock / 64) + (tid >> 6)) * n_steps + step) * 8 : nullptr;
@@ -1432,7 +1402,7 @@ k_step(const float* __restrict__ blob, int off_grid, int B, int N, int T, int ho
         int32_t* stats_l = st.stats;
         int zk = 0;   // this step's opaque zero: kernarg re-reads that depend on it cannot be hoisted out of the step loop
         if (!ONE) {   // (also makes the mode word's flag tests scalar compares inside the step, not
-            asm volatile("s_mov_b32 %0, 0" : "=s"(zk));   // 64-bit lane masks kept — and spilled — across the loop)
+            zk = opaque_zero();   // 64-bit lane masks kept — and spilled — across the loop)
             pl.mode += (uint32_t)zk;
         }
         StepOut so = {outl.obs + sBN * ATC_OBS_DIM, outl.flags + sBN, outl.reward + sB, outl.done + sB,
@@ -1494,11 +1464,7 @@ k_step(const float* __restrict__ blob, int off_grid, int B, int N, int T, int ho
     atc_state_t st_end = st;
     // (single-step launches also fetch the state pointers again for the final stores instead of carrying ten scalar registers
     // through the body: they were spilled to vector-register lanes)
-    if (ONE || loop_rereads_state(W)) {
-        int zk;
-        asm volatile("s_mov_b32 %0, 0" : "=s"(zk));
-        st_end = kernarg_reread<atc_state_t>(offsetof(StepArgs, st), zk);
-    }
+    if (ONE || loop_rereads_state(W)) st_end = kernarg_reread<atc_state_t>(offsetof(StepArgs, st), opaque_zero());
     store_lane_state(st_end, d, ls, la_live);
     store_env_state<W>(st_end, d, es, hi0);
     if (ATC_KARG_PREFETCH(W, ONE)) asm volatile("" ::"s"(karg_touch));   // (keeps the touches alive; nothing waits for them before here)
@@ -1574,19 +1540,8 @@ k_skip(const float* __restrict__ blob, int off_grid, int B, int N, int K_steps, 
     uint64_t refused_blk = 0ull;
     bool refused_known = false;
     bool all_active = false, mask_dirty = true;
-    QRates qr_next;
-    {
-        int zn;
-        asm volatile("s_mov_b32 %0, 0" : "=s"(zn));
-        qr_next = kernarg_reread<QRates>(offsetof(StepArgs, q) + offsetof(StepDerived, r), zn);
-    }
-    {   // the state loads are waited for before the loop (see k_step)
-        asm volatile("" : "+v"(ls.a.x), "+v"(ls.a.y), "+v"(ls.a.h), "+v"(ls.a.phi), "+v"(ls.a.v));
-        asm volatile("" : "+v"(ls.la_v), "+v"(ls.la_h), "+v"(ls.la_p), "+v"(es.t), "+v"(es.n_actions), "+v"(es.total_reward));
-        uint32_t m_lo = (uint32_t)es.amask, m_hi = (uint32_t)(es.amask >> 32);
-        asm volatile("" : "+v"(m_lo), "+v"(m_hi));
-        es.amask = (uint64_t)m_lo | ((uint64_t)m_hi << 32);
-    }
+    QRates qr_next = kernarg_reread<QRates>(offsetof(StepArgs, q) + offsetof(StepDerived, r), opaque_zero());
+    settle_state(ls, es);
     // accumulated over the executed steps, in step order: plain float32 additions (the library is built with -ffp-contract=off)
     float sum_r = 0.0f, sum_env = 0.0f, min_d2 = 1e30f;
     uint32_t or_fl = 0u;
@@ -1597,16 +1552,11 @@ k_skip(const float* __restrict__ blob, int off_grid, int B, int N, int K_steps, 
         dl.env_valid = lane_live;
         dl.lane_valid = d.lane_valid && lane_live;
         atc_params_t pl = p;
-        int zk;   // this step's opaque zero (see k_step)
-        asm volatile("s_mov_b32 %0, 0" : "=s"(zk));
+        const int zk = opaque_zero();   // this step's opaque zero (see k_step)
         pl.mode += (uint32_t)zk;
         const atc_out_t outl = out;
         const StepOut so = {outl.obs, outl.flags, outl.reward, outl.done, FULL ? outl.raw_obs : nullptr, FULL ? outl.ac_reward : nullptr,
-                            FULL ? outl.min_sep : nullptr, FULL ? outl.term_obs : nullptr, nullptr
-#if ATC_TRACE
-                            , nullptr
-#endif
-        };
+                            FULL ? outl.min_sep : nullptr, FULL ? outl.term_obs : nullptr, nullptr};
         const QRates qr = qr_next;
         const QScan qs = QGET(s);
         if (ATC_RARE(step == 0)) tg = decode_targets(qr, act);
@@ -1639,8 +1589,7 @@ k_skip(const float* __restrict__ blob, int off_grid, int B, int N, int K_steps, 
             df.env_valid = mine;
             df.lane_valid = d.lane_valid && mine;
             df.wave_full = d.wave_full && fin == ~0ull;
-            int zs;
-            asm volatile("s_mov_b32 %0, 0" : "=s"(zs));
+            const int zs = opaque_zero();
             const atc_state_t st_end = kernarg_reread<atc_state_t>(offsetof(StepArgs, st), zs);
             const atc_out_t o_end = kernarg_reread<atc_out_t>(offsetof(StepArgs, out), zs);
             store_obs_rows(o_end.obs, df, sv.o, obs_stage);
@@ -1693,11 +1642,7 @@ k_serve(const float* __restrict__ blob, int off_grid, atc_state_t st, atc_out_t 
     const double h0 = *at<double>(st.alt, 0u);
     const int4 la0 = *at<int4>(st.last_act, 0u);
     LaneState ls = {{ps.x, ps.y, h0, ps.z, (uint32_t)ps.w}, (uint32_t)la0.x, __hiloint2double(la0.w, la0.z), la0.y, false};
-    const StepOut so = {out.obs, out.flags, out.reward, out.done, out.raw_obs, out.ac_reward, out.min_sep, out.term_obs, out.packet
-#if ATC_TRACE
-                        , nullptr
-#endif
-    };
+    const StepOut so = {out.obs, out.flags, out.reward, out.done, out.raw_obs, out.ac_reward, out.min_sep, out.term_obs, out.packet};
     if (threadIdx.x == 0) __hip_atomic_store(mailbox + ATC_MB_STATE, (uint32_t)ATC_SERVE_RUNNING, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
     unsigned long long t_cmd = __builtin_amdgcn_s_memrealtime();
     uint32_t left_as = ATC_SERVE_LEFT_LEASE;
@@ -1751,6 +1696,8 @@ static int grid_for(const atc_scenario* s, long long threads) {
     if (blocks < 1) blocks = 1;
     return (int)blocks;
 }
+// the step kernels (k_step, k_skip): one workgroup per 256 slots of W per env, no grid-stride loop
+static int step_grid(int B, int W) { return (int)(((long long)B * W + kBlock - 1) / kBlock); }
 static size_t lds_bytes(const atc_scenario*, bool pair_scan, bool step_kernel = false) {
     size_t w = 0;  // the sector is not staged: LDS only holds the obs transpose stage and the pair-scan staging
     if (step_kernel) w += (size_t)(kBlock / 64) * 64 * ATC_OBS_DIM;
@@ -1774,8 +1721,7 @@ static int launch_step2(const atc_scenario* s, int B, int N, int T, int hold, co
             raised_for = s->device;
         }
     }
-    const long long slots = (long long)B * W;
-    const int grid = (int)((slots + kBlock - 1) / kBlock);  // one workgroup per 256 slots, no grid-stride loop
+    const int grid = step_grid(B, W);
     LdsTab lt = s->lt;
     if (!LDSG) lt.src = nullptr;
     hipLaunchKernelGGL((k_step<W, FULL, ONE, ALLV, LAT, LDSG>), dim3(grid), dim3(kBlock), lds, stream, s->d_blob, s->off_grid, B, N, T, hold, *st, actions, *out, *p, derive(*p, s, scan_horizon<W, FULL, ONE>()), inline_action(), lt);
@@ -1832,6 +1778,22 @@ static int check_dt(const atc_scenario_t* s, const atc_params_t* p) {
     return ATC_OK;
 }
 
+static int check_required_outputs(const atc_out_t* out) {
+    if (!out->obs || !out->reward || !out->done || !out->flags) return fail_arg("obs/reward/done/flags are required");
+    return ATC_OK;
+}
+// f(std::integral_constant<int, W>) for the lane-group width of N-aircraft envs: W = next_pow2(N)
+template <typename F>
+static int with_width(int N, F f) {
+    if (N == 1) return f(std::integral_constant<int, 1>());
+    if (N == 2) return f(std::integral_constant<int, 2>());
+    if (N <= 4) return f(std::integral_constant<int, 4>());
+    if (N <= 8) return f(std::integral_constant<int, 8>());
+    if (N <= 16) return f(std::integral_constant<int, 16>());
+    if (N <= 32) return f(std::integral_constant<int, 32>());
+    return f(std::integral_constant<int, 64>());
+}
+
 static int step_common(const atc_scenario_t* s, int B, int N, int T, int hold, const atc_state_t* st, const float* actions,
                        const atc_out_t* out, const atc_params_t* p, void* stream) {
     if (!actions || !out) return fail_arg("null pointer");
@@ -1839,17 +1801,10 @@ static int step_common(const atc_scenario_t* s, int B, int N, int T, int hold, c
     if (T < 1 || hold < 1) return fail_arg("need T >= 1 and hold >= 1");
     // actions is [T / hold] blocks: a partial last block would be read beyond what the header promises exists
     if (T % hold != 0) return fail_arg("T must be a multiple of hold (actions holds T / hold blocks)");
-    if (!out->obs || !out->reward || !out->done || !out->flags) return fail_arg("obs/reward/done/flags are required");
+    if (const int rc = check_required_outputs(out)) return rc;
     if (out->packet && (N != 1 || T != 1)) return fail_arg("atc_out_t.packet is for single steps of single-aircraft envs");
     if (const int rc = check_dt(s, p)) return rc;
-    hipStream_t q = (hipStream_t)stream;
-    if (N == 1) return launch_step<1>(s, B, N, T, hold, st, actions, out, p, q);
-    if (N == 2) return launch_step<2>(s, B, N, T, hold, st, actions, out, p, q);
-    if (N <= 4) return launch_step<4>(s, B, N, T, hold, st, actions, out, p, q);
-    if (N <= 8) return launch_step<8>(s, B, N, T, hold, st, actions, out, p, q);
-    if (N <= 16) return launch_step<16>(s, B, N, T, hold, st, actions, out, p, q);
-    if (N <= 32) return launch_step<32>(s, B, N, T, hold, st, actions, out, p, q);
-    return launch_step<64>(s, B, N, T, hold, st, actions, out, p, q);
+    return with_width(N, [&](auto w) { return launch_step<decltype(w)::value>(s, B, N, T, hold, st, actions, out, p, (hipStream_t)stream); });
 }
 
 // ---- frame skip (include/atc_step.h: atc_step_skip) ------------------------------------------------------------------------------
@@ -1860,8 +1815,7 @@ template <int W>
 static int launch_skip(const atc_scenario* s, int B, int N, int K, const atc_state_t* st, const float* actions, const atc_out_t* out,
                        uint8_t* n_steps, const atc_params_t* p, hipStream_t stream) {
     const size_t lds = lds_bytes(s, W >= 32, true);
-    const long long slots = (long long)B * W;
-    const int grid = (int)((slots + kBlock - 1) / kBlock);  // one workgroup per 256 slots, like k_step
+    const int grid = step_grid(B, W);
     const StepDerived& q = derive(*p, s, 0);
     // as for k_step: a launch that asks for no optional output runs the form that has them compiled out
     if (out->raw_obs || out->ac_reward || out->min_sep || out->term_obs) hipLaunchKernelGGL((k_skip<W, true>), dim3(grid), dim3(kBlock), lds, stream, s->d_blob, s->off_grid, B, N, K, 0, *st, actions, *out, *p, q, n_steps);
@@ -1877,18 +1831,11 @@ static int skip_common(const atc_scenario_t* s, int B, int N, int K, const atc_s
     if (K < 1 || K > ATC_SKIP_MAX) return fail_arg("K (the frame-skip length) must be 1 .. 255");
     if (!actions || !out) return fail_arg("null pointer");
     if (const int rc = check_env_args(s, B, N, st, p)) return rc;
-    if (!out->obs || !out->reward || !out->done || !out->flags) return fail_arg("obs/reward/done/flags are required");
+    if (const int rc = check_required_outputs(out)) return rc;
     if (out->packet) return fail_arg("atc_out_t.packet must be NULL for atc_step_skip (the packet is a single step's result)");
     if (p->mode & ATC_M_ACTIONS_HELD) return fail_arg("ATC_M_ACTIONS_HELD is for atc_step only: a frame-skip call's first step carries a fresh decision");
     if (const int rc = check_dt(s, p)) return rc;
-    hipStream_t q = (hipStream_t)stream;
-    if (N == 1) return launch_skip<1>(s, B, N, K, st, actions, out, n_steps, p, q);
-    if (N == 2) return launch_skip<2>(s, B, N, K, st, actions, out, n_steps, p, q);
-    if (N <= 4) return launch_skip<4>(s, B, N, K, st, actions, out, n_steps, p, q);
-    if (N <= 8) return launch_skip<8>(s, B, N, K, st, actions, out, n_steps, p, q);
-    if (N <= 16) return launch_skip<16>(s, B, N, K, st, actions, out, n_steps, p, q);
-    if (N <= 32) return launch_skip<32>(s, B, N, K, st, actions, out, n_steps, p, q);
-    return launch_skip<64>(s, B, N, K, st, actions, out, n_steps, p, q);
+    return with_width(N, [&](auto w) { return launch_skip<decltype(w)::value>(s, B, N, K, st, actions, out, n_steps, p, (hipStream_t)stream); });
 }
 
 #include "atc_abi.inc"   // the extern "C" entry points (host side)
