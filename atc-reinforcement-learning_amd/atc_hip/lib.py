@@ -52,7 +52,7 @@ EXPORTS = ("atc_abi_version", "atc_last_error", "atc_launch_counts", "atc_host_m
            "atc_scenario_attach_lds_table", "atc_query_mva", "atc_query_mva_lds",
            "atc_query_mva_index", "atc_query_corridor", "atc_query_shaping", "atc_reset", "atc_observe", "atc_step",
            "atc_step_multi", "atc_step_packet", "atc_rollout", "atc_rollout_hold", "atc_serve_start", "atc_serve_step", "atc_serve_stop",
-           "atc_step_skip", "atc_skip_launch_counts")
+           "atc_step_skip", "atc_skip_launch_counts", "atc_fill_prefetch_info")
 
 def load():
     """Loads libatcstep.so; raises (never falls back) when it has not been built."""
@@ -93,6 +93,7 @@ def load():
     lib.atc_rollout_hold.argtypes = [vp, ci, ci, ci, ci, C.POINTER(AtcState), vp, C.POINTER(AtcOut), C.POINTER(AtcParams), vp]
     lib.atc_step_skip.argtypes = [vp, ci, ci, ci, C.POINTER(AtcState), vp, C.POINTER(AtcOut), vp, C.POINTER(AtcParams), vp]
     lib.atc_skip_launch_counts.argtypes = [C.POINTER(C.c_uint64), ci]
+    lib.atc_fill_prefetch_info.argtypes = [vp, ci, ci, C.POINTER(ci), C.POINTER(ci)]
     for name in EXPORTS:
         if name not in ("atc_abi_version", "atc_last_error"):
             getattr(lib, name).restype = ci
@@ -128,6 +129,15 @@ def skip_launch_counts():
     buf = (C.c_uint64 * L.SKIP_LAUNCH_SLOTS)()
     check(load().atc_skip_launch_counts(buf, L.SKIP_LAUNCH_SLOTS))
     return {1 << i: int(v) for i, v in enumerate(buf) if v}
+
+
+def fill_prefetch_info(scenario, B, N):
+    """(resident, stride) of the fast single-step launch's fill-phase prefetch for a batch of B x N on `scenario`'s device
+    (include/atc_step.h: atc_fill_prefetch_info): the workgroups the device holds at once, and what an atc_step of that batch
+    passes to the kernel (0: prefetch off)."""
+    resident, stride = C.c_int(0), C.c_int(0)
+    check(load().atc_fill_prefetch_info(scenario.handle, int(B), int(N), C.byref(resident), C.byref(stride)))
+    return resident.value, stride.value
 
 
 def mapped_ptr(tensor):

@@ -16,6 +16,20 @@ int atc_skip_launch_counts(uint64_t* out, int n) {
     for (int i = 0; i < n && i < ATC_SKIP_LAUNCH_SLOTS; ++i) out[i] = t_skip_launches[i];
     return ATC_OK;
 }
+int atc_fill_prefetch_info(const atc_scenario_t* s, int B, int N, int* resident, int* stride) {
+    if (!s || !resident || !stride) return fail_arg("null pointer");
+    if (B < 1 || N < 1 || N > ATC_MAX_AIRCRAFT) return fail_arg("need B >= 1, 1 <= N <= 64");
+    *resident = *stride = 0;
+    return with_width(N, [&](auto w) {
+        constexpr int W = decltype(w)::value;
+        if constexpr (W <= 16) {
+            if (N != W || ((long long)B * W) % kBlock != 0) return ATC_OK;   // (not the all-valid form: no prefetch)
+            if (const int rc = fill_prefetch_resident<W>(s, resident)) return rc;
+            if (fill_prefetch_enabled() && step_grid(B, W) > *resident) *stride = *resident;
+        }
+        return ATC_OK;
+    });
+}
 const char* atc_last_error(void) { return g_err; }
 
 int atc_host_mapped_ptr(const void* host, void** dev) {

@@ -22,6 +22,7 @@
 #include <emmintrin.h>   // host side of atc_step_packet: 16-byte loads of the mapped result packet
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
 #include <type_traits>
 
@@ -80,11 +81,11 @@ constexpr int kBlock = 256;
 // one row of 8 stamps per wavefront AND step (row = wavefront * steps + step)
 #ifndef ATC_TRACE_MODE
 #define ATC_TRACE_MODE 0   // 0: the step's phases (tools/trace_rollout.py); 1: stamps 1..5 dissect the step's first phase instead
-#endif
+#endif                     // 3: mode 0 with stamp 1 taken when the state has ARRIVED (behind the rate limits): tools/trace_fill.py
 #define ATC_STAMP_AT(row, n) do { if ((threadIdx.x & 63) == 0 && (row)) (row)[(n)] = __builtin_amdgcn_s_memtime(); } while (0)
-#define ATC_STAMP(n) do { if (ATC_TRACE_MODE == 0) ATC_STAMP_AT(trow, n); } while (0)
-#define ATC_STAMP_B(n) do { if (ATC_TRACE_MODE == 0) ATC_STAMP_AT(so.trace, n); } while (0)
-#define ATC_STAMP_TOP(row, n) do { if (ATC_TRACE_MODE == 1) ATC_STAMP_AT(row, n); } while (0)
+#define ATC_STAMP(n) do { if (ATC_TRACE_MODE == 0 || (ATC_TRACE_MODE == 3 && (n) != 1)) ATC_STAMP_AT(trow, n); } while (0)
+#define ATC_STAMP_B(n) do { if (ATC_TRACE_MODE == 0 || ATC_TRACE_MODE == 3) ATC_STAMP_AT(so.trace, n); } while (0)
+#define ATC_STAMP_TOP(row, n) do { if (ATC_TRACE_MODE == 1) ATC_STAMP_AT(row, n); else if (ATC_TRACE_MODE == 3 && (n) == 2) ATC_STAMP_AT(row, 1); } while (0)
 #define ATC_STAMP_END(row, n) do { if (ATC_TRACE_MODE == 2) ATC_STAMP_AT(row, n); } while (0)   // mode 2: the step's LAST phase dissected
 #define ATC_TRACE_PARAM , unsigned long long* trace_row
 #define ATC_TRACE_PASS(x) , (x)
@@ -421,6 +422,7 @@ struct StepArgs {
     StepDerived q;
     InlineAction ia;
     LdsTab lt;
+    int pf_stride;   // fill-phase prefetch (k_step): behind everything k_skip's argument list shares with this one
 };
 template <typename T>
 __device__ __forceinline__ T kernarg_reread(size_t byte_off, int opaque_zero) {
@@ -1270,6 +1272,25 @@ __device__ __forceinline__ void settle_state(LaneState& ls, EnvState& es) {
     es.amask = (uint64_t)m_lo | ((uint64_t)m_hi << 32);
 }
 
+// Fill-phase prefetch (fast single-step launches of envs of up to 16 aircraft; DESIGN.md section 3, profiles/fill_prefetch_*).  The
+// workgroups of the launch's first round — blockIdx.x < pf_stride, the workgroups the device holds at once (host: launch_step2) —
+// also touch the ac and alt records of the slot pf_stride workgroups further on: they all wait for their own state together, compute
+// together and store together, and until their first stores leave the memory system has nothing to do.  The lines land in the L2 of
+// the XCD that will run workgroup blockIdx.x + pf_stride (workgroups are dealt round-robin to the 8 XCDs, pf_stride is a multiple
+// of 8), which then finds them there.
+//   ONE WORD of each record is requested, not the record: the line comes all the same, and two registers held to the end of the
+//   kernel keep the launch at 71 VGPRs = 7 wavefronts per SIMD (whole records: 78 and 6).  The request is unconditional — a
+//   workgroup with nothing to prefetch reads the first record of its own tile, one line it has just asked for — because behind a
+//   branch the compiler waits for EVERY load at the join, the prefetch included, before the first instruction of the decode.
+//   The values are discarded; the empty asm behind the kernel's last stores keeps them alive, so nothing waits for them before the
+//   in-order return of the lookup-cell gather does anyway.  Measured variants (action too, half a round, behind the gather, whole
+//   records): profiles/experiments/README.md.
+// Why it cannot change a result: the records touched are written in this launch by ONE workgroup, the one they belong to, which
+// reads them (its own loads) before it writes them — whatever this workgroup sees is thrown away; a line that lands in another
+// XCD's L2 than its reader's is never read in this launch, and the next launch starts with the L2 invalidate of every kernel
+// boundary (what makes fetched bytes equal algorithmic bytes today).  The index is in bounds: the whole target tile lies below B * N.
+#define ATC_FILL_PREFETCH(W, FULL, ONE, ALLV) ((ONE) && !(FULL) && (ALLV) && (W) <= 16)
+
 #define ATC_LAT_WAVES 2   // wavefronts per SIMD the latency-bound instantiation is register-budgeted for (<= 256 VGPRs)
 // ONE: single-step launch (T == 1); ALLV: every slot is an aircraft (make_ids); LAT: latency-bound multi-step instantiation (above)
 // LDSG: the latency-bound launch of ONE-aircraft envs with the sector's lookup table staged in LDS (csrc/atc_device.h: LdsTab) — one
@@ -1277,7 +1298,7 @@ __device__ __forceinline__ void settle_state(LaneState& ls, EnvState& es) {
 template <int W, bool FULL, bool ONE, bool ALLV, bool LAT = false, bool LDSG = false>
 __global__ void __launch_bounds__(kBlock, (LDSG ? 1 : LAT ? ATC_LAT_WAVES : ONE ? ATC_MIN_WAVES : ((FULL || W <= 8 || W >= 32) ? ATC_MIN_WAVES_LOOP - 1 : ATC_MIN_WAVES_LOOP)))
 k_step(const float* __restrict__ blob, int off_grid, int B, int N, int T, int hold, atc_state_t st,
-       const float* __restrict__ actions, atc_out_t out, atc_params_t p, StepDerived q_arg, InlineAction ia, LdsTab lt_arg) {
+       const float* __restrict__ actions, atc_out_t out, atc_params_t p, StepDerived q_arg, InlineAction ia, LdsTab lt_arg, int pf_stride) {
     static_assert(!LAT || (!ONE && !FULL), "LAT is an instantiation of the fast multi-step kernels");
     static_assert(!LDSG || (LAT && W == 1 && ALLV), "LDSG is an instantiation of the latency-bound one-aircraft kernel");
     StepDerived q_vec;
@@ -1334,6 +1355,13 @@ k_step(const float* __restrict__ blob, int off_grid, int B, int N, int T, int ho
     int4 la0 = make_int4(0, 0, 0, 0);   // v, heading, altitude target (float64)
     if (la_live) la0 = *at<int4>(st.last_act, d.i * 16u);
     LaneState ls = {{ps.x, ps.y, h0, ps.z, (uint32_t)ps.w}, (uint32_t)la0.x, __hiloint2double(la0.w, la0.z), la0.y, false};
+    int pf_ac = 0, pf_alt = 0;
+    if (ATC_FILL_PREFETCH(W, FULL, ONE, ALLV)) {   // (see ATC_FILL_PREFETCH)
+        const bool pf_on = blockIdx.x < (uint32_t)pf_stride && (blockIdx.x + (uint32_t)pf_stride) * kBlock < BN;
+        const uint32_t pi = pf_on ? d.i + (uint32_t)pf_stride * kBlock : d.slot0;
+        pf_ac = *at<int>(st.ac, pi * 16u);
+        pf_alt = *at<int>(st.alt, pi * 8u);
+    }
 
     // A single step is its own instantiation: with the step count a run-time value everything the loop carries (aircraft
     // and env records, output bases, hoisted sector constants) stays live across the whole body — the straight-line form
@@ -1468,6 +1496,7 @@ k_step(const float* __restrict__ blob, int off_grid, int B, int N, int T, int ho
     store_lane_state(st_end, d, ls, la_live);
     store_env_state<W>(st_end, d, es, hi0);
     if (ATC_KARG_PREFETCH(W, ONE)) asm volatile("" ::"s"(karg_touch));   // (keeps the touches alive; nothing waits for them before here)
+    if (ATC_FILL_PREFETCH(W, FULL, ONE, ALLV)) asm volatile("" ::"v"(pf_ac), "v"(pf_alt));   // (the prefetched words: discarded here)
 #if ATC_TRACE
     if (lane == 0 && trace) trace[((size_t)(blockIdx.x * (kBlock / 64) + (tid >> 6)) * n_steps + (n_steps - 1)) * 8 + 7] = __builtin_amdgcn_s_memtime();
 #endif
@@ -1709,6 +1738,29 @@ static size_t lds_bytes(const atc_scenario*, bool pair_scan, bool step_kernel = 
 // calling thread — a plain thread-local counter that nothing in the library reads back
 static thread_local uint64_t t_launches[ATC_LAUNCH_SLOTS] = {0};
 
+// Fill-phase prefetch of the fast single-step launches (k_step): `stride` = the workgroups the device holds at once = the first
+// round of the launch, from the runtime's occupancy for the instantiation (asked once per thread, instantiation and device) and the
+// device's CU count, rounded DOWN to a multiple of 8: workgroups are dealt round-robin to the 8 XCDs, so workgroup j + stride runs
+// on the XCD whose L2 workgroup j prefetched into.  0 (off) for a grid that fits the first round, and with ATC_NO_FILL_PREFETCH set
+// in the environment (developer knob, read once per process: the A/B run and tests/test_fill_prefetch.py).
+static bool fill_prefetch_enabled() {
+    static const bool on = [] { const char* e = getenv("ATC_NO_FILL_PREFETCH"); return !(e && *e && strcmp(e, "0") != 0); }();
+    return on;
+}
+template <int W>
+static int fill_prefetch_resident(const atc_scenario* s, int* resident) {
+    static thread_local int cached_for = -1, cached = 0;
+    if (cached_for != s->device) {
+        int per_cu = 0;
+        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(&k_step<W, false, true, true>), kBlock,
+                                                             lds_bytes(s, W >= 32, true)));
+        cached = (per_cu * s->n_cu) & ~7;
+        cached_for = s->device;
+    }
+    *resident = cached;
+    return ATC_OK;
+}
+
 template <int W, bool FULL, bool ONE, bool ALLV, bool LAT = false, bool LDSG = false>
 static int launch_step2(const atc_scenario* s, int B, int N, int T, int hold, const atc_state_t* st, const float* actions,
                         const atc_out_t* out, const atc_params_t* p, hipStream_t stream) {
@@ -1724,7 +1776,14 @@ static int launch_step2(const atc_scenario* s, int B, int N, int T, int hold, co
     const int grid = step_grid(B, W);
     LdsTab lt = s->lt;
     if (!LDSG) lt.src = nullptr;
-    hipLaunchKernelGGL((k_step<W, FULL, ONE, ALLV, LAT, LDSG>), dim3(grid), dim3(kBlock), lds, stream, s->d_blob, s->off_grid, B, N, T, hold, *st, actions, *out, *p, derive(*p, s, scan_horizon<W, FULL, ONE>()), inline_action(), lt);
+    int pf_stride = 0;
+    if constexpr (ATC_FILL_PREFETCH(W, FULL, ONE, ALLV)) {
+        if (fill_prefetch_enabled()) {
+            if (const int rc = fill_prefetch_resident<W>(s, &pf_stride)) return rc;
+            if (grid <= pf_stride) pf_stride = 0;
+        }
+    }
+    hipLaunchKernelGGL((k_step<W, FULL, ONE, ALLV, LAT, LDSG>), dim3(grid), dim3(kBlock), lds, stream, s->d_blob, s->off_grid, B, N, T, hold, *st, actions, *out, *p, derive(*p, s, scan_horizon<W, FULL, ONE>()), inline_action(), lt, pf_stride);
     HIP_TRY(hipGetLastError());
     constexpr int form = LDSG ? ATC_LF_LDSG : LAT ? ATC_LF_LAT : FULL ? (ONE ? ATC_LF_FULL_ONE : ATC_LF_FULL_MULTI)
                          : ONE ? (ALLV ? ATC_LF_ALLV_ONE : ATC_LF_GEN_ONE) : (ALLV ? ATC_LF_ALLV_MULTI : ATC_LF_GEN_MULTI);

@@ -448,6 +448,13 @@ enum {
     ATC_SKIP_LAUNCH_SLOTS = 7
 };
 int atc_skip_launch_counts(uint64_t* out, int n);
+/* Fill-phase prefetch of the fast single-step launch (required outputs only, N a power of two <= 16, B * N a multiple of 256): the
+ * workgroups the first `resident` hold at once also request the state and action lines of the workgroup `resident` further on,
+ * into the L2 that workgroup will read them from.  Results do not depend on it.  *resident = the device's resident workgroups for
+ * that kernel (the runtime's occupancy x CUs, rounded down to a multiple of 8; 0 where the form does not apply), *stride = what an
+ * atc_step of B x N passes to the kernel: `resident` when the launch has more workgroups (B * N / 256) than that, else 0 (off) —
+ * and 0 always with ATC_NO_FILL_PREFETCH set in the environment (developer knob, read once per process).  Host side only. */
+int atc_fill_prefetch_info(const atc_scenario_t* s, int B, int N, int* resident, int* stride);
 
 /* Uploads a compiled scenario blob (host pointer, n_words floats) to `device`.
  * Replaces: AtcGym.__init__ scenario unpacking, atc_gym.py:45-58. */
