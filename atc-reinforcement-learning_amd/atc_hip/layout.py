@@ -70,3 +70,8 @@ LAUNCH_SERVE, LAUNCH_SLOTS = 56, 57
 LF_NAMES = ("full-one", "full-multi", "gen-one", "allv-one", "gen-multi", "allv-multi", "lat", "ldsg")
 # frame skip (include/atc_step.h: atc_step_skip): largest block length; its own launch record, slot = log2(W)
 SKIP_MAX, SKIP_LAUNCH_SLOTS = 255, 7
+# traffic observation (include/atc_step.h: atc_observe_traffic): K <= TRAFFIC_MAX_K records of TRAFFIC_DIM words per aircraft; its own
+# launch record, slot = log2(W)
+TRAFFIC_DIM, TRAFFIC_MAX_K = 8, 8
+T_PRESENT, T_DIST, T_AHEAD, T_RIGHT, T_DH, T_DV_AHEAD, T_DV_RIGHT, T_SLOT = range(8)
+TRAFFIC_LAUNCH_SLOTS = 7

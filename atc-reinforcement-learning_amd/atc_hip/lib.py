@@ -52,7 +52,7 @@ EXPORTS = ("atc_abi_version", "atc_last_error", "atc_launch_counts", "atc_host_m
            "atc_scenario_attach_lds_table", "atc_query_mva", "atc_query_mva_lds",
            "atc_query_mva_index", "atc_query_corridor", "atc_query_shaping", "atc_reset", "atc_observe", "atc_step",
            "atc_step_multi", "atc_step_packet", "atc_rollout", "atc_rollout_hold", "atc_serve_start", "atc_serve_step", "atc_serve_stop",
-           "atc_step_skip", "atc_skip_launch_counts", "atc_fill_prefetch_info")
+           "atc_step_skip", "atc_skip_launch_counts", "atc_fill_prefetch_info", "atc_observe_traffic", "atc_traffic_launch_counts")
 
 def load():
     """Loads libatcstep.so; raises (never falls back) when it has not been built."""
@@ -65,7 +65,7 @@ def load():
     import torch  # noqa: F401  — first, so that libatcstep.so binds to the HIP runtime PyTorch-ROCm already loaded
     lib = C.CDLL(LIB_PATH)
     vp, ci = C.c_void_p, C.c_int
-    # (the ABI number did not change when atc_step_skip was added, so it does not catch a library built before it)
+    # (the ABI number did not change when atc_step_skip / atc_observe_traffic were added, so it does not catch a library built before them)
     missing = [name for name in EXPORTS if not hasattr(lib, name)]
     if missing:
         raise RuntimeError("libatcstep.so lacks %s — rebuild" % ", ".join(missing))
@@ -94,6 +94,8 @@ def load():
     lib.atc_step_skip.argtypes = [vp, ci, ci, ci, C.POINTER(AtcState), vp, C.POINTER(AtcOut), vp, C.POINTER(AtcParams), vp]
     lib.atc_skip_launch_counts.argtypes = [C.POINTER(C.c_uint64), ci]
     lib.atc_fill_prefetch_info.argtypes = [vp, ci, ci, C.POINTER(ci), C.POINTER(ci)]
+    lib.atc_observe_traffic.argtypes = [vp, ci, ci, ci, C.POINTER(AtcState), vp, C.POINTER(AtcParams), vp]
+    lib.atc_traffic_launch_counts.argtypes = [C.POINTER(C.c_uint64), ci]
     for name in EXPORTS:
         if name not in ("atc_abi_version", "atc_last_error"):
             getattr(lib, name).restype = ci
@@ -128,6 +130,14 @@ def skip_launch_counts():
     widths with a count of zero left out.  Separate from launch_counts(), which a skip call leaves as it is."""
     buf = (C.c_uint64 * L.SKIP_LAUNCH_SLOTS)()
     check(load().atc_skip_launch_counts(buf, L.SKIP_LAUNCH_SLOTS))
+    return {1 << i: int(v) for i, v in enumerate(buf) if v}
+
+
+def traffic_launch_counts():
+    """Launches of the traffic-observation kernel (atc_observe_traffic) made by the calling thread so far, by lane-group width:
+    {16: n, ...}, widths with a count of zero left out.  Separate from launch_counts() and skip_launch_counts()."""
+    buf = (C.c_uint64 * L.TRAFFIC_LAUNCH_SLOTS)()
+    check(load().atc_traffic_launch_counts(buf, L.TRAFFIC_LAUNCH_SLOTS))
     return {1 << i: int(v) for i, v in enumerate(buf) if v}
 
 

@@ -34,10 +34,15 @@ _Base = _vecenv_base()
 
 class AtcSBVecEnv(_Base):
     def __init__(self, num_envs, num_aircraft=1, sim_parameters=None, scenario=None, device=0, seed=0, sparse_infos=None,
-                 host_mapped=None, frame_skip=1, **kw):
+                 host_mapped=None, frame_skip=1, traffic=0, **kw):
         """frame_skip > 1: every step() holds its actions for up to `frame_skip` env steps (AtcVecEnv.step_skip: one launch; an env
         stops at its first done) and returns one transition per env — the summed reward, the last observation; infos carry
-        "frame_steps", the env steps the transition covers.  Monitor's episode["l"] keeps counting ENV steps.  1: a plain step."""
+        "frame_steps", the env steps the transition covers.  Monitor's episode["l"] keeps counting ENV steps.  1: a plain step.
+        traffic=K (1 .. 8) widens every observation to [N * 10 | N * K * 7]: behind the aircraft's own words, words 0..6 of each
+        aircraft's K traffic records (AtcVecEnv(traffic=K): present, distance, ahead, right, altitude difference, relative velocity
+        ahead / right of its K nearest other aircraft; the slot index is not a network input), of the state the returned
+        observation describes.  The traffic part of a "terminal_observation" is K ABSENT records (zeros) per aircraft: the state it
+        would describe is gone once the auto-reset has run inside the step.  0 (default): observations as they were."""
         try:   # gym's own space classes where gym is there (stable-baselines' policies type-check them; gym is its dependency)
             from gym.spaces import Box, MultiDiscrete
         except ImportError:
@@ -52,7 +57,7 @@ class AtcSBVecEnv(_Base):
             raise ValueError("1 <= frame_skip <= %d" % L.SKIP_MAX)
         self.vec = AtcVecEnv(num_envs, num_aircraft, sim_parameters=sim_parameters, scenario=scenario, device=device,
                              auto_reset=True, seed=seed, want_raw_obs=True, want_term_obs=True, host_mapped=host_mapped,
-                             **kw)
+                             traffic=traffic, **kw)
         self.num_envs = self.vec.B
         n = self.vec.N
         sp = self.vec.sim_parameters
@@ -60,7 +65,8 @@ class AtcSBVecEnv(_Base):
             self.action_space = MultiDiscrete([20, 380, 360] * n)
         else:                         # atc_gym.py:81-82
             self.action_space = Box(low=-np.ones(3 * n, np.float32), high=np.ones(3 * n, np.float32))
-        self.observation_space = Box(low=-1.0, high=1.0, shape=(L.OBS_DIM * n,))  # atc_gym.py:113
+        self.traffic_dim = n * self.vec.traffic_k * (L.TRAFFIC_DIM - 1)   # words 0..6 of every record
+        self.observation_space = Box(low=-1.0, high=1.0, shape=(L.OBS_DIM * n + self.traffic_dim,))  # atc_gym.py:113 [+ traffic]
         if _Base is not object:   # VecEnv.__init__(num_envs, observation_space, action_space): the same three attributes
             _Base.__init__(self, self.num_envs, self.observation_space, self.action_space)
         self.reward_range = (-3000.0, 23000.0)                                    # atc_gym.py:115
@@ -78,7 +84,14 @@ class AtcSBVecEnv(_Base):
     # -- VecEnv protocol ---------------------------------------------------------------------------------------------
     def reset(self):
         """All envs restart; returns the RAW reset observations [B, 10 N] (atc_gym.py:365 returns the raw state)."""
-        return self.vec.reset().cpu().numpy().copy()
+        obs = self.vec.reset()
+        if self.traffic_dim:
+            return self.vec.torch.cat([obs, self._traffic_words()], dim=1).cpu().numpy()
+        return obs.cpu().numpy().copy()
+
+    def _traffic_words(self):
+        """[B, N K 7]: words 0..6 of every record of vec.traffic (a copy, on the tensor's own device)"""
+        return self.vec.traffic[..., :L.TRAFFIC_DIM - 1].reshape(self.num_envs, self.traffic_dim)
 
     def step_async(self, actions):
         a = np.asarray(actions, dtype=np.float32).reshape(self.num_envs, self.vec.N, L.ACT_DIM)
@@ -104,15 +117,21 @@ class AtcSBVecEnv(_Base):
             # (host_mapped="io" keeps the state and the episode records in HBM: those two come over with a copy)
             ep_r, ep_l = vec.ep_return.cpu().numpy().copy(), vec.ep_length.cpu().numpy().copy()
             n_h = info["frame_steps"].numpy().copy() if skip else None
+            tr_h = self._traffic_words().numpy() if self.traffic_dim else None
         else:
             pack = torch.cat([obs, info["original_state"], info["terminal_observation"],
                               rew[:, None], done[:, None].to(torch.float32), vec.ep_return[:, None],
                               vec.ep_length[:, None].to(torch.float32)] +
-                             ([info["frame_steps"][:, None].to(torch.float32)] if skip else []), dim=1).cpu().numpy()   # one device->host hop
+                             ([info["frame_steps"][:, None].to(torch.float32)] if skip else []) +
+                             ([self._traffic_words()] if self.traffic_dim else []), dim=1).cpu().numpy()   # one device->host hop
             obs_h, raw_h, term_h = pack[:, :d], pack[:, d:2 * d], pack[:, 2 * d:3 * d]
             rew_h, done_h = pack[:, 3 * d], pack[:, 3 * d + 1] != 0
             ep_r, ep_l = pack[:, 3 * d + 2], pack[:, 3 * d + 3]
             n_h = pack[:, 3 * d + 4] if skip else None
+            tr_h = pack[:, pack.shape[1] - self.traffic_dim:] if self.traffic_dim else None
+        if self.traffic_dim:   # [own words | traffic]; a terminal observation's traffic part is absent records: zeros
+            obs_h = np.concatenate([obs_h, tr_h], axis=1)
+            term_h = np.concatenate([term_h, np.zeros((self.num_envs, self.traffic_dim), np.float32)], axis=1)
         now = round(time.time() - self._t0, 6)
         self.original_state = raw_h
         if self.sparse_infos:
@@ -179,7 +198,10 @@ class AtcSBVecEnv(_Base):
         if method_name == "reset":
             mask = np.zeros(self.num_envs, np.uint8)
             mask[idx] = 1
-            obs = self.vec.reset(mask=mask).cpu().numpy()
+            obs = self.vec.reset(mask=mask)
+            if self.traffic_dim:
+                obs = self.vec.torch.cat([obs, self._traffic_words()], dim=1)
+            obs = obs.cpu().numpy()
             return [obs[i].copy() for i in idx]
         if method_name == "seed":
             return [self.vec.seed(*method_args, **method_kwargs)[0] for _ in idx]

@@ -40,7 +40,7 @@ class AtcVecEnv:
     def __init__(self, num_envs, num_aircraft=1, sim_parameters=None, scenario=None, device=0, auto_reset=True,
                  spawn="auto", seed=0, grid_cell="auto", want_raw_obs=False, want_ac_reward=False, want_min_sep=False,
                  want_term_obs=False, timestep_limit=6000, sep_nm=3.0, sep_ft=1000.0, conflict_reward=-200.0,
-                 host_mapped=False, keep_active=False, want_packet=False, check_held=False, lds_table=True):
+                 host_mapped=False, keep_active=False, want_packet=False, check_held=False, lds_table=True, traffic=0):
         """host_mapped=True keeps state and outputs in pinned host memory mapped into the device (zero-copy): the kernels
         read / write it over the host link, every call ends with a stream synchronisation, and what is returned are CPU
         tensors.  Meant for tiny latency-bound batches (the single-env AtcGym); large batches belong in HBM.
@@ -50,7 +50,14 @@ class AtcVecEnv:
         keep_active=True is the reference's single-aircraft rule (ATC_M_KEEP_ACTIVE): an aircraft that reaches the corridor
         ends the episode and stays under control instead of being handed over.
         check_held=True (debugging aid) verifies the promise of step(..., held=True) — the actions equal those of the previous
-        step — on every such call and raises if it is broken (costs a device comparison and a synchronisation per step)."""
+        step — on every such call and raises if it is broken (costs a device comparison and a synchronisation per step).
+        traffic=K (1 .. 8) adds the traffic observation (atc_observe_traffic, include/atc_step.h): `self.traffic`, [B, N, K, 8]
+        float32 — for every aircraft its K nearest other aircraft under control, nearest first, as records (present, distance,
+        ahead, right, altitude difference, relative velocity ahead / right, slot) in the observing aircraft's own frame, scaled
+        like the observation when the sim parameters normalise.  reset(), observe(), step() and step_skip() then launch it after
+        their own call on the same stream and info["traffic"] is that tensor: it describes the state the env is in NOW (after an
+        auto-reset: the fresh spawn state, consistent with the raw reset observation the step returns).  traffic=0 (default): no
+        such tensor, launch or key."""
         torch = _lib._torch_cuda()
         self.torch = torch
         self._check_held = bool(check_held)
@@ -62,6 +69,9 @@ class AtcVecEnv:
         if not 1 <= num_aircraft <= L.MAX_AIRCRAFT:
             raise ValueError("1 <= num_aircraft <= %d" % L.MAX_AIRCRAFT)
         self.B, self.N = int(num_envs), int(num_aircraft)
+        self.traffic_k = int(traffic)
+        if not 0 <= self.traffic_k <= L.TRAFFIC_MAX_K:
+            raise ValueError("0 <= traffic <= %d" % L.TRAFFIC_MAX_K)
         self.num_envs = self.B
         if grid_cell == "auto":
             # the batch's preferred cell size, or the next coarser one the sector's blob can hold (a sector a few times LOWW's
@@ -139,6 +149,8 @@ class AtcVecEnv:
         if want_packet and not (self.host_mapped and N == 1):
             raise ValueError("want_packet needs host_mapped=True and num_aircraft=1")
         self.packet = z((B, L.PKT_CHUNKS, 4), i32) if want_packet else None
+        self.traffic = z((B, N, self.traffic_k, L.TRAFFIC_DIM), f32) if self.traffic_k else None
+        self._traffic_ptr = self._ptr(self.traffic)
         # exact heading counts / last heading target of aircraft whose 32-bit heading fields are saturated ("WIDE", ABI 19): the
         # reference's heading is unbounded (model.py:104-120).  Untouched while headings stay inside (-76, 436) deg.
         # (allocated after everything a step streams through, so that those tensors sit where they would without it)
@@ -236,6 +248,7 @@ class AtcVecEnv:
             _lib.check(self._lib.atc_reset(self.sector.handle, self.B, self.N, C.byref(self._state),
                                            m.data_ptr() if m is not None else None, self._ptr(self.obs),
                                            C.byref(self.params), int(first), self._stream()))
+            self._launch_traffic()
         self._finish()
         return self.obs
 
@@ -249,8 +262,27 @@ class AtcVecEnv:
             _lib.check(self._lib.atc_observe(self.sector.handle, self.B, self.N, C.byref(self._state),
                                              m.data_ptr() if m is not None else None, self._ptr(self.obs),
                                              C.byref(self.params), self._stream()))
+            self._launch_traffic()
         self._finish()
         return self.obs
+
+    def _launch_traffic(self):
+        """atc_observe_traffic of the current state into self.traffic, on the current stream (nothing with traffic=0)"""
+        if self.traffic_k:
+            rc = self._lib.atc_observe_traffic(self.sector.handle, self.B, self.N, self.traffic_k, self._state_ref, self._traffic_ptr,
+                                               self._params_ref, self.torch.cuda.current_stream().cuda_stream)
+            if rc:
+                _lib.check(rc)
+
+    def observe_traffic(self):
+        """The traffic observation of the CURRENT state (atc_observe_traffic): launches on the current stream and returns
+        self.traffic, [B, N, K, 8] — see the class's `traffic` argument.  Needs AtcVecEnv(traffic=K) with K >= 1."""
+        if not self.traffic_k:
+            raise ValueError("this env was made without a traffic observation: AtcVecEnv(..., traffic=K), 1 <= K <= %d" % L.TRAFFIC_MAX_K)
+        with self.torch.cuda.device(self.device):
+            self._launch_traffic()
+        self._finish()
+        return self.traffic
 
     def _as_actions(self, actions, lead=()):
         torch = self.torch
@@ -287,12 +319,15 @@ class AtcVecEnv:
                                     pref, torch.cuda.current_stream().cuda_stream)
             if rc:
                 _lib.check(rc)
+            if self.traffic_k:
+                self._launch_traffic()
             self._keep = actions
             return self.obs, self.reward, self.done, self._info_cache
         a = self._as_actions(actions)
         with torch.cuda.device(self.device):
             _lib.check(self._lib.atc_step(self.sector.handle, self.B, self.N, C.byref(self._state), self._ptr(a),
                                           C.byref(self._out), pref, self._stream()))
+            self._launch_traffic()
         self._keep = a
         self._finish()
         return self.obs, self.reward, self.done, self._info_cache
@@ -322,12 +357,15 @@ class AtcVecEnv:
                                          self._frame_steps_ptr, self._params_ref, torch.cuda.current_stream().cuda_stream)
             if rc:
                 _lib.check(rc)
+            if self.traffic_k:
+                self._launch_traffic()
             self._keep = actions
             return self.obs, self.reward, self.done, self._info_skip
         a = self._as_actions(actions)
         with torch.cuda.device(self.device):
             _lib.check(self._lib.atc_step_skip(self.sector.handle, self.B, self.N, skip, C.byref(self._state), self._ptr(a),
                                                C.byref(self._out), self._frame_steps_ptr, C.byref(self.params), self._stream()))
+            self._launch_traffic()
         self._keep = a
         self._finish()
         return self.obs, self.reward, self.done, self._info_skip
@@ -381,12 +419,16 @@ class AtcVecEnv:
             info["min_separation"] = self.min_sep
         if self.term_obs is not None:
             info["terminal_observation"] = self.term_obs
+        if self.traffic is not None:
+            info["traffic"] = self.traffic
         return info
 
     def rollout(self, actions, out=None, hold=1):
         """T consecutive steps in one launch (state stays in registers).  actions: [T / hold, B, N, 3]; each action block is
         applied for `hold` consecutive steps (frame skip, learning/atc-gym-demo.py:18-19), so T = hold * actions.shape[0].
-        Returns a dict of [T, ...] device tensors (obs, reward, done, flags [+ optional outputs when `out` provides them])."""
+        Returns a dict of [T, ...] device tensors (obs, reward, done, flags [+ optional outputs when `out` provides them]).
+        A rollout does not produce the traffic observation (AtcVecEnv(traffic=K)): there is no [T, ...] traffic output, and
+        self.traffic keeps what the last reset / observe / step left; call observe_traffic() afterwards for the final state."""
         torch = self.torch
         hold = int(hold)
         n_blocks = int(actions.shape[0])

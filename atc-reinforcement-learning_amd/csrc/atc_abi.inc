@@ -16,6 +16,11 @@ int atc_skip_launch_counts(uint64_t* out, int n) {
     for (int i = 0; i < n && i < ATC_SKIP_LAUNCH_SLOTS; ++i) out[i] = t_skip_launches[i];
     return ATC_OK;
 }
+int atc_traffic_launch_counts(uint64_t* out, int n) {
+    if (!out || n < 0) return fail_arg("null pointer");
+    for (int i = 0; i < n && i < ATC_TRAFFIC_LAUNCH_SLOTS; ++i) out[i] = t_traffic_launches[i];
+    return ATC_OK;
+}
 int atc_fill_prefetch_info(const atc_scenario_t* s, int B, int N, int* resident, int* stride) {
     if (!s || !resident || !stride) return fail_arg("null pointer");
     if (B < 1 || N < 1 || N > ATC_MAX_AIRCRAFT) return fail_arg("need B >= 1, 1 <= N <= 64");
@@ -404,6 +409,11 @@ int atc_rollout_hold(const atc_scenario_t* s, int B, int N, int T, int hold, con
 int atc_step_skip(const atc_scenario_t* s, int B, int N, int K, const atc_state_t* st, const float* actions, const atc_out_t* out,
                   uint8_t* n_steps, const atc_params_t* p, void* stream) {
     return skip_common(s, B, N, K, st, actions, out, n_steps, p, stream);
+}
+
+int atc_observe_traffic(const atc_scenario_t* s, int B, int N, int K, const atc_state_t* st, float* traffic, const atc_params_t* p,
+                        void* stream) {
+    return traffic_common(s, B, N, K, st, traffic, p, stream);
 }
 
 }  // extern "C"

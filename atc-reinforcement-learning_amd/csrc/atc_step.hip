@@ -1714,6 +1714,7 @@ k_serve(const float* __restrict__ blob, int off_grid, atc_state_t st, atc_out_t 
 }
 
 #include "atc_aux_kernels.inc"   // k_reset, k_observe, k_reset_env, k_query_*
+#include "atc_traffic.inc"       // k_traffic (atc_observe_traffic)
 
 // ---------------------------------------------------------------------------------------------------------------
 // host side of the C-ABI
@@ -1895,6 +1896,44 @@ static int skip_common(const atc_scenario_t* s, int B, int N, int K, const atc_s
     if (p->mode & ATC_M_ACTIONS_HELD) return fail_arg("ATC_M_ACTIONS_HELD is for atc_step only: a frame-skip call's first step carries a fresh decision");
     if (const int rc = check_dt(s, p)) return rc;
     return with_width(N, [&](auto w) { return launch_skip<decltype(w)::value>(s, B, N, K, st, actions, out, n_steps, p, (hipStream_t)stream); });
+}
+
+// ---- traffic observation (include/atc_step.h: atc_observe_traffic) -------------------------------------------------------------
+// its own launch record (atc_traffic_launch_counts): slot = log2(W), the rules of the frame-skip record
+static thread_local uint64_t t_traffic_launches[ATC_TRAFFIC_LAUNCH_SLOTS] = {0};
+
+template <int W, int KT>
+static int launch_traffic2(int B, int N, const atc_state_t* st, float* traffic, const TrafficArgs& q, hipStream_t stream) {
+    hipLaunchKernelGGL((k_traffic<W, KT>), dim3(step_grid(B, W)), dim3(kBlock), 0, stream, B, N, *st, traffic, q);
+    HIP_TRY(hipGetLastError());
+    ++t_traffic_launches[__builtin_ctz(W)];
+    return ATC_OK;
+}
+// the compiled list lengths are 1, 2, 4, 8: a K in between runs the next one and stores its first K records
+template <int W>
+static int launch_traffic(int B, int N, const atc_state_t* st, float* traffic, const TrafficArgs& q, hipStream_t stream) {
+    if (q.K == 1) return launch_traffic2<W, 1>(B, N, st, traffic, q, stream);
+    if (q.K == 2) return launch_traffic2<W, 2>(B, N, st, traffic, q, stream);
+    if (q.K <= 4) return launch_traffic2<W, 4>(B, N, st, traffic, q, stream);
+    return launch_traffic2<W, 8>(B, N, st, traffic, q, stream);
+}
+
+static int traffic_common(const atc_scenario_t* s, int B, int N, int K, const atc_state_t* st, float* traffic, const atc_params_t* p,
+                          void* stream) {
+    // K first, before any pointer is looked at
+    if (K < 1 || K > ATC_TRAFFIC_MAX_K) return fail_arg("K (traffic records per aircraft) must be 1 .. 8");
+    if (!traffic) return fail_arg("null pointer");
+    if (const int rc = check_env_args(s, B, N, st, p)) return rc;
+    TrafficArgs q;
+    q.pos_inv = (double)s->consts[ATC_C_POS_INV];
+    q.x0 = (double)s->consts[ATC_C_POS_X0];
+    q.y0 = (double)s->consts[ATC_C_POS_Y0];
+    const bool nrm = (p->mode & ATC_M_NORMALIZE) != 0;
+    q.s_pos = nrm ? 1.0f / s->consts[ATC_C_WORLD_DIAG] : 1.0f;
+    q.h_div = nrm ? s->consts[ATC_C_H_MAX] : 1.0f;
+    q.s_v = nrm ? 1.0f / (2.0f * s->consts[ATC_C_V_MAX]) : 1.0f;
+    q.K = K;
+    return with_width(N, [&](auto w) { return launch_traffic<decltype(w)::value>(B, N, st, traffic, q, (hipStream_t)stream); });
 }
 
 #include "atc_abi.inc"   // the extern "C" entry points (host side)

@@ -618,6 +618,50 @@ int atc_rollout_hold(const atc_scenario_t* s, int B, int N, int T, int hold, con
 int atc_step_skip(const atc_scenario_t* s, int B, int N, int K, const atc_state_t* st, const float* actions /* [B*N*3] */,
                   const atc_out_t* out, uint8_t* n_steps /* nullable [B] */, const atc_params_t* p, void* stream);
 
+/* TRAFFIC OBSERVATION (extension): what each aircraft sees of the others.  The ten observation words per aircraft (ATC_OBS_DIM,
+ * atc_gym.py:262-277) say nothing about any other aircraft, although envs of N > 1 aircraft carry the separation scan and its
+ * penalty.  atc_observe_traffic is a query of the CURRENT state — a launch of its own, separate from the step: for every aircraft
+ * the K nearest other aircraft under control in the same env, nearest first, each as a record of ATC_TRAFFIC_DIM words in the
+ * observing aircraft's own frame.  1 <= K <= ATC_TRAFFIC_MAX_K.
+ *
+ * Reads st->ac, st->alt, the active mask (ATC_ENV_MASK_LO, and ATC_STAT_MASK_HI for N > 32) and st->phi_wide (only for aircraft
+ * whose phi_fix is saturated); writes nothing but `traffic`: the state is bit-identical afterwards.
+ *
+ * Candidates and order.  For aircraft i of env e the candidates are the slots j != i of that env whose active-mask bit is set.
+ * With the fp32 positions every other formula sees (pos_to_real = (float)(origin + fix 2^-k), one rounding):
+ *     dx = xj - xi,  dy = yj - yi,  d2 = fma(dx, dx, dy * dy)          (the separation scan's own expression)
+ * Candidates are ordered by (d2, j) ascending — exact ties go to the lower slot; d2 is finite and non-negative, so its bit pattern
+ * orders it and the order is an integer result: exact.  Record r < min(K, candidates) describes the r-th candidate; the remaining
+ * records are ABSENT: words 0..6 = 0, word 7 = -1.  An aircraft that is itself not under control (mask bit clear) gets K absent
+ * records; so does every aircraft of a one-aircraft env.
+ *
+ * A present record (fp32 operations, each rounded once, unless stated):
+ *   ATC_T_PRESENT   1
+ *   ATC_T_DIST      sqrt(d2) [nm]
+ *   ATC_T_AHEAD     dx sin(th) + dy cos(th)          th = aircraft i's heading, a compass heading (model.py:122-129): "ahead" is
+ *   ATC_T_RIGHT     dx cos(th) - dy sin(th)          (sin th, cos th), "right" is (cos th, -sin th).  th comes from the heading
+ *                                                    counts (a WIDE heading wrapped first, as atc_observe does); sin / cos by the
+ *                                                    kinematics' float64 polynomials or any evaluation accurate to 1e-6
+ *   ATC_T_DH        (float)hj - (float)hi [ft]       the scan's expression without the absolute value: exact
+ *   ATC_T_DV_AHEAD  the relative ground velocity dv = vel_j - vel_i [kt], vel = v (sin phi, cos phi), v = v_fix 2^-23, rotated into
+ *   ATC_T_DV_RIGHT  i's frame exactly like (dx, dy).  An intruder ahead with a negative ATC_T_DV_AHEAD is closing.
+ *   ATC_T_SLOT      (float)j
+ * With ATC_M_NORMALIZE in p->mode words 1..3 are divided by ATC_C_WORLD_DIAG, word 4 by ATC_C_H_MAX, words 5..6 by 2 ATC_C_V_MAX
+ * (word 4 as the correctly rounded fp32 quotient — it is exact before; the others as a product with the fp32 reciprocal, they are
+ * values); words 0 and 7 are never scaled.
+ *
+ * ATC_ERR_ARG: K outside 1 .. 8 — checked first, before any pointer —, traffic == NULL, the argument errors of atc_observe.
+ * Counted by atc_traffic_launch_counts only: slot = log2(W), per calling thread, only grows, a refused or failed call is not
+ * counted (the rules of atc_skip_launch_counts). */
+#define ATC_TRAFFIC_DIM 8
+#define ATC_TRAFFIC_MAX_K 8
+enum { ATC_T_PRESENT = 0, ATC_T_DIST = 1, ATC_T_AHEAD = 2, ATC_T_RIGHT = 3, ATC_T_DH = 4,
+       ATC_T_DV_AHEAD = 5, ATC_T_DV_RIGHT = 6, ATC_T_SLOT = 7 };
+int atc_observe_traffic(const atc_scenario_t* s, int B, int N, int K, const atc_state_t* st,
+                        float* traffic /* [B*N][K][ATC_TRAFFIC_DIM] */, const atc_params_t* p, void* stream);
+enum { ATC_TRAFFIC_LAUNCH_SLOTS = 7 };
+int atc_traffic_launch_counts(uint64_t* out, int n);
+
 #ifdef __cplusplus
 }
 #endif
