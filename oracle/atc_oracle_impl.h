@@ -480,6 +480,29 @@ int FN(atc_oracle_reset)(const REAL* S, int B, int N, const FN(orc_state_t) * st
     return 0;
 }
 
+/* AtcGym._get_state(0) (atc_gym.py:262-277,351) of the CURRENT state of every env whose mask byte is non-zero (mask == NULL: all):
+ * the RAW observation with mva = 0, as reset_env writes it for a fresh spawn — here for whatever state the aircraft are in, handed-over
+ * aircraft included.  A WIDE heading (fp32 spec) goes through phi_eff / phi_obs exactly as in the step: word 9 from the wrapped
+ * counts, word 3 the unwrapped heading.  Rows of unmasked envs are not written; the state is only read. */
+int FN(atc_oracle_observe)(const REAL* S, int B, int N, const FN(orc_state_t) * st, const uint8_t* mask, float* obs) {
+    if (!S || !st || !obs || B < 0 || N < 1 || N > ATC_MAX_AIRCRAFT) return -1;
+    for (int e = 0; e < B; ++e) {
+        if (mask && !mask[e]) continue;
+        for (int k = 0; k < N; ++k) {
+            const size_t i = (size_t)e * N + k;
+#if ORC_FIXED_POS
+            const REAL phi_r = FN(phi_real)(FN(phi_eff)(st->phi[i], st->phi_wide[2 * i]));
+            const REAL phi_o = FN(phi_obs)(st->phi[i], st->phi_wide[2 * i]);
+#else
+            const REAL phi_r = st->phi[i], phi_o = st->phi[i];
+#endif
+            REAL d, pr, gp;
+            FN(get_state)(S, st->x[i], st->y[i], st->h[i], phi_r, phi_o, FN(v_real)(st->v[i]), (REAL)0, obs + i * 10, &d, &pr, &gp);
+        }
+    }
+    return 0;
+}
+
 /* AtcGym.step (atc_gym.py:128-192) for B envs x N aircraft. */
 int FN(atc_oracle_step)(const REAL* S, int B, int N, const FN(orc_state_t) * st, const REAL* actions,
                         const FN(orc_out_t) * out, const atc_params_t* p) {

@@ -124,6 +124,19 @@ class OracleEnv:
         assert rc == 0
         return self.obs.copy()
 
+    def observe(self, mask=None, out=None):
+        """AtcGym._get_state(0) of the CURRENT state (atc_oracle_observe): the RAW observation, mva = 0, of every env whose mask
+        byte is non-zero (None: all) written into `out` ([B, N, 10] float32, default self.obs — the array reset() writes); rows of
+        unmasked envs keep what they held.  Returns that array itself, not a copy."""
+        m = None if mask is None else np.ascontiguousarray(mask, np.uint8)
+        out = self.obs if out is None else out
+        assert out.dtype == np.float32 and out.flags.c_contiguous and out.size == self.B * self.N * 10
+        assert m is None or m.size == self.B
+        fn = getattr(lib(), "atc_oracle_observe" + self.sfx)
+        rc = fn(_ptr(self.blob), self.B, self.N, self._st, _ptr(m), _ptr(out))
+        assert rc == 0
+        return out
+
     def _nm(self, p, axis):
         if not self.fixed:
             return p

@@ -20,6 +20,7 @@ import sys
 import numpy as np
 import pytest
 
+import bars
 import helpers as H
 import skip_ref as R
 from atc_hip import layout as L
@@ -266,47 +267,19 @@ def _env(scn, B, N, auto_reset, seed, full, **kw):
 
 
 def _compare_outputs(env, ret, ref, comp, full, rows=slice(None), tag=None):
+    """the bars of this file's docstring, kept in tests/bars.py (the call-sequence tests apply them too)"""
     B, N = ref["obs"].shape[0], env.N
     obs, rew, done, info = ret
     cpu = lambda t: t.cpu().numpy()[rows]   # noqa: E731
-    assert np.array_equal(cpu(info["flags"]).astype(np.uint16), ref["flags"]), ("flags", tag)
-    assert np.array_equal(cpu(done), ref["done"]), ("done", tag)
-    assert np.array_equal(cpu(info["frame_steps"]), ref["n_steps"]), ("n_steps", tag)
-    on = cpu(obs).reshape(B, N, 10)
-    err = np.abs(on - ref["obs"]) / np.maximum(1.0, np.abs(ref["obs"]))
-    print("frame skip", tag, "max obs err %.3g" % err.max(), end=" ")
-    assert np.all(err <= 1e-5), ("obs", tag, err.max())
-    tol = 1e-5 * ref["reward_scale"]   # the per-step bar, added up over the executed steps
-    rerr = np.abs(cpu(rew).astype(np.float64) - ref["reward"])
-    print("max reward err / bar %.3g" % (rerr / tol).max())
-    assert np.all(rerr <= tol), ("reward", tag, (rerr / tol).max())
+    got = {"flags": cpu(info["flags"]), "done": cpu(done), "n_steps": cpu(info["frame_steps"]), "obs": cpu(obs).reshape(B, N, 10),
+           "reward": cpu(rew)}
     if full:
-        half = 0.5 * comp.norm_max.astype(np.float64)
-        raw = cpu(info["original_state"]).reshape(B, N, 10)
-        assert np.all(np.abs(raw - ref["raw_obs"]) <= 1e-5 * half), ("raw_obs", tag)
-        acr = cpu(info["aircraft_reward"])
-        assert np.all(np.abs(acr.astype(np.float64) - ref["ac_reward"]) <= 1e-5 * ref["ac_reward_scale"]), ("ac_reward", tag)
-        assert np.array_equal(cpu(info["min_separation"]), ref["min_sep"]), ("min_sep", tag)
-        tob = cpu(info["terminal_observation"]).reshape(B, N, 10)
-        assert np.all(np.abs(tob - ref["term_obs"]) <= 1e-5 * np.maximum(1.0, np.abs(ref["term_obs"]))), ("term_obs", tag)
+        got.update(raw_obs=cpu(info["original_state"]).reshape(B, N, 10), ac_reward=cpu(info["aircraft_reward"]),
+                   min_sep=cpu(info["min_separation"]), term_obs=cpu(info["terminal_observation"]).reshape(B, N, 10))
+    bars.check_skip_outputs(got, ref, bars.half_range(comp), full, tag)
 
 
-def _compare_state(env, orc, rows_env=slice(None), rows_ac=slice(None)):
-    e = lambda t: t.cpu().numpy()[rows_env]   # noqa: E731
-    a = lambda t: t.cpu().numpy()[rows_ac]    # noqa: E731
-    for name in ("timesteps", "actions_taken", "episodes", "ep_length", "ep_actions"):
-        assert np.array_equal(e(getattr(env, name)), getattr(orc, name)), name
-    assert np.array_equal(e(env.win_bits).astype(np.uint32), orc.win_bits)
-    assert np.array_equal(e(env.active_mask).astype(np.uint64), orc.active_mask)
-    assert np.array_equal(a(env.ac[:, 0]), orc.px) and np.array_equal(a(env.ac[:, 1]), orc.py)
-    assert np.array_equal(a(env.h), orc.h), "altitude (float64)"
-    assert np.array_equal(a(env.phi_fix), orc.phi_fix) and np.array_equal(a(env.v_fix), orc.v_fix)
-    assert np.array_equal(a(env.phi_counts), orc.phi_counts.astype(np.float64))
-    assert np.array_equal(a(env.last_act), orc.last_act)
-    la_wide = np.isin(orc.last_act[:, 1], (-2 ** 31, 2 ** 31 - 1))
-    assert np.array_equal(a(env.phi_wide[:, 1])[la_wide], orc.phi_wide[la_wide, 1])
-    assert np.allclose(e(env.total_reward), orc.total_reward, rtol=1e-5, atol=1e-3)
-    assert np.allclose(e(env.ep_return), orc.ep_return, rtol=1e-5, atol=1e-3)
+_compare_state = bars.check_state
 
 
 @pytest.mark.gpu

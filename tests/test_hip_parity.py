@@ -5,6 +5,7 @@ Run on the MI355X box with `pytest -m gpu`."""
 import numpy as np
 import pytest
 
+import bars
 import helpers as H
 
 pytestmark = pytest.mark.gpu
@@ -738,23 +739,7 @@ def _run_vs_oracle(scen_obj, comp, B, N, steps, seed, dt=1.0, discrete=False, sp
         for c in range(chunk):
             orc.step(acts[c])
             o, r, d, fl = res[c]
-            fl = fl.cpu().numpy().astype(np.uint32)
-            assert np.array_equal(fl, orc.flags), ("flags", t + c, np.argwhere(fl != orc.flags)[:5])
-            assert np.array_equal(d.cpu().numpy(), orc.done), ("done", t + c)
-            on = o.cpu().numpy().reshape(B, N, 10)
-            # envs that were auto-reset return RAW obs (large values): compare relative to magnitude; without
-            # normalisation every obs is raw and 1e-5 in obs units is 1e-5 of the component's normalisation half-range
-            scale = np.maximum(1.0, np.abs(orc.obs))
-            if not normalize:
-                scale = np.maximum(scale, half_range.astype(np.float32))
-            assert np.all(np.abs(on - orc.obs) <= 1e-5 * scale), ("obs", t + c)
-            rr = r.cpu().numpy()
-            # env reward = sum over the env's aircraft of per-aircraft rewards that each meet 1e-5 (checked below when the
-            # variant outputs them); the fp32 sum of N terms adds at most N/2 ulps of the running sum
-            rtol = 1e-5 * np.maximum(1.0, np.abs(orc.reward)) + 6e-8 * N * np.abs(orc.ac_reward).sum(1)
-            assert np.all(np.abs(rr - orc.reward) <= rtol), ("rew", t + c, np.abs(rr - orc.reward).max())
-            n_done += int(orc.done.sum())
-            seen |= int(np.bitwise_or.reduce(orc.flags.ravel()))
+            got = {"flags": fl.cpu().numpy(), "done": d.cpu().numpy(), "obs": o.cpu().numpy().reshape(B, N, 10), "reward": r.cpu().numpy()}
             if full:
                 # optional outputs (of the single step, or row c of the multi-step launch's buffers)
                 if use_rollout:
@@ -762,42 +747,13 @@ def _run_vs_oracle(scen_obj, comp, B, N, steps, seed, dt=1.0, discrete=False, sp
                 else:
                     raw, acr, msep, tob = (info[k].cpu().numpy() for k in ("original_state", "aircraft_reward", "min_separation",
                                                                            "terminal_observation"))
-                raw, tob = raw.reshape(B, N, 10), tob.reshape(B, N, 10)
-                # heading arithmetic is exact in both implementations -> relative_angle (raw[9]) must be bit-identical
-                # (checks the division-free Python-modulo of csrc/atc_device.h against the fmodf-based oracle)
-                assert np.array_equal(raw[..., 9], orc.raw_obs[..., 9]), t + c
-                assert np.array_equal(raw[..., 3], orc.raw_obs[..., 3]), t + c
-                # raw (un-normalised) values: 1e-5 of each component's normalisation half-range (= 1e-5 in obs units)
-                assert np.all(np.abs(raw - orc.raw_obs) <= 1e-5 * half_range), t + c
-                assert np.all(np.abs(acr - orc.ac_reward) <= 1e-5 * np.maximum(1.0, np.abs(orc.ac_reward))), t + c
-                # positions are bit-identical and d^2 is the same fma on both sides: the minimum separation is too
-                assert np.array_equal(msep, orc.min_sep), t + c
-                dn = orc.done.astype(bool)
-                if dn.any():
-                    tscale = np.maximum(1.0, np.abs(orc.term_obs[dn]))
-                    if not normalize:
-                        tscale = np.maximum(tscale, half_range.astype(np.float32))
-                    assert np.all(np.abs(tob[dn] - orc.term_obs[dn]) <= 1e-5 * tscale), t + c
+                got.update(raw_obs=raw.reshape(B, N, 10), ac_reward=acr, min_sep=msep, term_obs=tob.reshape(B, N, 10))
+            bars.check_step(got, orc, normalize, half_range, t + c)   # flags / done exact, obs / rewards 1e-5, optional outputs: tests/bars.py
+            n_done += int(orc.done.sum())
+            seen |= int(np.bitwise_or.reduce(orc.flags.ravel()))
         t += chunk
-    # persistent state after the run: integer state exact, float state within tolerance
-    assert np.array_equal(env.timesteps.cpu().numpy(), orc.timesteps)
-    assert np.array_equal(env.actions_taken.cpu().numpy(), orc.actions_taken)
-    assert np.array_equal(env.episodes.cpu().numpy(), orc.episodes)
-    assert np.array_equal(env.win_bits.cpu().numpy().astype(np.uint32), orc.win_bits)
-    assert np.array_equal(env.active_mask.cpu().numpy().astype(np.uint64), orc.active_mask)
-    assert np.array_equal(env.ep_length.cpu().numpy(), orc.ep_length)
-    # the fp32 spec (include/atc_step.h: fixed-point position grid, shared heading kinematics, exact rate-limit
-    # arithmetic) makes the whole aircraft state BIT-IDENTICAL to the fp32 oracle's
-    assert np.array_equal(env.ac[:, 0].cpu().numpy(), orc.px) and np.array_equal(env.ac[:, 1].cpu().numpy(), orc.py)
-    assert np.array_equal(env.h.cpu().numpy(), orc.h) and np.array_equal(env.phi_fix.cpu().numpy(), orc.phi_fix)
-    # ... the exact counts of WIDE headings / last heading targets (beyond the 32-bit fields, ABI 19) included
-    assert np.array_equal(env.phi_counts.cpu().numpy(), orc.phi_counts.astype(np.float64))
-    la_wide = np.isin(orc.last_act[:, 1], (-2 ** 31, 2 ** 31 - 1))
-    assert np.array_equal(env.phi_wide[:, 1].cpu().numpy()[la_wide], orc.phi_wide[la_wide, 1])
-    assert np.array_equal(env.v_fix.cpu().numpy(), orc.v_fix)
-    assert np.array_equal(env.last_act.cpu().numpy(), orc.last_act)
-    assert np.array_equal(env.ep_actions.cpu().numpy(), orc.ep_actions)
-    assert np.allclose(env.ep_return.cpu().numpy(), orc.ep_return, rtol=1e-5, atol=1e-3)
+    # persistent state after the run: integer state exact, float state within tolerance (tests/bars.py)
+    bars.check_state(env, orc, total_reward=False)
     env.close()
     return n_done, seen
 

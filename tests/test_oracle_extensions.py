@@ -161,3 +161,116 @@ def test_extension_known_answers(dtype):
             env.step(a)
             assert int(env.flags[0, 0]) == H.F_INACTIVE and np.all(env.obs[0, 0] == 0) and env.ac_reward[0, 0] == 0
             assert abs(env.reward[0] - (-0.10)) < 1e-6 and not env.done[0]
+
+
+# ---------------------------------------------------------------------------------------------- atc_oracle_observe
+SENTINEL = np.float32(-7.25e8)   # no observation word of any sector comes near it
+
+
+def _fly(env, steps, seed):
+    rng = np.random.default_rng(seed)
+    for t in range(steps):
+        if t % 4 == 0:
+            a = rng.uniform(-1, 1, (env.B, env.N, 3)).astype(np.float32)
+        env.step(a)
+    return a
+
+
+@pytest.mark.parametrize("dtype", [np.float64, np.float32])
+def test_observe_after_reset_is_the_reset_observation(dtype):
+    """_get_state(0) of a fresh spawn IS what reset returned (atc_gym.py:351,365) — lattice and random entry, bit for bit."""
+    for random_entry in (False, True):
+        env = _env("LOWW_random", 7, 5, dtype, random_entry=random_entry, seed=4, auto_reset=True, timestep_limit=9)
+        first = env.obs.copy()
+        assert np.array_equal(env.observe(out=np.full_like(first, SENTINEL)), first)
+        _fly(env, 30, 1)                      # ... and of the spawn of a later episode (random entry: keyed by the episode counter)
+        assert env.episodes.min() >= 2
+        again = env.reset().copy()
+        assert random_entry == (not np.array_equal(again, first))
+        assert np.array_equal(env.observe(out=np.full_like(first, SENTINEL)), again)
+
+
+@pytest.mark.parametrize("dtype", [np.float64, np.float32])
+@pytest.mark.parametrize("normalize", [True, False])
+def test_observe_after_a_step_is_the_raw_observation_with_mva_zero(dtype, normalize):
+    """Mid-episode: words 0..4 and 6..9 are the step's raw observation bit for bit; word 5 is h - 0 = word 2 (the step's word 5
+    subtracts the MVA height); never normalised.  Handed-over aircraft are observed like any other (their state is kept)."""
+    env = _env("LOWW_random", 40, 3, dtype, normalize=normalize, sep_nm=0.0)
+    for b in range(0, 40, 4):                 # some aircraft win in the first step and are handed over
+        env.set_state(b, 1, *H.WIN_STATE)
+    a = _fly(env, 1, 2)
+    a[0::4, 1] = H.WIN_ACTION
+    env.step(a)
+    _fly(env, 6, 3)
+    raw = env.raw_obs.copy()
+    live = (env.flags & H.F_INACTIVE) == 0
+    assert (~live).sum() >= 5 and live.sum() > 60 and np.any(raw[live][:, 5] != raw[live][:, 2])
+    got = env.observe(out=np.full_like(raw, SENTINEL))
+    for w in (0, 1, 2, 3, 4, 6, 7, 8, 9):
+        assert np.array_equal(got[live][:, w], raw[live][:, w]), w
+    assert np.array_equal(got[..., 5], got[..., 2])
+    # a handed-over aircraft: its kept state, not the step's zero row
+    assert np.all(raw[~live] == 0) and np.all(got[~live][:, 4] >= 100.0) and not np.any(got == SENTINEL)
+    assert np.array_equal(got[~live][:, 2], env.h.reshape(40, 3)[~live].astype(np.float32))
+
+
+@pytest.mark.parametrize("dtype", [np.float64, np.float32])
+def test_observe_mask_leaves_unmasked_rows_alone(dtype):
+    env = _env("LOWW_random", 9, 4, dtype)
+    _fly(env, 5, 6)
+    full = env.observe(out=np.zeros_like(env.obs)).copy()
+    for mask in (np.array([1, 0, 0, 1, 1, 0, 1, 0, 0], np.uint8), np.zeros(9, np.uint8), np.ones(9, np.uint8), 3 * np.eye(9, dtype=np.uint8)[8]):
+        out = np.full_like(full, SENTINEL)
+        env.observe(mask=mask, out=out)
+        m = mask.astype(bool)
+        assert np.array_equal(out[m], full[m]) and np.all(out[~m] == SENTINEL)
+    state = {k: getattr(env, k).copy() for k in ("px", "py", "h", "_phi", "_v", "last_act", "timesteps", "active_mask", "phi_wide")}
+    env.observe()
+    assert all(np.array_equal(getattr(env, k), v) for k, v in state.items())            # a query: the state is only read
+    assert env.observe() is env.obs and np.array_equal(env.obs, full)
+
+
+@pytest.mark.parametrize("dtype", [np.float64, np.float32])
+def test_observe_wide_heading(dtype):
+    """An aircraft placed at a heading of several hundred turns (fp32 spec: beyond the 32-bit field, WIDE): word 3 is the unwrapped
+    heading — the float32 of the reference's float64 heading —, word 9 the relative angle of the heading modulo a turn."""
+    env = _env("LOWW", 1, 3, dtype)
+    q = O.OracleQueries(H.compiled("LOWW"), dtype)
+    to_rwy = float(H.compiled("LOWW").blob64[19])    # ATC_C_PHI_TO_RWY
+    headings = (417 * 360.0 + 75.5, -388 * 360.0 - 12.25, 250.0)
+    for k, phi in enumerate(headings):
+        env.set_state(0, k, 30.0 + k, 50.0, 9000.0, phi, 240.0)
+    if dtype == np.float32:
+        assert list(np.isin(env.phi_fix, (-2 ** 31, 2 ** 31 - 1))) == [True, True, False]
+    got = env.observe(out=np.full_like(env.obs, SENTINEL))[0]
+    for k, phi in enumerate(headings):
+        assert got[k, 3] == np.float32(phi)                    # (multiples of 2^-23 deg: the counts hold them exactly)
+        wrapped = phi - 360.0 * round(phi / 360.0)
+        want9 = q.relative_angle([to_rwy], [wrapped if dtype == np.float32 else phi])[0]
+        assert got[k, 9] == np.float32(want9), (k, got[k, 9], want9)
+        assert abs(float(got[k, 9]) - ((wrapped - to_rwy + 180.0) % 360.0 - 180.0)) <= 1e-5 * 180.0   # fp32 rounding of a 5e4-turn sum would miss this
+    # ... and the step's own raw observation of the same aircraft agrees (hold every target: only the position moves)
+    a = np.array([[H.hold_action((0, 0, 9000.0, p, 240.0)) for p in headings]], np.float32)
+    a[0, :, 2] = [p / 180.0 - 1.0 for p in headings]
+    env.step(a)
+    after = env.observe(out=np.full_like(env.obs, SENTINEL))[0]
+    assert np.array_equal(after[:, [3, 9]], env.raw_obs[0][:, [3, 9]])
+
+
+def test_observe_replays_the_reference_reset_observations():
+    """tests/golden/g2, g6: every episode recorded from the reference's own reset state holds that state next to the reference's
+    reset observation — _get_state(0) of it.  Placed in the float64 oracle and observed, at the fixture's bar for float32
+    observations of the float64 instantiation (2e-6 of the component's half range, tests/test_oracle_golden.py)."""
+    n = 0
+    for name in ("g2_scripted.npz", "g6_rollouts.npz"):
+        for ep in H.episodes_of(H.golden_npz(name)):
+            want = np.array(ep["reset_obs"])
+            if not np.array_equal(np.float32(ep["init_state"]), np.float32(want[:5])):
+                continue        # a state injected after reset(): the recorded observation belongs to another state
+            env = _env(ep["scen"], 1, 1, np.float64, dt=ep["dt"], shaping=ep["shaping"], normalize=ep["normalize"], discrete=ep["discrete"])
+            env.set_state(0, 0, *ep["init_state"])
+            got = env.observe(out=np.full_like(env.obs, SENTINEL))[0, 0]
+            half = 0.5 * H.compiled(ep["scen"]).norm_max.astype(np.float64)
+            assert np.all(np.abs(got - want) <= 2e-6 * half), (name, ep["start"], got, want)
+            n += 1
+    assert n >= 100

@@ -416,3 +416,103 @@ def test_full_size_batch():
         print("full size, envs %s: %s" % (rows, bad or "ok"))
         assert not bad, bad
     env.close()
+
+
+def _episode(info):
+    return (info["episode"]["r"], info["episode"]["l"]) if "episode" in info else None
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("frame_skip", [1, 5])
+@pytest.mark.parametrize("n_envs,N,K,host_mapped", [(40, 8, 3, False), (600, 2, 1, None)], ids=["40x8 K3 dense infos", "600x2 K1 sparse infos"])
+def test_sb_adapter_device_path_with_traffic(n_envs, N, K, host_mapped, frame_skip):
+    """The adapter's DEVICE path (state in HBM: one packed device-to-host tensor per step, sliced by offsets — frame_steps at 3 d + 4,
+    the traffic words in the last traffic_dim columns) with traffic, with and without frame_skip, next to a plain twin fed the same
+    actions: own words, rewards, dones, frame_steps and episode records equal the twin's; the traffic columns are vec.traffic's words
+    0..6, themselves checked against the reference on the state copied back; terminal observations carry zero traffic."""
+    from atc_hip.sb_adapter import AtcSBVecEnv
+    kw = dict(scenario=_sector()[0], seed=11, grid_cell=0.5, spawn="lattice", timestep_limit=6, sep_nm=0.05, frame_skip=frame_skip,
+              host_mapped=host_mapped)
+    wide, plain = AtcSBVecEnv(n_envs, N, traffic=K, **kw), AtcSBVecEnv(n_envs, N, **kw)
+    assert not wide.vec.host_mapped and not plain.vec.host_mapped and wide.sparse_infos == plain.sparse_infos == (n_envs > 512)
+    own, tw = N * L.OBS_DIM, N * K * 7
+    assert wide.traffic_dim == tw and wide.observation_space.shape == (own + tw,)
+
+    def traffic_columns(o, what):
+        _check_env_traffic(wide.vec, wide.vec.traffic, what)
+        assert np.array_equal(o[:, own:], wide.vec.traffic.cpu().numpy()[..., :7].reshape(n_envs, tw)), what
+
+    o_w, o_p = wide.reset(), plain.reset()
+    assert o_w.shape == (n_envs, own + tw) and np.array_equal(o_w[:, :own], o_p)
+    traffic_columns(o_w, "reset")
+    rng = np.random.default_rng(7)
+    ends = 0
+    for t in range(14 if frame_skip == 1 else 6):
+        a = rng.uniform(-1, 1, (n_envs, 3 * N)).astype(np.float32)
+        (o_w, r_w, d_w, i_w), (o_p, r_p, d_p, i_p) = wide.step(a), plain.step(a)
+        assert o_w.shape == (n_envs, own + tw) and o_w.dtype == np.float32
+        assert np.array_equal(o_w[:, :own], o_p) and np.array_equal(r_w, r_p) and np.array_equal(d_w, d_p), t
+        traffic_columns(o_w, "step %d" % t)
+        for b in range(n_envs):
+            assert _episode(i_w[b]) == _episode(i_p[b]) and i_w[b].get("frame_steps") == i_p[b].get("frame_steps"), (t, b)
+            assert ("episode" in i_w[b]) == bool(d_w[b])
+            if d_w[b]:
+                ends += 1
+                term = i_w[b]["terminal_observation"]
+                assert term.shape == (own + tw,) and np.array_equal(term[:own], i_p[b]["terminal_observation"])
+                assert np.all(term[own:] == 0), "the traffic part of a terminal observation is absent records"
+                assert frame_skip == 1 or 1 <= i_w[b]["frame_steps"] <= frame_skip
+            elif wide.sparse_infos:
+                assert i_w[b] == {} and i_p[b] == {}
+            elif frame_skip > 1:
+                assert i_w[b]["frame_steps"] == frame_skip
+    assert ends >= n_envs, "episodes ended in every env"
+    # env_method("reset", indices=...): [own | traffic] rows of the reset envs, the traffic that of the fresh state
+    idx = [1, 5, n_envs - 1]
+    rows_w, rows_p = wide.env_method("reset", indices=idx), plain.env_method("reset", indices=idx)
+    _check_env_traffic(wide.vec, wide.vec.traffic, "env_method reset")
+    tr = wide.vec.traffic.cpu().numpy()[..., :7].reshape(n_envs, tw)
+    assert np.all(wide.vec.timesteps.cpu().numpy()[idx] == 0)
+    for i, rw, rp in zip(idx, rows_w, rows_p):
+        assert rw.shape == (own + tw,) and np.array_equal(rw[:own], rp) and np.array_equal(rw[own:], tr[i])
+        assert rw[own] == 1.0, "a fresh env of %d aircraft: the first record of aircraft 0 is present" % N
+    wide.close()
+    plain.close()
+
+
+@pytest.mark.gpu
+def test_device_tensor_fast_path_with_traffic_on_a_side_stream():
+    """AtcVecEnv(traffic=4).step / .step_skip handed a contiguous float32 DEVICE tensor (the fast path: no argument handling, the
+    launches go to torch's current stream) under torch.cuda.stream(side): once that stream has drained, info["traffic"] matches the
+    reference on the state, and everything — outputs, traffic, state — equals a twin env's numpy-actions path bit for bit."""
+    import torch
+    from atc_hip.vec_env import AtcVecEnv
+    kw = dict(scenario=_sector()[0], auto_reset=True, spawn="lattice", grid_cell=0.5, traffic=4, timestep_limit=7, sep_nm=0.05, seed=2,
+              want_raw_obs=True, want_term_obs=True)
+    env, twin = AtcVecEnv(37, 16, **kw), AtcVecEnv(37, 16, **kw)
+    side = torch.cuda.Stream(device=env.device)
+    rng = np.random.default_rng(12)
+    dones = 0
+    for t in range(10):
+        a = rng.uniform(-1, 1, (37, 16, 3)).astype(np.float32)
+        at = torch.as_tensor(a, device=env.device)
+        assert at.is_cuda and at.is_contiguous() and at.dtype is torch.float32
+        side.wait_stream(torch.cuda.current_stream(env.device))     # the tensor was filled on the current stream
+        skip = t % 3 == 2
+        with torch.cuda.stream(side):
+            obs, rew, done, info = env.step_skip(at, 4) if skip else env.step(at, held=False)
+        side.synchronize()
+        assert info["traffic"] is env.traffic
+        _check_env_traffic(env, info["traffic"], "fast path %s %d" % ("step_skip" if skip else "step", t))
+        o2, r2, d2, i2 = twin.step_skip(a, 4) if skip else twin.step(a)
+        twin.synchronize()
+        assert torch.equal(obs, o2) and torch.equal(rew, r2) and torch.equal(done, d2), t
+        assert set(info) == set(i2)
+        for k in info:
+            assert torch.equal(info[k], i2[k]), (t, k)
+        for k in ("ac", "alt", "last_act", "env", "stats", "phi_wide"):
+            assert torch.equal(getattr(env, k), getattr(twin, k)), (t, k)
+        dones += int(done.sum())
+    assert dones > 0
+    env.close()
+    twin.close()
