@@ -75,3 +75,6 @@ SKIP_MAX, SKIP_LAUNCH_SLOTS = 255, 7
 TRAFFIC_DIM, TRAFFIC_MAX_K = 8, 8
 T_PRESENT, T_DIST, T_AHEAD, T_RIGHT, T_DH, T_DV_AHEAD, T_DV_RIGHT, T_SLOT = range(8)
 TRAFFIC_LAUNCH_SLOTS = 7
+# what-if look-ahead (include/atc_step.h: atc_lookahead): at most LOOKAHEAD_MAX_M candidate action blocks per call; its own launch
+# record (slot = log2(W))
+LOOKAHEAD_MAX_M, LOOKAHEAD_LAUNCH_SLOTS = 64, 7

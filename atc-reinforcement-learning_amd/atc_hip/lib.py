@@ -42,6 +42,14 @@ class AtcOut(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in OUT_FIELDS]
 
 
+LOOKAHEAD_FIELDS = ("reward", "done", "n_steps", "flags", "ac_reward", "min_sep", "obs")
+
+
+class AtcLookaheadOut(C.Structure):
+    """atc_lookahead_out_t"""
+    _fields_ = [(n, C.c_void_p) for n in LOOKAHEAD_FIELDS]
+
+
 class AtcStepCall(C.Structure):
     """atc_step_call_t"""
     _fields_ = [("s", C.c_void_p), ("B", C.c_int32), ("N", C.c_int32), ("st", C.POINTER(AtcState)), ("actions", C.c_void_p),
@@ -52,7 +60,8 @@ EXPORTS = ("atc_abi_version", "atc_last_error", "atc_launch_counts", "atc_host_m
            "atc_scenario_attach_lds_table", "atc_query_mva", "atc_query_mva_lds",
            "atc_query_mva_index", "atc_query_corridor", "atc_query_shaping", "atc_reset", "atc_observe", "atc_step",
            "atc_step_multi", "atc_step_packet", "atc_rollout", "atc_rollout_hold", "atc_serve_start", "atc_serve_step", "atc_serve_stop",
-           "atc_step_skip", "atc_skip_launch_counts", "atc_fill_prefetch_info", "atc_observe_traffic", "atc_traffic_launch_counts")
+           "atc_step_skip", "atc_skip_launch_counts", "atc_fill_prefetch_info", "atc_observe_traffic", "atc_traffic_launch_counts",
+           "atc_lookahead", "atc_lookahead_launch_counts", "atc_lookahead_set_mapping")
 
 def load():
     """Loads libatcstep.so; raises (never falls back) when it has not been built."""
@@ -65,7 +74,7 @@ def load():
     import torch  # noqa: F401  — first, so that libatcstep.so binds to the HIP runtime PyTorch-ROCm already loaded
     lib = C.CDLL(LIB_PATH)
     vp, ci = C.c_void_p, C.c_int
-    # (the ABI number did not change when atc_step_skip / atc_observe_traffic were added, so it does not catch a library built before them)
+    # (the ABI number did not change when atc_step_skip / atc_observe_traffic / atc_lookahead were added, so it does not catch a library built before them)
     missing = [name for name in EXPORTS if not hasattr(lib, name)]
     if missing:
         raise RuntimeError("libatcstep.so lacks %s — rebuild" % ", ".join(missing))
@@ -96,6 +105,9 @@ def load():
     lib.atc_fill_prefetch_info.argtypes = [vp, ci, ci, C.POINTER(ci), C.POINTER(ci)]
     lib.atc_observe_traffic.argtypes = [vp, ci, ci, ci, C.POINTER(AtcState), vp, C.POINTER(AtcParams), vp]
     lib.atc_traffic_launch_counts.argtypes = [C.POINTER(C.c_uint64), ci]
+    lib.atc_lookahead.argtypes = [vp, ci, ci, ci, ci, C.POINTER(AtcState), vp, C.POINTER(AtcLookaheadOut), C.POINTER(AtcParams), vp]
+    lib.atc_lookahead_launch_counts.argtypes = [C.POINTER(C.c_uint64), ci]
+    lib.atc_lookahead_set_mapping.argtypes = [ci]
     for name in EXPORTS:
         if name not in ("atc_abi_version", "atc_last_error"):
             getattr(lib, name).restype = ci
@@ -139,6 +151,20 @@ def traffic_launch_counts():
     buf = (C.c_uint64 * L.TRAFFIC_LAUNCH_SLOTS)()
     check(load().atc_traffic_launch_counts(buf, L.TRAFFIC_LAUNCH_SLOTS))
     return {1 << i: int(v) for i, v in enumerate(buf) if v}
+
+
+def lookahead_launch_counts():
+    """Launches of the look-ahead kernel (atc_lookahead) made by the calling thread so far, by lane-group width: {16: n, ...},
+    widths with a count of zero left out.  Separate from the other launch records, which a look-ahead leaves as they are."""
+    buf = (C.c_uint64 * L.LOOKAHEAD_LAUNCH_SLOTS)()
+    check(load().atc_lookahead_launch_counts(buf, L.LOOKAHEAD_LAUNCH_SLOTS))
+    return {1 << i: int(v) for i, v in enumerate(buf) if v}
+
+
+def lookahead_set_mapping(candidates_per_workgroup=0):
+    """Developer knob (atc_lookahead_set_mapping): candidates a workgroup of the calling thread's later look-aheads evaluates;
+    1 = one workgroup per (tile, candidate), M = a loop over all candidates, 0 = the library's choice.  Results do not depend on it."""
+    check(load().atc_lookahead_set_mapping(int(candidates_per_workgroup)))
 
 
 def fill_prefetch_info(scenario, B, N):

@@ -370,6 +370,45 @@ class AtcVecEnv:
         self._finish()
         return self.obs, self.reward, self.done, self._info_skip
 
+    LOOKAHEAD_OUTPUTS = ("flags", "min_sep", "ac_reward", "obs")
+
+    def lookahead(self, actions, K, outputs=("flags", "min_sep")):
+        """What-if query (atc_lookahead, include/atc_step.h): for each of M candidate decisions per env, what step_skip(actions[m], K)
+        would return from the state the env is in NOW — in one launch that writes no state.  actions: [M, B, N, 3] (or [M, B, N*3]),
+        1 <= M <= 64, 1 <= K <= 255.  Returns a dict of device tensors: reward [M, B] float32, done [M, B] uint8, n_steps [M, B]
+        uint8 always, and each of flags [M, B, N] int16, min_sep [M, B], ac_reward [M, B, N], obs [M, B, N*10] that `outputs`
+        names (none of them: the kernel's fast form).  The tensors are allocated once per (M, outputs) and overwritten by the next
+        such call.  Runs on the current stream; env.obs / env.traffic, every bound step output and the whole env state — episode
+        records included — are left as they are.  An env-candidate with a WIDE heading (an out-of-range heading action or state) is
+        not evaluated: n_steps == 0 and zeros.  AtcSBVecEnv and AtcGym deliberately have no such method."""
+        torch = self.torch
+        K = int(K)
+        if not 1 <= K <= L.SKIP_MAX:
+            raise ValueError("1 <= K <= %d" % L.SKIP_MAX)
+        M = int(actions.shape[0]) if hasattr(actions, "shape") else len(actions)
+        if not 1 <= M <= L.LOOKAHEAD_MAX_M:
+            raise ValueError("1 <= M (actions.shape[0]) <= %d" % L.LOOKAHEAD_MAX_M)
+        outputs = tuple(n for n in self.LOOKAHEAD_OUTPUTS if n in outputs) if set(outputs) <= set(self.LOOKAHEAD_OUTPUTS) else None
+        if outputs is None:
+            raise ValueError("outputs must be a subset of %r" % (self.LOOKAHEAD_OUTPUTS,))
+        a = self._as_actions(actions, lead=(M,))
+        cache = self.__dict__.setdefault("_lookahead_cache", {})
+        key = (M, outputs)
+        if key not in cache:
+            B, N, z = self.B, self.N, self._new_output
+            shapes = {"reward": ((M, B), torch.float32), "done": ((M, B), torch.uint8), "n_steps": ((M, B), torch.uint8),
+                      "flags": ((M, B, N), torch.int16), "min_sep": ((M, B), torch.float32), "ac_reward": ((M, B, N), torch.float32),
+                      "obs": ((M, B, N * L.OBS_DIM), torch.float32)}
+            res = {n: z(*shapes[n]) for n in ("reward", "done", "n_steps") + outputs}
+            cache[key] = (res, _lib.AtcLookaheadOut(*[self._ptr(res.get(n)) for n in _lib.LOOKAHEAD_FIELDS]))
+        res, out = cache[key]
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.atc_lookahead(self.sector.handle, self.B, self.N, K, M, C.byref(self._state), self._ptr(a), C.byref(out),
+                                               C.byref(self.params), self._stream()))
+        self._keep_lookahead = a
+        self._finish()
+        return res
+
     def make_launcher(self, actions, stream=None, held=False):
         """Pre-bound `atc_step` call for FIXED buffers (this env's state / outputs, the given device action tensor, the
         given torch stream or the current one): returns a no-argument callable that only launches — host cost of a few

@@ -21,6 +21,16 @@ int atc_traffic_launch_counts(uint64_t* out, int n) {
     for (int i = 0; i < n && i < ATC_TRAFFIC_LAUNCH_SLOTS; ++i) out[i] = t_traffic_launches[i];
     return ATC_OK;
 }
+int atc_lookahead_launch_counts(uint64_t* out, int n) {
+    if (!out || n < 0) return fail_arg("null pointer");
+    for (int i = 0; i < n && i < ATC_LOOKAHEAD_LAUNCH_SLOTS; ++i) out[i] = t_look_launches[i];
+    return ATC_OK;
+}
+int atc_lookahead_set_mapping(int candidates_per_workgroup) {
+    if (candidates_per_workgroup < 0 || candidates_per_workgroup > ATC_LOOKAHEAD_MAX_M) return fail_arg("candidates per workgroup must be 0 (the library's choice) .. 64");
+    t_look_cpg = candidates_per_workgroup;
+    return ATC_OK;
+}
 int atc_fill_prefetch_info(const atc_scenario_t* s, int B, int N, int* resident, int* stride) {
     if (!s || !resident || !stride) return fail_arg("null pointer");
     if (B < 1 || N < 1 || N > ATC_MAX_AIRCRAFT) return fail_arg("need B >= 1, 1 <= N <= 64");
@@ -414,6 +424,11 @@ int atc_step_skip(const atc_scenario_t* s, int B, int N, int K, const atc_state_
 int atc_observe_traffic(const atc_scenario_t* s, int B, int N, int K, const atc_state_t* st, float* traffic, const atc_params_t* p,
                         void* stream) {
     return traffic_common(s, B, N, K, st, traffic, p, stream);
+}
+
+int atc_lookahead(const atc_scenario_t* s, int B, int N, int K, int M, const atc_state_t* st, const float* actions,
+                  const atc_lookahead_out_t* out, const atc_params_t* p, void* stream) {
+    return lookahead_common(s, B, N, K, M, st, actions, out, p, stream);
 }
 
 }  // extern "C"

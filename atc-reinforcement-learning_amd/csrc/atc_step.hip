@@ -562,7 +562,9 @@ __device__ __forceinline__ int clamp_sym(int d, int r) { return max(min(d, r), -
 __device__ __forceinline__ bool within(int d, int D) { return (uint32_t)d + (uint32_t)(D - 1) < (uint32_t)(2 * D - 1); }
 
 // ---- first half of AtcGym.step: timestep, rate limits towards the targets, kinematics, MVA floor ---------------------
-template <bool ONE, bool LAT, bool LDSG = false>
+// RO ("read only", the look-ahead kernel: csrc/atc_lookahead.inc): every store to atc_state_t on the step path is compiled out — here
+// the side-record stores of WIDE headings.  Default off: every other instantiation is what it was.
+template <bool ONE, bool LAT, bool LDSG = false, bool RO = false>
 __device__ __forceinline__ Mid step_part_a(const float* __restrict__ grid, const QRates& q, const QKin& qk, const QGrid& qg,
                                            const LaneIds& d, uint32_t tv, double th, int tp, float act_p, LaneState& ls, EnvState& es,
                                            bool repeated, bool all_active, double* wide_named, int zk,
@@ -678,14 +680,16 @@ __device__ __forceinline__ Mid step_part_a(const float* __restrict__ grid, const
                     phi_k = phi_new;
                     if (is_wide(phi_new)) {   // the exact counts, and their views for the rest of this step (wide_view)
                         phi_k = phi_wrap(Pn);
-                        w[0] = Pn;
-                        *reinterpret_cast<int2*>(w + 2) = make_int2(phi_k, __float_as_int(phi_obs_wide(Pn)));
+                        if (!RO) {
+                            w[0] = Pn;
+                            *reinterpret_cast<int2*>(w + 2) = make_int2(phi_k, __float_as_int(phi_obs_wide(Pn)));
+                        }
                     }
                     if (book && active) {
                         const double L = is_wide(ls.la_p) ? w[1] : (double)ls.la_p;
                         counted = !(__builtin_fabs(T - L) < (double)kDiscrPhiFix);
                         la_new = cvt_i32_f64(T);
-                        if (is_wide(la_new)) w[1] = T;
+                        if (!RO && is_wide(la_new)) w[1] = T;
                     }
                     fl |= (lim && active) ? (uint32_t)ATC_F_PHI_LIMIT : 0u;
                 }
@@ -815,7 +819,9 @@ struct StepVals {
     uint32_t fl;
     bool done;
 };
-template <int W, bool FULL, bool ONE, bool LAT, bool LDSG = false, bool SKIP = false>
+// RO: see step_part_a — here the auto-reset path reads the episode number and writes nothing: no per-episode record update, no fences
+// around it, no terminal observation.
+template <int W, bool FULL, bool ONE, bool LAT, bool LDSG = false, bool SKIP = false, bool RO = false>
 __device__ __forceinline__ bool step_part_b(const float* __restrict__ K, const float* __restrict__ grid,
                                             const atc_params_t& p, const StepDerived& q, const QScan& qs, int zk, int N,
                                             const LaneIds& d, const Mid& m, LaneState& ls,
@@ -1180,21 +1186,21 @@ __device__ __forceinline__ bool step_part_b(const float* __restrict__ K, const f
         // The per-episode record is read, updated and written here and nowhere else on the step path.  In a multi-step launch
         // an earlier step of this wavefront may have written it (lane k == 0 writes, all lanes of the env read): wavefront-
         // scope fences order those accesses (they compile to nothing — a wavefront's memory operations are issued in order).
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        if (!RO) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
         // (multi-step launches fetch the record's base here, on the rare path: carried from the top of the step it sat in
         // vector-register lanes)
         int32_t* stats = ONE ? stp : kernarg_reread<int32_t*>(offsetof(StepArgs, st) + offsetof(atc_state_t, stats), zk);
         int4* sr = at<int4>(stats, (uint32_t)e * (ATC_STAT_WORDS * 4u));
         const int4 s0 = sr[0];  // episodes, ep_length, ep_return, win_bits
         const int episode = s0.x;
-        if (d.env_valid && k == 0) {
+        if (!RO && d.env_valid && k == 0) {
             const uint32_t win_bits = (((uint32_t)s0.w << 1) | (env_won ? 1u : 0u)) & 0x3ffu;
             sr[0] = make_int4(episode + 1, es.t, __float_as_int(es.total_reward), (int)win_bits);
             *at<int>(stats, (uint32_t)e * (ATC_STAT_WORDS * 4u) + ATC_STAT_EP_ACTIONS * 4u) = es.n_actions;
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        if (!RO) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         if (d.lane_valid) {
-            if (FULL && so.term_obs) store_obs(at<float>(so.term_obs, times40(i)), o);
+            if (!RO && FULL && so.term_obs) store_obs(at<float>(so.term_obs, times40(i)), o);
             // (slot through this step's opaque zero: the spawn-record address is then formed here, on the rare path, instead of
             // being carried — and spilled — across the step loop as a 64-bit per-lane pointer)
             a = spawn(K, qs.off_spawn, p, e, k + zk, episode, o);   // state + raw reset observation from the blob's spawn records
@@ -1715,6 +1721,7 @@ k_serve(const float* __restrict__ blob, int off_grid, atc_state_t st, atc_out_t 
 
 #include "atc_aux_kernels.inc"   // k_reset, k_observe, k_reset_env, k_query_*
 #include "atc_traffic.inc"       // k_traffic (atc_observe_traffic)
+#include "atc_lookahead.inc"     // k_lookahead (atc_lookahead)
 
 // ---------------------------------------------------------------------------------------------------------------
 // host side of the C-ABI
@@ -1934,6 +1941,48 @@ static int traffic_common(const atc_scenario_t* s, int B, int N, int K, const at
     q.s_v = nrm ? 1.0f / (2.0f * s->consts[ATC_C_V_MAX]) : 1.0f;
     q.K = K;
     return with_width(N, [&](auto w) { return launch_traffic<decltype(w)::value>(B, N, st, traffic, q, (hipStream_t)stream); });
+}
+
+// ---- what-if look-ahead (include/atc_step.h: atc_lookahead) ---------------------------------------------------------------------
+// its own launch record (atc_lookahead_launch_counts): slot = log2(W), the rules of the frame-skip record
+static thread_local uint64_t t_look_launches[ATC_LOOKAHEAD_LAUNCH_SLOTS] = {0};
+// candidates per workgroup (csrc/atc_lookahead.inc) asked for by atc_lookahead_set_mapping; 0: the library's choice
+static thread_local int t_look_cpg = 0;
+#define ATC_LOOKAHEAD_CPG_DEFAULT 1   // one workgroup per (tile, candidate): measured against the in-workgroup loop in DESIGN.md, section 3c
+
+template <int W>
+static int launch_lookahead(const atc_scenario* s, int B, int N, int K, int M, const atc_state_t* st, const float* actions,
+                            const atc_lookahead_out_t* lo, const atc_params_t* p, hipStream_t stream) {
+    const size_t lds = lds_bytes(s, W >= 32, true);
+    const int tiles = step_grid(B, W);
+    int cpg = t_look_cpg > 0 ? t_look_cpg : ATC_LOOKAHEAD_CPG_DEFAULT;
+    if (cpg > M) cpg = M;
+    const int groups = (M + cpg - 1) / cpg;
+    const long long grid = (long long)((tiles + 7) / 8) * 8 * groups;   // whole chunks of 8 tiles x groups (look_tile)
+    if (grid > 0x7fffffffll) return fail_arg("B*N*M too large for one launch: split the candidates");
+    atc_out_t out;
+    memset(&out, 0, sizeof out);
+    out.obs = lo->obs; out.reward = lo->reward; out.ac_reward = lo->ac_reward; out.done = lo->done; out.flags = lo->flags; out.min_sep = lo->min_sep;
+    const StepDerived& q = derive(*p, s, 0);
+    // the fast form has the four optional outputs compiled out
+    if (lo->flags || lo->ac_reward || lo->min_sep || lo->obs) hipLaunchKernelGGL((k_lookahead<W, true>), dim3((unsigned)grid), dim3(kBlock), lds, stream, s->d_blob, s->off_grid, B, N, K, M, *st, actions, out, *p, q, lo->n_steps, cpg, groups, tiles);
+    else hipLaunchKernelGGL((k_lookahead<W, false>), dim3((unsigned)grid), dim3(kBlock), lds, stream, s->d_blob, s->off_grid, B, N, K, M, *st, actions, out, *p, q, lo->n_steps, cpg, groups, tiles);
+    HIP_TRY(hipGetLastError());
+    ++t_look_launches[__builtin_ctz(W)];
+    return ATC_OK;
+}
+
+static int lookahead_common(const atc_scenario_t* s, int B, int N, int K, int M, const atc_state_t* st, const float* actions,
+                            const atc_lookahead_out_t* out, const atc_params_t* p, void* stream) {
+    // K, then M, before any pointer is looked at
+    if (K < 1 || K > ATC_SKIP_MAX) return fail_arg("K (the look-ahead length) must be 1 .. 255");
+    if (M < 1 || M > ATC_LOOKAHEAD_MAX_M) return fail_arg("M (the number of candidates) must be 1 .. 64");
+    if (!out || !out->reward || !out->done) return fail_arg("null pointer: atc_lookahead_out_t.reward and .done are required");
+    if (!actions) return fail_arg("null pointer");
+    if (const int rc = check_env_args(s, B, N, st, p)) return rc;
+    if (const int rc = check_dt(s, p)) return rc;
+    if (p->mode & ATC_M_ACTIONS_HELD) return fail_arg("ATC_M_ACTIONS_HELD is for atc_step only: every candidate's first step carries a fresh decision");
+    return with_width(N, [&](auto w) { return launch_lookahead<decltype(w)::value>(s, B, N, K, M, st, actions, out, p, (hipStream_t)stream); });
 }
 
 #include "atc_abi.inc"   // the extern "C" entry points (host side)

@@ -662,6 +662,54 @@ int atc_observe_traffic(const atc_scenario_t* s, int B, int N, int K, const atc_
 enum { ATC_TRAFFIC_LAUNCH_SLOTS = 7 };
 int atc_traffic_launch_counts(uint64_t* out, int n);
 
+/* WHAT-IF LOOK-AHEAD (extension): "from the state this env is in now, what happens if I hold decision m for K steps?" for M candidate
+ * action blocks per env in ONE launch that never writes state — the primitive behind MPC / CEM action selection, action shields and
+ * tree-search rollouts.  1 <= K <= ATC_SKIP_MAX, 1 <= M <= ATC_LOOKAHEAD_MAX_M.  Defined per candidate m and env e as
+ *
+ *     atc_step_skip(s, B, N, K, <a bit-exact private copy of the env's state>, actions[m], ..., p, stream)
+ *
+ * i.e. the env steps with actions[m] (the same [N][3] block every time) until a step reports done or n == K, exactly as there:
+ *   reward, ac_reward [m] float32 sum of the executed steps' values, accumulated sequentially in step order
+ *   flags [m]         bitwise OR of the executed steps' flag words
+ *   min_sep [m]       minimum over the executed steps
+ *   done [m]          1 iff the last executed step reported done
+ *   n_steps [m]       n, the number of executed steps
+ *   obs [m]           that of the last executed step (under ATC_M_AUTO_RESET and done: the raw reset observation, drawn with the
+ *                     episode number the copy would have used)
+ * Candidates are independent: candidate m's result does not depend on M, on the other candidates or on neighbouring envs; M == 1
+ * with every output requested reproduces atc_step_skip's corresponding outputs bit for bit.  reward and done are required, every
+ * other output pointer may be NULL; a launch that asks for none of flags, ac_reward, min_sep, obs runs a form with them compiled out.
+ * STATE: the call reads atc_state_t and writes none of it — all six arrays are byte-identical afterwards, `stats` (no per-episode
+ * record update on a look-ahead reset) and `phi_wide` (the step's scratch word 2 included).  There is no term_obs.
+ * LIMIT — WIDE headings (ABI 19).  The step hands a WIDE heading from step to step through the phi_wide side record in memory, which
+ * this call may not write.  An env-candidate is therefore NOT EVALUATED when any aircraft's heading or accepted heading target is
+ * WIDE at the start (phi_fix or last_act[.][1] saturated) or becomes WIDE during the K steps: n_steps = 0, done = 0, reward = 0 and
+ * every requested per-aircraft / per-env output word of that (m, e) is 0.  Other candidates of the env are unaffected.  Every action
+ * inside the action space keeps headings within (-76, 436) deg: only callers that feed out-of-range heading actions meet this.
+ * ATC_ERR_ARG, in this order, the first two before any pointer is looked at: K outside 1 .. ATC_SKIP_MAX; M outside 1 ..
+ * ATC_LOOKAHEAD_MAX_M; out, out->reward or out->done NULL; the argument errors of atc_step; ATC_M_ACTIONS_HELD in p->mode.
+ * Counted by atc_lookahead_launch_counts only (slot = log2(W); the rules of atc_skip_launch_counts): atc_launch_counts and
+ * atc_skip_launch_counts do not move. */
+#define ATC_LOOKAHEAD_MAX_M 64
+typedef struct atc_lookahead_out {
+    float*    reward;    /* [M][B]      required */
+    uint8_t*  done;      /* [M][B]      required */
+    uint8_t*  n_steps;   /* [M][B]      nullable; 0 = not evaluated (see WIDE above) */
+    uint16_t* flags;     /* [M][B*N]    nullable */
+    float*    ac_reward; /* [M][B*N]    nullable */
+    float*    min_sep;   /* [M][B]      nullable */
+    float*    obs;       /* [M][B*N*10] nullable */
+} atc_lookahead_out_t;
+int atc_lookahead(const atc_scenario_t* s, int B, int N, int K, int M, const atc_state_t* st, const float* actions /* [M][B*N*3] */,
+                  const atc_lookahead_out_t* out, const atc_params_t* p, void* stream);
+enum { ATC_LOOKAHEAD_LAUNCH_SLOTS = 7 };
+int atc_lookahead_launch_counts(uint64_t* out, int n);
+/* Developer knob (A/B runs, tests): how the candidates map onto the launch, for the calling thread's later atc_lookahead calls.
+ * n = 1: one workgroup per (256-slot tile, candidate); n = M or more: one workgroup per tile that loops over all candidates; in
+ * between: n candidates per workgroup; 0: the library's choice (the default).  Results do not depend on it.  ATC_ERR_ARG outside
+ * 0 .. ATC_LOOKAHEAD_MAX_M. */
+int atc_lookahead_set_mapping(int candidates_per_workgroup);
+
 #ifdef __cplusplus
 }
 #endif
