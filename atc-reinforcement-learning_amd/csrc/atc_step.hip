@@ -1860,6 +1860,11 @@ static int with_width(int N, F f) {
     if (N <= 32) return f(std::integral_constant<int, 32>());
     return f(std::integral_constant<int, 64>());
 }
+// f(std::integral_constant<bool, b>) for a run-time flag
+template <typename F>
+static int with_flag(bool b, F f) {
+    return b ? f(std::true_type()) : f(std::false_type());
+}
 
 static int step_common(const atc_scenario_t* s, int B, int N, int T, int hold, const atc_state_t* st, const float* actions,
                        const atc_out_t* out, const atc_params_t* p, void* stream) {
@@ -1885,11 +1890,12 @@ static int launch_skip(const atc_scenario* s, int B, int N, int K, const atc_sta
     const int grid = step_grid(B, W);
     const StepDerived& q = derive(*p, s, 0);
     // as for k_step: a launch that asks for no optional output runs the form that has them compiled out
-    if (out->raw_obs || out->ac_reward || out->min_sep || out->term_obs) hipLaunchKernelGGL((k_skip<W, true>), dim3(grid), dim3(kBlock), lds, stream, s->d_blob, s->off_grid, B, N, K, 0, *st, actions, *out, *p, q, n_steps);
-    else hipLaunchKernelGGL((k_skip<W, false>), dim3(grid), dim3(kBlock), lds, stream, s->d_blob, s->off_grid, B, N, K, 0, *st, actions, *out, *p, q, n_steps);
-    HIP_TRY(hipGetLastError());
-    ++t_skip_launches[__builtin_ctz(W)];
-    return ATC_OK;
+    return with_flag(out->raw_obs || out->ac_reward || out->min_sep || out->term_obs, [&](auto full) {
+        hipLaunchKernelGGL((k_skip<W, decltype(full)::value>), dim3(grid), dim3(kBlock), lds, stream, s->d_blob, s->off_grid, B, N, K, 0, *st, actions, *out, *p, q, n_steps);
+        HIP_TRY(hipGetLastError());
+        ++t_skip_launches[__builtin_ctz(W)];
+        return ATC_OK;
+    });
 }
 
 static int skip_common(const atc_scenario_t* s, int B, int N, int K, const atc_state_t* st, const float* actions, const atc_out_t* out,
@@ -1965,11 +1971,12 @@ static int launch_lookahead(const atc_scenario* s, int B, int N, int K, int M, c
     out.obs = lo->obs; out.reward = lo->reward; out.ac_reward = lo->ac_reward; out.done = lo->done; out.flags = lo->flags; out.min_sep = lo->min_sep;
     const StepDerived& q = derive(*p, s, 0);
     // the fast form has the four optional outputs compiled out
-    if (lo->flags || lo->ac_reward || lo->min_sep || lo->obs) hipLaunchKernelGGL((k_lookahead<W, true>), dim3((unsigned)grid), dim3(kBlock), lds, stream, s->d_blob, s->off_grid, B, N, K, M, *st, actions, out, *p, q, lo->n_steps, cpg, groups, tiles);
-    else hipLaunchKernelGGL((k_lookahead<W, false>), dim3((unsigned)grid), dim3(kBlock), lds, stream, s->d_blob, s->off_grid, B, N, K, M, *st, actions, out, *p, q, lo->n_steps, cpg, groups, tiles);
-    HIP_TRY(hipGetLastError());
-    ++t_look_launches[__builtin_ctz(W)];
-    return ATC_OK;
+    return with_flag(lo->flags || lo->ac_reward || lo->min_sep || lo->obs, [&](auto full) {
+        hipLaunchKernelGGL((k_lookahead<W, decltype(full)::value>), dim3((unsigned)grid), dim3(kBlock), lds, stream, s->d_blob, s->off_grid, B, N, K, M, *st, actions, out, *p, q, lo->n_steps, cpg, groups, tiles);
+        HIP_TRY(hipGetLastError());
+        ++t_look_launches[__builtin_ctz(W)];
+        return ATC_OK;
+    });
 }
 
 static int lookahead_common(const atc_scenario_t* s, int B, int N, int K, int M, const atc_state_t* st, const float* actions,
