@@ -78,3 +78,7 @@ TRAFFIC_LAUNCH_SLOTS = 7
 # what-if look-ahead (include/atc_step.h: atc_lookahead): at most LOOKAHEAD_MAX_M candidate action blocks per call; its own launch
 # record (slot = log2(W))
 LOOKAHEAD_MAX_M, LOOKAHEAD_LAUNCH_SLOTS = 64, 7
+# plan look-ahead (include/atc_step.h: atc_lookahead_plan): at most PLAN_MAX_H held action blocks per candidate; its own launch
+# record (slot = log2(W))
+PLAN_MAX_H = 16
+PLAN_LAUNCH_SLOTS = 7

@@ -50,6 +50,14 @@ class AtcLookaheadOut(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in LOOKAHEAD_FIELDS]
 
 
+PLAN_FIELDS = ("reward", "done", "n_steps", "seg_reward", "flags", "ac_reward", "min_sep", "obs")
+
+
+class AtcPlanOut(C.Structure):
+    """atc_plan_out_t"""
+    _fields_ = [(n, C.c_void_p) for n in PLAN_FIELDS]
+
+
 class AtcStepCall(C.Structure):
     """atc_step_call_t"""
     _fields_ = [("s", C.c_void_p), ("B", C.c_int32), ("N", C.c_int32), ("st", C.POINTER(AtcState)), ("actions", C.c_void_p),
@@ -61,7 +69,7 @@ EXPORTS = ("atc_abi_version", "atc_last_error", "atc_launch_counts", "atc_host_m
            "atc_query_mva_index", "atc_query_corridor", "atc_query_shaping", "atc_reset", "atc_observe", "atc_step",
            "atc_step_multi", "atc_step_packet", "atc_rollout", "atc_rollout_hold", "atc_serve_start", "atc_serve_step", "atc_serve_stop",
            "atc_step_skip", "atc_skip_launch_counts", "atc_fill_prefetch_info", "atc_observe_traffic", "atc_traffic_launch_counts",
-           "atc_lookahead", "atc_lookahead_launch_counts", "atc_lookahead_set_mapping")
+           "atc_lookahead", "atc_lookahead_launch_counts", "atc_lookahead_set_mapping", "atc_lookahead_plan", "atc_plan_launch_counts")
 
 def load():
     """Loads libatcstep.so; raises (never falls back) when it has not been built."""
@@ -74,7 +82,7 @@ def load():
     import torch  # noqa: F401  — first, so that libatcstep.so binds to the HIP runtime PyTorch-ROCm already loaded
     lib = C.CDLL(LIB_PATH)
     vp, ci = C.c_void_p, C.c_int
-    # (the ABI number did not change when atc_step_skip / atc_observe_traffic / atc_lookahead were added, so it does not catch a library built before them)
+    # (the ABI number did not change when atc_step_skip / atc_observe_traffic / atc_lookahead / atc_lookahead_plan were added, so it does not catch a library built before them)
     missing = [name for name in EXPORTS if not hasattr(lib, name)]
     if missing:
         raise RuntimeError("libatcstep.so lacks %s — rebuild" % ", ".join(missing))
@@ -108,6 +116,8 @@ def load():
     lib.atc_lookahead.argtypes = [vp, ci, ci, ci, ci, C.POINTER(AtcState), vp, C.POINTER(AtcLookaheadOut), C.POINTER(AtcParams), vp]
     lib.atc_lookahead_launch_counts.argtypes = [C.POINTER(C.c_uint64), ci]
     lib.atc_lookahead_set_mapping.argtypes = [ci]
+    lib.atc_lookahead_plan.argtypes = [vp, ci, ci, ci, ci, ci, C.POINTER(AtcState), vp, C.POINTER(AtcPlanOut), C.POINTER(AtcParams), vp]
+    lib.atc_plan_launch_counts.argtypes = [C.POINTER(C.c_uint64), ci]
     for name in EXPORTS:
         if name not in ("atc_abi_version", "atc_last_error"):
             getattr(lib, name).restype = ci
@@ -161,8 +171,16 @@ def lookahead_launch_counts():
     return {1 << i: int(v) for i, v in enumerate(buf) if v}
 
 
+def plan_launch_counts():
+    """Launches of the plan look-ahead kernel (atc_lookahead_plan) made by the calling thread so far, by lane-group width:
+    {16: n, ...}, widths with a count of zero left out.  Separate from the other launch records, which a plan call leaves as they are."""
+    buf = (C.c_uint64 * L.PLAN_LAUNCH_SLOTS)()
+    check(load().atc_plan_launch_counts(buf, L.PLAN_LAUNCH_SLOTS))
+    return {1 << i: int(v) for i, v in enumerate(buf) if v}
+
+
 def lookahead_set_mapping(candidates_per_workgroup=0):
-    """Developer knob (atc_lookahead_set_mapping): candidates a workgroup of the calling thread's later look-aheads evaluates;
+    """Developer knob (atc_lookahead_set_mapping): candidates a workgroup of the calling thread's later look-aheads (plans included) evaluates;
     1 = one workgroup per (tile, candidate), M = a loop over all candidates, 0 = the library's choice.  Results do not depend on it."""
     check(load().atc_lookahead_set_mapping(int(candidates_per_workgroup)))
 

@@ -409,6 +409,51 @@ class AtcVecEnv:
         self._finish()
         return res
 
+    PLAN_OUTPUTS = ("seg_reward", "flags", "min_sep", "ac_reward", "obs")
+
+    def lookahead_plan(self, actions, K, outputs=("seg_reward", "flags", "min_sep")):
+        """Plan query (atc_lookahead_plan, include/atc_step.h): lookahead() for candidates that are sequences.  actions:
+        [M, H, B, N, 3] (or [M, H, B, N*3]) — M plans per env, each H decisions held for K steps one after the other, 1 <= M <= 64,
+        1 <= H <= 16, 1 <= K <= 255.  For each plan: what chaining step_skip(actions[m, h], K) over h would return from the state the
+        env is in NOW, stopping at the env's first done — in one launch that writes no state.  Returns a dict of device tensors:
+        reward [M, B] float32 (the sum of the executed segments' rewards, in segment order), done [M, B] uint8, n_steps [M, B] int16
+        (executed steps in total) always, and each of seg_reward [M, H, B] (per-segment rewards, 0 behind the stop: weight them by a
+        discount in torch), flags [M, B, N] int16, min_sep [M, B], ac_reward [M, B, N], obs [M, B, N*10] that `outputs` names
+        (none of the last four: the kernel's fast form).  The tensors are allocated once per (M, H, outputs) and overwritten by the
+        next such call.  Runs on the current stream; env.obs / env.traffic, every bound step output and the whole env state are left
+        as they are.  An env-candidate with a WIDE heading is not evaluated: n_steps == 0 and zeros.  H == 1 is lookahead()."""
+        torch = self.torch
+        K = int(K)
+        if not 1 <= K <= L.SKIP_MAX:
+            raise ValueError("1 <= K <= %d" % L.SKIP_MAX)
+        if not hasattr(actions, "shape") or len(actions.shape) < 2:
+            raise ValueError("actions must be [M, H, B, N, 3] or [M, H, B, N*3]")
+        M, H = int(actions.shape[0]), int(actions.shape[1])
+        if not 1 <= M <= L.LOOKAHEAD_MAX_M:
+            raise ValueError("1 <= M (actions.shape[0]) <= %d" % L.LOOKAHEAD_MAX_M)
+        if not 1 <= H <= L.PLAN_MAX_H:
+            raise ValueError("1 <= H (actions.shape[1]) <= %d" % L.PLAN_MAX_H)
+        outputs = tuple(n for n in self.PLAN_OUTPUTS if n in outputs) if set(outputs) <= set(self.PLAN_OUTPUTS) else None
+        if outputs is None:
+            raise ValueError("outputs must be a subset of %r" % (self.PLAN_OUTPUTS,))
+        a = self._as_actions(actions, lead=(M, H))
+        cache = self.__dict__.setdefault("_plan_cache", {})
+        key = (M, H, outputs)
+        if key not in cache:
+            B, N, z = self.B, self.N, self._new_output
+            shapes = {"reward": ((M, B), torch.float32), "done": ((M, B), torch.uint8), "n_steps": ((M, B), torch.int16),
+                      "seg_reward": ((M, H, B), torch.float32), "flags": ((M, B, N), torch.int16), "min_sep": ((M, B), torch.float32),
+                      "ac_reward": ((M, B, N), torch.float32), "obs": ((M, B, N * L.OBS_DIM), torch.float32)}
+            res = {n: z(*shapes[n]) for n in ("reward", "done", "n_steps") + outputs}
+            cache[key] = (res, _lib.AtcPlanOut(*[self._ptr(res.get(n)) for n in _lib.PLAN_FIELDS]))
+        res, out = cache[key]
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.atc_lookahead_plan(self.sector.handle, self.B, self.N, K, H, M, C.byref(self._state), self._ptr(a),
+                                                    C.byref(out), C.byref(self.params), self._stream()))
+        self._keep_plan = a
+        self._finish()
+        return res
+
     def make_launcher(self, actions, stream=None, held=False):
         """Pre-bound `atc_step` call for FIXED buffers (this env's state / outputs, the given device action tensor, the
         given torch stream or the current one): returns a no-argument callable that only launches — host cost of a few

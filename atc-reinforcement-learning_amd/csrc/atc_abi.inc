@@ -31,6 +31,11 @@ int atc_lookahead_set_mapping(int candidates_per_workgroup) {
     t_look_cpg = candidates_per_workgroup;
     return ATC_OK;
 }
+int atc_plan_launch_counts(uint64_t* out, int n) {
+    if (!out || n < 0) return fail_arg("null pointer");
+    for (int i = 0; i < n && i < ATC_PLAN_LAUNCH_SLOTS; ++i) out[i] = t_plan_launches[i];
+    return ATC_OK;
+}
 int atc_fill_prefetch_info(const atc_scenario_t* s, int B, int N, int* resident, int* stride) {
     if (!s || !resident || !stride) return fail_arg("null pointer");
     if (B < 1 || N < 1 || N > ATC_MAX_AIRCRAFT) return fail_arg("need B >= 1, 1 <= N <= 64");
@@ -429,6 +434,11 @@ int atc_observe_traffic(const atc_scenario_t* s, int B, int N, int K, const atc_
 int atc_lookahead(const atc_scenario_t* s, int B, int N, int K, int M, const atc_state_t* st, const float* actions,
                   const atc_lookahead_out_t* out, const atc_params_t* p, void* stream) {
     return lookahead_common(s, B, N, K, M, st, actions, out, p, stream);
+}
+
+int atc_lookahead_plan(const atc_scenario_t* s, int B, int N, int K, int H, int M, const atc_state_t* st, const float* actions,
+                       const atc_plan_out_t* out, const atc_params_t* p, void* stream) {
+    return plan_common(s, B, N, K, H, M, st, actions, out, p, stream);
 }
 
 }  // extern "C"

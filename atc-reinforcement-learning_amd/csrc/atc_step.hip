@@ -1722,6 +1722,7 @@ k_serve(const float* __restrict__ blob, int off_grid, atc_state_t st, atc_out_t 
 #include "atc_aux_kernels.inc"   // k_reset, k_observe, k_reset_env, k_query_*
 #include "atc_traffic.inc"       // k_traffic (atc_observe_traffic)
 #include "atc_lookahead.inc"     // k_lookahead (atc_lookahead)
+#include "atc_plan.inc"          // k_plan (atc_lookahead_plan)
 
 // ---------------------------------------------------------------------------------------------------------------
 // host side of the C-ABI
@@ -1990,6 +1991,48 @@ static int lookahead_common(const atc_scenario_t* s, int B, int N, int K, int M,
     if (const int rc = check_dt(s, p)) return rc;
     if (p->mode & ATC_M_ACTIONS_HELD) return fail_arg("ATC_M_ACTIONS_HELD is for atc_step only: every candidate's first step carries a fresh decision");
     return with_width(N, [&](auto w) { return launch_lookahead<decltype(w)::value>(s, B, N, K, M, st, actions, out, p, (hipStream_t)stream); });
+}
+
+// ---- plan look-ahead (include/atc_step.h: atc_lookahead_plan) -------------------------------------------------------------------
+// its own launch record (atc_plan_launch_counts): slot = log2(W), the rules of the frame-skip record
+static thread_local uint64_t t_plan_launches[ATC_PLAN_LAUNCH_SLOTS] = {0};
+
+// k_lookahead's launch: the same tiles, candidate groups (atc_lookahead_set_mapping) and grid
+template <int W>
+static int launch_plan(const atc_scenario* s, int B, int N, int K, int H, int M, const atc_state_t* st, const float* actions,
+                       const atc_plan_out_t* po, const atc_params_t* p, hipStream_t stream) {
+    const size_t lds = lds_bytes(s, W >= 32, true);
+    const int tiles = step_grid(B, W);
+    int cpg = t_look_cpg > 0 ? t_look_cpg : ATC_LOOKAHEAD_CPG_DEFAULT;
+    if (cpg > M) cpg = M;
+    const int groups = (M + cpg - 1) / cpg;
+    const long long grid = (long long)((tiles + 7) / 8) * 8 * groups;   // whole chunks of 8 tiles x groups (look_tile)
+    if (grid > 0x7fffffffll) return fail_arg("B*N*M too large for one launch: split the candidates");
+    atc_out_t out;
+    memset(&out, 0, sizeof out);
+    out.obs = po->obs; out.reward = po->reward; out.ac_reward = po->ac_reward; out.done = po->done; out.flags = po->flags; out.min_sep = po->min_sep;
+    const StepDerived& q = derive(*p, s, 0);
+    // the fast form has the four optional outputs compiled out
+    return with_flag(po->flags || po->ac_reward || po->min_sep || po->obs, [&](auto full) {
+        hipLaunchKernelGGL((k_plan<W, decltype(full)::value>), dim3((unsigned)grid), dim3(kBlock), lds, stream, s->d_blob, s->off_grid, B, N, K, H, M, *st, actions, out, *p, q, po->n_steps, po->seg_reward, cpg, groups, tiles);
+        HIP_TRY(hipGetLastError());
+        ++t_plan_launches[__builtin_ctz(W)];
+        return ATC_OK;
+    });
+}
+
+static int plan_common(const atc_scenario_t* s, int B, int N, int K, int H, int M, const atc_state_t* st, const float* actions,
+                       const atc_plan_out_t* out, const atc_params_t* p, void* stream) {
+    // K, then H, then M, before any pointer is looked at
+    if (K < 1 || K > ATC_SKIP_MAX) return fail_arg("K (the segment length) must be 1 .. 255");
+    if (H < 1 || H > ATC_PLAN_MAX_H) return fail_arg("H (the number of segments of a plan) must be 1 .. 16");
+    if (M < 1 || M > ATC_LOOKAHEAD_MAX_M) return fail_arg("M (the number of candidates) must be 1 .. 64");
+    if (!out || !out->reward || !out->done) return fail_arg("null pointer: atc_plan_out_t.reward and .done are required");
+    if (!actions) return fail_arg("null pointer");
+    if (const int rc = check_env_args(s, B, N, st, p)) return rc;
+    if (const int rc = check_dt(s, p)) return rc;
+    if (p->mode & ATC_M_ACTIONS_HELD) return fail_arg("ATC_M_ACTIONS_HELD is for atc_step only: every segment's first step carries a fresh decision");
+    return with_width(N, [&](auto w) { return launch_plan<decltype(w)::value>(s, B, N, K, H, M, st, actions, out, p, (hipStream_t)stream); });
 }
 
 #include "atc_abi.inc"   // the extern "C" entry points (host side)

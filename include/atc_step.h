@@ -710,6 +710,60 @@ int atc_lookahead_launch_counts(uint64_t* out, int n);
  * 0 .. ATC_LOOKAHEAD_MAX_M. */
 int atc_lookahead_set_mapping(int candidates_per_workgroup);
 
+/* PLAN LOOK-AHEAD (extension): atc_lookahead for candidates that are SEQUENCES — M plans per env, each H action blocks held for K
+ * steps one after the other ("turn now, descend in 20 s, slow down after that"), scored in ONE launch that never writes state: what
+ * CEM / MPPI sample and weight by a discount.  1 <= K <= ATC_SKIP_MAX, 1 <= H <= ATC_PLAN_MAX_H, 1 <= M <= ATC_LOOKAHEAD_MAX_M.
+ * Defined per candidate m and env e, on a bit-exact private copy of the env's state, as
+ *
+ *     n = 0
+ *     for h = 0 .. H-1:
+ *         r_h = atc_step_skip(copy, K, actions[m][h])      everything atc_step_skip defines
+ *         n += r_h.n_steps
+ *         if r_h.done: break                               a plan never spans two episodes, ATC_M_AUTO_RESET or not
+ *
+ *   seg_reward [m][h]  r_h.reward for an executed segment, 0 for a segment after the break
+ *   reward [m]         the float32 sum of the executed segments' r_h.reward, accumulated sequentially in segment order
+ *                      (acc = r_0; acc = acc + r_1; ...; plain additions, never fused): a host loop over atc_step_skip outputs
+ *                      reproduces it bit for bit
+ *   ac_reward [m]      the same two-level sum per aircraft
+ *   flags [m]          bitwise OR over all executed steps
+ *   min_sep [m]        minimum over all executed steps
+ *   done [m]           the last executed segment's done
+ *   obs [m]            the last executed segment's obs (after a look-ahead reset under ATC_M_AUTO_RESET: the raw reset observation,
+ *                      as atc_lookahead defines it)
+ *   n_steps [m]        n, the total of executed steps (<= H K = 4080); the number of executed segments is ceil(n / K)
+ * The first step of every segment carries a fresh decision: the last-action record, actions_taken and the refused-target verdict
+ * behave as the chain above makes them (carried inside the launch, never stored).
+ * Candidates are independent of each other, of M and of neighbouring envs.  H == 1 reproduces atc_lookahead bit for bit in every
+ * shared output (n_steps carries the same values).  The first h segments of a plan give the seg_reward of a call with H = h on the
+ * plan's prefix.  reward and done are required, every other output pointer may be NULL; a launch that asks for none of flags,
+ * ac_reward, min_sep, obs runs a form with them compiled out (seg_reward and n_steps are available in both forms).
+ * STATE: the call reads atc_state_t and writes none of it — all six arrays are byte-identical afterwards, `stats` and the phi_wide
+ * scratch word included.
+ * LIMIT — WIDE headings: atc_lookahead's rule over all segments.  An env-candidate is NOT EVALUATED when any aircraft's heading or
+ * accepted heading target is WIDE at the start or becomes WIDE in any executed step of any segment: n_steps = 0, done = 0, reward = 0
+ * and every requested word of that (m, e) is 0 — the seg_reward of segments already run included.
+ * ATC_ERR_ARG, in this order, the first three before any pointer is looked at: K outside 1 .. ATC_SKIP_MAX; H outside 1 ..
+ * ATC_PLAN_MAX_H; M outside 1 .. ATC_LOOKAHEAD_MAX_M; out, out->reward or out->done NULL; the argument errors of atc_step;
+ * ATC_M_ACTIONS_HELD in p->mode.
+ * Counted by atc_plan_launch_counts only (slot = log2(W); the rules of atc_skip_launch_counts): the other launch records do not move.
+ * atc_lookahead_set_mapping governs this call's candidates per workgroup as well. */
+#define ATC_PLAN_MAX_H 16
+typedef struct atc_plan_out {
+    float*    reward;     /* [M][B]      required */
+    uint8_t*  done;       /* [M][B]      required */
+    uint16_t* n_steps;    /* [M][B]      nullable; total executed steps (<= H*K = 4080); 0 = not evaluated */
+    float*    seg_reward; /* [M][H][B]   nullable */
+    uint16_t* flags;      /* [M][B*N]    nullable */
+    float*    ac_reward;  /* [M][B*N]    nullable */
+    float*    min_sep;    /* [M][B]      nullable */
+    float*    obs;        /* [M][B*N*10] nullable */
+} atc_plan_out_t;
+int atc_lookahead_plan(const atc_scenario_t* s, int B, int N, int K, int H, int M, const atc_state_t* st,
+                       const float* actions /* [M][H][B*N*3] */, const atc_plan_out_t* out, const atc_params_t* p, void* stream);
+enum { ATC_PLAN_LAUNCH_SLOTS = 7 };
+int atc_plan_launch_counts(uint64_t* out, int n);
+
 #ifdef __cplusplus
 }
 #endif
