@@ -75,6 +75,38 @@ def check_skip_outputs(got, ref, half, full, tag=None):
         assert np.all(np.abs(got["term_obs"] - ref["term_obs"]) <= 1e-5 * np.maximum(1.0, np.abs(ref["term_obs"]))), ("term_obs", tag)
 
 
+_SKIP_KEYS = ("flags", "done", "n_steps", "obs", "reward", "reward_scale", "raw_obs", "ac_reward", "ac_reward_scale", "min_sep", "term_obs")
+
+
+def check_candidate_outputs(got, ref, ok, half, tag=None):
+    """One candidate of a look-ahead or plan call against its reference dict (tests/skip_ref.py: skip_reference / plan_chain), under
+    check_skip_outputs' bars.  got: the candidate's rows of the outputs the call returned — reward, done, n_steps always, flags,
+    ac_reward, min_sep, obs where requested — as numpy arrays with the env axis first; ok [B] bool: the envs that are evaluated.  An output
+    the call does not have (raw_obs, term_obs) or was not asked for takes the reference's own value.  Envs outside `ok` (WIDE at the
+    start): n_steps == 0 and every returned word zero."""
+    B, N = ref["obs"].shape[:2]
+    r = {k: np.asarray(ref[k])[ok] for k in _SKIP_KEYS}
+    g = {k: (np.asarray(got[k]).reshape(np.asarray(ref[k]).shape)[ok] if k in got else r[k]) for k in _SKIP_KEYS if not k.endswith("_scale")}
+    g["n_steps"] = g["n_steps"].astype(np.int64)
+    r["n_steps"] = r["n_steps"].astype(np.int64)
+    if ok.any():
+        check_skip_outputs(g, r, half, True, tag)
+    for k, v in got.items():
+        v = np.ascontiguousarray(np.asarray(v).reshape(B, -1)[~ok])
+        assert not v.view(np.uint8).any(), ("an env that is not evaluated must return zeros", k, tag)
+
+
+def check_plan_segments(seg_reward, ref, ok, K, tag=None):
+    """seg_reward [H, B] of one plan against tests/skip_ref.py::plan_chain: each segment's reward is one frame-skip call's reward and gets
+    that call's bar; zero words behind the env's stop, and everywhere for an env that is not evaluated."""
+    seg_reward = np.ascontiguousarray(seg_reward)
+    err = np.abs(seg_reward.astype(np.float64) - ref["seg_reward"])
+    assert np.all((err <= 1e-5 * ref["seg_reward_scale"])[:, ok]), ("seg_reward", tag, float((err[:, ok] / np.maximum(1e-5 * ref["seg_reward_scale"][:, ok], 1e-300)).max()))
+    segs = -(-ref["n_steps"].astype(np.int64) // K)
+    behind = np.arange(seg_reward.shape[0])[:, None] >= np.where(ok, segs, 0)[None, :]
+    assert not seg_reward.view(np.uint32)[behind].any(), ("seg_reward behind the stop", tag)
+
+
 def check_state(env, orc, rows_env=slice(None), rows_ac=slice(None), total_reward=True):
     """The persistent state of an AtcVecEnv against the oracle's: the fp32 spec (include/atc_step.h: fixed-point position grid, shared
     heading kinematics, exact rate-limit arithmetic) makes the whole aircraft state BIT-IDENTICAL to the fp32 oracle's — the exact

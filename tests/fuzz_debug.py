@@ -1,12 +1,33 @@
 """Debugging aid for a failing case of test_fuzz_parity.py (not collected by pytest):
     python tests/fuzz_debug.py <seed>
-replays the case step by step and prints the first deviation of every kind with its context."""
+replays the case step by step and prints the first deviation of every kind with its context;
+    python tests/fuzz_debug.py --held <seed>
+replays one case of test_fuzz_held.py (tests/held_fuzz.py) and prints the first deviation with the call, candidate, segment, env and
+aircraft it is in and the oracle's per-step record of that env."""
 import os
 import sys
 
 _ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [_ROOT, os.path.join(_ROOT, "atc-reinforcement-learning_amd"), os.path.dirname(os.path.abspath(__file__))]
 import numpy as np
+
+if sys.argv[1] == "--held":
+    import held_fuzz as F
+    from atc_hip import lib
+    seed = int(sys.argv[2])
+    scn, comp, kw = F.case(seed)
+    print(type(scn).__name__, kw)
+    try:
+        rec = F.run(seed, device=True)
+        print("launched", rec["launches"])
+        print("events", rec["events"], "\nwide", rec["wide"], "traffic_short", rec["traffic_short"])
+        print("no deviation")
+    except F.Mismatch as m:
+        F.describe(m, comp)
+        print("launched so far: step", lib.launch_counts(), "skip", lib.skip_launch_counts(), "lookahead", lib.lookahead_launch_counts(),
+              "plan", lib.plan_launch_counts(), "traffic", lib.traffic_launch_counts())
+    sys.exit(0)
+
 import test_fuzz_parity as T
 from atc_hip.vec_env import AtcVecEnv
 from envs.atc import model

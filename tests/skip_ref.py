@@ -4,7 +4,11 @@ skip_reference(orc, actions, K) is the definition — per env: step with the sam
 taken; outputs and state are those of the n executed steps — evaluated for a whole batch: the oracle steps K times on ALL envs,
 every step's state and outputs are kept, each env's n follows from the done column, and the env's rows of its step-n snapshot go
 back into the oracle's arrays, so that consecutive calls chain.  Envs are independent and the oracle's reset sampler is keyed by
-(seed, env, episode, slot), so what an env does after its own step n changes nothing for the others."""
+(seed, env, episode, slot), so what an env does after its own step n changes nothing for the others.
+
+candidate_references / plan_references are the look-ahead and the plan call (atc_lookahead, atc_lookahead_plan) on the same footing: the
+frame-skip reference per candidate — chained over a plan's segments, an env leaving at its first done — from a snapshot of the oracle
+that is restored after each candidate."""
 import numpy as np
 
 # the 16 state arrays of oracle.OracleEnv (its _st table) and which of them have one row per aircraft (the others: one per env)
@@ -16,6 +20,24 @@ OUTPUTS = ("obs", "raw_obs", "reward", "ac_reward", "done", "flags", "min_sep", 
 
 def snapshot_state(orc):
     return {k: getattr(orc, k).copy() for k in STATE}
+
+
+def snapshot(orc):
+    """state and output arrays of the oracle, for restore()"""
+    return snapshot_state(orc), {k: getattr(orc, k).copy() for k in OUTPUTS}
+
+
+def restore(orc, snap):
+    for part in snap:
+        for k, v in part.items():
+            getattr(orc, k)[...] = v
+
+
+def wide_envs(orc):
+    """[B] bool: envs with an aircraft whose heading or last heading target is WIDE (saturated 32-bit field, include/atc_step.h ABI 19):
+    the look-ahead calls do not evaluate them"""
+    edge = (-2 ** 31, 2 ** 31 - 1)
+    return np.isin(orc.last_act[:, 1], edge).reshape(orc.B, orc.N).any(1) | np.isin(orc.phi_fix, edge).reshape(orc.B, orc.N).any(1)
 
 
 def f32_sequential_sum(terms, n):
@@ -98,3 +120,64 @@ def literal_skip(orc1, actions, K):
             "done": orc1.done.copy(), "flags": np.bitwise_or.reduce(np.stack(flags), axis=0),
             "min_sep": np.stack(seps).min(axis=0).astype(np.float32),
             "term_obs": orc1.term_obs.copy() if orc1.done[0] else term_before}
+
+
+def candidate_references(orc, cand, K):
+    """The look-ahead call (atc_lookahead) on the oracle: skip_reference per candidate of cand [M, B, N, 3] from a snapshot of the oracle,
+    restored after each candidate — the oracle is left as it was.  Returns the M reference dicts."""
+    snap = snapshot(orc)
+    refs = []
+    for m in range(cand.shape[0]):
+        refs.append(skip_reference(orc, cand[m], K))
+        restore(orc, snap)
+    return refs
+
+
+def plan_chain(orc, plan, K, record=None):
+    """The plan call (atc_lookahead_plan) on the oracle for ONE candidate ([H, B, N, 3]): chained skip_reference calls, an env leaving at
+    its first done.  The oracle is left wherever the chain ends: the caller restores it.  Returns what bars.check_skip_outputs reads, plus
+    seg_reward [H, B] and seg_reward_scale [H, B] (each segment's own bar: that of one frame-skip call).  record: a list that gets one
+    (alive [B] before the segment, the segment's skip_reference dict) per segment."""
+    B = orc.B
+    alive = np.ones(B, bool)
+    out = None
+    seg = np.zeros((plan.shape[0], B), np.float32)
+    seg_scale = np.zeros((plan.shape[0], B))
+    for h in range(plan.shape[0]):
+        r = skip_reference(orc, plan[h], K)
+        if record is not None:
+            record.append((alive.copy(), r))
+        if out is None:
+            out = {k: np.array(r[k]).copy() for k in ("obs", "raw_obs", "term_obs", "reward", "ac_reward", "done", "flags", "min_sep",
+                                                      "reward_scale", "ac_reward_scale")}
+            out["n_steps"] = r["n_steps"].astype(np.int64)
+        else:
+            a1, a2, a3 = alive, alive[:, None], alive[:, None, None]
+            for k, m in (("obs", a3), ("raw_obs", a3), ("term_obs", a3), ("done", a1)):
+                out[k] = np.where(m, r[k], out[k])
+            out["reward"] = np.where(a1, (out["reward"] + r["reward"]).astype(np.float32), out["reward"])
+            out["ac_reward"] = np.where(a2, (out["ac_reward"] + r["ac_reward"]).astype(np.float32), out["ac_reward"])
+            out["reward_scale"] = out["reward_scale"] + np.where(a1, r["reward_scale"], 0.0)
+            out["ac_reward_scale"] = out["ac_reward_scale"] + np.where(a2, r["ac_reward_scale"], 0.0)
+            out["flags"] = np.where(a2, out["flags"] | r["flags"], out["flags"])
+            out["min_sep"] = np.where(a1, np.minimum(out["min_sep"], r["min_sep"]), out["min_sep"])
+            out["n_steps"] = out["n_steps"] + np.where(a1, r["n_steps"].astype(np.int64), 0)
+        seg[h] = np.where(alive, r["reward"], 0.0)
+        seg_scale[h] = np.where(alive, r["reward_scale"], 0.0)
+        alive = alive & ~r["done"].astype(bool)
+    out["seg_reward"], out["seg_reward_scale"] = seg, seg_scale
+    return out
+
+
+def plan_references(orc, cand, K, records=None):
+    """plan_chain per candidate of cand [M, H, B, N, 3] from a snapshot of the oracle, restored after each candidate.  records: a list that
+    gets each candidate's plan_chain record."""
+    snap = snapshot(orc)
+    refs = []
+    for m in range(cand.shape[0]):
+        rec = [] if records is not None else None
+        refs.append(plan_chain(orc, cand[m], K, rec))
+        if records is not None:
+            records.append(rec)
+        restore(orc, snap)
+    return refs

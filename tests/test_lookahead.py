@@ -328,28 +328,14 @@ def test_lookahead_against_the_oracle(N):
     # headings inside the action space (a WIDE target is not evaluated: its own test), speeds and altitudes partly refused
     cand = TF._actions(rng, M * B, N).reshape(M, B, N, 3)
     cand[..., 2] = np.clip(cand[..., 2], -1.0, 1.0)
-    wide0 = np.isin(orc.last_act[:, 1], (-2 ** 31, 2 ** 31 - 1)).reshape(B, N).any(1) | \
-        np.isin(orc.phi_fix, (-2 ** 31, 2 ** 31 - 1)).reshape(B, N).any(1)
+    wide0 = R.wide_envs(orc)
     assert not wide0.all()
     res = env.lookahead(torch.as_tensor(cand, device=env.device), K, outputs=ALL)
     got = {k: v.cpu().numpy() for k, v in res.items()}
-    saved, outs = R.snapshot_state(orc), {k: getattr(orc, k).copy() for k in R.OUTPUTS}
     early = 0
-    for m in range(M):
-        ref = R.skip_reference(orc, cand[m], K)
-        for k, v in saved.items():
-            getattr(orc, k)[...] = v
-        for k, v in outs.items():
-            getattr(orc, k)[...] = v
-        ok = ~wide0
-        g = {"flags": got["flags"][m][ok], "done": got["done"][m][ok], "n_steps": got["n_steps"][m][ok],
-             "obs": got["obs"][m].reshape(B, N, 10)[ok], "reward": got["reward"][m][ok], "ac_reward": got["ac_reward"][m][ok],
-             "min_sep": got["min_sep"][m][ok]}
-        r = {k: (np.asarray(v)[ok] if np.asarray(v).shape[:1] == (B,) else v) for k, v in ref.items()}
-        g["raw_obs"], g["term_obs"] = r["raw_obs"], r["term_obs"]     # (outputs the look-ahead does not have)
-        bars.check_skip_outputs(g, r, bars.half_range(comp), True, tag=(N, m))
-        assert (got["n_steps"][m][wide0] == 0).all()
-        early += int((ref["n_steps"][ok] < K).sum())
+    for m, ref in enumerate(R.candidate_references(orc, cand, K)):
+        bars.check_candidate_outputs({k: v[m] for k, v in got.items()}, ref, ~wide0, bars.half_range(comp), tag=(N, m))
+        early += int((ref["n_steps"][~wide0] < K).sum())
     assert early > 0
     bars.check_state(env, orc)
     env.close()

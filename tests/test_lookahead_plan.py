@@ -156,46 +156,7 @@ def _oracle_inputs(rng, B, N):
     return flown, cand
 
 
-def _oracle_chain(orc, plan, K):
-    """The definition on the oracle for ONE candidate ([H, B, N, 3]): chained skip_reference calls, an env leaving at its first done.
-    The oracle is left wherever the chain ends: the caller restores it.  Returns what bars.check_skip_outputs reads, plus seg_reward."""
-    B, N = orc.B, orc.N
-    alive = np.ones(B, bool)
-    out = None
-    seg = np.zeros((plan.shape[0], B), np.float32)
-    for h in range(plan.shape[0]):
-        r = R.skip_reference(orc, plan[h], K)
-        if out is None:
-            out = {k: np.array(r[k]).copy() for k in ("obs", "raw_obs", "term_obs", "reward", "ac_reward", "done", "flags", "min_sep",
-                                                      "reward_scale", "ac_reward_scale")}
-            out["n_steps"] = r["n_steps"].astype(np.int64)
-        else:
-            a1, a2, a3 = alive, alive[:, None], alive[:, None, None]
-            for k, m in (("obs", a3), ("raw_obs", a3), ("term_obs", a3), ("done", a1)):
-                out[k] = np.where(m, r[k], out[k])
-            out["reward"] = np.where(a1, (out["reward"] + r["reward"]).astype(np.float32), out["reward"])
-            out["ac_reward"] = np.where(a2, (out["ac_reward"] + r["ac_reward"]).astype(np.float32), out["ac_reward"])
-            out["reward_scale"] = out["reward_scale"] + np.where(a1, r["reward_scale"], 0.0)
-            out["ac_reward_scale"] = out["ac_reward_scale"] + np.where(a2, r["ac_reward_scale"], 0.0)
-            out["flags"] = np.where(a2, out["flags"] | r["flags"], out["flags"])
-            out["min_sep"] = np.where(a1, np.minimum(out["min_sep"], r["min_sep"]), out["min_sep"])
-            out["n_steps"] = out["n_steps"] + np.where(a1, r["n_steps"].astype(np.int64), 0)
-        seg[h] = np.where(alive, r["reward"], 0.0)
-        alive = alive & ~r["done"].astype(bool)
-    out["seg_reward"] = seg
-    return out
-
-
-def _oracle_refs(orc, cand, K):
-    saved, outs = R.snapshot_state(orc), {k: getattr(orc, k).copy() for k in R.OUTPUTS}
-    refs = []
-    for m in range(cand.shape[0]):
-        refs.append(_oracle_chain(orc, cand[m], K))
-        for k, v in saved.items():
-            getattr(orc, k)[...] = v
-        for k, v in outs.items():
-            getattr(orc, k)[...] = v
-    return refs
+_oracle_chain, _oracle_refs = R.plan_chain, R.plan_references   # (the definition on the oracle: shared with tests/held_fuzz.py)
 
 
 @pytest.mark.parametrize("N", WIDTH_N)
@@ -561,26 +522,15 @@ def test_plan_against_the_oracle(N):
         R.skip_reference(orc, a, Kf)
         env.step_skip(a, Kf)
     bars.check_state(env, orc)
-    wide0 = np.isin(orc.last_act[:, 1], (-2 ** 31, 2 ** 31 - 1)).reshape(B, N).any(1) | \
-        np.isin(orc.phi_fix, (-2 ** 31, 2 ** 31 - 1)).reshape(B, N).any(1)
+    wide0 = R.wide_envs(orc)
     assert not wide0.all()
     ok = ~wide0
     res = env.lookahead_plan(torch.as_tensor(cand, device=env.device), K, outputs=ALL)
     got = {k: v.cpu().numpy() for k, v in res.items()}
     early = 0
     for m, ref in enumerate(_oracle_refs(orc, cand, K)):
-        g = {"flags": got["flags"][m][ok], "done": got["done"][m][ok], "n_steps": got["n_steps"][m][ok].astype(np.int64),
-             "obs": got["obs"][m].reshape(B, N, 10)[ok], "reward": got["reward"][m][ok], "ac_reward": got["ac_reward"][m][ok],
-             "min_sep": got["min_sep"][m][ok]}
-        r = {k: np.asarray(v)[ok] for k, v in ref.items() if k != "seg_reward"}
-        g["raw_obs"], g["term_obs"] = r["raw_obs"], r["term_obs"]     # (outputs the plan call does not have)
-        bars.check_skip_outputs(g, r, bars.half_range(comp), True, tag=(N, m))
-        # per-segment rewards: each is one frame-skip call's reward — its bar is that call's, bounded by the plan's summed bar
-        assert np.all(np.abs(got["seg_reward"][m][:, ok].astype(np.float64) - ref["seg_reward"][:, ok]) <= 1e-5 * r["reward_scale"][None, :])
-        segs = -(-ref["n_steps"] // K)
-        for e in np.nonzero(ok)[0]:
-            assert not got["seg_reward"][m][segs[e]:, e].view(np.uint32).any()
-        assert (got["n_steps"][m][wide0] == 0).all()
+        bars.check_candidate_outputs({k: v[m] for k, v in got.items() if k != "seg_reward"}, ref, ok, bars.half_range(comp), tag=(N, m))
+        bars.check_plan_segments(got["seg_reward"][m], ref, ok, K, tag=(N, m))
         early += int((ref["n_steps"][ok] < Hn * K).sum())
     assert early > 0
     bars.check_state(env, orc)

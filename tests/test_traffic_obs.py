@@ -308,13 +308,7 @@ def test_refusals_count_nothing():
 def _check_env_traffic(env, traffic, what):
     """info["traffic"] against the reference on the state copied back from the device"""
     env.synchronize()
-    comp = env.compiled
-    ref = R.traffic_reference(R.state_from_env(env), comp.pos_origin, comp.pos_k)
-    scales = R.norm_scales(comp) if env.params.mode & L.M_NORMALIZE else None
-    bad = R.compare(traffic.cpu().numpy(), ref, env.traffic_k, scales)
-    print("%s: %s" % (what, bad or "ok"))
-    assert not bad, (what, bad)
-    return ref
+    return R.check_traffic(traffic.cpu().numpy(), R.state_from_env(env), env.compiled, env.traffic_k, bool(env.params.mode & L.M_NORMALIZE), what)
 
 
 @pytest.mark.gpu

@@ -201,3 +201,20 @@ def state_from_env(env):
     return dict(x_fix=ac[..., L.AC_X], y_fix=ac[..., L.AC_Y], h=env.alt.cpu().numpy().reshape(B, N),
                 P=env.phi_counts.cpu().numpy().reshape(B, N), v_fix=ac[..., L.AC_V].view(np.uint32),
                 mask=env.active_mask.cpu().numpy().astype(np.uint64))
+
+
+def state_from_oracle(orc):
+    """the reference's input from an oracle.OracleEnv of the fp32 instantiation"""
+    B, N = orc.B, orc.N
+    return dict(x_fix=orc.px.reshape(B, N), y_fix=orc.py.reshape(B, N), h=orc.h.reshape(B, N),
+                P=orc.phi_counts.astype(np.float64).reshape(B, N), v_fix=orc.v_fix.view(np.uint32).reshape(B, N), mask=orc.active_mask)
+
+
+def check_traffic(got, state, comp, K, normalize, what):
+    """got [B, N, K, 8] (a launch's records, copied back) against the reference on `state` under compare()'s bars; comp: the compiled
+    sector, normalize: whether the launch normalised.  Prints the verdict, asserts it and returns the reference."""
+    ref = traffic_reference(state, comp.pos_origin, comp.pos_k)
+    bad = compare(got, ref, K, norm_scales(comp) if normalize else None)
+    print("%s: %s" % (what, bad or "ok"))
+    assert not bad, (what, bad)
+    return ref
