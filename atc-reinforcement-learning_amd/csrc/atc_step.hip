@@ -589,9 +589,12 @@ __device__ __forceinline__ Mid step_part_a(const float* __restrict__ grid, const
     // Speed and heading are 32-bit fixed point (include/atc_step.h): the move is integer arithmetic — exact, like the
     // reference's float64 — with wrapping differences for the speed (valid speeds and the initial last_action 0 are less than
     // 2^31 counts apart) and saturating ones for the heading (its targets are not validated: any action is accepted).
-    constexpr double h_min = kHMin, h_max = kHMax;   // (model.py:91-94: float64 compares with the float64 target)
+    // (model.py:91-94: float64 compares with the float64 target — written so that a NaN target, the altitude action NaN, is REFUSED like
+    // a NaN speed target (include/atc_step.h "Non-finite actions"): accepted iff h_min <= target <= h_max)
+    constexpr double h_min = kHMin, h_max = kHMax;
     const bool valid_v = !(tv < kVMinFix || tv > kVMaxFix);
-    const bool valid_h = !(th < h_min || th > h_max);
+    const bool h_low = !(th >= h_min), h_high = !(th <= h_max);   // (both true for NaN; the same two compares feed `refused` below)
+    const bool valid_h = !(h_low || h_high);
     // `plain` (wave-uniform): every lane of the wavefront flies an aircraft under control towards valid targets — the normal
     // case by far (a refused target or a handed-over aircraft in 64 is the exception).  Then nothing is conditional: no
     // select per state component, no refusal penalties, no flag bits.  Otherwise the branch-free general form below.  Both
@@ -605,7 +608,7 @@ __device__ __forceinline__ Mid step_part_a(const float* __restrict__ grid, const
     uint64_t refused = refused_blk;
     if (!refused_known) {
         refused = __builtin_amdgcn_ballot_w64(tv < kVMinFix) | __builtin_amdgcn_ballot_w64(tv > kVMaxFix) |
-                  __builtin_amdgcn_ballot_w64(th < h_min) | __builtin_amdgcn_ballot_w64(th > h_max) |
+                  __builtin_amdgcn_ballot_w64(h_low) | __builtin_amdgcn_ballot_w64(h_high) |
                   (__builtin_amdgcn_ballot_w64(tp == INT32_MAX) | __builtin_amdgcn_ballot_w64(tp == INT32_MIN));
         refused_blk = refused;
     }

@@ -11,6 +11,7 @@ reference does in Python (win ring buffer, counters), in the same order, includi
   * no auto-reset, stepping a finished episode keeps counting (learning/atc-gym-compute-performance.py relies on it)
   * the win buffer gets one append per terminal CAUSE (atc_gym.py:151,158,165) and reset() pops exactly one (:359-363)
 """
+import math
 import random
 import weakref
 from time import perf_counter as _perf_counter
@@ -265,7 +266,10 @@ class AtcGym(Env):
         if flags & (L.F_INVALID_V | L.F_INVALID_H):  # atc_gym.py:314
             for bit, idx in ((L.F_INVALID_V, 0), (L.F_INVALID_H, 1)):
                 if flags & bit:
-                    print("Warning invalid action: %d for index: %d" % (self._denormalized_action(self._act_np[idx], idx), idx))
+                    # (the reference's "%d" raises on a non-finite target — OverflowError for +-Inf, out of its own warning; a NaN
+                    # target is refused here, include/atc_step.h "Non-finite actions": the step has been taken, so say it and go on)
+                    tgt = float(self._denormalized_action(self._act_np[idx], idx))
+                    print("Warning invalid action: %s for index: %d" % ("%d" % tgt if math.isfinite(tgt) else tgt, idx))
         assert self.done == bool(dn)
         self.state = raw
         self._update_metrics(rew)

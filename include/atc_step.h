@@ -27,6 +27,10 @@
 extern "C" {
 #endif
 
+/* The ABI number guards what a caller built against another version of this header would get WRONG IN MEMORY: it moves when a record
+ * layout, a blob word, a struct or the signature of an existing entry point changes (18, 19, 20, 22 each changed a record).  It does not
+ * move for a new entry point, nor for a change of documented behaviour that leaves every layout and signature as it is — such a change
+ * is stated where the behaviour is described (e.g. "NON-FINITE ACTIONS" below). */
 #define ATC_ABI_VERSION 22
 
 /* ---------------------------------------------------------------------------------------------
@@ -265,7 +269,9 @@ typedef struct atc_params {
  *     [44, 356] kt, within 256 kt of every acceptable target: the host mirror's set_v refuses others —, exact for the heading: the 32-bit saturating
  *     form gives the same result whenever target and heading are both inside the 32-bit range, which is what the kernels
  *     evaluate for such lanes); the "action taken" discriminator (atc_gym.py:84,305-306) compares the same integer differences
- *     with 5 * 2^23 / 0.5 * 2^23 counts;
+ *     with 5 * 2^23 / 0.5 * 2^23 counts (targets are TRUNCATED to counts, each by less than one: two targets whose float64 difference is
+ *     within a count — 1.2e-7 kt / deg — below the threshold can be exactly D counts apart and are then counted here and not by the
+ *     reference; tests/golden/g15 holds such pairs);
  *   - what the heading feeds: the kinematics and every relative angle / the corridor window are periodic in the heading, the
  *     observation's raw heading (atc_gym.py:269) is not.  A heading inside the 32-bit range is used as it is:
  *       fp32 heading = fmaf((float)phi_fix, 2^-23, 180),  kinematics from phi_fix (below).
@@ -288,7 +294,8 @@ typedef struct atc_params {
  *     0.4 ulp off PER STEP for 0.1 s: the below-MVA flag came one step late in 19 of 120 sustained descents, tests/golden/g12):
  *       target = a * m + c        one float64 fma on the fp32 action (the product is exact): the reference's a * f / 2 + f / 2 + off
  *                                 (atc_gym.py:333-335; discrete: a * 100 + 0, :329-330) bit for bit
- *       refused iff target < h_min or target > h_max                                        (model.py:91-94, float64 compares)
+ *       refused iff NOT (target >= h_min and target <= h_max)       (float64 compares; for every finite action the reference's
+ *                                 `target < h_min or target > h_max`, model.py:91-94 — and a NaN target is refused, see below)
  *       h += max(min(target - h, 15 dt), -41 dt)       three float64 operations, dt the float64 of atc_params_t (model.py:95-102)
  *       below the MVA iff h < mva                       (atc_gym.py:149-153; the MVA height is an integer)
  *       observation words 2 and 5 = (float)h and (float)(h - mva), the difference in float64          (atc_gym.py:266,276)
@@ -297,6 +304,26 @@ typedef struct atc_params {
  *     glide-path test of the corridor (model.py:201-208), the shaping terms, the separation scan — is (float)h, one rounding.
  *     The last accepted altitude target (last_action[1], atc_gym.py:311) is kept as the same float64.
  *   - state placed from outside (entry points, fixtures) is the NEAREST count.
+ *   - NON-FINITE ACTIONS.  A diverged policy emits NaN and +-Inf; the reference does not survive them, this library does.  No action
+ *     value can put a NaN or an infinity into the state or into any output.  Per component (tests/test_action_edges.py, every value
+ *     on every entry point; tests/golden/g15 pins the reference's side):
+ *       speed     NaN -> 0 counts, refused (ATC_F_INVALID_V, -1, nothing applied, last_action kept).  +-Inf and +-FLT_MAX saturate at
+ *                 the ends of the uint32 range and are refused like any target outside [100, 300] kt.
+ *       altitude  NaN is REFUSED like a NaN speed (ATC_F_INVALID_H, -1, nothing applied, last_action kept): the refusal is written
+ *                 `not (target >= h_min and target <= h_max)`.  +-Inf and +-FLT_MAX (6.5e42 ft as a float64) are outside the bounds
+ *                 and refused.
+ *       heading   never refused.  NaN -> 0 counts (180 deg), an ordinary target that is counted like one.  +-Inf and +-FLT_MAX are
+ *                 clamped to +-2^52 counts with ATC_F_PHI_LIMIT; held, the clamped targets are EQUAL and counted once.
+ *       +-0.0 and subnormal actions are ordinary numbers: the one rounding of the fma absorbs them.
+ *     The reference, for comparison (nothing here follows it): its compares let a NaN target through (model.py:69-72, 91-94: `nan <
+ *     v_min` is False), min / max pass it on and v, h or phi is NaN from then on — state, observation and reward stay NaN until
+ *     reset, and every later step counts an action (`abs(nan - x) < d` is False, atc_gym.py:305).  An infinite speed or altitude
+ *     target is refused, and the warning it prints, "%d" % inf (atc_gym.py:314), raises OverflowError out of step().  An infinite
+ *     heading target turns the aircraft at the rate limit like here, but abs(inf - inf) is NaN, so the reference counts an action in
+ *     EVERY step it is held where this library counts the first: that, like two different targets beyond +-2^52 above, is a
+ *     difference of the action counter alone.
+ *     (A change of results for actions no action space contains, with no record layout or signature touched: the ABI number stays,
+ *     see ATC_ABI_VERSION.)
  * Heading kinematics (model.py:122-129, 345-348) in float64, shared bit for bit by every fp32 implementation (the HIP
  * kernels, the fp32 instantiation of the test oracle):
  *   k = rint(phi_fix * ATC_KIN_INV180)  [(180 * 2^23)^-1, nearest-even],  t = fma(k, -180 * 2^23, phi_fix)  (exact: the
@@ -328,7 +355,8 @@ typedef struct atc_params {
  * times the fp32 evaluation error) therefore cannot be in conflict during the next n steps, whatever the actions.  Multi-step launches
  * (atc_rollout, atc_rollout_hold) of envs of more than 16 aircraft that do not report min_sep use this: a full scan notes which
  * groups of partners hold a pair inside those thresholds, and for the next n steps only those groups are scanned (none: no scan) —
- * unless an aircraft is above 300 kt or an altitude is beyond 2^17 ft in magnitude or NaN (then every step scans in full); an env
+ * unless an aircraft is above 300 kt or an altitude is beyond 2^17 ft in magnitude or NaN (then every step scans in full; no ACTION can
+ * produce such an altitude any more — a NaN target is refused, see "NON-FINITE ACTIONS" — but state placed from outside still can, so the guard stays); an env
  * that is reset inside the launch ends the horizon of its wavefront.  tests/test_hip_edge_cases.py
  * (test_scan_horizon_on_the_fastest_closing_courses) drives pairs at exactly these closing rates through every phase of a horizon. */
 #define ATC_V_FIX_SHIFT 23

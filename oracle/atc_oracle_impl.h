@@ -582,7 +582,7 @@ int FN(atc_oracle_step)(const REAL* S, int B, int N, const FN(orc_state_t) * st,
                    * the rate limits h_dot * timestep and the sum are its float64 operations */
                     const double td = discrete ? fma((double)ah, (double)fac[1], (double)off[1])
                                                : fma((double)ah, (double)fac[1] / 2.0, (double)fac[1] / 2.0 + (double)off[1]);
-                    if (td < (double)h_min || td > (double)h_max) {
+                    if (!(td >= (double)h_min && td <= (double)h_max)) { /* a NaN target is refused (include/atc_step.h "Non-finite actions") */
                         reward -= (REAL)1.0;
                         fl[k] |= ATC_F_INVALID_H;
                     } else {
@@ -632,7 +632,10 @@ int FN(atc_oracle_step)(const REAL* S, int B, int N, const FN(orc_state_t) * st,
                         st->v[i] = st->v[i] + d;
                     }
                 } else if (c == 1) { /* model.py:82-102 */
-                    if (tgt < h_min || tgt > h_max) valid = 0;
+                    if (tgt < h_min || tgt > h_max) valid = 0; /* the reference's compares as they are: a NaN target passes and
+                                                                 * propagates, like there.  This instantiation mirrors the reference for
+                                                                 * FINITE actions and is not specified for others (the fp32 path above
+                                                                 * refuses a NaN altitude target: include/atc_step.h "Non-finite actions") */
                     else {
                         REAL d = tgt - st->h[i];
                         d = R_MIN(d, S[ATC_C_HDOT_MAX] * dtd);

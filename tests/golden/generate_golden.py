@@ -37,6 +37,10 @@ inputs + expected outputs of the AtcGym.step() hot path as small fixtures:
                       dt 0.1 / 1 / 5, one discrete and one unshaped un-normalised episode; fixed actions and seeded float32 Box draws,
                       headings that fly through the window where the vector to the FAF exceeds the 32-bit grid range while the
                       position is still on the grid, then off the position grid (compact format of g9, stride 16)
+  g15_action_edges.npz  the action values of tests/action_edges.py the reference can be run on — every FINITE table entry (refusal boundaries,
+                      saturation ends, heading bounds, discriminator pairs, +-FLT_MAX, +-0, subnormals) and a +-Inf HEADING — one aircraft on
+                      LOWW, the entry held for 3 steps, then changed for one; continuous and discrete; the format of g2.  (An infinite speed
+                      or altitude raises OverflowError out of the reference's own warning print; a NaN makes its state NaN: not recorded.)
   model_test_known_answers.json  the 8 known answers of the reference's own envs/atc/model_test.py
 
 Usage:
@@ -1106,8 +1110,37 @@ def gen_g14():
     return rec, crossing
 
 
+# ----------------------------------------------------------------------------------------------- G15
+G15_STATE = (20.0, 60.0, 15000.0, 90.0, 250.0)   # helpers.FAR_A: inside LOWW, far above its floor
+G15_HOLD = {False: ((250.0 - 200.0) / 100.0, 15000.0 / 19000.0 - 1.0, 90.0 / 180.0 - 1.0), True: (15.0, 150.0, 90.0)}
+
+
+def gen_g15():
+    """tests/action_edges.py's table through the reference: see the module docstring.  Episode records carry `edge` (the entry's name),
+    `component` and `inf_heading`."""
+    import math
+    sys.path.insert(0, os.path.dirname(HERE))
+    import action_edges as AE
+    rec = Recorder()
+    for discrete in (False, True):
+        env = make_env("LOWW", 1, shaping=False, normalize=False, discrete=discrete)
+        for comp in range(3):
+            for e in AE.table(discrete)[comp]:
+                inf_heading = comp == 2 and math.isinf(e.value)
+                if not (math.isfinite(e.value) or inf_heading):
+                    continue
+                acts = np.tile(np.asarray(G15_HOLD[discrete], np.float32).astype(np.float64), (4, 1))
+                acts[:3, comp] = e.value
+                acts[3, comp] = e.follow
+                n = rec.run(env, acts, "LOWW", 1, False, False, discrete, init_state=G15_STATE, stop_on_done=False, last_action=[0, 0, 0])
+                assert n == 4 and not any(rec.rows["done"][-4:]), (e.name, comp)
+                rec.ep[-1].update(edge=e.name, component=comp, inf_heading=bool(inf_heading))
+    rec.save(os.path.join(HERE, "g15_action_edges.npz"))
+    return rec
+
+
 if __name__ == "__main__":
-    which = sys.argv[1:] or ["g1", "g2", "g3", "g4", "g5", "g6", "g7", "mt", "g8", "g9", "g10", "g11", "g12", "g13", "g14"]
+    which = sys.argv[1:] or ["g1", "g2", "g3", "g4", "g5", "g6", "g7", "mt", "g8", "g9", "g10", "g11", "g12", "g13", "g14", "g15"]
     if "g1" in which:
         gen_g1()
     if "mt" in which:
@@ -1170,4 +1203,7 @@ if __name__ == "__main__":
               "window rows", [e["window_rows"] for e in r.ep])
         for name, bit in (("below", 1), ("outside", 2), ("won", 4), ("timeout", 8), ("inv_v", 16), ("inv_h", 32)):
             print(name, int(((fl & bit) != 0).sum()), "terminal:", int((((fl & bit) != 0) & (dn != 0)).sum()))
+    if "g15" in which:
+        r = gen_g15()
+        print("g15 episodes", len(r.ep), "steps", len(r.rows["reward"]), "+-Inf heading episodes", sum(e["inf_heading"] for e in r.ep))
     print("done")
