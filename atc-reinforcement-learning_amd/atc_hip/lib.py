@@ -139,44 +139,41 @@ def launch_name(slot):
     return "%d/%s" % (1 << (slot // L.LF_FORMS), L.LF_NAMES[slot % L.LF_FORMS])
 
 
+def _counts(getter, slots, name=lambda i: 1 << i):
+    """{name(slot): count} of one of the library's launch records (`getter`: its atc_*_launch_counts), zero counts left out."""
+    buf = (C.c_uint64 * slots)()
+    check(getattr(load(), getter)(buf, slots))
+    return {name(i): int(v) for i, v in enumerate(buf) if v}
+
+
 def launch_counts():
     """Launches made by the calling thread so far, per kernel instantiation: {"16/allv-multi": n, ..., "serve": n}, names with a
     count of zero left out.  The counters only grow; take the difference of two calls around a block of code."""
-    buf = (C.c_uint64 * L.LAUNCH_SLOTS)()
-    check(load().atc_launch_counts(buf, L.LAUNCH_SLOTS))
-    return {launch_name(i): int(v) for i, v in enumerate(buf) if v}
+    return _counts("atc_launch_counts", L.LAUNCH_SLOTS, launch_name)
 
 
 def skip_launch_counts():
     """Launches of the frame-skip kernel (atc_step_skip) made by the calling thread so far, by lane-group width: {16: n, ...},
     widths with a count of zero left out.  Separate from launch_counts(), which a skip call leaves as it is."""
-    buf = (C.c_uint64 * L.SKIP_LAUNCH_SLOTS)()
-    check(load().atc_skip_launch_counts(buf, L.SKIP_LAUNCH_SLOTS))
-    return {1 << i: int(v) for i, v in enumerate(buf) if v}
+    return _counts("atc_skip_launch_counts", L.SKIP_LAUNCH_SLOTS)
 
 
 def traffic_launch_counts():
     """Launches of the traffic-observation kernel (atc_observe_traffic) made by the calling thread so far, by lane-group width:
     {16: n, ...}, widths with a count of zero left out.  Separate from launch_counts() and skip_launch_counts()."""
-    buf = (C.c_uint64 * L.TRAFFIC_LAUNCH_SLOTS)()
-    check(load().atc_traffic_launch_counts(buf, L.TRAFFIC_LAUNCH_SLOTS))
-    return {1 << i: int(v) for i, v in enumerate(buf) if v}
+    return _counts("atc_traffic_launch_counts", L.TRAFFIC_LAUNCH_SLOTS)
 
 
 def lookahead_launch_counts():
     """Launches of the look-ahead kernel (atc_lookahead) made by the calling thread so far, by lane-group width: {16: n, ...},
     widths with a count of zero left out.  Separate from the other launch records, which a look-ahead leaves as they are."""
-    buf = (C.c_uint64 * L.LOOKAHEAD_LAUNCH_SLOTS)()
-    check(load().atc_lookahead_launch_counts(buf, L.LOOKAHEAD_LAUNCH_SLOTS))
-    return {1 << i: int(v) for i, v in enumerate(buf) if v}
+    return _counts("atc_lookahead_launch_counts", L.LOOKAHEAD_LAUNCH_SLOTS)
 
 
 def plan_launch_counts():
     """Launches of the plan look-ahead kernel (atc_lookahead_plan) made by the calling thread so far, by lane-group width:
     {16: n, ...}, widths with a count of zero left out.  Separate from the other launch records, which a plan call leaves as they are."""
-    buf = (C.c_uint64 * L.PLAN_LAUNCH_SLOTS)()
-    check(load().atc_plan_launch_counts(buf, L.PLAN_LAUNCH_SLOTS))
-    return {1 << i: int(v) for i, v in enumerate(buf) if v}
+    return _counts("atc_plan_launch_counts", L.PLAN_LAUNCH_SLOTS)
 
 
 def lookahead_set_mapping(candidates_per_workgroup=0):

@@ -238,15 +238,16 @@ class AtcVecEnv:
         C.memmove(C.byref(self._params_held), C.byref(self.params), C.sizeof(self.params))
         self._params_held.mode |= L.M_ACTIONS_HELD
 
+    def _as_mask(self, mask):
+        """An env mask (None: every env) as the contiguous uint8 device tensor atc_reset / atc_observe read"""
+        return None if mask is None else self.torch.as_tensor(mask, device=self.device).to(self.torch.uint8).contiguous()
+
     def reset(self, mask=None, first=False):
         """AtcGym.reset (atc_gym.py:337-365) for all envs (or those with mask != 0); returns RAW obs [B, N*10]."""
-        torch = self.torch
-        m = None
-        if mask is not None:
-            m = torch.as_tensor(mask, device=self.device).to(torch.uint8).contiguous()
-        with torch.cuda.device(self.device):
+        m = self._as_mask(mask)
+        with self.torch.cuda.device(self.device):
             _lib.check(self._lib.atc_reset(self.sector.handle, self.B, self.N, C.byref(self._state),
-                                           m.data_ptr() if m is not None else None, self._ptr(self.obs),
+                                           self._ptr(m), self._ptr(self.obs),
                                            C.byref(self.params), int(first), self._stream()))
             self._launch_traffic()
         self._finish()
@@ -254,13 +255,10 @@ class AtcVecEnv:
 
     def observe(self, mask=None):
         """Raw observation (mva = 0) of the current state, like the tail of AtcGym.reset (atc_gym.py:351,365)."""
-        torch = self.torch
-        m = None
-        if mask is not None:
-            m = torch.as_tensor(mask, device=self.device).to(torch.uint8).contiguous()
-        with torch.cuda.device(self.device):
+        m = self._as_mask(mask)
+        with self.torch.cuda.device(self.device):
             _lib.check(self._lib.atc_observe(self.sector.handle, self.B, self.N, C.byref(self._state),
-                                             m.data_ptr() if m is not None else None, self._ptr(self.obs),
+                                             self._ptr(m), self._ptr(self.obs),
                                              C.byref(self.params), self._stream()))
             self._launch_traffic()
         self._finish()
@@ -381,33 +379,7 @@ class AtcVecEnv:
         such call.  Runs on the current stream; env.obs / env.traffic, every bound step output and the whole env state — episode
         records included — are left as they are.  An env-candidate with a WIDE heading (an out-of-range heading action or state) is
         not evaluated: n_steps == 0 and zeros.  AtcSBVecEnv and AtcGym deliberately have no such method."""
-        torch = self.torch
-        K = int(K)
-        if not 1 <= K <= L.SKIP_MAX:
-            raise ValueError("1 <= K <= %d" % L.SKIP_MAX)
-        M = int(actions.shape[0]) if hasattr(actions, "shape") else len(actions)
-        if not 1 <= M <= L.LOOKAHEAD_MAX_M:
-            raise ValueError("1 <= M (actions.shape[0]) <= %d" % L.LOOKAHEAD_MAX_M)
-        outputs = tuple(n for n in self.LOOKAHEAD_OUTPUTS if n in outputs) if set(outputs) <= set(self.LOOKAHEAD_OUTPUTS) else None
-        if outputs is None:
-            raise ValueError("outputs must be a subset of %r" % (self.LOOKAHEAD_OUTPUTS,))
-        a = self._as_actions(actions, lead=(M,))
-        cache = self.__dict__.setdefault("_lookahead_cache", {})
-        key = (M, outputs)
-        if key not in cache:
-            B, N, z = self.B, self.N, self._new_output
-            shapes = {"reward": ((M, B), torch.float32), "done": ((M, B), torch.uint8), "n_steps": ((M, B), torch.uint8),
-                      "flags": ((M, B, N), torch.int16), "min_sep": ((M, B), torch.float32), "ac_reward": ((M, B, N), torch.float32),
-                      "obs": ((M, B, N * L.OBS_DIM), torch.float32)}
-            res = {n: z(*shapes[n]) for n in ("reward", "done", "n_steps") + outputs}
-            cache[key] = (res, _lib.AtcLookaheadOut(*[self._ptr(res.get(n)) for n in _lib.LOOKAHEAD_FIELDS]))
-        res, out = cache[key]
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.atc_lookahead(self.sector.handle, self.B, self.N, K, M, C.byref(self._state), self._ptr(a), C.byref(out),
-                                               C.byref(self.params), self._stream()))
-        self._keep_lookahead = a
-        self._finish()
-        return res
+        return self._score_candidates(actions, K, outputs, plan=False)
 
     PLAN_OUTPUTS = ("seg_reward", "flags", "min_sep", "ac_reward", "obs")
 
@@ -422,35 +394,44 @@ class AtcVecEnv:
         (none of the last four: the kernel's fast form).  The tensors are allocated once per (M, H, outputs) and overwritten by the
         next such call.  Runs on the current stream; env.obs / env.traffic, every bound step output and the whole env state are left
         as they are.  An env-candidate with a WIDE heading is not evaluated: n_steps == 0 and zeros.  H == 1 is lookahead()."""
+        return self._score_candidates(actions, K, outputs, plan=True)
+
+    def _score_candidates(self, actions, K, outputs, plan):
+        """lookahead() (plan=False: actions [M, ...]) and lookahead_plan() (plan=True: actions [M, H, ...]): the argument checks in
+        their order, the result tensors and output struct cached per (M[, H], outputs), the launch"""
         torch = self.torch
         K = int(K)
         if not 1 <= K <= L.SKIP_MAX:
             raise ValueError("1 <= K <= %d" % L.SKIP_MAX)
-        if not hasattr(actions, "shape") or len(actions.shape) < 2:
+        if plan and (not hasattr(actions, "shape") or len(actions.shape) < 2):
             raise ValueError("actions must be [M, H, B, N, 3] or [M, H, B, N*3]")
-        M, H = int(actions.shape[0]), int(actions.shape[1])
+        M = int(actions.shape[0]) if hasattr(actions, "shape") else len(actions)
         if not 1 <= M <= L.LOOKAHEAD_MAX_M:
             raise ValueError("1 <= M (actions.shape[0]) <= %d" % L.LOOKAHEAD_MAX_M)
-        if not 1 <= H <= L.PLAN_MAX_H:
+        lead = (M, int(actions.shape[1])) if plan else (M,)
+        if plan and not 1 <= lead[1] <= L.PLAN_MAX_H:
             raise ValueError("1 <= H (actions.shape[1]) <= %d" % L.PLAN_MAX_H)
-        outputs = tuple(n for n in self.PLAN_OUTPUTS if n in outputs) if set(outputs) <= set(self.PLAN_OUTPUTS) else None
-        if outputs is None:
-            raise ValueError("outputs must be a subset of %r" % (self.PLAN_OUTPUTS,))
-        a = self._as_actions(actions, lead=(M, H))
-        cache = self.__dict__.setdefault("_plan_cache", {})
-        key = (M, H, outputs)
+        allowed = self.PLAN_OUTPUTS if plan else self.LOOKAHEAD_OUTPUTS
+        if not set(outputs) <= set(allowed):
+            raise ValueError("outputs must be a subset of %r" % (allowed,))
+        outputs = tuple(n for n in allowed if n in outputs)
+        a = self._as_actions(actions, lead=lead)
+        cache = self.__dict__.setdefault("_plan_cache" if plan else "_lookahead_cache", {})
+        key = lead + (outputs,)
         if key not in cache:
             B, N, z = self.B, self.N, self._new_output
-            shapes = {"reward": ((M, B), torch.float32), "done": ((M, B), torch.uint8), "n_steps": ((M, B), torch.int16),
-                      "seg_reward": ((M, H, B), torch.float32), "flags": ((M, B, N), torch.int16), "min_sep": ((M, B), torch.float32),
+            shapes = {"reward": ((M, B), torch.float32), "done": ((M, B), torch.uint8), "n_steps": ((M, B), torch.int16 if plan else torch.uint8),
+                      "seg_reward": (lead + (B,), torch.float32), "flags": ((M, B, N), torch.int16), "min_sep": ((M, B), torch.float32),
                       "ac_reward": ((M, B, N), torch.float32), "obs": ((M, B, N * L.OBS_DIM), torch.float32)}
             res = {n: z(*shapes[n]) for n in ("reward", "done", "n_steps") + outputs}
-            cache[key] = (res, _lib.AtcPlanOut(*[self._ptr(res.get(n)) for n in _lib.PLAN_FIELDS]))
+            out_type, fields = (_lib.AtcPlanOut, _lib.PLAN_FIELDS) if plan else (_lib.AtcLookaheadOut, _lib.LOOKAHEAD_FIELDS)
+            cache[key] = (res, out_type(*[self._ptr(res.get(n)) for n in fields]))
         res, out = cache[key]
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.atc_lookahead_plan(self.sector.handle, self.B, self.N, K, H, M, C.byref(self._state), self._ptr(a),
-                                                    C.byref(out), C.byref(self.params), self._stream()))
-        self._keep_plan = a
+        call = self._lib.atc_lookahead_plan if plan else self._lib.atc_lookahead
+        with torch.cuda.device(self.device):   # (the C argument order: K, [H,] M)
+            _lib.check(call(self.sector.handle, self.B, self.N, K, *lead[::-1], C.byref(self._state), self._ptr(a), C.byref(out),
+                            C.byref(self.params), self._stream()))
+        setattr(self, "_keep_plan" if plan else "_keep_lookahead", a)   # the actions outlive the launch, one tensor per call kind
         self._finish()
         return res
 

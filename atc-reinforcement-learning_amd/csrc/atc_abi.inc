@@ -6,34 +6,20 @@ extern "C" {
 
 int atc_abi_version(void) { return ATC_ABI_VERSION; }
 
-int atc_launch_counts(uint64_t* out, int n) {
+// every launch record's getter: the first min(n, slots) counters of the calling thread
+static int copy_counts(const uint64_t* record, int slots, uint64_t* out, int n) {
     if (!out || n < 0) return fail_arg("null pointer");
-    for (int i = 0; i < n && i < ATC_LAUNCH_SLOTS; ++i) out[i] = t_launches[i];
+    for (int i = 0; i < n && i < slots; ++i) out[i] = record[i];
     return ATC_OK;
 }
-int atc_skip_launch_counts(uint64_t* out, int n) {
-    if (!out || n < 0) return fail_arg("null pointer");
-    for (int i = 0; i < n && i < ATC_SKIP_LAUNCH_SLOTS; ++i) out[i] = t_skip_launches[i];
-    return ATC_OK;
-}
-int atc_traffic_launch_counts(uint64_t* out, int n) {
-    if (!out || n < 0) return fail_arg("null pointer");
-    for (int i = 0; i < n && i < ATC_TRAFFIC_LAUNCH_SLOTS; ++i) out[i] = t_traffic_launches[i];
-    return ATC_OK;
-}
-int atc_lookahead_launch_counts(uint64_t* out, int n) {
-    if (!out || n < 0) return fail_arg("null pointer");
-    for (int i = 0; i < n && i < ATC_LOOKAHEAD_LAUNCH_SLOTS; ++i) out[i] = t_look_launches[i];
-    return ATC_OK;
-}
+int atc_launch_counts(uint64_t* out, int n) { return copy_counts(t_launches, ATC_LAUNCH_SLOTS, out, n); }
+int atc_skip_launch_counts(uint64_t* out, int n) { return copy_counts(t_skip_launches, ATC_SKIP_LAUNCH_SLOTS, out, n); }
+int atc_traffic_launch_counts(uint64_t* out, int n) { return copy_counts(t_traffic_launches, ATC_TRAFFIC_LAUNCH_SLOTS, out, n); }
+int atc_lookahead_launch_counts(uint64_t* out, int n) { return copy_counts(t_look_launches, ATC_LOOKAHEAD_LAUNCH_SLOTS, out, n); }
+int atc_plan_launch_counts(uint64_t* out, int n) { return copy_counts(t_plan_launches, ATC_PLAN_LAUNCH_SLOTS, out, n); }
 int atc_lookahead_set_mapping(int candidates_per_workgroup) {
     if (candidates_per_workgroup < 0 || candidates_per_workgroup > ATC_LOOKAHEAD_MAX_M) return fail_arg("candidates per workgroup must be 0 (the library's choice) .. 64");
     t_look_cpg = candidates_per_workgroup;
-    return ATC_OK;
-}
-int atc_plan_launch_counts(uint64_t* out, int n) {
-    if (!out || n < 0) return fail_arg("null pointer");
-    for (int i = 0; i < n && i < ATC_PLAN_LAUNCH_SLOTS; ++i) out[i] = t_plan_launches[i];
     return ATC_OK;
 }
 int atc_fill_prefetch_info(const atc_scenario_t* s, int B, int N, int* resident, int* stride) {
@@ -423,22 +409,45 @@ int atc_rollout_hold(const atc_scenario_t* s, int B, int N, int T, int hold, con
 
 int atc_step_skip(const atc_scenario_t* s, int B, int N, int K, const atc_state_t* st, const float* actions, const atc_out_t* out,
                   uint8_t* n_steps, const atc_params_t* p, void* stream) {
-    return skip_common(s, B, N, K, st, actions, out, n_steps, p, stream);
+    // K first, before any pointer is looked at
+    if (K < 1 || K > ATC_SKIP_MAX) return fail_arg("K (the frame-skip length) must be 1 .. 255");
+    if (!actions || !out) return fail_arg("null pointer");
+    if (const int rc = check_env_args(s, B, N, st, p)) return rc;
+    if (const int rc = check_required_outputs(out)) return rc;
+    if (out->packet) return fail_arg("atc_out_t.packet must be NULL for atc_step_skip (the packet is a single step's result)");
+    if (p->mode & ATC_M_ACTIONS_HELD) return fail_arg("ATC_M_ACTIONS_HELD is for atc_step only: a frame-skip call's first step carries a fresh decision");
+    if (const int rc = check_dt(s, p)) return rc;
+    return with_width(N, [&](auto w) { return launch_skip<decltype(w)::value>(s, B, N, K, st, actions, out, n_steps, p, (hipStream_t)stream); });
 }
 
 int atc_observe_traffic(const atc_scenario_t* s, int B, int N, int K, const atc_state_t* st, float* traffic, const atc_params_t* p,
                         void* stream) {
-    return traffic_common(s, B, N, K, st, traffic, p, stream);
+    // K first, before any pointer is looked at
+    if (K < 1 || K > ATC_TRAFFIC_MAX_K) return fail_arg("K (traffic records per aircraft) must be 1 .. 8");
+    if (!traffic) return fail_arg("null pointer");
+    if (const int rc = check_env_args(s, B, N, st, p)) return rc;
+    TrafficArgs q;
+    q.pos_inv = (double)s->consts[ATC_C_POS_INV];
+    q.x0 = (double)s->consts[ATC_C_POS_X0];
+    q.y0 = (double)s->consts[ATC_C_POS_Y0];
+    const bool nrm = (p->mode & ATC_M_NORMALIZE) != 0;
+    q.s_pos = nrm ? 1.0f / s->consts[ATC_C_WORLD_DIAG] : 1.0f;
+    q.h_div = nrm ? s->consts[ATC_C_H_MAX] : 1.0f;
+    q.s_v = nrm ? 1.0f / (2.0f * s->consts[ATC_C_V_MAX]) : 1.0f;
+    q.K = K;
+    return with_width(N, [&](auto w) { return launch_traffic<decltype(w)::value>(B, N, st, traffic, q, (hipStream_t)stream); });
 }
 
 int atc_lookahead(const atc_scenario_t* s, int B, int N, int K, int M, const atc_state_t* st, const float* actions,
                   const atc_lookahead_out_t* out, const atc_params_t* p, void* stream) {
-    return lookahead_common(s, B, N, K, M, st, actions, out, p, stream);
+    if (const int rc = check_candidates(s, B, N, K, nullptr, M, st, actions, out, p, "look-ahead", "atc_lookahead_out_t", "candidate")) return rc;
+    return with_width(N, [&](auto w) { return launch_lookahead<decltype(w)::value>(s, B, N, K, M, st, actions, out, p, (hipStream_t)stream); });
 }
 
 int atc_lookahead_plan(const atc_scenario_t* s, int B, int N, int K, int H, int M, const atc_state_t* st, const float* actions,
                        const atc_plan_out_t* out, const atc_params_t* p, void* stream) {
-    return plan_common(s, B, N, K, H, M, st, actions, out, p, stream);
+    if (const int rc = check_candidates(s, B, N, K, &H, M, st, actions, out, p, "segment", "atc_plan_out_t", "segment")) return rc;
+    return with_width(N, [&](auto w) { return launch_plan<decltype(w)::value>(s, B, N, K, H, M, st, actions, out, p, (hipStream_t)stream); });
 }
 
 }  // extern "C"

@@ -1902,19 +1902,6 @@ static int launch_skip(const atc_scenario* s, int B, int N, int K, const atc_sta
     });
 }
 
-static int skip_common(const atc_scenario_t* s, int B, int N, int K, const atc_state_t* st, const float* actions, const atc_out_t* out,
-                       uint8_t* n_steps, const atc_params_t* p, void* stream) {
-    // K first, before any pointer is looked at
-    if (K < 1 || K > ATC_SKIP_MAX) return fail_arg("K (the frame-skip length) must be 1 .. 255");
-    if (!actions || !out) return fail_arg("null pointer");
-    if (const int rc = check_env_args(s, B, N, st, p)) return rc;
-    if (const int rc = check_required_outputs(out)) return rc;
-    if (out->packet) return fail_arg("atc_out_t.packet must be NULL for atc_step_skip (the packet is a single step's result)");
-    if (p->mode & ATC_M_ACTIONS_HELD) return fail_arg("ATC_M_ACTIONS_HELD is for atc_step only: a frame-skip call's first step carries a fresh decision");
-    if (const int rc = check_dt(s, p)) return rc;
-    return with_width(N, [&](auto w) { return launch_skip<decltype(w)::value>(s, B, N, K, st, actions, out, n_steps, p, (hipStream_t)stream); });
-}
-
 // ---- traffic observation (include/atc_step.h: atc_observe_traffic) -------------------------------------------------------------
 // its own launch record (atc_traffic_launch_counts): slot = log2(W), the rules of the frame-skip record
 static thread_local uint64_t t_traffic_launches[ATC_TRAFFIC_LAUNCH_SLOTS] = {0};
@@ -1935,24 +1922,6 @@ static int launch_traffic(int B, int N, const atc_state_t* st, float* traffic, c
     return launch_traffic2<W, 8>(B, N, st, traffic, q, stream);
 }
 
-static int traffic_common(const atc_scenario_t* s, int B, int N, int K, const atc_state_t* st, float* traffic, const atc_params_t* p,
-                          void* stream) {
-    // K first, before any pointer is looked at
-    if (K < 1 || K > ATC_TRAFFIC_MAX_K) return fail_arg("K (traffic records per aircraft) must be 1 .. 8");
-    if (!traffic) return fail_arg("null pointer");
-    if (const int rc = check_env_args(s, B, N, st, p)) return rc;
-    TrafficArgs q;
-    q.pos_inv = (double)s->consts[ATC_C_POS_INV];
-    q.x0 = (double)s->consts[ATC_C_POS_X0];
-    q.y0 = (double)s->consts[ATC_C_POS_Y0];
-    const bool nrm = (p->mode & ATC_M_NORMALIZE) != 0;
-    q.s_pos = nrm ? 1.0f / s->consts[ATC_C_WORLD_DIAG] : 1.0f;
-    q.h_div = nrm ? s->consts[ATC_C_H_MAX] : 1.0f;
-    q.s_v = nrm ? 1.0f / (2.0f * s->consts[ATC_C_V_MAX]) : 1.0f;
-    q.K = K;
-    return with_width(N, [&](auto w) { return launch_traffic<decltype(w)::value>(B, N, st, traffic, q, (hipStream_t)stream); });
-}
-
 // ---- what-if look-ahead (include/atc_step.h: atc_lookahead) ---------------------------------------------------------------------
 // its own launch record (atc_lookahead_launch_counts): slot = log2(W), the rules of the frame-skip record
 static thread_local uint64_t t_look_launches[ATC_LOOKAHEAD_LAUNCH_SLOTS] = {0};
@@ -1960,82 +1929,79 @@ static thread_local uint64_t t_look_launches[ATC_LOOKAHEAD_LAUNCH_SLOTS] = {0};
 static thread_local int t_look_cpg = 0;
 #define ATC_LOOKAHEAD_CPG_DEFAULT 1   // one workgroup per (tile, candidate): measured against the in-workgroup loop in DESIGN.md, section 3c
 
+// the launch shape k_lookahead and k_plan share: 256-slot tiles of the batch x groups of `cpg` candidates (atc_lookahead_set_mapping)
+struct CandGrid {
+    int tiles, cpg, groups;
+    unsigned grid;
+};
+static int cand_grid(int B, int W, int M, CandGrid* g) {
+    g->tiles = step_grid(B, W);
+    g->cpg = std::min(t_look_cpg > 0 ? t_look_cpg : ATC_LOOKAHEAD_CPG_DEFAULT, M);
+    g->groups = (M + g->cpg - 1) / g->cpg;
+    const long long grid = (long long)((g->tiles + 7) / 8) * 8 * g->groups;   // whole chunks of 8 tiles x groups (look_tile)
+    if (grid > 0x7fffffffll) return fail_arg("B*N*M too large for one launch: split the candidates");
+    g->grid = (unsigned)grid;
+    return ATC_OK;
+}
+// the kernels' atc_out_t from the six fields atc_lookahead_out_t and atc_plan_out_t name alike; true: one of the four optional outputs
+// is asked for (the fast form has them compiled out)
+template <typename O>
+static bool cand_out(const O* o, atc_out_t* out) {
+    memset(out, 0, sizeof *out);
+    out->obs = o->obs; out->reward = o->reward; out->ac_reward = o->ac_reward; out->done = o->done; out->flags = o->flags; out->min_sep = o->min_sep;
+    return o->flags || o->ac_reward || o->min_sep || o->obs;
+}
+// the argument checks of atc_lookahead (H null) and atc_lookahead_plan: K, then H, then M, before any pointer is looked at
+template <typename O>
+static int check_candidates(const atc_scenario_t* s, int B, int N, int K, const int* H, int M, const atc_state_t* st, const float* actions,
+                            const O* out, const atc_params_t* p, const char* k_is, const char* out_type, const char* fresh_per) {
+    char msg[160];
+    auto fail = [&](const char* fmt, const char* word) { snprintf(msg, sizeof msg, fmt, word); return fail_arg(msg); };
+    if (K < 1 || K > ATC_SKIP_MAX) return fail("K (the %s length) must be 1 .. 255", k_is);
+    if (H && (*H < 1 || *H > ATC_PLAN_MAX_H)) return fail_arg("H (the number of segments of a plan) must be 1 .. 16");
+    if (M < 1 || M > ATC_LOOKAHEAD_MAX_M) return fail_arg("M (the number of candidates) must be 1 .. 64");
+    if (!out || !out->reward || !out->done) return fail("null pointer: %s.reward and .done are required", out_type);
+    if (!actions) return fail_arg("null pointer");
+    if (const int rc = check_env_args(s, B, N, st, p)) return rc;
+    if (const int rc = check_dt(s, p)) return rc;
+    if (p->mode & ATC_M_ACTIONS_HELD) return fail("ATC_M_ACTIONS_HELD is for atc_step only: every %s's first step carries a fresh decision", fresh_per);
+    return ATC_OK;
+}
+
 template <int W>
 static int launch_lookahead(const atc_scenario* s, int B, int N, int K, int M, const atc_state_t* st, const float* actions,
                             const atc_lookahead_out_t* lo, const atc_params_t* p, hipStream_t stream) {
-    const size_t lds = lds_bytes(s, W >= 32, true);
-    const int tiles = step_grid(B, W);
-    int cpg = t_look_cpg > 0 ? t_look_cpg : ATC_LOOKAHEAD_CPG_DEFAULT;
-    if (cpg > M) cpg = M;
-    const int groups = (M + cpg - 1) / cpg;
-    const long long grid = (long long)((tiles + 7) / 8) * 8 * groups;   // whole chunks of 8 tiles x groups (look_tile)
-    if (grid > 0x7fffffffll) return fail_arg("B*N*M too large for one launch: split the candidates");
+    CandGrid g;
+    if (const int rc = cand_grid(B, W, M, &g)) return rc;
     atc_out_t out;
-    memset(&out, 0, sizeof out);
-    out.obs = lo->obs; out.reward = lo->reward; out.ac_reward = lo->ac_reward; out.done = lo->done; out.flags = lo->flags; out.min_sep = lo->min_sep;
+    const bool any = cand_out(lo, &out);
     const StepDerived& q = derive(*p, s, 0);
-    // the fast form has the four optional outputs compiled out
-    return with_flag(lo->flags || lo->ac_reward || lo->min_sep || lo->obs, [&](auto full) {
-        hipLaunchKernelGGL((k_lookahead<W, decltype(full)::value>), dim3((unsigned)grid), dim3(kBlock), lds, stream, s->d_blob, s->off_grid, B, N, K, M, *st, actions, out, *p, q, lo->n_steps, cpg, groups, tiles);
+    return with_flag(any, [&](auto full) {
+        hipLaunchKernelGGL((k_lookahead<W, decltype(full)::value>), dim3(g.grid), dim3(kBlock), lds_bytes(s, W >= 32, true), stream, s->d_blob, s->off_grid, B, N, K, M, *st, actions, out, *p, q, lo->n_steps, g.cpg, g.groups, g.tiles);
         HIP_TRY(hipGetLastError());
         ++t_look_launches[__builtin_ctz(W)];
         return ATC_OK;
     });
 }
 
-static int lookahead_common(const atc_scenario_t* s, int B, int N, int K, int M, const atc_state_t* st, const float* actions,
-                            const atc_lookahead_out_t* out, const atc_params_t* p, void* stream) {
-    // K, then M, before any pointer is looked at
-    if (K < 1 || K > ATC_SKIP_MAX) return fail_arg("K (the look-ahead length) must be 1 .. 255");
-    if (M < 1 || M > ATC_LOOKAHEAD_MAX_M) return fail_arg("M (the number of candidates) must be 1 .. 64");
-    if (!out || !out->reward || !out->done) return fail_arg("null pointer: atc_lookahead_out_t.reward and .done are required");
-    if (!actions) return fail_arg("null pointer");
-    if (const int rc = check_env_args(s, B, N, st, p)) return rc;
-    if (const int rc = check_dt(s, p)) return rc;
-    if (p->mode & ATC_M_ACTIONS_HELD) return fail_arg("ATC_M_ACTIONS_HELD is for atc_step only: every candidate's first step carries a fresh decision");
-    return with_width(N, [&](auto w) { return launch_lookahead<decltype(w)::value>(s, B, N, K, M, st, actions, out, p, (hipStream_t)stream); });
-}
-
 // ---- plan look-ahead (include/atc_step.h: atc_lookahead_plan) -------------------------------------------------------------------
 // its own launch record (atc_plan_launch_counts): slot = log2(W), the rules of the frame-skip record
 static thread_local uint64_t t_plan_launches[ATC_PLAN_LAUNCH_SLOTS] = {0};
 
-// k_lookahead's launch: the same tiles, candidate groups (atc_lookahead_set_mapping) and grid
 template <int W>
 static int launch_plan(const atc_scenario* s, int B, int N, int K, int H, int M, const atc_state_t* st, const float* actions,
                        const atc_plan_out_t* po, const atc_params_t* p, hipStream_t stream) {
-    const size_t lds = lds_bytes(s, W >= 32, true);
-    const int tiles = step_grid(B, W);
-    int cpg = t_look_cpg > 0 ? t_look_cpg : ATC_LOOKAHEAD_CPG_DEFAULT;
-    if (cpg > M) cpg = M;
-    const int groups = (M + cpg - 1) / cpg;
-    const long long grid = (long long)((tiles + 7) / 8) * 8 * groups;   // whole chunks of 8 tiles x groups (look_tile)
-    if (grid > 0x7fffffffll) return fail_arg("B*N*M too large for one launch: split the candidates");
+    CandGrid g;
+    if (const int rc = cand_grid(B, W, M, &g)) return rc;
     atc_out_t out;
-    memset(&out, 0, sizeof out);
-    out.obs = po->obs; out.reward = po->reward; out.ac_reward = po->ac_reward; out.done = po->done; out.flags = po->flags; out.min_sep = po->min_sep;
+    const bool any = cand_out(po, &out);
     const StepDerived& q = derive(*p, s, 0);
-    // the fast form has the four optional outputs compiled out
-    return with_flag(po->flags || po->ac_reward || po->min_sep || po->obs, [&](auto full) {
-        hipLaunchKernelGGL((k_plan<W, decltype(full)::value>), dim3((unsigned)grid), dim3(kBlock), lds, stream, s->d_blob, s->off_grid, B, N, K, H, M, *st, actions, out, *p, q, po->n_steps, po->seg_reward, cpg, groups, tiles);
+    return with_flag(any, [&](auto full) {
+        hipLaunchKernelGGL((k_plan<W, decltype(full)::value>), dim3(g.grid), dim3(kBlock), lds_bytes(s, W >= 32, true), stream, s->d_blob, s->off_grid, B, N, K, H, M, *st, actions, out, *p, q, po->n_steps, po->seg_reward, g.cpg, g.groups, g.tiles);
         HIP_TRY(hipGetLastError());
         ++t_plan_launches[__builtin_ctz(W)];
         return ATC_OK;
     });
-}
-
-static int plan_common(const atc_scenario_t* s, int B, int N, int K, int H, int M, const atc_state_t* st, const float* actions,
-                       const atc_plan_out_t* out, const atc_params_t* p, void* stream) {
-    // K, then H, then M, before any pointer is looked at
-    if (K < 1 || K > ATC_SKIP_MAX) return fail_arg("K (the segment length) must be 1 .. 255");
-    if (H < 1 || H > ATC_PLAN_MAX_H) return fail_arg("H (the number of segments of a plan) must be 1 .. 16");
-    if (M < 1 || M > ATC_LOOKAHEAD_MAX_M) return fail_arg("M (the number of candidates) must be 1 .. 64");
-    if (!out || !out->reward || !out->done) return fail_arg("null pointer: atc_plan_out_t.reward and .done are required");
-    if (!actions) return fail_arg("null pointer");
-    if (const int rc = check_env_args(s, B, N, st, p)) return rc;
-    if (const int rc = check_dt(s, p)) return rc;
-    if (p->mode & ATC_M_ACTIONS_HELD) return fail_arg("ATC_M_ACTIONS_HELD is for atc_step only: every segment's first step carries a fresh decision");
-    return with_width(N, [&](auto w) { return launch_plan<decltype(w)::value>(s, B, N, K, H, M, st, actions, out, p, (hipStream_t)stream); });
 }
 
 #include "atc_abi.inc"   // the extern "C" entry points (host side)

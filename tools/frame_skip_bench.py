@@ -12,17 +12,12 @@ longer than that to leave the airspace), so that almost no episode ends and the 
 uniform actions, a third outside the action space, a time limit of 60 steps, the default 3 nm minimum, no resets between samples.  A sample is the device time (HIP events) of `inner` decisions launched back to back with pre-bound foreign
 calls; the three variants take turns sample by sample, after a warm-up of every variant; reported are median and quartiles in us
 per decision and per executed env-step (variant 3: per mean n_steps of the sampled decisions).  One JSON file; needs the GPU."""
-import argparse
 import ctypes as C
-import json
-import os
-import socket
-import sys
+import itertools
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [os.path.join(ROOT, "atc-reinforcement-learning_amd")]
+import benchlib
 
 CONFIGS = ((65536, 16), (65536, 1), (8192, 16), (4096, 64))
 KS = (4, 20)
@@ -33,8 +28,8 @@ def action_pool(series, B, N, seed):
     rng = np.random.default_rng(seed)
     pool = []
     for _ in range(POOL):
-        if series == "same_work":   # speed towards 150-200 kt, altitude towards 30 000 ft and up, any heading
-            a = np.stack([rng.uniform(-0.5, 0.0, (B, N)), rng.uniform(0.6, 1.0, (B, N)), rng.uniform(-1.0, 1.0, (B, N))], axis=-1)
+        if series == "same_work":
+            a = benchlib.same_work_actions(rng, (B, N))
         else:
             a = rng.uniform(-1.05, 1.05, (B, N, 3))
             far = rng.uniform(-4.0, 4.0, (B, N, 3))
@@ -86,50 +81,28 @@ def measure(B, N, K, series, samples, inner, seed=11):
 
     if series == "same_work":
         inner = max(2, min(inner, 60 // K))
-    times = {v: [] for v in calls}
     n_mean = []
-    turn = 0
-    for s in range(-2, samples):   # two warm-up rounds of every variant
-        for v, fn in calls.items():
-            if series == "same_work":
-                envs[v].reset()
-            t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            t0.record(stream)
-            for j in range(inner):
-                fn((turn + j) % POOL)
-            t1.record(stream)
-            t1.synchronize()
-            if s >= 0:
-                times[v].append(t0.elapsed_time(t1) * 1000.0 / inner)
-                if v == "skip":
-                    n_mean.append(float(envs["skip"].frame_steps.float().mean()))
-        turn += inner
+
+    def rotating(fn):   # the action blocks take turns call by call, every variant through the same sequence
+        n = itertools.count()
+        return lambda: fn(next(n) % POOL)
+    times = benchlib.sample({v: rotating(fn) for v, fn in calls.items()}, samples, inner, benchlib.hip_clock(torch, stream),
+                            prepare=(lambda v: envs[v].reset()) if series == "same_work" else None,
+                            after=lambda v: v == "skip" and n_mean.append(float(envs["skip"].frame_steps.float().mean())))
     res = {"B": B, "N": N, "K": K, "series": series, "timestep_limit": limit, "sep_nm": sep_nm, "samples": samples, "decisions_per_sample": inner,
            "mean_n_steps_skip": float(np.mean(n_mean)), "episodes_ended": {v: int(envs[v].episodes.sum()) for v in envs}}
     for v, t in times.items():
-        q1, med, q3 = (float(x) for x in np.percentile(t, (25, 50, 75)))
         per = res["mean_n_steps_skip"] if v == "skip" else float(K)
-        res[v] = {"us_per_decision": {"median": med, "q1": q1, "q3": q3, "min": float(min(t)), "max": float(max(t))},
-                  "executed_steps_per_decision": per, "us_per_env_step_median": med / per}
+        res[v] = {"us_per_decision": benchlib.quartiles(t), "executed_steps_per_decision": per}
+        res[v]["us_per_env_step_median"] = res[v]["us_per_decision"]["median"] / per
     for v in envs:
         envs[v].close()
     return res
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "frame_skip_bench.json"))
-    ap.add_argument("--samples", type=int, default=15)
-    ap.add_argument("--inner", type=int, default=10)
-    ap.add_argument("--quick", action="store_true", help="the headline batch only")
-    ap.add_argument("--lib", help="a build variant of libatcstep.so to measure instead of the in-tree one (A/B runs)")
-    a = ap.parse_args()
-    if a.lib:
-        from atc_hip import lib as _lib
-        _lib.use_library(a.lib)
-    import torch
-    if not torch.cuda.is_available():
-        raise SystemExit("frame_skip_bench needs the GPU: nothing is measured without one")
+    a = benchlib.parser("frame_skip_bench.json", inner=10, quick="the headline batch only").parse_args()
+    torch = benchlib.start(a, "frame_skip_bench")
     rows = []
     for B, N in (CONFIGS[:1] if a.quick else CONFIGS):
         for K in KS:
@@ -141,14 +114,8 @@ def main():
                          r["skip"]["us_per_decision"]["median"], r["mean_n_steps_skip"]), flush=True)
     doc = {"what": "us per decision of a frame-skipping caller: K x atc_step (held hint) | atc_rollout_hold(T = K, hold = K) | atc_step_skip(K)",
            "method": "HIP events around `decisions_per_sample` back-to-back decisions, variants alternating per sample, 2 warm-up rounds",
-           "box": {"host": socket.gethostname(), "device": torch.cuda.get_device_name(0),
-                   "cus": torch.cuda.get_device_properties(0).multi_processor_count, "torch": torch.__version__},
-           "library": a.lib or "in-tree build", "rows": rows}
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "w") as f:
-        json.dump(doc, f, indent=1)
-        f.write("\n")
-    print(a.out)
+           "box": benchlib.box(torch), "library": a.lib or "in-tree build", "rows": rows}
+    benchlib.write_json(a.out, doc)
 
 
 if __name__ == "__main__":

@@ -14,28 +14,16 @@ M x K steps per env), every sample started from a reset of all envs plus one ste
   host_recipe     (b) the honest host recipe: copy the six state tensors aside, then per candidate atc_step_skip + copy them back
 A sample is the device time (HIP events) of `decisions_per_sample` decisions launched back to back; the variants take turns sample by
 sample after two warm-up rounds; reported are median and quartiles in us per decision.  One JSON file; needs the GPU."""
-import argparse
 import ctypes as C
-import json
-import os
-import socket
-import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [os.path.join(ROOT, "atc-reinforcement-learning_amd")]
+import benchlib
 
 CONFIGS = ((65536, 16), (4096, 64))
 KS = (4, 20)
 MS = (4, 8)
 STATE = ("ac", "alt", "last_act", "env", "stats", "phi_wide")
-
-
-def candidates(M, B, N, seed):
-    rng = np.random.default_rng(seed)   # speed towards 150-200 kt, altitude towards 30 000 ft and up, any heading
-    a = np.stack([rng.uniform(-0.5, 0.0, (M, B, N)), rng.uniform(0.6, 1.0, (M, B, N)), rng.uniform(-1.0, 1.0, (M, B, N))], axis=-1)
-    return a.astype(np.float32)
 
 
 def measure(B, N, K, M, samples, seed=11):
@@ -46,7 +34,7 @@ def measure(B, N, K, M, samples, seed=11):
     scn = scenarios.LOWWDense()
     env = AtcVecEnv(B, N, scenario=scn, auto_reset=True, seed=seed, timestep_limit=6000, sep_nm=0.0)
     dev = env.device
-    cand = torch.as_tensor(candidates(M, B, N, seed), device=dev)
+    cand = torch.as_tensor(benchlib.same_work_actions(np.random.default_rng(seed), (M, B, N)), device=dev)
     h = _lib.load()
     stream = torch.cuda.current_stream(dev)
     q = C.c_void_p(stream.cuda_stream)
@@ -87,48 +75,31 @@ def measure(B, N, K, M, samples, seed=11):
     calls = {"look_fast": look(a_fast, 1), "look_fm": look(a_fm, 1), "look_fast_loop": look(a_fast, other), "look_fm_loop": look(a_fm, other),
              "skip_x_M": skip_x_m, "host_recipe": host_recipe}
     inner = max(1, 60 // (M * K))
-    times = {v: [] for v in calls}
     n_mean = {"look": [], "skip": []}
-    for s in range(-2, samples):   # two warm-up rounds of every variant
-        for v, fn in calls.items():
-            env.reset()
-            env.step(cand[0])
-            t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            t0.record(stream)
-            for _ in range(inner):
-                fn()
-            t1.record(stream)
-            t1.synchronize()
-            if s >= 0:
-                times[v].append(t0.elapsed_time(t1) * 1000.0 / inner)
-                if v == "look_fast":
-                    n_mean["look"].append(float(o["n_steps"].float().mean()))
-                if v == "skip_x_M":
-                    n_mean["skip"].append(float(env.frame_steps.float().mean()))
+
+    def prepare(v):
+        env.reset()
+        env.step(cand[0])
+
+    def after(v):
+        if v == "look_fast":
+            n_mean["look"].append(float(o["n_steps"].float().mean()))
+        if v == "skip_x_M":
+            n_mean["skip"].append(float(env.frame_steps.float().mean()))
+    times = benchlib.sample(calls, samples, inner, benchlib.hip_clock(torch, stream), prepare, after)
     h.atc_lookahead_set_mapping(0)
     res = {"B": B, "N": N, "K": K, "M": M, "samples": samples, "decisions_per_sample": inner,
            "mean_n_steps": {"lookahead": float(np.mean(n_mean["look"])), "last_skip_launch": float(np.mean(n_mean["skip"]))}}
     for v, t in times.items():
-        q1, med, q3 = (float(x) for x in np.percentile(t, (25, 50, 75)))
-        res[v] = {"us_per_decision": {"median": med, "q1": q1, "q3": q3, "min": float(min(t)), "max": float(max(t))},
-                  "us_per_candidate_step_median": med / (M * K)}
+        res[v] = {"us_per_decision": benchlib.quartiles(t)}
+        res[v]["us_per_candidate_step_median"] = res[v]["us_per_decision"]["median"] / (M * K)
     env.close()
     return res
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "lookahead_bench.json"))
-    ap.add_argument("--samples", type=int, default=15)
-    ap.add_argument("--quick", action="store_true", help="65 536 x 16 only")
-    ap.add_argument("--lib", help="a build variant of libatcstep.so to measure instead of the in-tree one (A/B runs)")
-    a = ap.parse_args()
-    if a.lib:
-        from atc_hip import lib as _lib
-        _lib.use_library(a.lib)
-    import torch
-    if not torch.cuda.is_available():
-        raise SystemExit("lookahead_bench needs the GPU: nothing is measured without one")
+    a = benchlib.parser("lookahead_bench.json", quick="65 536 x 16 only").parse_args()
+    torch = benchlib.start(a, "lookahead_bench")
     rows = []
     for B, N in (CONFIGS[:1] if a.quick else CONFIGS):
         for K in KS:
@@ -142,14 +113,8 @@ def main():
            "method": "HIP events around `decisions_per_sample` back-to-back decisions, variants alternating per sample, 2 warm-up rounds, "
                      "every sample from a reset of all envs plus one step",
            "mappings": "look_* : one workgroup per (tile, candidate) (atc_lookahead_set_mapping(1)); look_*_loop: one workgroup per tile, all M candidates in a loop",
-           "box": {"host": socket.gethostname(), "device": torch.cuda.get_device_name(0),
-                   "cus": torch.cuda.get_device_properties(0).multi_processor_count, "torch": torch.__version__},
-           "library": a.lib or "in-tree build", "rows": rows}
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "w") as f:
-        json.dump(doc, f, indent=1)
-        f.write("\n")
-    print(a.out)
+           "box": benchlib.box(torch), "library": a.lib or "in-tree build", "rows": rows}
+    benchlib.write_json(a.out, doc)
 
 
 if __name__ == "__main__":

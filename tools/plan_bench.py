@@ -13,17 +13,11 @@ variant executes M x H x K steps per env), every sample started from a reset of 
 A sample is the device time (HIP events) of `decisions_per_sample` decisions launched back to back; the variants take turns sample by
 sample after two warm-up rounds; reported are median and quartiles in us per decision, and the ratio of the medians plan_fast /
 skip_x_MH (the expectation of section 3d: at most 1 in every row).  One JSON file; needs the GPU."""
-import argparse
 import ctypes as C
-import json
-import os
-import socket
-import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [os.path.join(ROOT, "atc-reinforcement-learning_amd")]
+import benchlib
 
 CONFIGS = ((65536, 16), (4096, 64))
 KS = (5, 20)
@@ -33,12 +27,6 @@ STATE = ("ac", "alt", "last_act", "env", "stats", "phi_wide")
 VARIANTS = ("plan_fast", "plan_default", "skip_x_MH", "host_recipe")
 
 
-def plans(M, H, B, N, seed):
-    rng = np.random.default_rng(seed)   # speed towards 150-200 kt, altitude towards 30 000 ft and up, any heading
-    s = (M, H, B, N)
-    return np.stack([rng.uniform(-0.5, 0.0, s), rng.uniform(0.6, 1.0, s), rng.uniform(-1.0, 1.0, s)], axis=-1).astype(np.float32)
-
-
 def measure(B, N, K, H, M, samples, seed=11):
     import torch
     from atc_hip import lib as _lib
@@ -46,7 +34,7 @@ def measure(B, N, K, H, M, samples, seed=11):
     from envs.atc import scenarios
     env = AtcVecEnv(B, N, scenario=scenarios.LOWWDense(), auto_reset=True, seed=seed, timestep_limit=6000, sep_nm=0.0)
     dev = env.device
-    cand = torch.as_tensor(plans(M, H, B, N, seed), device=dev)
+    cand = torch.as_tensor(benchlib.same_work_actions(np.random.default_rng(seed), (M, H, B, N)), device=dev)
     h = _lib.load()
     stream = torch.cuda.current_stream(dev)
     q = C.c_void_p(stream.cuda_stream)
@@ -84,27 +72,17 @@ def measure(B, N, K, H, M, samples, seed=11):
                 getattr(env, k).copy_(t)
     calls = dict(zip(VARIANTS, (plan(a_fast), plan(a_def), skip_x_mh, host_recipe)))
     inner = max(1, 60 // (M * H * K))
-    times = {v: [] for v in calls}
     n_mean = []
-    for s in range(-2, samples):   # two warm-up rounds of every variant
-        for v, fn in calls.items():
-            env.reset()
-            env.step(cand[0, 0])
-            t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            t0.record(stream)
-            for _ in range(inner):
-                fn()
-            t1.record(stream)
-            t1.synchronize()
-            if s >= 0:
-                times[v].append(t0.elapsed_time(t1) * 1000.0 / inner)
-                if v == "plan_fast":
-                    n_mean.append(float(o["n_steps"].float().mean()))
+
+    def prepare(v):
+        env.reset()
+        env.step(cand[0, 0])
+    times = benchlib.sample(calls, samples, inner, benchlib.hip_clock(torch, stream), prepare,
+                            after=lambda v: v == "plan_fast" and n_mean.append(float(o["n_steps"].float().mean())))
     res = {"B": B, "N": N, "K": K, "H": H, "M": M, "samples": samples, "decisions_per_sample": inner, "mean_n_steps": float(np.mean(n_mean))}
     for v, t in times.items():
-        q1, med, q3 = (float(x) for x in np.percentile(t, (25, 50, 75)))
-        res[v] = {"us_per_decision": {"median": med, "q1": q1, "q3": q3, "min": float(min(t)), "max": float(max(t))},
-                  "us_per_candidate_step_median": med / (M * H * K)}
+        res[v] = {"us_per_decision": benchlib.quartiles(t)}
+        res[v]["us_per_candidate_step_median"] = res[v]["us_per_decision"]["median"] / (M * H * K)
     med = lambda v: res[v]["us_per_decision"]["median"]   # noqa: E731
     res["ratio_to_skip_x_MH"] = {v: med(v) / med("skip_x_MH") for v in ("plan_fast", "plan_default", "host_recipe")}
     res["fast_within_expectation"] = med("plan_fast") <= med("skip_x_MH")
@@ -113,18 +91,8 @@ def measure(B, N, K, H, M, samples, seed=11):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "plan_bench.json"))
-    ap.add_argument("--samples", type=int, default=15)
-    ap.add_argument("--quick", action="store_true", help="65 536 x 16 only")
-    ap.add_argument("--lib", help="a build variant of libatcstep.so to measure instead of the in-tree one (A/B runs)")
-    a = ap.parse_args()
-    if a.lib:
-        from atc_hip import lib as _lib
-        _lib.use_library(a.lib)
-    import torch
-    if not torch.cuda.is_available():
-        raise SystemExit("plan_bench needs the GPU: nothing is measured without one")
+    a = benchlib.parser("plan_bench.json", quick="65 536 x 16 only").parse_args()
+    torch = benchlib.start(a, "plan_bench")
     rows = []
     for B, N in (CONFIGS[:1] if a.quick else CONFIGS):
         for K in KS:
@@ -140,14 +108,8 @@ def main():
                      "every sample from a reset of all envs plus one step",
            "expectation": "plan_fast median <= skip_x_MH median in every row (no margin)",
            "rows_missed": [[r["B"], r["N"], r["K"], r["H"], r["M"]] for r in rows if not r["fast_within_expectation"]],
-           "box": {"host": socket.gethostname(), "device": torch.cuda.get_device_name(0),
-                   "cus": torch.cuda.get_device_properties(0).multi_processor_count, "torch": torch.__version__},
-           "library": a.lib or "in-tree build", "rows": rows}
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "w") as f:
-        json.dump(doc, f, indent=1)
-        f.write("\n")
-    print(a.out)
+           "box": benchlib.box(torch), "library": a.lib or "in-tree build", "rows": rows}
+    benchlib.write_json(a.out, doc)
 
 
 if __name__ == "__main__":

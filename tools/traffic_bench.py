@@ -13,18 +13,15 @@ medians and quartiles.  The kernel has to beat the torch composition at both sha
 whether it does (`kernel_faster_than_torch_at_K4`).
 Each shape is measured by a child process of its own under `timeout -k 10`, one after the other; the first that fails ends the run
 (nothing more is started on the device).  One JSON file; needs the GPU."""
-import argparse
 import ctypes as C
 import json
 import os
-import socket
 import subprocess
 import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [os.path.join(ROOT, "atc-reinforcement-learning_amd")]
+import benchlib
 
 CONFIGS = ((65536, 16), (4096, 64))
 KS = (1, 2, 4, 8)
@@ -96,23 +93,12 @@ def measure(B, N, samples, inner, seed=11):
         calls["kernel"]()
         ref = torch_traffic(torch, env, K, scales)
         agree = float((out[..., L.T_DIST] - ref[..., L.T_DIST]).abs().max())
-        times = {v: [] for v in calls}
-        for s in range(-2, samples):
-            for v, fn in calls.items():
-                t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                t0.record(stream)
-                for _ in range(inner):
-                    fn()
-                t1.record(stream)
-                t1.synchronize()
-                if s >= 0:
-                    times[v].append(t0.elapsed_time(t1) * 1000.0 / inner)
+        times = benchlib.sample(calls, samples, inner, benchlib.hip_clock(torch, stream))
         nbytes = B * N * (24 + 32 * K)
         row = {"B": B, "N": N, "K": K, "normalize": nrm, "samples": samples, "launches_per_sample": inner, "bytes_per_launch": nbytes,
                "max_abs_distance_difference_kernel_vs_torch": agree}
         for v, t in times.items():
-            q1, med, q3 = (float(z) for z in np.percentile(t, (25, 50, 75)))
-            row[v] = {"us_per_launch": {"median": med, "q1": q1, "q3": q3, "min": float(min(t)), "max": float(max(t))}}
+            row[v] = {"us_per_launch": benchlib.quartiles(t)}
         med = row["kernel"]["us_per_launch"]["median"]
         row["kernel"]["bytes_per_s"] = nbytes / (med * 1e-6)
         row["kernel"]["share_of_8TBps"] = nbytes / (med * 1e-6) / HBM_BYTES_PER_S
@@ -121,26 +107,16 @@ def measure(B, N, samples, inner, seed=11):
               % (B, N, K, med, row["step"]["us_per_launch"]["median"], row["torch"]["us_per_launch"]["median"], row["kernel"]["share_of_8TBps"]),
               flush=True)
     env.close()
-    return {"rows": rows, "box": {"host": socket.gethostname(), "device": torch.cuda.get_device_name(0),
-                                  "cus": torch.cuda.get_device_properties(0).multi_processor_count, "torch": torch.__version__}}
+    return {"rows": rows, "box": benchlib.box(torch)}
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "traffic_bench.json"))
-    ap.add_argument("--samples", type=int, default=15)
-    ap.add_argument("--inner", type=int, default=10)
+    ap = benchlib.parser("traffic_bench.json", inner=10)
     ap.add_argument("--shape", type=int, nargs=2, metavar=("B", "N"), help="(internal) measure this shape in this process, print JSON to --part")
     ap.add_argument("--part")
-    ap.add_argument("--lib", help="a build variant of libatcstep.so to measure instead of the in-tree one (A/B runs)")
     a = ap.parse_args()
-    if a.lib:
-        from atc_hip import lib as _lib
-        _lib.use_library(a.lib)
     if a.shape:
-        import torch
-        if not torch.cuda.is_available():
-            raise SystemExit("traffic_bench needs the GPU: nothing is measured without one")
+        benchlib.start(a, "traffic_bench")
         with open(a.part, "w") as f:
             json.dump(measure(a.shape[0], a.shape[1], a.samples, a.inner), f)
         return
@@ -164,10 +140,7 @@ def main():
                      "state: 200 random steps after reset (LOWWDense)",
            "bytes": "24 B read + 32 K B written per aircraft; share_of_8TBps = bytes / time / 8e12",
            "kernel_faster_than_torch_at_K4": at4, "box": box, "library": a.lib or "in-tree build", "rows": rows}
-    with open(a.out, "w") as f:
-        json.dump(doc, f, indent=1)
-        f.write("\n")
-    print(a.out)
+    benchlib.write_json(a.out, doc)
     if not all(at4.values()):
         raise SystemExit("the hand kernel is NOT faster than the torch composition at K = 4: %r" % at4)
 
