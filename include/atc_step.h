@@ -287,6 +287,22 @@ typedef struct atc_params {
  *     heading holds it to within the fp32 rounding of its ACTION (340 -/+ 1e-5 deg), one third of an fp32 ulp at 340 — the reference's
  *     float64 tells the two apart, and so must the flag (tests/golden/g11: the winning intercepts flown at heading - 360).  The
  *     relative angles of the observation and the shaping terms are values (1e-5 bar) and stay fp32;
+ *   - Vertical separation (extension: no reference code).  dh = |(float)h_a - (float)h_b|, the float32 difference of the altitudes
+ *     rounded to float32 (what observation word 2 reports), in conflict iff dh < sep_ft and d^2 < sep_nm^2.  Levels a whole number of
+ *     feet apart are exact in float32, so two aircraft levelled at commanded levels exactly sep_ft apart are not in conflict, whatever
+ *     rounding noise their float64 altitudes carry (h + (target - h) need not equal target).  The float64 test oracle uses the same
+ *     definition: with a float64 difference the verdict of such a pair hung on 3.6e-10 ft of noise.
+ *   - Observation word 9 at the wrap.  relative_angle(phi_to_runway, phi) = (phi - phi_to_runway + 180) % 360 - 180 (atc_gym.py:284-287,
+ *     model.py:340-342) is DISCONTINUOUS where the heading is the runway's reciprocal R: the reference returns -180 for phi == R and
+ *     above, and +180 (the float32 of 179.99999999999997) for a heading a float64 rounding BELOW R — which its accumulated heading
+ *     is whenever a turn in steps of 3 dt arrives at R with rounding noise (heading 159.99999999999997 for R = 160).  The float64
+ *     oracle transcribes this as it is.  The fp32 spec evaluates the same formula on the fp32 heading fmaf(phi_fix, 2^-23, 180): every
+ *     count within half an fp32 ulp of R (7.6e-6 deg at 160) reads -180, so word 9 — and the normalised word, by 2.0, its whole
+ *     range — can sit on the other side of the wrap from the reference: where the reference's heading is a rounding below R while
+ *     the counts are on it, and on every step of an aircraft that HOLDS R by a continuous action (the fp32 action, truncated, is one
+ *     count below R: the reference reads +180, the spec -180).  -180 and +180 are the same angle; the shaping terms differ by less
+ *     than 1e-8 there.  Tests compare word 9 modulo a turn inside 1e-3 deg of the wrap and count the rows (tests/helpers.py: obs_close;
+ *     tests/ref_diff.py; pinned by tests/test_ref_diff.py).
  *   - the fp32 speed every other formula of the reference sees is (float)v_fix * 2^-23; both conversions are exact for every value
  *     with <= 24 significant bits, e.g. all integer speeds and headings;
  *   - the ALTITUDE (model.py:82-102) is the reference's float64, operation for operation (ABI 20; rounds 1-5 kept an fp32

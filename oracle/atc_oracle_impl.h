@@ -698,7 +698,11 @@ int FN(atc_oracle_step)(const REAL* S, int B, int N, const FN(orc_state_t) * st,
                 REAL dx = FN(pos_to_real)(S, 0, st->x[ia]) - FN(pos_to_real)(S, 0, st->x[ib]);
                 REAL dy = FN(pos_to_real)(S, 1, st->y[ia]) - FN(pos_to_real)(S, 1, st->y[ib]);
                 REAL d2 = R_FMA(dx, dx, dy * dy); /* fused: the definition shared with the device kernel */
-                REAL dh = R_ABS((REAL)st->h[ia] - (REAL)st->h[ib]); /* (fp32 spec: the altitudes rounded once, then the difference) */
+                /* the extension's ONE definition, in both instantiations (include/atc_step.h, "Vertical separation"): the altitudes rounded
+                 * to float32 — what observation word 2 reports — then their float32 difference.  Two aircraft levelled at commanded levels
+                 * exactly sep_ft apart are NOT in conflict; a float64 difference of two accumulated altitudes falls a rounding below the
+                 * threshold or not by luck (1 000 - 3.6e-10 ft: 28 of 32 envs of tests/ref_diff.py's seed 1118) */
+                REAL dh = (REAL)fabsf((float)st->h[ia] - (float)st->h[ib]);
                 REAL d = R_SQRT(d2);
                 if (d < min_sep) min_sep = d;
                 if (d2 < (REAL)p->sep_nm * (REAL)p->sep_nm && dh < (REAL)p->sep_ft) {

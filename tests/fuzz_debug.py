@@ -3,13 +3,32 @@
 replays the case step by step and prints the first deviation of every kind with its context;
     python tests/fuzz_debug.py --held <seed>
 replays one case of test_fuzz_held.py (tests/held_fuzz.py) and prints the first deviation with the call, candidate, segment, env and
-aircraft it is in and the oracle's per-step record of that env."""
+aircraft it is in and the oracle's per-step record of that env;
+    python tests/fuzz_debug.py --ref <seed>
+replays one case of test_ref_diff.py (tests/ref_diff.py: the fp32 spec against the float64 oracle, no GPU) and prints the first
+deviation, or the ties it attributed with their predicates and margins."""
 import os
 import sys
 
 _ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [_ROOT, os.path.join(_ROOT, "atc-reinforcement-learning_amd"), os.path.dirname(os.path.abspath(__file__))]
 import numpy as np
+
+if sys.argv[1] == "--ref":
+    import ref_diff as D
+    seed = int(sys.argv[2])
+    scn, comp, kw = D.case(seed)
+    print(type(scn).__name__, kw)
+    try:
+        print("\n".join(D.report(D.fly(seed))))
+        print("no deviation")
+    except D.Mismatch as m:
+        c = m.ctx
+        print("FIRST DEVIATION:", m.what)
+        print(" quantity %s, step %s, env %s, index %s: fp32 spec %r, float64 %r" % tuple(c.get(k) for k in ("quantity", "t", "env", "index", "got", "ref")))
+        why = D.attribute(c["ref_env"], comp, c["env"], c["spec"].flags, c["spec"].mva, c["spec"]) if c.get("quantity") in D.EXACT_OUT + D.EXACT_STATE else None
+        print(" tie rule:", why or "none applies")
+    sys.exit(0)
 
 if sys.argv[1] == "--held":
     import held_fuzz as F

@@ -35,19 +35,20 @@ def restore(orc, snap):
 
 def wide_envs(orc):
     """[B] bool: envs with an aircraft whose heading or last heading target is WIDE (saturated 32-bit field, include/atc_step.h ABI 19):
-    the look-ahead calls do not evaluate them"""
+    the look-ahead calls do not evaluate them.  (orc: the fp32 instantiation — the float64 one has no such field)"""
     edge = (-2 ** 31, 2 ** 31 - 1)
     return np.isin(orc.last_act[:, 1], edge).reshape(orc.B, orc.N).any(1) | np.isin(orc.phi_fix, edge).reshape(orc.B, orc.N).any(1)
 
 
-def f32_sequential_sum(terms, n):
-    """acc = t[0]; acc = acc + t[1]; ... over the first n[b] terms of every column, plain float32 additions.  terms: [K, ...] with
-    the env axis second; n: [B] (broadcast over trailing axes)."""
-    terms = np.asarray(terms, np.float32)
+def f32_sequential_sum(terms, n, dtype=np.float32):
+    """acc = t[0]; acc = acc + t[1]; ... over the first n[b] terms of every column, plain additions in `dtype` (float32: the kernels' and
+    the fp32 oracle's; float64 for a reference built on the float64 oracle).  terms: [K, ...] with the env axis second; n: [B] (broadcast
+    over trailing axes)."""
+    terms = np.asarray(terms, dtype)
     acc = terms[0].copy()
     for j in range(1, terms.shape[0]):
         live = (j < n).reshape((-1,) + (1,) * (acc.ndim - 1))
-        acc = np.where(live, (acc + terms[j]).astype(np.float32), acc)
+        acc = np.where(live, (acc + terms[j]).astype(dtype), acc)
     return acc
 
 
@@ -55,7 +56,8 @@ def skip_reference(orc, actions, K):
     """Runs one frame-skip call of length K on the oracle env `orc` (left in the state after the call) and returns a dict:
     obs, raw_obs, reward, ac_reward, done, flags, min_sep, term_obs, n_steps as the call defines them, plus
     reward_scale [B] / ac_reward_scale [B, N] = sum over the executed steps of max(1, |r_j|) (the per-step 1e-5 bar, added up),
-    step_done [K, B], step_flags [K, B, N] (the oracle's own per-step record, for event checks) and n_steps."""
+    step_done [K, B], step_flags [K, B, N] (the oracle's own per-step record, for event checks) and n_steps.
+    The sums and the minimum are taken in the oracle's dtype: a float64 OracleEnv gives the float64-built reference."""
     B, N = orc.B, orc.N
     actions = np.ascontiguousarray(np.asarray(actions, np.float32).reshape(B, N, 3))
     term_before = orc.term_obs.copy()
@@ -80,12 +82,12 @@ def skip_reference(orc, actions, K):
     res = {
         "n_steps": n.astype(np.uint8),
         "obs": at_last("obs"), "raw_obs": at_last("raw_obs"),
-        "reward": f32_sequential_sum(rew, n), "ac_reward": f32_sequential_sum(acr, n),
+        "reward": f32_sequential_sum(rew, n, orc.dtype), "ac_reward": f32_sequential_sum(acr, n, orc.dtype),
         "reward_scale": np.where(executed, np.maximum(1.0, np.abs(rew.astype(np.float64))), 0.0).sum(axis=0),
         "ac_reward_scale": np.where(executed[:, :, None], np.maximum(1.0, np.abs(acr.astype(np.float64))), 0.0).sum(axis=0),
         "done": done[last, env_rows].astype(np.uint8),
         "flags": np.bitwise_or.reduce(np.where(executed[:, :, None], flags, 0).astype(np.uint16), axis=0),
-        "min_sep": np.where(executed, np.stack([o["min_sep"] for o in outs]), np.inf).min(axis=0).astype(np.float32),
+        "min_sep": np.where(executed, np.stack([o["min_sep"] for o in outs]), np.inf).min(axis=0).astype(orc.dtype),
         "step_done": done, "step_flags": flags,
     }
     # the terminal observation is written by the terminating step of envs that are auto-reset in this call; untouched otherwise
@@ -94,6 +96,9 @@ def skip_reference(orc, actions, K):
     # state: every env's rows of its step-n snapshot
     for k in STATE:
         stack = np.stack([s[k] for s in states])
+        if k == "last_act" and not orc.fixed:      # the float64 instantiation keeps it [3, B N]: the aircraft on the second axis
+            orc.last_act[...] = stack[last_ac, :, ac_rows].T
+            continue
         getattr(orc, k)[...] = stack[last_ac, ac_rows] if k in PER_AIRCRAFT else stack[last, env_rows]
     for k in OUTPUTS:   # the oracle's output arrays show the call's result, like the product's
         getattr(orc, k)[...] = res[k].reshape(getattr(orc, k).shape)
@@ -137,11 +142,11 @@ def plan_chain(orc, plan, K, record=None):
     """The plan call (atc_lookahead_plan) on the oracle for ONE candidate ([H, B, N, 3]): chained skip_reference calls, an env leaving at
     its first done.  The oracle is left wherever the chain ends: the caller restores it.  Returns what bars.check_skip_outputs reads, plus
     seg_reward [H, B] and seg_reward_scale [H, B] (each segment's own bar: that of one frame-skip call).  record: a list that gets one
-    (alive [B] before the segment, the segment's skip_reference dict) per segment."""
+    (alive [B] before the segment, the segment's skip_reference dict) per segment.  Sums in the oracle's dtype, like skip_reference."""
     B = orc.B
     alive = np.ones(B, bool)
     out = None
-    seg = np.zeros((plan.shape[0], B), np.float32)
+    seg = np.zeros((plan.shape[0], B), orc.dtype)
     seg_scale = np.zeros((plan.shape[0], B))
     for h in range(plan.shape[0]):
         r = skip_reference(orc, plan[h], K)
@@ -155,8 +160,8 @@ def plan_chain(orc, plan, K, record=None):
             a1, a2, a3 = alive, alive[:, None], alive[:, None, None]
             for k, m in (("obs", a3), ("raw_obs", a3), ("term_obs", a3), ("done", a1)):
                 out[k] = np.where(m, r[k], out[k])
-            out["reward"] = np.where(a1, (out["reward"] + r["reward"]).astype(np.float32), out["reward"])
-            out["ac_reward"] = np.where(a2, (out["ac_reward"] + r["ac_reward"]).astype(np.float32), out["ac_reward"])
+            out["reward"] = np.where(a1, (out["reward"] + r["reward"]).astype(orc.dtype), out["reward"])
+            out["ac_reward"] = np.where(a2, (out["ac_reward"] + r["ac_reward"]).astype(orc.dtype), out["ac_reward"])
             out["reward_scale"] = out["reward_scale"] + np.where(a1, r["reward_scale"], 0.0)
             out["ac_reward_scale"] = out["ac_reward_scale"] + np.where(a2, r["ac_reward_scale"], 0.0)
             out["flags"] = np.where(a2, out["flags"] | r["flags"], out["flags"])
