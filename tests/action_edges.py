@@ -23,6 +23,8 @@ from fractions import Fraction
 
 import numpy as np
 
+import helpers as H
+
 Q = 1 << 23                      # ATC_V_FIX_SHIFT / ATC_PHI_FIX_SHIFT
 PHI_LIMIT = 1 << 52              # ATC_PHI_LIMIT
 I32_MIN, I32_MAX = -(1 << 31), (1 << 31) - 1
@@ -252,13 +254,9 @@ def n_values(discrete):
 
 
 # ---------------------------------------------------------------------------------------------------------------- placement
-def lane_width(N):
-    return 1 << max(0, (int(N) - 1).bit_length())
-
-
 def free_envs(B, N):
     """the envs of one whole wavefront (64 lanes = 64 / W envs) that placement leaves alone: the second wavefront of the batch"""
-    per = max(1, 64 // lane_width(N))
+    per = max(1, 64 // H.lane_width(N))
     assert B >= 2 * per + 1, "the batch has no room for a free wavefront next to a first and a last env"
     return list(range(per, 2 * per))
 

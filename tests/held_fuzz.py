@@ -1,10 +1,10 @@
 """Randomised differential harness for the held-block kernels — k_skip (atc_step_skip), k_lookahead (atc_lookahead), k_plan
 (atc_lookahead_plan) — and k_traffic (atc_observe_traffic) against the fp32 oracle.  TEST INFRASTRUCTURE ONLY; importing it needs no GPU.
 
-case(seed) draws the env configuration with tests/test_fuzz_parity.py::_case (that function and its draws are untouched: the batch size,
+case(seed) draws the env configuration with tests/fuzz_space.py::parity_case (that function and its draws are untouched: the batch size,
 the step count and the launch form it draws are simply not used here) and, from a random stream of its own, a small batch, a time limit
 that ends episodes inside held blocks, and the calls.  run(seed) flies them on an AtcVecEnv and an oracle.OracleEnv built from the same
-configuration, the way test_hip_parity._run_vs_oracle builds them:
+configuration by fuzz_space.make_env / make_oracle, the way fuzz_space.run_vs_oracle builds them:
   reset observation; 2-4 step_skip calls (tests/skip_ref.py, bars.check_skip_outputs, bars.check_state); observe_traffic (tests/traffic_ref.py
   on the oracle's state); lookahead (skip_ref.candidate_references) and lookahead_plan (skip_ref.plan_references) with the six state
   tensors compared byte for byte with a clone taken before and bars.check_state against the untouched oracle; one more step_skip.
@@ -17,7 +17,7 @@ import bars
 import helpers as H
 import skip_ref as R
 import traffic_ref
-from test_fuzz_parity import _case as _parity_case
+from fuzz_space import NON_DYADIC, Mismatch, draw_actions, make_env, make_oracle, parity_case
 
 FLOWN_K = (1, 2, 5, 20, 60)
 LOOK_M, LOOK_K = (1, 3, 8), (1, 4, 20)
@@ -26,7 +26,6 @@ LOOK_OUTPUTS = ("flags", "min_sep", "ac_reward", "obs")
 PLAN_OUTPUTS = ("seg_reward",) + LOOK_OUTPUTS
 KERNELS = ("skip", "lookahead", "plan")
 WIDTHS = (1, 2, 4, 8, 16, 32, 64)
-NON_DYADIC = (0.05, 0.1, 0.15, 0.3, 0.7, 1.3, 3.7, 0.37, 2.1)     # test_fuzz_parity._case's round-6 timesteps
 REFUSED = H.F_INVALID_V | H.F_INVALID_H
 HEADING_WILD_ENVS = 0.25    # share of a flown call's envs whose HEADING components take part in the `wild` draw (env 0 never does)
 _ENV_KEYS = ("N", "seed", "dt", "discrete", "spawn", "grid_cell", "full", "shaping", "normalize", "sep_nm", "keep_active")
@@ -34,10 +33,10 @@ _ENV_KEYS = ("N", "seed", "dt", "discrete", "spawn", "grid_cell", "full", "shapi
 
 # ---------------------------------------------------------------------------------------------------------------- the draw
 def case(seed):
-    """(scn, comp, kw) of one case.  kw: the env configuration (test_fuzz_parity._case's, with B in 1 .. 120 — fewer at N > 16, so that the
+    """(scn, comp, kw) of one case.  kw: the env configuration (fuzz_space.parity_case's, with B in 1 .. 120 — fewer at N > 16, so that the
     oracle stays cheap — and timestep_limit in {6000, 40, 12}), auto_reset_off (a quarter of the cases: switched off after flying), and
     the calls: flown [K, ...], lookahead / plan dicts, traffic (K of observe_traffic; 0 at N == 1), last (K of the closing step_skip)."""
-    scn, comp, drawn = _parity_case(int(seed), n_cu=256)    # (n_cu given: no device is asked for its CU count)
+    scn, comp, drawn = parity_case(int(seed), n_cu=256)    # (n_cu given: no device is asked for its CU count)
     kw = {k: drawn[k] for k in _ENV_KEYS}
     kw["wild"] = float(drawn.get("wild", 0.0))
     rng = np.random.default_rng([int(seed), 0x48454C44])
@@ -60,29 +59,17 @@ def case(seed):
     return scn, comp, kw
 
 
-def draw_actions(rng, shape, discrete, wild, heading_wild=None):
-    """Actions [*shape, 3] (shape ends in B, N) as test_hip_parity._run_vs_oracle draws them: discrete indices when discrete, U(-1.05, 1.05)
-    otherwise, and with wild > 0 that share of the components from U(-4, 4) (a tenth of those a further factor 50 out).  The HEADING
-    component takes part in the wild share only in the envs of heading_wild ([B] bool; None: in none) — a heading target outside the
-    32-bit heading field is WIDE, and a WIDE env is not evaluated by the look-ahead calls."""
-    full = tuple(shape) + (3,)
-    if discrete:
-        act = np.floor(rng.uniform(0, 1, full) * np.array([20, 380, 360])).astype(np.float32)
-    else:
-        act = rng.uniform(-1.05, 1.05, full).astype(np.float32)
-    if wild > 0.0:
-        out_of_space = rng.uniform(-4.0, 4.0, full) * np.where(rng.uniform(size=full) < 0.1, 50.0, 1.0)
-        if discrete:
-            out_of_space = np.floor(out_of_space * np.array([20, 380, 360]))
-        pick = rng.uniform(size=full) < wild
-        pick[..., 2] &= False if heading_wild is None else np.asarray(heading_wild, bool)[:, None]
-        act = np.where(pick, out_of_space, act).astype(np.float32)
-    return act
+def draw_flown(rng, B, N, discrete, wild):
+    """The actions of a flown step_skip call: fuzz_space.draw_actions, with the HEADING components taking part in the `wild` share in
+    HEADING_WILD_ENVS of the envs (env 0 never does)."""
+    heading_wild = rng.uniform(size=B) < HEADING_WILD_ENVS
+    heading_wild[0] = False
+    return draw_actions(rng, (B, N), discrete, wild, heading_wild)
 
 
 def draw_candidates(rng, shape, discrete, wild):
     """Candidate / plan actions: wild in the speed and altitude components only, headings inside the action space."""
-    a = draw_actions(rng, shape, discrete, wild)
+    a = draw_actions(rng, shape, discrete, wild, False)
     if not discrete:
         a[..., 2] = np.clip(a[..., 2], -1.0, 1.0)
     return a
@@ -129,33 +116,7 @@ def _add_block(ev, ref, K, mask, auto_reset):
         ev["reset_in_block"] += int((ref["done"].astype(bool) & (n < K) & mask).sum())
 
 
-class Mismatch(AssertionError):
-    """a failed comparison of run(), with the context tests/fuzz_debug.py prints"""
-
-    def __init__(self, ctx, cause):
-        super().__init__("held fuzz case %s, %s: %s" % (ctx.get("seed"), ctx.get("call"), cause))
-        self.ctx, self.cause = ctx, cause
-
-
 # ---------------------------------------------------------------------------------------------------------------- the run
-def _make_env(scn, kw):
-    from atc_hip.vec_env import AtcVecEnv
-    from envs.atc import model
-    sp = model.SimParameters(kw["dt"], discrete_action_space=kw["discrete"], reward_shaping=kw["shaping"], normalize_state=kw["normalize"])
-    full = kw["full"]
-    return AtcVecEnv(kw["B"], kw["N"], sim_parameters=sp, scenario=scn, auto_reset=True, spawn=kw["spawn"], seed=kw["seed"],
-                     grid_cell=kw["grid_cell"], want_raw_obs=full, want_ac_reward=full, want_min_sep=full, want_term_obs=full,
-                     timestep_limit=kw["timestep_limit"], sep_nm=kw["sep_nm"], keep_active=kw["keep_active"], traffic=kw["traffic"])
-
-
-def _make_oracle(comp, kw):
-    from oracle import oracle as O
-    p = O.make_params(dt=kw["dt"], discrete=kw["discrete"], auto_reset=True, random_entry=(kw["spawn"] == "random"), seed=kw["seed"],
-                      timestep_limit=kw["timestep_limit"], shaping=kw["shaping"], normalize=kw["normalize"], sep_nm=kw["sep_nm"],
-                      keep_active=kw["keep_active"])
-    return O.OracleEnv(comp, kw["B"], kw["N"], p, np.float32)
-
-
 def _counters():
     from atc_hip import lib
     return dict(step=lib.launch_counts(), skip=lib.skip_launch_counts(), lookahead=lib.lookahead_launch_counts(),
@@ -198,15 +159,15 @@ def run(seed, device=True):
     env = None
     try:
         start = _counters() if device else None
-        orc = _make_oracle(comp, kw)
-        env = _make_env(scn, kw) if device else None
+        orc = make_oracle(comp, kw, auto_reset=True)
+        env = make_env(scn, kw, auto_reset=True) if device else None
         _fly(env, orc, comp, kw, rec, ctx)
         if device:
             rec["launches"] = _gained(start, _counters())
     except AssertionError as e:
         if isinstance(e, Mismatch):
             raise
-        raise Mismatch(ctx, e) from e
+        raise Mismatch(ctx, e, "held fuzz case %s, %s" % (ctx.get("seed"), ctx.get("call"))) from e
     finally:
         if env is not None:
             from atc_hip import lib
@@ -223,16 +184,13 @@ def _fly(env, orc, comp, kw, rec, ctx):
     if env is not None:
         import torch
         from atc_hip import lib
-        from test_lookahead import _bytes_equal, _set_auto_reset, _snapshot
         # 1. the reset observation
         ctx.update(call="reset")
         o0 = env.obs.cpu().numpy().reshape(B, N, 10)
         assert np.all(np.abs(o0 - orc.obs) <= 1e-5 * np.maximum(1.0, np.abs(orc.obs))), "reset observation"
 
     def skip_call(tag, K, auto_reset):
-        heading_wild = rng.uniform(size=B) < HEADING_WILD_ENVS
-        heading_wild[0] = False
-        a = draw_actions(rng, (B, N), discrete, wild, heading_wild)
+        a = draw_flown(rng, B, N, discrete, wild)
         ref = R.skip_reference(orc, a, K)
         _add_n(ev["skip"], ref["n_steps"].astype(int), ref["done"].astype(bool), K)
         _add_block(ev["skip"], ref, K, np.ones(B, bool), auto_reset)
@@ -250,7 +208,7 @@ def _fly(env, orc, comp, kw, rec, ctx):
         from oracle import oracle as O
         orc.params.mode &= ~O.M_AUTO_RESET
         if env is not None:
-            _set_auto_reset(env, False)
+            H.set_auto_reset(env, False)
 
     # 3. the traffic observation of the state the calls left
     if kw["traffic"]:
@@ -267,7 +225,7 @@ def _fly(env, orc, comp, kw, rec, ctx):
     # 4. / 5. the look-ahead and the plan, from the same state; 6. which they leave as it is
     ok = ~R.wide_envs(orc)
     if env is not None:
-        snap = _snapshot(env)
+        snap = H.snapshot(env)
     for kernel in ("lookahead", "plan"):
         c = kw[kernel]
         M, K, Hn = c["M"], c["K"], c.get("H")
@@ -311,7 +269,7 @@ def _fly(env, orc, comp, kw, rec, ctx):
             if "seg_reward" in g:
                 bars.check_plan_segments(g["seg_reward"], refs[m], ok, K, tag=(kernel, m))
         ctx.update(call=tag + ": state afterwards", got=None, ref=None, cand=None)
-        _bytes_equal(env, snap)
+        H.bytes_equal(env, snap)
         bars.check_state(env, orc)
 
     # 7. one more frame-skip call: the queries left nothing behind
@@ -355,7 +313,7 @@ def describe(mismatch, comp):
     """prints a Mismatch: the call, the candidate, the segment, the env and aircraft of the first deviation and the oracle's per-step
     record (skip_reference's step_done / step_flags) of that env"""
     ctx = mismatch.ctx
-    print("FIRST DEVIATION in", ctx.get("call"), "-", mismatch.cause)
+    print("FIRST DEVIATION in", ctx.get("call"), "-", mismatch.what)
     got, ref = ctx.get("got"), ctx.get("ref")
     if got is None or ref is None:
         return

@@ -1,4 +1,5 @@
-"""Shared test helpers: golden loading, scenario factory, episode replay against any env adapter."""
+"""Shared test helpers: golden loading, scenario factory, batch shapes, the env's state tensors (snapshot / restore / compare),
+episode replay against any env adapter."""
 import contextlib
 import json
 import os
@@ -27,6 +28,40 @@ def launches():
 def lane_width(N):
     """W of k_step<W, ...>: the aircraft count rounded up to a power of two."""
     return 1 << max(0, (int(N) - 1).bit_length())
+
+
+def ragged(N):
+    """a batch of two whole 256-lane workgroups plus a part"""
+    per = 256 // lane_width(N)
+    B = 2 * per + max(1, per // 3) if per > 1 else 2 * per + 1
+    assert (B * lane_width(N)) % 256 != 0
+    return B
+
+
+# the six state tensors of an AtcVecEnv: everything a call may change
+STATE = ("ac", "alt", "last_act", "env", "stats", "phi_wide")
+
+
+def snapshot(env):
+    return {k: getattr(env, k).clone() for k in STATE}
+
+
+def restore(env, snap):
+    for k, v in snap.items():
+        getattr(env, k).copy_(v)
+
+
+def bytes_equal(env, snap):
+    import torch
+    for k, v in snap.items():
+        a, b = getattr(env, k).contiguous().view(torch.uint8), v.contiguous().view(torch.uint8)
+        assert torch.equal(a, b), "state array %s changed" % k
+
+
+def set_auto_reset(env, on):
+    from atc_hip import layout as L
+    env.params.mode = (env.params.mode | L.M_AUTO_RESET) if on else (env.params.mode & ~L.M_AUTO_RESET)
+    env.refresh_params()
 
 
 def golden_json(name):

@@ -4,9 +4,9 @@
   fp32 oracle == reference    the fp32 instantiation is a SPEC co-designed with the kernels (include/atc_step.h); the float64
                               instantiation is the reference as it is (oracle/atc_oracle_impl.h).  This module flies both side by side.
 
-fly(seed) draws a configuration with tests/test_fuzz_parity.py::_case (its draws are untouched; the batch is capped at MAX_B envs, the
-step count kept), builds the two oracle.OracleEnv instantiations from identical parameters, draws the actions the way
-test_hip_parity._run_vs_oracle does and compares after every step through a Comparator, the float64 instantiation as the reference.
+fly(seed) draws a configuration with tests/fuzz_space.py::parity_case (its draws are untouched; the batch is capped at MAX_B envs, the
+step count kept), builds the two oracle.OracleEnv instantiations from identical parameters (fuzz_space.make_oracle), draws the actions with
+fuzz_space.draw_actions as run_vs_oracle does and compares after every step through a Comparator, the float64 instantiation as the reference.
 The same Comparator holds a KERNEL result to the float64 oracle directly (tests/test_ref_diff.py, -m gpu) with extra=True.
 
 THE BARS (Comparator): none is invented here.
@@ -48,7 +48,7 @@ import numpy as np
 
 import bars
 import helpers as H
-from test_fuzz_parity import _case as _parity_case
+from fuzz_space import Mismatch, draw_actions, make_env, make_oracle, parity_case
 
 MAX_B = 32
 WRAP_WINDOW_DEG = 1e-3
@@ -81,32 +81,10 @@ TIE_SEP_FT = 2.0 ** -8
 
 
 def case(seed):
-    """(scn, comp, kw): test_fuzz_parity._case's draw with the batch capped at MAX_B"""
-    scn, comp, kw = _parity_case(int(seed), n_cu=256)   # (n_cu given: no device is asked for its CU count)
+    """(scn, comp, kw): fuzz_space.parity_case's draw with the batch capped at MAX_B"""
+    scn, comp, kw = parity_case(int(seed), n_cu=256)   # (n_cu given: no device is asked for its CU count)
     kw = dict(kw, B=min(kw["B"], MAX_B))
     return scn, comp, kw
-
-
-def make_oracle(comp, kw, dtype):
-    from oracle import oracle as O
-    p = O.make_params(dt=kw["dt"], discrete=kw["discrete"], auto_reset=kw.get("auto_reset", True), random_entry=(kw["spawn"] == "random"),
-                      seed=kw["seed"], timestep_limit=kw["timestep_limit"], shaping=kw["shaping"], normalize=kw["normalize"],
-                      sep_nm=kw["sep_nm"], keep_active=kw["keep_active"])
-    return O.OracleEnv(comp, kw["B"], kw["N"], p, dtype)
-
-
-def draw_actions(rng, B, N, discrete, wild):
-    """one action block exactly as test_hip_parity._run_vs_oracle draws it"""
-    if discrete:
-        act = np.floor(rng.uniform(0, 1, (B, N, 3)) * np.array([20, 380, 360])).astype(np.float32)
-    else:
-        act = rng.uniform(-1.05, 1.05, (B, N, 3)).astype(np.float32)
-    if wild > 0.0:
-        out_of_space = rng.uniform(-4.0, 4.0, (B, N, 3)) * np.where(rng.uniform(size=(B, N, 3)) < 0.1, 50.0, 1.0)
-        if discrete:
-            out_of_space = np.floor(out_of_space * np.array([20, 380, 360]))
-        act = np.where(rng.uniform(size=(B, N, 3)) < wild, out_of_space, act).astype(np.float32)
-    return act
 
 
 def properties(scn, kw):
@@ -141,14 +119,6 @@ def merge(total, rec):
         if v > total["maxdev"].get(k, -1.0):
             total["maxdev"][k], total["where"][k] = v, rec["where"][k]
     return total
-
-
-class Mismatch(AssertionError):
-    """a failed comparison, with the context tests/fuzz_debug.py --ref prints"""
-
-    def __init__(self, ctx, what):
-        super().__init__("ref diff %s: %s" % (ctx.get("tag"), what))
-        self.ctx, self.what = ctx, what
 
 
 # ---------------------------------------------------------------------------------------------------------------- geometry for the ties
@@ -267,7 +237,7 @@ class Comparator:
 
     def _fail(self, what, **more):
         self.ctx.update(more)
-        raise Mismatch(self.ctx, what)
+        raise Mismatch(self.ctx, what, "ref diff %s" % self.ctx.get("tag"))
 
     def _float(self, name, got, ref, unit, bar, t, rows):
         """|got - ref| / unit <= bar on the rows of `rows` ([B] bool); records the largest ratio"""
@@ -433,7 +403,7 @@ def fly(seed, measure_only=(), max_steps=None, probe=None):
     act = None
     for t in range(steps):
         if t % kw["hold"] == 0 or act is None:
-            act = draw_actions(rng, B, N, kw["discrete"], kw.get("wild", 0.0))
+            act = draw_actions(rng, (B, N), kw["discrete"], kw.get("wild", 0.0), True)
         ref.step(act.astype(np.float64))
         spec.step(act)
         if probe is not None:
@@ -486,18 +456,13 @@ def fly_kernel(i):
     under the tie rules) and, the side check that says which link broke, to the fp32 oracle by bars.check_step / bars.check_state.
     Returns (event record, launch record)."""
     import torch
-    from atc_hip.vec_env import AtcVecEnv
-    from envs.atc import model
     scn, comp, kw = gpu_case(i)
     B, N, full, chunk, rh = kw["B"], kw["N"], kw["full"], kw["chunk"], kw["rollout_hold"]
-    sp = model.SimParameters(kw["dt"], discrete_action_space=kw["discrete"], reward_shaping=kw["shaping"], normalize_state=kw["normalize"])
     ref, spec = make_oracle(comp, kw, np.float64), make_oracle(comp, kw, np.float32)
     cmp_ = Comparator(ref, comp, kw["normalize"], extra=True, tag="gpu case %d" % i)
     cmp_.rec["cases"], cmp_.rec["props"] = 1, properties(scn, kw) | {kw["form"]}
     with H.launches() as launched:
-        env = AtcVecEnv(B, N, sim_parameters=sp, scenario=scn, auto_reset=True, spawn=kw["spawn"], seed=kw["seed"], grid_cell=kw["grid_cell"],
-                        want_raw_obs=full, want_ac_reward=full, want_min_sep=full, want_term_obs=full, timestep_limit=kw["timestep_limit"],
-                        sep_nm=kw["sep_nm"], keep_active=kw["keep_active"])
+        env = make_env(scn, kw)
         try:
             rng = np.random.default_rng(kw["seed"])
             cpu = lambda t: t.cpu().numpy()   # noqa: E731
@@ -506,7 +471,7 @@ def fly_kernel(i):
                 acts = []
                 for c in range(chunk):
                     if (t + c) % kw["hold"] == 0 or act is None:
-                        act = draw_actions(rng, B, N, kw["discrete"], kw["wild"])
+                        act = draw_actions(rng, (B, N), kw["discrete"], kw["wild"], True)
                     acts.append(act)
                 if chunk > 1:
                     bufs = None if not full else {k: torch.zeros((chunk,) + shape, dtype=dt, device=env.device) for k, shape, dt in (
@@ -549,10 +514,6 @@ def fly_kernel(i):
 
 # ---------------------------------------------------------------------------------------------------------------- the held-block calls
 HELD_KERNELS = ("skip", "lookahead", "plan")
-
-
-def _held_oracle(comp, kw, dtype):
-    return make_oracle(comp, dict(kw, auto_reset=True), dtype)
 
 
 class HeldDiff:
@@ -647,23 +608,20 @@ def fly_held(seed, device=False):
     from oracle import oracle as O
     scn, comp, kw = F.case(seed)
     B, N, full, discrete, wild = kw["B"], kw["N"], kw["full"], kw["discrete"], kw["wild"]
-    o64, o32 = _held_oracle(comp, kw, np.float64), _held_oracle(comp, kw, np.float32)
+    o64, o32 = make_oracle(comp, kw, np.float64, auto_reset=True), make_oracle(comp, kw, np.float32, auto_reset=True)
     hd = HeldDiff(o64, o32, comp, kw["normalize"], device, "held case %d" % seed)
     hd.rec["cases"], hd.rec["props"] = 1, F.properties(scn, kw)
     half = bars.half_range(comp)
     rng = np.random.default_rng([kw["seed"], 0x464C59])
-    env = F._make_env(scn, kw) if device else None
+    env = make_env(scn, kw, auto_reset=True) if device else None
     try:
         if device:
             import torch
             from atc_hip import lib
-            from test_lookahead import _set_auto_reset
         auto_reset = True
 
         def skip_call(tag, K):
-            heading_wild = rng.uniform(size=B) < F.HEADING_WILD_ENVS
-            heading_wild[0] = False
-            a = F.draw_actions(rng, (B, N), discrete, wild, heading_wild)
+            a = F.draw_flown(rng, B, N, discrete, wild)
             before = R.snapshot(o64), R.snapshot(o32)
             r64, r32 = R.skip_reference(o64, a, K), R.skip_reference(o32, a, K)
             got = r32
@@ -679,7 +637,7 @@ def fly_held(seed, device=False):
             for o in (o64, o32):
                 o.params.mode &= ~O.M_AUTO_RESET
             if device:
-                _set_auto_reset(env, False)
+                H.set_auto_reset(env, False)
         ok = ~R.wide_envs(o32)
         for kernel in ("lookahead", "plan"):
             c_ = kw[kernel]

@@ -28,6 +28,7 @@ import collections
 import numpy as np
 
 import bars
+import fuzz_space
 import helpers as H
 import skip_ref
 import traffic_ref
@@ -43,14 +44,6 @@ Case = collections.namedtuple("Case", "N B auto_reset normalize dt keep_active s
 
 class IllegalScript(AssertionError):
     pass
-
-
-def ragged(N):
-    """two whole workgroups plus a part (tests/test_frame_skip.py::_cases, tests/test_traffic_obs.py::_ragged)"""
-    per = 256 // H.lane_width(N)
-    B = 2 * per + max(1, per // 3) if per > 1 else 2 * per + 1
-    assert (B * H.lane_width(N)) % 256 != 0
-    return B
 
 
 def setup(N):
@@ -78,10 +71,8 @@ def held_is_legal(prev_actions, la_touched, actions):
 
 
 def draw_actions(rng, B, N):
-    """a third of the components outside the action space (tests/test_frame_skip.py::_actions)"""
-    act = rng.uniform(-1.05, 1.05, (B, N, 3)).astype(np.float32)
-    far = rng.uniform(-4.0, 4.0, (B, N, 3)) * np.where(rng.uniform(size=(B, N, 3)) < 0.1, 50.0, 1.0)
-    return np.where(rng.uniform(size=(B, N, 3)) < 0.33, far, act).astype(np.float32)
+    """a third of the components outside the action space (tests/held_tools.py::skip_actions)"""
+    return fuzz_space.draw_actions(rng, (B, N), False, 0.33, True)
 
 
 class Session:

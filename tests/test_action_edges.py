@@ -133,7 +133,7 @@ def test_the_table_holds_what_it_names():
 
 @pytest.mark.parametrize("N", NS)
 def test_placement_delivers_every_pair_everywhere(N):
-    B = session_ref.ragged(N)
+    B = H.ragged(N)
     for discrete in (False, True):
         tab = AE.table(discrete)
         fam, in_free = AE.coverage(5, B, N, discrete, AE.n_values(discrete))
@@ -160,7 +160,7 @@ def test_placement_delivers_every_pair_everywhere(N):
 def _setup(N, discrete, full, device):
     from oracle import oracle as O
     scn, comp = session_ref.setup(N)
-    B = session_ref.ragged(N)
+    B = H.ragged(N)
     p = O.make_params(dt=1.0, discrete=discrete, auto_reset=True, random_entry=(N == 1), seed=9)
     orc = O.OracleEnv(comp, B, N, p, np.float32)
     env = None
@@ -310,8 +310,7 @@ def _look(N, discrete, full, device):
         assert ok0.all()
         if env is not None:
             from atc_hip import lib
-            from test_lookahead import _bytes_equal, _snapshot
-            snap = _snapshot(env)
+            snap = H.snapshot(env)
         for kernel, c in (("lookahead", LOOK), ("plan", PLAN)):
             M, K, Hn = c["M"], c["K"], c.get("H")
             pl = [AE.place(33, 11 * i + (0 if Hn is None else 5), B, N, discrete, wide_envs) for i in range(M * (Hn or 1))]
@@ -358,7 +357,7 @@ def _look(N, discrete, full, device):
                         rows = v.T[~ok] if k == "seg_reward" else v[~ok]
                         assert not np.ascontiguousarray(rows).view(np.uint8).any(), (k, tag)
                     assert (g["n_steps"][ok] > 0).all(), tag
-                _bytes_equal(env, snap)
+                H.bytes_equal(env, snap)
                 bars.check_state(env, orc)
                 _finite(env, orc, extra=[(k, v) for k, v in res.items()])
     finally:

@@ -18,13 +18,13 @@ import session_ref as S
 # limits in the twenties (22 or more: see session_ref.PREAMBLE) so that episodes end inside skips and rollouts; random entry where it does not put aircraft on top of each
 # other at once (few aircraft), the slot lattice otherwise; both auto_reset settings, normalised and raw, dt 1 and 0.3, keep_active once.
 FIXED = [
-    S.Case(1, S.ragged(1), True, True, 1.0, False, "random", 23, 3.0, 101),
-    S.Case(2, S.ragged(2), False, False, 1.0, False, "random", 23, 5.0, 102),
-    S.Case(3, S.ragged(3), True, True, 0.3, True, "random", 25, 5.0, 103),
-    S.Case(8, S.ragged(8), True, False, 1.0, False, "random", 22, 5.0, 104),
-    S.Case(16, S.ragged(16), False, True, 0.3, False, "lattice", 27, 13.0, 105),
-    S.Case(33, S.ragged(33), True, True, 1.0, False, "lattice", 24, 3.0, 106),
-    S.Case(64, S.ragged(64), True, False, 1.0, False, "lattice", 26, 3.0, 107),
+    S.Case(1, H.ragged(1), True, True, 1.0, False, "random", 23, 3.0, 101),
+    S.Case(2, H.ragged(2), False, False, 1.0, False, "random", 23, 5.0, 102),
+    S.Case(3, H.ragged(3), True, True, 0.3, True, "random", 25, 5.0, 103),
+    S.Case(8, H.ragged(8), True, False, 1.0, False, "random", 22, 5.0, 104),
+    S.Case(16, H.ragged(16), False, True, 0.3, False, "lattice", 27, 13.0, 105),
+    S.Case(33, H.ragged(33), True, True, 1.0, False, "lattice", 24, 3.0, 106),
+    S.Case(64, H.ragged(64), True, False, 1.0, False, "lattice", 26, 3.0, 107),
 ]
 
 
@@ -34,7 +34,7 @@ def _drawn():
     out = []
     for i in range(n):
         N = int(rng.choice([1, 2, 3, 5, 8, 13, 16, 17, 33, 40, 64]))
-        out.append(S.Case(N, S.ragged(N), bool(rng.integers(0, 2)), bool(rng.integers(0, 2)), float(rng.choice([1.0, 0.3])),
+        out.append(S.Case(N, H.ragged(N), bool(rng.integers(0, 2)), bool(rng.integers(0, 2)), float(rng.choice([1.0, 0.3])),
                           bool(rng.uniform() < 0.2), "random" if N <= 8 else "lattice", int(rng.integers(22, 30)),
                           float(rng.choice([3.0, 5.0, 13.0])), seed * 1000 + i))
     return out

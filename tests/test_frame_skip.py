@@ -21,6 +21,7 @@ import numpy as np
 import pytest
 
 import bars
+import held_tools as T
 import helpers as H
 import skip_ref as R
 from atc_hip import layout as L
@@ -40,10 +41,7 @@ def _cases():
     so every width has a case with and one without them —, auto-reset on; auto-reset off on a few shapes, both ways."""
     out = []
     for N in (1, 2, 3, 8, 16, 32, 33, 64):
-        per = 256 // H.lane_width(N)
-        ragged = 2 * per + max(1, per // 3) if per > 1 else 2 * per + 1
-        assert (ragged * H.lane_width(N)) % 256 != 0
-        out += [(N, ragged, True, True), (N, 2 * per, True, False)]
+        out += [(N, H.ragged(N), True, True), (N, 2 * (256 // H.lane_width(N)), True, False)]
     out += [(1, 600, False, False), (3, 150, False, True), (16, 37, False, True), (16, 32, False, False), (33, 9, False, False),
             (64, 8, False, True)]
     return out
@@ -70,34 +68,6 @@ IDS = ["N%d B%d %s %s" % (N, B, "reset" if ar else "noreset", "full" if full els
 
 def _seed(N, B, auto_reset, full):
     return 9000 + 13 * CASES.index((N, B, auto_reset, full))
-
-
-def _setup(N):
-    from envs.atc import scenarios
-    scn = scenarios.LOWW(random_entrypoints=True) if N == 1 else scenarios.LOWWDense()
-    key = ("skip", N == 1)
-    if key not in H._compiled:
-        H._compiled[key] = scenarios.compile_scenario(scn, grid_cell=0.5)
-    return scn, H._compiled[key]
-
-
-def _plan(N):
-    """Spawn, separation minimum and time limit as tests/test_kernel_matrix.py::_plan chooses them (aircraft meet in flight, episodes
-    last a few steps), so that blocks of 5 and 20 steps contain episode ends and blocks of 1 .. 3 mostly do not."""
-    return dict(spawn="random", sep_nm=5.0, timestep_limit=7) if N <= 8 else dict(spawn="lattice", sep_nm=13.0, timestep_limit=12)
-
-
-def _actions(rng, B, N):
-    """fresh actions, a third of the components outside the action space (the draws of test_hip_parity._run_vs_oracle, wild = 0.33)"""
-    act = rng.uniform(-1.05, 1.05, (B, N, 3)).astype(np.float32)
-    far = rng.uniform(-4.0, 4.0, (B, N, 3)) * np.where(rng.uniform(size=(B, N, 3)) < 0.1, 50.0, 1.0)
-    return np.where(rng.uniform(size=(B, N, 3)) < 0.33, far, act).astype(np.float32)
-
-
-def _oracle(comp, B, N, auto_reset, seed, **kw):
-    from oracle import oracle as O
-    return O.OracleEnv(comp, B, N, O.make_params(auto_reset=auto_reset, random_entry=kw["spawn"] == "random", seed=seed,
-                                                 timestep_limit=kw["timestep_limit"], sep_nm=kw["sep_nm"]), np.float32)
 
 
 class Events:
@@ -132,17 +102,17 @@ def test_helper_equals_the_literal_loop():
     loop, against the batched helper on every output and every state array, over chained calls; K = 1 is OracleEnv.step."""
     from oracle import oracle as O
     N, B = 3, 12
-    scn, comp = _setup(N)
+    scn, comp = T.skip_setup(N)
     kw = dict(spawn="lattice", sep_nm=13.0, timestep_limit=6)
     for auto_reset in (True, False):
-        batch = _oracle(comp, B, N, auto_reset, 5, **kw)
-        ones = [_oracle(comp, 1, N, auto_reset, 5, **kw) for _ in range(B)]
+        batch = T.skip_oracle(comp, B, N, auto_reset, 5, **kw)
+        ones = [T.skip_oracle(comp, 1, N, auto_reset, 5, **kw) for _ in range(B)]
         rng = np.random.default_rng(17)
         ev = Events()
         for K in (3, 1, 8, 2, 20, 5, 1, 4):
-            a = _actions(rng, B, N)
+            a = T.skip_actions(rng, B, N)
             if K == 1:
-                plain = _oracle(comp, B, N, auto_reset, 5, **kw)
+                plain = T.skip_oracle(comp, B, N, auto_reset, 5, **kw)
                 for k in R.STATE:
                     getattr(plain, k)[...] = getattr(batch, k)
                 plain.step(a)
@@ -169,50 +139,50 @@ def test_case_events_on_the_oracle(N, B, auto_reset, full):
     """A condition on the INPUTS of the GPU cases, checked on the oracle alone: within the run an env stops with n < K, one runs all K
     steps without done, one is done exactly on step K, an auto-reset env then waits for at least a step, a target is refused and
     (N >= 2) a separation is lost — the GPU run cannot pass by flying nothing."""
-    scn, comp = _setup(N)
-    kw = _plan(N)
+    scn, comp = T.skip_setup(N)
+    kw = T.skip_plan(N)
     seed = _seed(N, B, auto_reset, full)
-    orc = _oracle(comp, B, N, auto_reset, seed, **kw)
+    orc = T.skip_oracle(comp, B, N, auto_reset, seed, **kw)
     rng = np.random.default_rng(seed)
     ev = Events()
     for K in K_SCHEDULE:
-        ev.add(R.skip_reference(orc, _actions(rng, B, N), K), K)
+        ev.add(R.skip_reference(orc, T.skip_actions(rng, B, N), K), K)
     ev.check(N, auto_reset)
 
 
 @pytest.mark.parametrize("N,B,auto_reset,full", TWIN_CASES, ids=TWIN_IDS)
 def test_twin_case_events_on_the_oracle(N, B, auto_reset, full):
     """The same condition on the inputs of the bit-for-bit cases (their shapes, their seed 77 + N)."""
-    scn, comp = _setup(N)
-    orc = _oracle(comp, B, N, auto_reset, 77 + N, **_plan(N))
+    scn, comp = T.skip_setup(N)
+    orc = T.skip_oracle(comp, B, N, auto_reset, 77 + N, **T.skip_plan(N))
     rng = np.random.default_rng(77 + N)
     ev = Events()
     for K in K_SCHEDULE:
-        ev.add(R.skip_reference(orc, _actions(rng, B, N), K), K)
+        ev.add(R.skip_reference(orc, T.skip_actions(rng, B, N), K), K)
     ev.check(N, auto_reset)
 
 
 @pytest.mark.parametrize("W", WIDTHS)
 def test_k1_case_events_on_the_oracle(W):
     """... and of the K = 1 cases: episodes end and restart, others go on, a target is refused, a separation is lost."""
-    scn, comp = _setup(W)
-    orc = _oracle(comp, _k1_batch(W), W, True, K1_SEED, **_plan(W))
+    scn, comp = T.skip_setup(W)
+    orc = T.skip_oracle(comp, _k1_batch(W), W, True, K1_SEED, **T.skip_plan(W))
     rng = np.random.default_rng(W)
     ev = Events()
     for t in range(K1_STEPS):
-        ev.add(R.skip_reference(orc, _actions(rng, _k1_batch(W), W), 1), 1)
+        ev.add(R.skip_reference(orc, T.skip_actions(rng, _k1_batch(W), W), 1), 1)
     ev.check(W, True, k_is_one=True)
 
 
 def test_full_size_case_events_on_the_oracle():
     """... and of the full-size case, on the envs it compares with the oracle (envs are independent: the first 256 of 65 536)."""
     f = FULL_SIZE
-    scn, comp = _setup(f["N"])
-    orc = _oracle(comp, f["oracle_envs"], f["N"], True, f["seed"], **FULL_SIZE_PLAN)
+    scn, comp = T.skip_setup(f["N"])
+    orc = T.skip_oracle(comp, f["oracle_envs"], f["N"], True, f["seed"], **FULL_SIZE_PLAN)
     rng = np.random.default_rng(f["seed"])
     ev = Events()
     for c in range(f["calls"]):
-        ev.add(R.skip_reference(orc, _actions(rng, f["B"], f["N"])[:f["oracle_envs"]], f["K"]), f["K"])
+        ev.add(R.skip_reference(orc, T.skip_actions(rng, f["B"], f["N"])[:f["oracle_envs"]], f["K"]), f["K"])
     ev.check(f["N"], True)
 
 
@@ -260,12 +230,6 @@ def test_stale_library_is_a_rebuild_error(tmp_path):
 
 
 # ---------------------------------------------------------------------------------------------------------------- GPU
-def _env(scn, B, N, auto_reset, seed, full, **kw):
-    from atc_hip.vec_env import AtcVecEnv
-    return AtcVecEnv(B, N, scenario=scn, auto_reset=auto_reset, spawn=kw["spawn"], seed=seed, grid_cell=0.5, want_raw_obs=full,
-                     want_ac_reward=full, want_min_sep=full, want_term_obs=full, timestep_limit=kw["timestep_limit"], sep_nm=kw["sep_nm"])
-
-
 def _compare_outputs(env, ret, ref, comp, full, rows=slice(None), tag=None):
     """the bars of this file's docstring, kept in tests/bars.py (the call-sequence tests apply them too)"""
     B, N = ref["obs"].shape[0], env.N
@@ -287,16 +251,16 @@ _compare_state = bars.check_state
 @pytest.mark.parametrize("N,B,auto_reset,full", CASES, ids=IDS)
 def test_step_skip_matches_oracle(N, B, auto_reset, full):
     from atc_hip import lib
-    scn, comp = _setup(N)
-    kw = _plan(N)
+    scn, comp = T.skip_setup(N)
+    kw = T.skip_plan(N)
     seed = _seed(N, B, auto_reset, full)
-    env = _env(scn, B, N, auto_reset, seed, full, **kw)
-    orc = _oracle(comp, B, N, auto_reset, seed, **kw)
+    env = T.skip_env(scn, B, N, auto_reset, seed, full, **kw)
+    orc = T.skip_oracle(comp, B, N, auto_reset, seed, **kw)
     rng = np.random.default_rng(seed)
     ev = Events()
     skip0, step0 = lib.skip_launch_counts(), lib.launch_counts()
     for c, K in enumerate(K_SCHEDULE):
-        a = _actions(rng, B, N)
+        a = T.skip_actions(rng, B, N)
         ref = R.skip_reference(orc, a, K)
         ev.add(ref, K)
         _compare_outputs(env, env.step_skip(a, K), ref, comp, full, tag=(c, K))
@@ -366,15 +330,15 @@ def _host_loop_skip(twin, a, K):
 def test_step_skip_equals_host_loop_of_steps_bit_for_bit(N, B, auto_reset, full):
     """Pins the summation order and "a stopped env is not touched again": torch.equal on every output and state tensor."""
     import torch
-    scn, comp = _setup(N)
-    kw = _plan(N)
+    scn, comp = T.skip_setup(N)
+    kw = T.skip_plan(N)
     seed = 77 + N
-    env = _env(scn, B, N, auto_reset, seed, full, **kw)
-    twin = _env(scn, B, N, auto_reset, seed, full, **kw)
+    env = T.skip_env(scn, B, N, auto_reset, seed, full, **kw)
+    twin = T.skip_env(scn, B, N, auto_reset, seed, full, **kw)
     rng = np.random.default_rng(seed)
     early = 0
     for c, K in enumerate(K_SCHEDULE):
-        a = torch.as_tensor(_actions(rng, B, N), device=env.device)
+        a = torch.as_tensor(T.skip_actions(rng, B, N), device=env.device)
         ref = _host_loop_skip(twin, a, K)
         obs, rew, done, info = env.step_skip(a, K)
         got = {"obs": obs, "reward": rew, "done": done, "flags": info["flags"], "n_steps": info["frame_steps"],
@@ -396,15 +360,15 @@ def test_step_skip_equals_host_loop_of_steps_bit_for_bit(N, B, auto_reset, full)
 def test_k1_is_step_bit_for_bit(W):
     import torch
     N = W
-    scn, comp = _setup(N)
-    kw = _plan(N)
+    scn, comp = T.skip_setup(N)
+    kw = T.skip_plan(N)
     B = _k1_batch(W)
     for full in (True, False):
-        env = _env(scn, B, N, True, K1_SEED, full, **kw)
-        twin = _env(scn, B, N, True, K1_SEED, full, **kw)
+        env = T.skip_env(scn, B, N, True, K1_SEED, full, **kw)
+        twin = T.skip_env(scn, B, N, True, K1_SEED, full, **kw)
         rng = np.random.default_rng(W)
         for t in range(K1_STEPS):
-            a = torch.as_tensor(_actions(rng, B, N), device=env.device)
+            a = torch.as_tensor(T.skip_actions(rng, B, N), device=env.device)
             o1, r1, d1, i1 = env.step_skip(a, 1)
             o2, r2, d2, i2 = twin.step(a)
             assert torch.equal(o1, o2) and torch.equal(r1, r2) and torch.equal(d1, d2) and torch.equal(i1["flags"], i2["flags"]), t
@@ -426,14 +390,14 @@ def test_full_size_batch():
     import torch
     from envs.atc import scenarios
     B, N, K = FULL_SIZE["B"], FULL_SIZE["N"], FULL_SIZE["K"]
-    scn, comp = _setup(N)
+    scn, comp = T.skip_setup(N)
     kw = FULL_SIZE_PLAN
-    env = _env(scn, B, N, True, 3, False, **kw)
-    orc = _oracle(comp, 256, N, True, 3, **kw)
+    env = T.skip_env(scn, B, N, True, 3, False, **kw)
+    orc = T.skip_oracle(comp, 256, N, True, 3, **kw)
     rng = np.random.default_rng(3)
     term = L.F_BELOW_MVA | L.F_OUTSIDE | L.F_CONFLICT | L.F_TIMEOUT | L.F_WON
     for c in range(4):
-        a = _actions(rng, B, N)
+        a = T.skip_actions(rng, B, N)
         t_before = env.timesteps.clone()
         ref = R.skip_reference(orc, a[:256], K)
         ret = env.step_skip(torch.as_tensor(a, device=env.device), K)

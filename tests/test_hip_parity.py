@@ -5,8 +5,8 @@ Run on the MI355X box with `pytest -m gpu`."""
 import numpy as np
 import pytest
 
-import bars
 import helpers as H
+from fuzz_space import run_vs_oracle
 
 pytestmark = pytest.mark.gpu
 
@@ -666,107 +666,15 @@ def test_atcgym_keeps_flying_after_a_win():
 
 
 # ------------------------------------------------------------------------------------------------ batched vs fp32 oracle
-def _run_vs_oracle(scen_obj, comp, B, N, steps, seed, dt=1.0, discrete=False, spawn="lattice", hold=20, grid_cell=0.5,
-                   use_rollout=0, timestep_limit=6000, full=True, shaping=True, normalize=True, sep_nm=3.0,
-                   keep_active=False, held_hint=False, rollout_hold=1, wild=0.0, auto_reset=True):
-    """full=False drives the fast kernel variant (obs / reward / done / flags only), full=True the one with every optional
-    output; everything the variant produces is compared with the fp32 oracle.  held_hint: single steps that repeat the
-    previous step's action array are launched with ATC_M_ACTIONS_HELD (must change nothing).
-    rollout_hold > 1 (with use_rollout): the multi-step launches go through atc_rollout_hold — one action block per
-    `rollout_hold` steps (frame skip, learning/atc-gym-demo.py:18-19), whose repeated steps skip the last-action bookkeeping
-    inside the kernel; the oracle is stepped once per step with the block's actions.
-    wild > 0: that fraction of the drawn action COMPONENTS lies outside the action space — U(-4, 4) (a tenth of those a further
-    factor 50 out): the reference enforces no Box (atc_gym.py:128-141); speed / altitude targets beyond their limits are refused,
-    heading targets are never validated and headings leave the state format's 32-bit range (include/atc_step.h, ABI 19).
-    auto_reset=False: no env is ever reset — the reference's FPS protocol; held long enough, aircraft fly off the position grid."""
-    torch = _torch()
-    from atc_hip.vec_env import AtcVecEnv
-    from envs.atc import model
-    from oracle import oracle as O
-    sp = model.SimParameters(dt, discrete_action_space=discrete, reward_shaping=shaping, normalize_state=normalize)
-    env = AtcVecEnv(B, N, sim_parameters=sp, scenario=scen_obj, auto_reset=auto_reset, spawn=spawn, seed=seed,
-                    grid_cell=grid_cell, want_raw_obs=full, want_ac_reward=full, want_min_sep=full, want_term_obs=full,
-                    timestep_limit=timestep_limit, sep_nm=sep_nm, keep_active=keep_active)
-    p = O.make_params(dt=dt, discrete=discrete, auto_reset=auto_reset, random_entry=(spawn == "random"), seed=seed,
-                      timestep_limit=timestep_limit, shaping=shaping, normalize=normalize, sep_nm=sep_nm,
-                      keep_active=keep_active)
-    orc = O.OracleEnv(comp, B, N, p, np.float32)
-    o0 = env.obs.cpu().numpy().reshape(B, N, 10)
-    assert np.all(np.abs(o0 - orc.obs) <= 1e-5 * np.maximum(1.0, np.abs(orc.obs)))
-    rng = np.random.default_rng(seed)
-    half_range = 0.5 * comp.norm_max.astype(np.float64)
-    n_done = 0
-    seen = 0
-    act = None
-    if use_rollout:
-        assert steps % use_rollout == 0
-    if rollout_hold > 1:
-        assert use_rollout and use_rollout % rollout_hold == 0 and hold % rollout_hold == 0
-    t = 0
-    while t < steps:
-        chunk = use_rollout or 1
-        acts = []
-        repeated = act is not None and t % hold != 0
-        for c in range(chunk):
-            if (t + c) % hold == 0 or act is None:
-                if discrete:
-                    act = np.floor(rng.uniform(0, 1, (B, N, 3)) * np.array([20, 380, 360])).astype(np.float32)
-                else:
-                    act = rng.uniform(-1.05, 1.05, (B, N, 3)).astype(np.float32)
-                if wild > 0.0:   # (drawn after the regular actions: a case without wild draws keeps its stream)
-                    out_of_space = rng.uniform(-4.0, 4.0, (B, N, 3)) * np.where(rng.uniform(size=(B, N, 3)) < 0.1, 50.0, 1.0)
-                    if discrete:
-                        out_of_space = np.floor(out_of_space * np.array([20, 380, 360]))
-                    act = np.where(rng.uniform(size=(B, N, 3)) < wild, out_of_space, act).astype(np.float32)
-            acts.append(act)
-        if use_rollout:
-            step = 1
-            if rollout_hold > 1:
-                assert all(acts[c] is acts[c - c % rollout_hold] for c in range(chunk))   # blocks are constant by construction
-                step = rollout_hold
-            # full=True: the launch gets [T, ...] buffers for every optional output — without them AtcVecEnv.rollout asks for the
-            # required four only and the library launches a fast form whatever the env was built with.  (Zeroed: term_obs is written
-            # for envs that were auto-reset only, and the oracle's stays zero elsewhere — so must the launch's.)
-            bufs = None if not full else {k: torch.zeros((chunk,) + shape, dtype=dt, device=env.device) for k, shape, dt in (
-                ("obs", (B, N * 10), torch.float32), ("reward", (B,), torch.float32), ("done", (B,), torch.uint8),
-                ("flags", (B, N), torch.int16), ("raw_obs", (B, N * 10), torch.float32), ("ac_reward", (B, N), torch.float32),
-                ("min_sep", (B,), torch.float32), ("term_obs", (B, N * 10), torch.float32))}
-            out = env.rollout(torch.as_tensor(np.stack(acts[::step])), out=bufs, hold=step)
-            res = [(out["obs"][c], out["reward"][c], out["done"][c], out["flags"][c]) for c in range(chunk)]
-        else:
-            o, r, d, info = env.step(acts[0], held=held_hint and repeated)
-            res = [(o, r, d, info["flags"])]
-        for c in range(chunk):
-            orc.step(acts[c])
-            o, r, d, fl = res[c]
-            got = {"flags": fl.cpu().numpy(), "done": d.cpu().numpy(), "obs": o.cpu().numpy().reshape(B, N, 10), "reward": r.cpu().numpy()}
-            if full:
-                # optional outputs (of the single step, or row c of the multi-step launch's buffers)
-                if use_rollout:
-                    raw, acr, msep, tob = (out[k][c].cpu().numpy() for k in ("raw_obs", "ac_reward", "min_sep", "term_obs"))
-                else:
-                    raw, acr, msep, tob = (info[k].cpu().numpy() for k in ("original_state", "aircraft_reward", "min_separation",
-                                                                           "terminal_observation"))
-                got.update(raw_obs=raw.reshape(B, N, 10), ac_reward=acr, min_sep=msep, term_obs=tob.reshape(B, N, 10))
-            bars.check_step(got, orc, normalize, half_range, t + c)   # flags / done exact, obs / rewards 1e-5, optional outputs: tests/bars.py
-            n_done += int(orc.done.sum())
-            seen |= int(np.bitwise_or.reduce(orc.flags.ravel()))
-        t += chunk
-    # persistent state after the run: integer state exact, float state within tolerance (tests/bars.py)
-    bars.check_state(env, orc, total_reward=False)
-    env.close()
-    return n_done, seen
-
-
 def test_batched_n1_vs_oracle():
     from envs.atc import scenarios
-    n_done, seen = _run_vs_oracle(scenarios.LOWW(), H.compiled("LOWW", 0.5), B=2048, N=1, steps=600, seed=5)
+    n_done, seen = run_vs_oracle(scenarios.LOWW(), H.compiled("LOWW", 0.5), B=2048, N=1, steps=600, seed=5)
     assert n_done > 100 and (seen & H.F_OUTSIDE) and (seen & (H.F_INVALID_V | H.F_INVALID_H))
 
 
 def test_batched_n1_random_entries_discrete_vs_oracle():
     from envs.atc import scenarios
-    n_done, seen = _run_vs_oracle(scenarios.LOWW(random_entrypoints=True), H.compiled("LOWW_random", 0.5), B=1024, N=1,
+    n_done, seen = run_vs_oracle(scenarios.LOWW(random_entrypoints=True), H.compiled("LOWW_random", 0.5), B=1024, N=1,
                                   steps=400, seed=9, discrete=True, spawn="random", dt=2.0)
     assert n_done > 20
 
@@ -774,14 +682,14 @@ def test_batched_n1_random_entries_discrete_vs_oracle():
 def test_batched_n16_vs_oracle():
     from envs.atc import scenarios
     scn = scenarios.LOWW(random_entrypoints=True)
-    n_done, seen = _run_vs_oracle(scn, scenarios.compile_scenario(scn, grid_cell=0.5), B=512, N=16, steps=400, seed=21, held_hint=True)
+    n_done, seen = run_vs_oracle(scn, scenarios.compile_scenario(scn, grid_cell=0.5), B=512, N=16, steps=400, seed=21, held_hint=True)
     assert n_done > 50 and (seen & H.F_CONFLICT)
 
 
 def test_batched_n64_noise_vs_oracle():
     from envs.atc import scenarios
     scn = scenarios.LOWWDense()
-    n_done, seen = _run_vs_oracle(scn, scenarios.compile_scenario(scn, grid_cell=0.5), B=128, N=64, steps=240, seed=33)
+    n_done, seen = run_vs_oracle(scn, scenarios.compile_scenario(scn, grid_cell=0.5), B=128, N=64, steps=240, seed=33)
     assert n_done > 20 and (seen & H.F_CONFLICT)
 
 
@@ -790,7 +698,7 @@ def test_batched_odd_n_and_short_timeout_vs_oracle():
     resets happen often, no lookup grid."""
     from envs.atc import scenarios
     scn = scenarios.LOWW(random_entrypoints=True)
-    n_done, seen = _run_vs_oracle(scn, scenarios.compile_scenario(scn), B=300, N=5, steps=200, seed=4, grid_cell=None,
+    n_done, seen = run_vs_oracle(scn, scenarios.compile_scenario(scn), B=300, N=5, steps=200, seed=4, grid_cell=None,
                                   timestep_limit=37)
     assert seen & H.F_TIMEOUT
 
@@ -798,8 +706,8 @@ def test_batched_odd_n_and_short_timeout_vs_oracle():
 def test_rollout_equals_single_steps_vs_oracle():
     from envs.atc import scenarios
     scn = scenarios.LOWW(random_entrypoints=True)
-    _run_vs_oracle(scn, scenarios.compile_scenario(scn, grid_cell=0.5), B=256, N=16, steps=120, seed=8, use_rollout=24)
-    _run_vs_oracle(scenarios.LOWW(), H.compiled("LOWW", 0.5), B=1000, N=1, steps=250, seed=2, use_rollout=50)
+    run_vs_oracle(scn, scenarios.compile_scenario(scn, grid_cell=0.5), B=256, N=16, steps=120, seed=8, use_rollout=24)
+    run_vs_oracle(scenarios.LOWW(), H.compiled("LOWW", 0.5), B=1000, N=1, steps=250, seed=2, use_rollout=50)
 
 
 @pytest.mark.parametrize("N,B,T,rh,hold,full", [(16, 256, 20, 20, 20, False), (16, 256, 40, 20, 20, True), (16, 300, 20, 4, 20, False),
@@ -811,7 +719,7 @@ def test_rollout_hold_matches_oracle(N, B, T, rh, hold, full):
     state incl. actions_taken and the last-action records bit-identical."""
     from envs.atc import scenarios
     scn = scenarios.LOWWDense() if N > 16 else scenarios.LOWW(random_entrypoints=True)
-    n_done, seen = _run_vs_oracle(scn, scenarios.compile_scenario(scn, grid_cell=0.5), B=B, N=N, steps=12 * T, seed=100 + N + T,
+    n_done, seen = run_vs_oracle(scn, scenarios.compile_scenario(scn, grid_cell=0.5), B=B, N=N, steps=12 * T, seed=100 + N + T,
                                   use_rollout=T, rollout_hold=rh, hold=hold, full=full, spawn="lattice")
     assert n_done > 0
 
@@ -833,7 +741,7 @@ def test_actions_outside_the_action_space_vs_oracle(N, B, kw):
     if kw.get("use_rollout"):
         kw["steps"] = (kw["steps"] // kw["use_rollout"]) * kw["use_rollout"]
         kw.setdefault("hold", max(kw.get("rollout_hold", 1), 20 if kw.get("rollout_hold", 1) in (1, 20) else 8))
-    n_done, seen = _run_vs_oracle(scn, scenarios.compile_scenario(scn, grid_cell=0.5), B=B, N=N, **kw)
+    n_done, seen = run_vs_oracle(scn, scenarios.compile_scenario(scn, grid_cell=0.5), B=B, N=N, **kw)
     assert n_done > 0 and (seen & H.F_INVALID_V) and (seen & H.F_INVALID_H)
 
 
@@ -1164,7 +1072,7 @@ def test_full_size_rollout_hold(B, N):
             on = sm[j]["obs"][t].cpu().numpy().reshape(small, N, 10)
             assert np.all(np.abs(on - orc.obs) <= 1e-5 * np.maximum(1.0, np.abs(orc.obs))), (j, t)
             rw = sm[j]["reward"][t].cpu().numpy()
-            # (the fp32 sum of N per-aircraft terms adds at most N/2 ulps of the running sum: the bound of _run_vs_oracle)
+            # (the fp32 sum of N per-aircraft terms adds at most N/2 ulps of the running sum: the bound of bars.check_step)
             rtol = 1e-5 * np.maximum(1.0, np.abs(orc.reward)) + 6e-8 * N * np.abs(orc.ac_reward).sum(1)
             assert np.all(np.abs(rw - orc.reward) <= rtol), (j, t)
             n_done += int(orc.done.sum())

@@ -7,7 +7,7 @@ LDS table.  Each row of MATRIX names one instantiation the way the library's lau
 
   * is shaped to reach that instantiation — sizes that depend on the device come from its multi_processor_count —, and asserts
     from the launch record that every step launch of the case went there and nowhere else;
-  * runs against the fp32 oracle through test_hip_parity._run_vs_oracle at its bars: flags / done / counters and the integer
+  * runs against the fp32 oracle through fuzz_space.run_vs_oracle at its bars: flags / done / counters and the integer
     aircraft state exact, obs / reward within 1e-5, every optional output for the full forms — on EVERY env of the batch, the
     131 072-slot batches of the lat and allv-multi rows included (the oracle steps those in about 0.1 s);
   * is not a trivial flight: a third of the action components outside the action space, a time limit of a few steps, spawn
@@ -28,6 +28,7 @@ import pytest
 
 import helpers as H
 from atc_hip import layout as L
+from fuzz_space import draw_actions, run_vs_oracle
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB = os.path.join(ROOT, "atc-reinforcement-learning_amd", "atc_hip", "libatcstep.so")
@@ -52,8 +53,7 @@ def _cases():
     out = []
     for W in WIDTHS:
         per = 256 // W                                 # envs per workgroup
-        ragged = 2 * per + max(1, per // 3) if per > 1 else 2 * per + 1     # two workgroups and a partly filled third
-        assert (ragged * W) % 256 != 0
+        ragged = H.ragged(W)                           # two workgroups and a partly filled third
         shapes = ([("n<w", N_BELOW[W])] if W in N_BELOW else []) + [("n=w", W)]
         for form, (full, one, allv, lat, ldsg) in FORMS.items():
             if ldsg:
@@ -157,10 +157,8 @@ def test_case_events_on_the_oracle(row, label, N):
     rng = np.random.default_rng(seed)
     n_done = seen = 0
     for t in range(kw["steps"]):
-        if t % kw["hold"] == 0:     # the draws of _run_vs_oracle, in its order
-            act = rng.uniform(-1.05, 1.05, (B, N, 3)).astype(np.float32)
-            far = rng.uniform(-4.0, 4.0, (B, N, 3)) * np.where(rng.uniform(size=(B, N, 3)) < 0.1, 50.0, 1.0)
-            act = np.where(rng.uniform(size=(B, N, 3)) < kw["wild"], far, act).astype(np.float32)
+        if t % kw["hold"] == 0:     # the draws of run_vs_oracle
+            act = draw_actions(rng, (B, N), False, kw["wild"], True)
         orc.step(act)
         n_done += int(orc.done.sum())
         seen |= int(np.bitwise_or.reduce(orc.flags.ravel()))
@@ -171,7 +169,6 @@ def test_case_events_on_the_oracle(row, label, N):
 @pytest.mark.parametrize("row,label,N,batch,full,multi", CASES, ids=["%s %s" % c[:2] for c in CASES])
 def test_instantiation_matches_oracle(row, label, N, batch, full, multi):
     import torch
-    from test_hip_parity import _run_vs_oracle
     if _t0[0] is None:
         _t0[0] = time.time()
     n_cu = torch.cuda.get_device_properties(0).multi_processor_count
@@ -179,7 +176,7 @@ def test_instantiation_matches_oracle(row, label, N, batch, full, multi):
     scn, comp = _setup(N)
     kw = _plan(N, B, multi)
     with H.launches() as got:
-        n_done, seen = _run_vs_oracle(scn, comp, B=B, N=N, seed=_seed(row, label), full=full, **kw)
+        n_done, seen = run_vs_oracle(scn, comp, B=B, N=N, seed=_seed(row, label), full=full, **kw)
     print("matrix case", row, label, "B", B, "N", N, "launched", got, "episodes ended", n_done, "flags seen", hex(seen))
     for name, n in got.items():
         _ran[name] = _ran.get(name, 0) + n

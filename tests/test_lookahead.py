@@ -13,7 +13,6 @@ Inputs are valid only if the REFERENCE results show, where the case can have the
 (M > 1, K >= 4), a look-ahead reset (auto-reset), a conflict flag and a handed-over aircraft (N > 1).  _check_events asserts it."""
 import ctypes as C
 import inspect
-import os
 import re
 import shutil
 import subprocess
@@ -22,14 +21,12 @@ import numpy as np
 import pytest
 
 import bars
+import held_tools as T
 import helpers as H
 import skip_ref as R
 from atc_hip import layout as L
+from held_tools import HEADER, LIB
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "atc_step.h")
-LIB = os.path.join(ROOT, "atc-reinforcement-learning_amd", "atc_hip", "libatcstep.so")
-STATE = ("ac", "alt", "last_act", "env", "stats", "phi_wide")
 OPTIONAL = ("flags", "min_sep", "ac_reward", "obs")
 ALL = OPTIONAL
 
@@ -88,97 +85,12 @@ def test_python_surface():
 
 
 # ---------------------------------------------------------------------------------------------------------------- GPU
-def _ragged(N):
-    W = H.lane_width(N)
-    return 256 // W + 3    # B * W = 256 + 3 W: two workgroups, the last one partial
-
-
-def _scenario():
-    from envs.atc import scenarios
-    return scenarios.LOWWDense()
-
-
-def _env(N, B, spawn="lattice", normalize=True, seed=11, timestep_limit=60, auto_reset=True, scn=None):
-    """The env of a case, always made with auto-reset ON (the flown state family needs it); _set_auto_reset switches it off after."""
-    from atc_hip.vec_env import AtcVecEnv
-    from envs.atc import model
-    return AtcVecEnv(B, N, sim_parameters=model.SimParameters(1, normalize_state=normalize), scenario=scn or _scenario(), auto_reset=auto_reset,
-                     spawn=spawn, seed=seed, grid_cell=0.5, want_ac_reward=True, want_min_sep=True, timestep_limit=timestep_limit,
-                     sep_nm=5.0 if N <= 8 else 13.0 if N <= 16 else 3.0)
-
-
-def _set_auto_reset(env, on):
-    env.params.mode = (env.params.mode | L.M_AUTO_RESET) if on else (env.params.mode & ~L.M_AUTO_RESET)
-    env.refresh_params()
-
-
-def _draw(rng, *shape):
-    """actions inside the action space, a tenth of the speed / altitude components outside it (refused targets); headings inside"""
-    a = rng.uniform(-1.0, 1.0, shape + (3,)).astype(np.float32)
-    wild = rng.uniform(size=shape + (3,)) < 0.1
-    wild[..., 2] = False
-    return np.where(wild, rng.uniform(-3.0, 3.0, shape + (3,)), a).astype(np.float32)
-
-
-def _fly(env, rng, steps=200, hold=10):
-    """State family: `steps` random steps after reset (one launch), then three placed situations so that every case has its events:
-    env 0 — aircraft 0, alone under control, a step above its MVA floor (candidates that descend end the episode within a few steps,
-    the others do not);
-    env 1 (N > 1) — aircraft 0 and 1 half a mile apart (a conflict in step one); env 2 (N > 1) — aircraft 0 handed over."""
-    import torch
-    a = torch.as_tensor(_draw(rng, steps // hold, env.B, env.N), device=env.device)
-    env.rollout(a, hold=hold)
-    x, y, _, phi, v = H.FAR_A
-    floor = float(env.sector.query_mva([x], [y])[0])
-    assert floor > 0
-    env.set_state(0, 0, x, y, floor + 100.0, phi, v)
-    env.set_last_action(0, 0, [v, floor + 100.0, phi])
-    env.env[0, L.ENV_TIMESTEPS] = 5
-    env.env[0, L.ENV_MASK_LO] = 1          # ... and its other aircraft handed over: nothing else ends env 0's episode
-    env.stats[0, L.STAT_MASK_HI] = 0
-    if env.N > 1:
-        env.set_state(1, 0, x, y, 15000.0, phi, v)
-        env.set_state(1, 1, x + 0.5, y, 15000.0, phi, v)
-        env.env[1, L.ENV_MASK_LO] |= 3
-        env.env[2, L.ENV_MASK_LO] &= ~1
-    env.synchronize()
-
-
-def _snapshot(env):
-    return {k: getattr(env, k).clone() for k in STATE}
-
-
-def _restore(env, snap):
-    for k, v in snap.items():
-        getattr(env, k).copy_(v)
-
-
-def _bytes_equal(env, snap, rows=None):
-    import torch
-    for k, v in snap.items():
-        a, b = getattr(env, k).contiguous().view(torch.uint8), v.contiguous().view(torch.uint8)
-        assert torch.equal(a, b), "state array %s changed" % k
-
-
 def _reference(env, actions, K):
-    """The definition on the product itself: per candidate, atc_step_skip on a private copy of the state (the env's own tensors, put
-    back afterwards).  Returns [M, ...] CPU tensors."""
+    """held_tools.chained_skip_reference at H = 1, without its per-segment keys; n_steps as atc_lookahead's uint8 (assert_equal reinterprets
+    the reference by the result's dtype)"""
     import torch
-    snap = _snapshot(env)
-    keep = {k: getattr(env, k).clone() for k in ("obs", "reward", "done", "flags", "ac_reward", "min_sep")}
-    fs = env.frame_steps.clone() if env.frame_steps is not None else None
-    rows = {k: [] for k in ("reward", "done", "n_steps", "flags", "ac_reward", "min_sep", "obs")}
-    for m in range(actions.shape[0]):
-        obs, rew, done, info = env.step_skip(actions[m], K)
-        for k, t in (("reward", rew), ("done", done), ("n_steps", info["frame_steps"]), ("flags", info["flags"]),
-                     ("ac_reward", info["aircraft_reward"]), ("min_sep", info["min_separation"]), ("obs", obs)):
-            rows[k].append(t.clone())
-        _restore(env, snap)
-    for k, v in keep.items():     # the env's bound outputs show what they showed before
-        getattr(env, k).copy_(v)
-    if fs is not None:
-        env.frame_steps.copy_(fs)
-    return {k: torch.stack(v).cpu() for k, v in rows.items()}
+    ref = T.chained_skip_reference(env, actions[:, None], K)
+    return {k: (v.to(torch.uint8) if k == "n_steps" else v) for k, v in ref.items() if not k.startswith("seg_")}
 
 
 def _check_events(ref, N, M, K, auto_reset):
@@ -192,45 +104,6 @@ def _check_events(ref, N, M, K, auto_reset):
     if N > 1:
         assert (fl & H.F_CONFLICT).any(), "no conflict flag"
         assert (fl & H.F_INACTIVE).any(), "no handed-over aircraft"
-
-
-GUARD = 2   # sentinel rows in front of and behind every output
-
-
-def _lookahead_guarded(env, actions, K, outputs, n_steps=True):
-    """atc_lookahead through ctypes into sentinel-filled tensors with guard rows; returns the [M, ...] results (CPU) after checking
-    that the guards are intact and that outputs that were not requested (NULL) do not exist."""
-    import torch
-    from atc_hip import lib
-    M, B, N = actions.shape[0], env.B, env.N
-    shapes = {"reward": ((B,), torch.float32, 7.5), "done": ((B,), torch.uint8, 0xA5), "n_steps": ((B,), torch.uint8, 0xA5),
-              "flags": ((B, N), torch.int16, 0x5A5A), "ac_reward": ((B, N), torch.float32, 7.5), "min_sep": ((B,), torch.float32, 7.5),
-              "obs": ((B, N * 10), torch.float32, 7.5)}
-    want = ("reward", "done") + (("n_steps",) if n_steps else ()) + tuple(outputs)
-    buf = {k: torch.full((M + 2 * GUARD,) + shapes[k][0], shapes[k][2], dtype=shapes[k][1], device=env.device) for k in want}
-    out = lib.AtcLookaheadOut(*[buf[k][GUARD:].data_ptr() if k in buf else None for k in lib.LOOKAHEAD_FIELDS])
-    a = actions.contiguous()
-    lib.check(lib.load().atc_lookahead(env.sector.handle, B, N, K, M, C.byref(env._state), a.data_ptr(), C.byref(out),
-                                       C.byref(env.params), torch.cuda.current_stream().cuda_stream))
-    env.synchronize()
-    res = {}
-    for k, t in buf.items():
-        g = torch.cat([t[:GUARD], t[GUARD + M:]])
-        assert bool((g == torch.full_like(g, shapes[k][2])).all()), "guard rows of %s overwritten" % k
-        res[k] = t[GUARD:GUARD + M].cpu()
-    return res
-
-
-def _assert_equal(got, ref, tag, mask=None):
-    """bit for bit; mask [M, B] selects the (candidate, env) pairs to compare"""
-    import torch
-    for k, g in got.items():
-        r = ref[k]
-        gi = g.contiguous().view(torch.int32 if g.dtype == torch.float32 else g.dtype)
-        ri = r.contiguous().view(gi.dtype).view(gi.shape)
-        if mask is not None:
-            gi, ri = gi[mask], ri[mask]
-        assert torch.equal(gi, ri), (tag, k, int((gi != ri).sum()))
 
 
 # (N, M, K, auto_reset, spawn, normalize, outputs): every N of the grid, M in {1, 3, 8}, K in {1, 4, 20}, each switch both ways, the fast
@@ -264,22 +137,22 @@ IDS = ["N%d M%d K%d %s %s %s %s" % (c[0], c[1], c[2], "reset" if c[3] else "nore
 def test_lookahead_equals_step_skip_on_copies(N, M, K, auto_reset, spawn, normalize, outputs):
     import torch
     from atc_hip import lib
-    B = _ragged(N)
+    B = T.look_ragged(N)
     rng = np.random.default_rng(1000 + 7 * CASES.index((N, M, K, auto_reset, spawn, normalize, outputs)))
-    env = _env(N, B, spawn, normalize)
-    _fly(env, rng)
-    _set_auto_reset(env, auto_reset)
-    actions = torch.as_tensor(_draw(rng, M, B, N), device=env.device)
+    env = T.look_env(N, B, spawn, normalize)
+    T.look_fly(env, rng)
+    H.set_auto_reset(env, auto_reset)
+    actions = torch.as_tensor(T.look_draw(rng, M, B, N), device=env.device)
     if M > 1:   # env 0: candidate 0 descends as fast as it may, candidate 1 climbs
         actions[0, 0, 0, 1], actions[1, 0, 0, 1] = -0.9, 0.9
     ref = _reference(env, actions, K)
     _check_events(ref, N, M, K, auto_reset)
-    snap = _snapshot(env)
+    snap = H.snapshot(env)
     before = (lib.lookahead_launch_counts(), lib.skip_launch_counts(), lib.launch_counts(), lib.traffic_launch_counts())
-    got = _lookahead_guarded(env, actions, K, outputs, n_steps=(CASES.index((N, M, K, auto_reset, spawn, normalize, outputs)) % 4 != 3))
+    got = T.guarded_call(env, "lookahead", actions, K, outputs, n_steps=(CASES.index((N, M, K, auto_reset, spawn, normalize, outputs)) % 4 != 3))
     assert set(got) >= {"reward", "done"} | set(outputs)
-    _assert_equal(got, ref, "guarded")
-    _bytes_equal(env, snap)
+    T.assert_equal(got, ref, "guarded")
+    H.bytes_equal(env, snap)
     now = lib.lookahead_launch_counts()
     W = H.lane_width(N)
     assert {w: n - before[0].get(w, 0) for w, n in now.items() if n != before[0].get(w, 0)} == {W: 1}
@@ -292,16 +165,16 @@ def test_lookahead_equals_step_skip_on_copies(N, M, K, auto_reset, spawn, normal
         res = env.lookahead(actions.view(M, B, N * 3), K, outputs=outputs)
         assert set(res) == {"reward", "done", "n_steps"} | set(outputs)
         assert res["reward"].shape == (M, B) and res["n_steps"].dtype == torch.uint8
-        _assert_equal({k: v.cpu() for k, v in res.items()}, ref, ("python", cpg))
+        T.assert_equal({k: v.cpu() for k, v in res.items()}, ref, ("python", cpg))
         first = env.lookahead(actions, K, outputs=outputs)
         assert all(first[k].data_ptr() == res[k].data_ptr() for k in res), "output tensors are allocated once per (M, outputs)"
         p = env.lookahead(actions[perm], K, outputs=outputs)
-        _assert_equal({k: v.cpu() for k, v in p.items()}, {k: v[perm.cpu()] for k, v in ref.items()}, ("permuted", cpg))
+        T.assert_equal({k: v.cpu() for k, v in p.items()}, {k: v[perm.cpu()] for k, v in ref.items()}, ("permuted", cpg))
         one = env.lookahead(actions[:1], K, outputs=outputs)
-        _assert_equal({k: v.cpu() for k, v in one.items()}, {k: v[:1] for k, v in ref.items()}, ("M = 1", cpg))
+        T.assert_equal({k: v.cpu() for k, v in one.items()}, {k: v[:1] for k, v in ref.items()}, ("M = 1", cpg))
     for k, v in bound.items():
         assert torch.equal(getattr(env, k), v), k
-    _bytes_equal(env, snap)
+    H.bytes_equal(env, snap)
     env.close()
 
 
@@ -312,21 +185,20 @@ def test_lookahead_against_the_oracle(N):
     """A second reference, one case per width: tests/skip_ref.py on the CPU oracle, under the bars of tests/bars.py — device and oracle
     fly the same frame-skip calls from the same seed, then every candidate is evaluated on the oracle from a snapshot."""
     import torch
-    import test_frame_skip as TF
-    scn, comp = TF._setup(N)
-    kw = TF._plan(N)
-    B, M, K, seed = _ragged(N), 3, 10, 4321 + N    # (4 steps flown + K exceed the plans' time limits of 7 / 12: envs stop early)
-    env = TF._env(scn, B, N, True, seed, True, **kw)
-    orc = TF._oracle(comp, B, N, True, seed, **kw)
+    scn, comp = T.skip_setup(N)
+    kw = T.skip_plan(N)
+    B, M, K, seed = T.look_ragged(N), 3, 10, 4321 + N    # (4 steps flown + K exceed the plans' time limits of 7 / 12: envs stop early)
+    env = T.skip_env(scn, B, N, True, seed, True, **kw)
+    orc = T.skip_oracle(comp, B, N, True, seed, **kw)
     rng = np.random.default_rng(seed)
     for Kf in (3, 1):
-        a = TF._actions(rng, B, N)
+        a = T.skip_actions(rng, B, N)
         a[..., 2] = np.clip(a[..., 2], -1.0, 1.0)    # (headings inside the action space: nothing is WIDE when the look-ahead starts)
         R.skip_reference(orc, a, Kf)
         env.step_skip(a, Kf)
     bars.check_state(env, orc)
     # headings inside the action space (a WIDE target is not evaluated: its own test), speeds and altitudes partly refused
-    cand = TF._actions(rng, M * B, N).reshape(M, B, N, 3)
+    cand = T.skip_actions(rng, M * B, N).reshape(M, B, N, 3)
     cand[..., 2] = np.clip(cand[..., 2], -1.0, 1.0)
     wide0 = R.wide_envs(orc)
     assert not wide0.all()
@@ -346,71 +218,45 @@ def test_lookahead_against_the_oracle(N):
 @pytest.mark.parametrize("N", [1, 16, 33])
 def test_wide_headings_are_not_evaluated(N):
     import torch
-    B, M, K = _ragged(N), 3, 4
+    B, M, K = T.look_ragged(N), 3, 4
     rng = np.random.default_rng(77 + N)
-    env = _env(N, B, "lattice", True)
-    _fly(env, rng, steps=40)
+    env = T.look_env(N, B, "lattice", True)
+    T.look_fly(env, rng, steps=40)
     e_wide = B - 1
     env.set_state(e_wide, N - 1, *H.FAR_B[:3], 500.0, H.FAR_B[4])    # 500 deg: beyond the 32-bit heading field
     assert int(env.phi_fix[e_wide * N + N - 1]) == L.I32_MAX
-    actions = torch.as_tensor(_draw(rng, M, B, N), device=env.device)
+    actions = torch.as_tensor(T.look_draw(rng, M, B, N), device=env.device)
     actions[1, 3, 0, 2] = 3.0          # candidate 1, env 3: a heading target of 720 deg saturates the accepted target
     bad = torch.zeros((M, B), dtype=torch.bool)
     bad[:, e_wide] = True
     bad[1, 3] = True
     ref = _reference(env, actions, K)    # (step_skip evaluates WIDE headings: its rows of `bad` are not compared)
-    snap = _snapshot(env)
-    got = _lookahead_guarded(env, actions, K, ALL)
-    _bytes_equal(env, snap)
-    _assert_equal(got, ref, "evaluated", mask=~bad)
+    snap = H.snapshot(env)
+    got = T.guarded_call(env, "lookahead", actions, K, ALL)
+    H.bytes_equal(env, snap)
+    T.assert_equal(got, ref, "evaluated", mask=~bad)
     for k, v in got.items():
         assert not bool(v[bad].view(torch.uint8 if v.dtype == torch.uint8 else torch.int32 if v.dtype == torch.float32 else torch.int16).any()), k
     assert bool((got["n_steps"][~bad] >= 1).all())
     env.close()
 
 
-def _scripted(with_lookahead, N=16):
-    """reset, step, step (held), step_skip, masked reset, observe_traffic, rollout from one seed; returns every output and the state"""
+def _lookaheads(env):
+    """the look-ahead calls of both forms that tests/held_tools.py::scripted makes between its calls"""
     import torch
-    from atc_hip.vec_env import AtcVecEnv
-    B = _ragged(N)
-    env = AtcVecEnv(B, N, scenario=_scenario(), auto_reset=True, spawn="lattice", seed=5, grid_cell=0.5, timestep_limit=15, sep_nm=13.0,
-                    traffic=2)
-    rng = np.random.default_rng(9)
-    cand = torch.as_tensor(_draw(np.random.default_rng(10), 3, B, N), device=env.device)
-    log = []
+    cand = torch.as_tensor(T.look_draw(np.random.default_rng(10), 3, env.B, env.N), device=env.device)
 
     def look():
-        if with_lookahead:
-            env.lookahead(cand, 6, outputs=ALL)
-            env.lookahead(cand[:2], 3, outputs=())
-
-    def keep(*ts):
-        log.extend(t.clone().cpu() for t in ts)
-        look()
-
-    keep(env.reset())
-    a = torch.as_tensor(_draw(rng, B, N), device=env.device)
-    o, r, d, i = env.step(a)
-    keep(o, r, d, i["flags"], i["traffic"])
-    o, r, d, i = env.step(a, held=True)
-    keep(o, r, d, i["flags"])
-    o, r, d, i = env.step_skip(torch.as_tensor(_draw(rng, B, N), device=env.device), 7)
-    keep(o, r, d, i["flags"], i["frame_steps"])
-    keep(env.reset(mask=(np.arange(B) % 3 == 0)))
-    keep(env.observe_traffic())
-    out = env.rollout(torch.as_tensor(_draw(rng, 4, B, N), device=env.device), hold=3)
-    keep(*[out[k] for k in ("obs", "reward", "done", "flags")])
-    log.extend(getattr(env, k).clone().cpu() for k in STATE)
-    env.close()
-    return log
+        env.lookahead(cand, 6, outputs=ALL)
+        env.lookahead(cand[:2], 3, outputs=())
+    return look
 
 
 @pytest.mark.gpu
 @pytest.mark.timeout(120)
 def test_lookaheads_between_calls_change_nothing():
     import torch
-    plain, mixed = _scripted(False), _scripted(True)
+    plain, mixed = T.scripted(), T.scripted(_lookaheads)
     assert len(plain) == len(mixed)
     for j, (a, b) in enumerate(zip(plain, mixed)):
         assert torch.equal(a.contiguous().view(torch.uint8), b.contiguous().view(torch.uint8)), j
@@ -424,23 +270,23 @@ def test_full_size_batch():
     import torch
     B, N, M, K = 65536, 16, 4, 4
     rng = np.random.default_rng(3)
-    env = _env(N, B, "lattice", True, seed=3, timestep_limit=30)
-    small = _env(N, 256, "lattice", True, seed=3, timestep_limit=30)
-    a0 = _draw(rng, 3, B, N)
+    env = T.look_env(N, B, "lattice", True, seed=3, timestep_limit=30)
+    small = T.look_env(N, 256, "lattice", True, seed=3, timestep_limit=30)
+    a0 = T.look_draw(rng, 3, B, N)
     env.rollout(torch.as_tensor(a0, device=env.device), hold=9)
     small.rollout(torch.as_tensor(a0[:, :256].copy(), device=env.device), hold=9)
-    for k in STATE:     # envs are independent and the sampler is keyed by the env index: the small env IS the first 256
+    for k in H.STATE:     # envs are independent and the sampler is keyed by the env index: the small env IS the first 256
         rows = 256 * N if getattr(env, k).shape[0] == B * N else 256
         assert torch.equal(getattr(env, k)[:rows], getattr(small, k))
-    actions = torch.as_tensor(_draw(rng, M, B, N), device=env.device)
+    actions = torch.as_tensor(T.look_draw(rng, M, B, N), device=env.device)
     ref = _reference(small, actions[:, :256].contiguous(), K)
     assert ref["done"].any()
-    snap = _snapshot(env)
+    snap = H.snapshot(env)
     res = env.lookahead(actions, K, outputs=ALL)
-    _assert_equal({k: v[:, :256].cpu() for k, v in res.items()}, ref, "full size")
+    T.assert_equal({k: v[:, :256].cpu() for k, v in res.items()}, ref, "full size")
     fast = env.lookahead(actions, K, outputs=())
-    _assert_equal({k: v[:, :256].cpu() for k, v in fast.items()}, ref, "full size, fast form")
-    _bytes_equal(env, snap)
+    T.assert_equal({k: v[:, :256].cpu() for k, v in fast.items()}, ref, "full size, fast form")
+    H.bytes_equal(env, snap)
     n = res["n_steps"]
     assert bool(((n >= 1) & (n <= K)).all()) and bool((n[res["done"] == 0] == K).all())
     env.close()

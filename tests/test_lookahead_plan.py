@@ -20,14 +20,14 @@ import numpy as np
 import pytest
 
 import bars
+import held_tools as T
 import helpers as H
 import skip_ref as R
-import test_lookahead as TL
 from atc_hip import layout as L
-from test_lookahead import HEADER, LIB, _assert_equal, _bytes_equal, _draw, _env, _fly, _ragged, _set_auto_reset, _snapshot, _restore
+from held_tools import HEADER, LIB, TIME_LIMIT
 
-GUARD = TL.GUARD
 OPTIONAL = ("seg_reward", "flags", "min_sep", "ac_reward", "obs")
+LOOK_ALL = OPTIONAL[1:]     # atc_lookahead's optional outputs
 ALL = OPTIONAL
 WIDTH_N = (1, 2, 3, 8, 16, 32, 64)
 
@@ -137,21 +137,19 @@ ORACLE_M, ORACLE_H, ORACLE_K = 2, 3, 4
 
 def _oracle_case(N):
     """device-independent part of the oracle case of width N: (scn, comp, kw, B, seed)"""
-    import test_frame_skip as TF
-    scn, comp = TF._setup(N)
+    scn, comp = T.skip_setup(N)
     # (time limit: 4 steps are flown, so an env that was never reset stops in the plan's last segment; conflicts end others earlier)
-    return scn, comp, dict(TF._plan(N), timestep_limit=14), _ragged(N), 8642 + N
+    return scn, comp, dict(T.skip_plan(N), timestep_limit=14), T.look_ragged(N), 8642 + N
 
 
 def _oracle_inputs(rng, B, N):
     """the flown calls' actions and the plans: headings inside the action space (a WIDE target is not evaluated: its own test)"""
-    import test_frame_skip as TF
     flown = []
     for Kf in (3, 1):
-        a = TF._actions(rng, B, N)
+        a = T.skip_actions(rng, B, N)
         a[..., 2] = np.clip(a[..., 2], -1.0, 1.0)
         flown.append((a, Kf))
-    cand = TF._actions(rng, ORACLE_M * ORACLE_H * B, N).reshape(ORACLE_M, ORACLE_H, B, N, 3)
+    cand = T.skip_actions(rng, ORACLE_M * ORACLE_H * B, N).reshape(ORACLE_M, ORACLE_H, B, N, 3)
     cand[..., 2] = np.clip(cand[..., 2], -1.0, 1.0)
     return flown, cand
 
@@ -163,9 +161,8 @@ _oracle_chain, _oracle_refs = R.plan_chain, R.plan_references   # (the definitio
 def test_oracle_case_events_on_the_oracle(N):
     """A condition on the INPUTS of the oracle cases, checked without a GPU: an env-candidate stops before the plan's end, and one
     does so in a segment h >= 1 (whole plans without a done: the equality grid's events)."""
-    import test_frame_skip as TF
     scn, comp, kw, B, seed = _oracle_case(N)
-    orc = TF._oracle(comp, B, N, True, seed, **kw)
+    orc = T.skip_oracle(comp, B, N, True, seed, **kw)
     flown, cand = _oracle_inputs(np.random.default_rng(seed), B, N)
     for a, Kf in flown:
         R.skip_reference(orc, a, Kf)
@@ -178,10 +175,10 @@ def _grid_inputs(case):
     """the plans of a grid case as the GPU test draws them (the same generator, the same order of draws)"""
     import torch
     N, M, Hn, K = CASES[case][:4]
-    B = _ragged(N)
+    B = T.look_ragged(N)
     rng = np.random.default_rng(2000 + 7 * case)
-    _draw(rng, 200 // 10, B, N)                      # (_fly's draw)
-    actions = torch.as_tensor(_draw(rng, M, Hn, B, N))
+    T.look_draw(rng, 200 // 10, B, N)                      # (_fly's draw)
+    actions = torch.as_tensor(T.look_draw(rng, M, Hn, B, N))
     return actions.numpy(), _place_plans(actions, M, Hn)
 
 
@@ -195,7 +192,7 @@ def test_placed_envs_show_their_events_on_the_oracle(case):
     from oracle import oracle as O
     N, M, Hn, K, auto_reset, spawn = CASES[case][:6]
     if "grid" not in H._compiled:
-        H._compiled["grid"] = scenarios.compile_scenario(TL._scenario(), grid_cell=0.5)
+        H._compiled["grid"] = scenarios.compile_scenario(T.look_scenario(), grid_cell=0.5)
     comp = H._compiled["grid"]
     actions, late = _grid_inputs(case)
     x, y, _, phi, v = H.FAR_A
@@ -232,51 +229,8 @@ def test_placed_envs_show_their_events_on_the_oracle(case):
 
 
 # ---------------------------------------------------------------------------------------------------------------- GPU
-def _reference(env, actions, K):
-    """The definition on the product itself: per candidate, env.step_skip chained over the H segments on a private copy of the state
-    (the env's own tensors, put back afterwards); an env leaves the chain at its first done.  Returns [M, ...] CPU tensors, plus
-    seg_flags [M, H, B, N] (each executed segment's own flag word, for the event checks)."""
-    import torch
-    M, Hn = actions.shape[:2]
-    snap = _snapshot(env)
-    keep = {k: getattr(env, k).clone() for k in ("obs", "reward", "done", "flags", "ac_reward", "min_sep")}
-    fs = env.frame_steps.clone() if env.frame_steps is not None else None
-    rows = {k: [] for k in ("reward", "done", "n_steps", "seg_reward", "flags", "ac_reward", "min_sep", "obs", "seg_flags")}
-    for m in range(M):
-        alive = torch.ones(env.B, dtype=torch.bool, device=env.device)
-        seg, seg_fl = [], []
-        for h in range(Hn):
-            obs, rew, done, info = env.step_skip(actions[m, h], K)
-            fl, acr, ms, n = info["flags"].view(env.B, env.N), info["aircraft_reward"].view(env.B, env.N), info["min_separation"], info["frame_steps"]
-            obs = obs.view(env.B, -1)
-            a2 = alive[:, None]
-            if h == 0:
-                c = {"reward": rew.clone(), "done": done.clone(), "n_steps": n.to(torch.int16), "flags": fl.clone(), "ac_reward": acr.clone(),
-                     "min_sep": ms.clone(), "obs": obs.clone()}
-            else:
-                c["reward"] = torch.where(alive, c["reward"] + rew, c["reward"])          # acc = acc + r_h: one float32 addition
-                c["ac_reward"] = torch.where(a2, c["ac_reward"] + acr, c["ac_reward"])
-                c["done"] = torch.where(alive, done, c["done"])
-                c["n_steps"] = c["n_steps"] + torch.where(alive, n.to(torch.int16), torch.zeros_like(c["n_steps"]))
-                c["flags"] = torch.where(a2, c["flags"] | fl, c["flags"])
-                c["min_sep"] = torch.where(alive, torch.minimum(c["min_sep"], ms), c["min_sep"])
-                c["obs"] = torch.where(a2, obs, c["obs"])
-            seg.append(torch.where(alive, rew, torch.zeros_like(rew)))
-            seg_fl.append(torch.where(a2, fl, torch.zeros_like(fl)))
-            alive = alive & (done == 0)
-        _restore(env, snap)
-        c["seg_reward"], c["seg_flags"] = torch.stack(seg), torch.stack(seg_fl)
-        for k in rows:
-            rows[k].append(c[k])
-    for k, v in keep.items():     # the env's bound outputs show what they showed before
-        getattr(env, k).copy_(v)
-    if fs is not None:
-        env.frame_steps.copy_(fs)
-    return {k: torch.stack(v).cpu() for k, v in rows.items()}
-
-
 def _place_plans(actions, M, Hn):
-    """env 0 (tests/test_lookahead.py::_fly: aircraft 0 alone under control, a step above its MVA floor, far from the time limit):
+    """env 0 (tests/held_tools.py::look_fly: aircraft 0 alone under control, a step above its MVA floor, far from the time limit):
     its plans stop in different segments, and aircraft 0's altitude / speed targets are refused in one segment and accepted in the
     next, in each order.  `late` is the plan that holds its altitude in segment 0 (refused target) and descends from segment 1 on; it
     flies east into an area with a lower floor, so it reaches segment 1 but need not end there: _place_timeout ends plans there."""
@@ -291,9 +245,6 @@ def _place_plans(actions, M, Hn):
         actions[late, 0, 0, 0, 0] = 0.3           # speed: accepted in segment 0 ...
         actions[late, 1, 0, 0, 0] = 2.5           # ... refused in segment 1
     return late
-
-
-TIME_LIMIT = 60    # test_lookahead._env's
 
 
 def _place_timeout(env, K):
@@ -337,30 +288,6 @@ def _check_events(ref, N, M, Hn, K, auto_reset, late):
         assert sfl[late, 1, 0, 0] & H.F_INVALID_V and not sfl[late, 1, 0, 0] & H.F_INVALID_H
 
 
-def _plan_guarded(env, actions, K, outputs, n_steps=True):
-    """atc_lookahead_plan through ctypes into sentinel-filled tensors with guard rows; returns the [M, ...] results (CPU) after
-    checking that the guards are intact."""
-    import torch
-    from atc_hip import lib
-    M, Hn, B, N = actions.shape[0], actions.shape[1], env.B, env.N
-    shapes = {"reward": ((B,), torch.float32, 7.5), "done": ((B,), torch.uint8, 0xA5), "n_steps": ((B,), torch.int16, 0x5A5A),
-              "seg_reward": ((Hn, B), torch.float32, 7.5), "flags": ((B, N), torch.int16, 0x5A5A), "ac_reward": ((B, N), torch.float32, 7.5),
-              "min_sep": ((B,), torch.float32, 7.5), "obs": ((B, N * 10), torch.float32, 7.5)}
-    want = ("reward", "done") + (("n_steps",) if n_steps else ()) + tuple(outputs)
-    buf = {k: torch.full((M + 2 * GUARD,) + shapes[k][0], shapes[k][2], dtype=shapes[k][1], device=env.device) for k in want}
-    out = lib.AtcPlanOut(*[buf[k][GUARD:].data_ptr() if k in buf else None for k in lib.PLAN_FIELDS])
-    a = actions.contiguous()
-    lib.check(lib.load().atc_lookahead_plan(env.sector.handle, B, N, K, Hn, M, C.byref(env._state), a.data_ptr(), C.byref(out),
-                                            C.byref(env.params), torch.cuda.current_stream().cuda_stream))
-    env.synchronize()
-    res = {}
-    for k, t in buf.items():
-        g = torch.cat([t[:GUARD], t[GUARD + M:]])
-        assert bool((g == torch.full_like(g, shapes[k][2])).all()), "guard rows of %s overwritten" % k
-        res[k] = t[GUARD:GUARD + M].cpu()
-    return res
-
-
 def _cpu(res):
     return {k: v.cpu() for k, v in res.items()}
 
@@ -372,23 +299,23 @@ def test_plan_equals_chained_step_skip_on_copies(N, M, Hn, K, auto_reset, spawn,
     import torch
     from atc_hip import lib
     case = CASES.index((N, M, Hn, K, auto_reset, spawn, normalize, outputs))
-    B = _ragged(N)
+    B = T.look_ragged(N)
     rng = np.random.default_rng(2000 + 7 * case)
-    env = _env(N, B, spawn, normalize)
-    _fly(env, rng)
+    env = T.look_env(N, B, spawn, normalize)
+    T.look_fly(env, rng)
     _place_timeout(env, K)
-    _set_auto_reset(env, auto_reset)
-    actions = torch.as_tensor(_draw(rng, M, Hn, B, N), device=env.device)
+    H.set_auto_reset(env, auto_reset)
+    actions = torch.as_tensor(T.look_draw(rng, M, Hn, B, N), device=env.device)
     late = _place_plans(actions, M, Hn)
-    ref = _reference(env, actions, K)
+    ref = T.chained_skip_reference(env, actions, K)
     _check_events(ref, N, M, Hn, K, auto_reset, late)
     ref.pop("seg_flags")
-    snap = _snapshot(env)
+    snap = H.snapshot(env)
     before = (lib.plan_launch_counts(), lib.lookahead_launch_counts(), lib.skip_launch_counts(), lib.launch_counts(), lib.traffic_launch_counts())
-    got = _plan_guarded(env, actions, K, outputs, n_steps=(case % 4 != 3))
+    got = T.guarded_call(env, "plan", actions, K, outputs, n_steps=(case % 4 != 3))
     assert set(got) >= {"reward", "done"} | set(outputs)
-    _assert_equal(got, ref, "guarded")
-    _bytes_equal(env, snap)
+    T.assert_equal(got, ref, "guarded")
+    H.bytes_equal(env, snap)
     now = lib.plan_launch_counts()
     W = H.lane_width(N)
     assert {w: n - before[0].get(w, 0) for w, n in now.items() if n != before[0].get(w, 0)} == {W: 1}
@@ -403,18 +330,18 @@ def test_plan_equals_chained_step_skip_on_copies(N, M, Hn, K, auto_reset, spawn,
             assert set(res) == {"reward", "done", "n_steps"} | set(outputs)
             assert res["reward"].shape == (M, B) and res["n_steps"].dtype == torch.int16
             assert "seg_reward" not in res or res["seg_reward"].shape == (M, Hn, B)
-            _assert_equal(_cpu(res), ref, ("python", cpg))
+            T.assert_equal(_cpu(res), ref, ("python", cpg))
             first = env.lookahead_plan(actions, K, outputs=outputs)
             assert all(first[k].data_ptr() == res[k].data_ptr() for k in res), "output tensors are allocated once per (M, H, outputs)"
             p = env.lookahead_plan(actions[perm], K, outputs=outputs)
-            _assert_equal(_cpu(p), {k: v[perm.cpu()] for k, v in ref.items()}, ("permuted", cpg))
+            T.assert_equal(_cpu(p), {k: v[perm.cpu()] for k, v in ref.items()}, ("permuted", cpg))
             one = env.lookahead_plan(actions[:1], K, outputs=outputs)
-            _assert_equal(_cpu(one), {k: v[:1] for k, v in ref.items()}, ("M = 1", cpg))
+            T.assert_equal(_cpu(one), {k: v[:1] for k, v in ref.items()}, ("M = 1", cpg))
     finally:
         lib.lookahead_set_mapping(0)
     for k, v in bound.items():
         assert torch.equal(getattr(env, k), v), k
-    _bytes_equal(env, snap)
+    H.bytes_equal(env, snap)
     env.close()
 
 
@@ -424,19 +351,19 @@ def test_plan_equals_chained_step_skip_on_copies(N, M, Hn, K, auto_reset, spawn,
 def test_one_segment_is_lookahead(N):
     """H == 1 reproduces env.lookahead bit for bit in every shared output, n_steps' values included; both forms."""
     import torch
-    B, M, K = _ragged(N), 3, 6
+    B, M, K = T.look_ragged(N), 3, 6
     rng = np.random.default_rng(300 + N)
-    env = _env(N, B, "lattice", True)
-    _fly(env, rng)
-    actions = torch.as_tensor(_draw(rng, M, B, N), device=env.device)
+    env = T.look_env(N, B, "lattice", True)
+    T.look_fly(env, rng)
+    actions = torch.as_tensor(T.look_draw(rng, M, B, N), device=env.device)
     actions[0, 0, 0, 1], actions[1, 0, 0, 1] = -0.9, 0.9
-    for outs in (TL.ALL, ()):
+    for outs in (LOOK_ALL, ()):
         look = {k: v.clone().cpu() for k, v in env.lookahead(actions, K, outputs=outs).items()}
         plan = _cpu(env.lookahead_plan(actions[:, None], K, outputs=outs + ("seg_reward",)))
         assert (look["n_steps"].numpy() != K).any() and (look["n_steps"].numpy() == K).any()
         assert np.array_equal(plan["n_steps"].numpy().astype(int), look["n_steps"].numpy().astype(int))
-        _assert_equal({k: plan[k] for k in look if k != "n_steps"}, look, ("H = 1", outs))
-        _assert_equal({"seg_reward": plan["seg_reward"][:, 0]}, {"seg_reward": look["reward"]}, ("H = 1 seg", outs))
+        T.assert_equal({k: plan[k] for k in look if k != "n_steps"}, look, ("H = 1", outs))
+        T.assert_equal({"seg_reward": plan["seg_reward"][:, 0]}, {"seg_reward": look["reward"]}, ("H = 1 seg", outs))
     env.close()
 
 
@@ -445,12 +372,12 @@ def test_one_segment_is_lookahead(N):
 @pytest.mark.parametrize("N", [1, 16, 64])
 def test_prefix_property(N):
     import torch
-    B, M, Hn, K = _ragged(N), 3, 4, 3
+    B, M, Hn, K = T.look_ragged(N), 3, 4, 3
     rng = np.random.default_rng(500 + N)
-    env = _env(N, B, "random", True)
-    _fly(env, rng)
+    env = T.look_env(N, B, "random", True)
+    T.look_fly(env, rng)
     _place_timeout(env, K)      # (the last env's plans end in segment 1; env 0's plan 0 in segment 0, its plan 2 not at all)
-    actions = torch.as_tensor(_draw(rng, M, Hn, B, N), device=env.device)
+    actions = torch.as_tensor(T.look_draw(rng, M, Hn, B, N), device=env.device)
     _place_plans(actions, M, Hn)
     whole = {k: v.clone().cpu() for k, v in env.lookahead_plan(actions, K, outputs=("seg_reward",)).items()}
     segs = -(-whole["n_steps"].numpy().astype(int) // K)
@@ -458,9 +385,9 @@ def test_prefix_property(N):
     assert ended_by(1).any() and ended_by(2).any() and not ended_by(3).all()
     for h in (1, 2, 3):
         part = _cpu(env.lookahead_plan(actions[:, :h].contiguous(), K, outputs=("seg_reward",)))
-        _assert_equal({"seg_reward": part["seg_reward"]}, {"seg_reward": whole["seg_reward"][:, :h].contiguous()}, ("prefix", h))
+        T.assert_equal({"seg_reward": part["seg_reward"]}, {"seg_reward": whole["seg_reward"][:, :h].contiguous()}, ("prefix", h))
         mask = ended_by(h)
-        _assert_equal({k: part[k] for k in ("reward", "done", "n_steps")}, whole, ("prefix rows", h), mask=mask)
+        T.assert_equal({k: part[k] for k in ("reward", "done", "n_steps")}, whole, ("prefix rows", h), mask=mask)
         assert bool((part["n_steps"][~mask] == h * K).all())
     env.close()
 
@@ -470,14 +397,14 @@ def test_prefix_property(N):
 @pytest.mark.parametrize("N", [1, 16, 33])
 def test_wide_headings_are_not_evaluated(N):
     import torch
-    B, M, Hn, K = _ragged(N), 3, 3, 4
+    B, M, Hn, K = T.look_ragged(N), 3, 3, 4
     rng = np.random.default_rng(177 + N)
-    env = _env(N, B, "lattice", True)
-    _fly(env, rng, steps=40)
+    env = T.look_env(N, B, "lattice", True)
+    T.look_fly(env, rng, steps=40)
     e_wide = B - 1
     env.set_state(e_wide, N - 1, *H.FAR_B[:3], 500.0, H.FAR_B[4])    # 500 deg: beyond the 32-bit heading field
     assert int(env.phi_fix[e_wide * N + N - 1]) == L.I32_MAX
-    actions = torch.as_tensor(_draw(rng, M, Hn, B, N), device=env.device)
+    actions = torch.as_tensor(T.look_draw(rng, M, Hn, B, N), device=env.device)
     actions[1, 0, 3, 0, 2] = 3.0          # candidate 1, env 3: a heading target of 720 deg in segment 0
     actions[2, 1, 4, 0, 2] = 3.0          # candidate 2, env 4: ... in segment 1
     for e in (3, 4):                      # (both envs run into segment 1: aircraft 0 alone under control, far from everything)
@@ -491,14 +418,14 @@ def test_wide_headings_are_not_evaluated(N):
     bad[:, e_wide] = True
     bad[1, 3] = True
     bad[2, 4] = True
-    ref = _reference(env, actions, K)    # (step_skip evaluates WIDE headings: its rows of `bad` are not compared)
+    ref = T.chained_skip_reference(env, actions, K)    # (step_skip evaluates WIDE headings: its rows of `bad` are not compared)
     ref.pop("seg_flags")
     assert int(ref["n_steps"][2, 4]) > K, "env 4 does not reach the segment with the WIDE target"
-    snap = _snapshot(env)
-    got = _plan_guarded(env, actions, K, ALL)
-    _bytes_equal(env, snap)
+    snap = H.snapshot(env)
+    got = T.guarded_call(env, "plan", actions, K, ALL)
+    H.bytes_equal(env, snap)
     swap = lambda d: {k: (v.transpose(1, 2) if k == "seg_reward" else v) for k, v in d.items()}   # noqa: E731  ([M, B, H]: the mask's axes first)
-    _assert_equal(swap(got), swap(ref), "evaluated", mask=~bad)
+    T.assert_equal(swap(got), swap(ref), "evaluated", mask=~bad)
     for k, v in swap(got).items():
         assert not bool(v[bad].contiguous().view(torch.uint8 if v.dtype == torch.uint8 else torch.int32 if v.dtype == torch.float32 else torch.int16).any()), k
     assert bool((got["n_steps"][~bad] >= 1).all())
@@ -512,11 +439,10 @@ def test_plan_against_the_oracle(N):
     """A second reference, one case per width: chained tests/skip_ref.py calls on the CPU oracle from a snapshot, under the bars of
     tests/bars.py.  M = 2, H = 3, K = 4 under a time limit of 14 steps: envs stop early (asserted)."""
     import torch
-    import test_frame_skip as TF
     scn, comp, kw, B, seed = _oracle_case(N)
     M, Hn, K = ORACLE_M, ORACLE_H, ORACLE_K
-    env = TF._env(scn, B, N, True, seed, True, **kw)
-    orc = TF._oracle(comp, B, N, True, seed, **kw)
+    env = T.skip_env(scn, B, N, True, seed, True, **kw)
+    orc = T.skip_oracle(comp, B, N, True, seed, **kw)
     flown, cand = _oracle_inputs(np.random.default_rng(seed), B, N)
     for a, Kf in flown:
         R.skip_reference(orc, a, Kf)
@@ -537,45 +463,22 @@ def test_plan_against_the_oracle(N):
     env.close()
 
 
-def _scripted_with_plans(with_plans, N=16):
-    """tests/test_lookahead.py::_scripted's sequence, with lookahead_plan calls of both forms between the calls"""
+def _plans(env):
+    """the lookahead_plan calls of both forms that tests/held_tools.py::scripted makes between its calls"""
     import torch
-    from atc_hip.vec_env import AtcVecEnv
-    B = _ragged(N)
-    env = AtcVecEnv(B, N, scenario=TL._scenario(), auto_reset=True, spawn="lattice", seed=5, grid_cell=0.5, timestep_limit=15, sep_nm=13.0,
-                    traffic=2)
-    rng = np.random.default_rng(9)
-    cand = torch.as_tensor(_draw(np.random.default_rng(10), 3, 3, B, N), device=env.device)
-    log = []
+    cand = torch.as_tensor(T.look_draw(np.random.default_rng(10), 3, 3, env.B, env.N), device=env.device)
 
-    def keep(*ts):
-        log.extend(t.clone().cpu() for t in ts)
-        if with_plans:
-            env.lookahead_plan(cand, 4, outputs=ALL)
-            env.lookahead_plan(cand[:2, :2].contiguous(), 3, outputs=("seg_reward",))
-
-    keep(env.reset())
-    a = torch.as_tensor(_draw(rng, B, N), device=env.device)
-    o, r, d, i = env.step(a)
-    keep(o, r, d, i["flags"], i["traffic"])
-    o, r, d, i = env.step(a, held=True)
-    keep(o, r, d, i["flags"])
-    o, r, d, i = env.step_skip(torch.as_tensor(_draw(rng, B, N), device=env.device), 7)
-    keep(o, r, d, i["flags"], i["frame_steps"])
-    keep(env.reset(mask=(np.arange(B) % 3 == 0)))
-    keep(env.observe_traffic())
-    out = env.rollout(torch.as_tensor(_draw(rng, 4, B, N), device=env.device), hold=3)
-    keep(*[out[k] for k in ("obs", "reward", "done", "flags")])
-    log.extend(getattr(env, k).clone().cpu() for k in TL.STATE)
-    env.close()
-    return log
+    def plan():
+        env.lookahead_plan(cand, 4, outputs=ALL)
+        env.lookahead_plan(cand[:2, :2].contiguous(), 3, outputs=("seg_reward",))
+    return plan
 
 
 @pytest.mark.gpu
 @pytest.mark.timeout(120)
 def test_plans_between_calls_change_nothing():
     import torch
-    plain, mixed = TL._scripted(False), _scripted_with_plans(True)
+    plain, mixed = T.scripted(), T.scripted(_plans)
     assert len(plain) == len(mixed)
     for j, (a, b) in enumerate(zip(plain, mixed)):
         assert torch.equal(a.contiguous().view(torch.uint8), b.contiguous().view(torch.uint8)), j
@@ -589,25 +492,25 @@ def test_full_size_batch():
     import torch
     B, N, M, Hn, K = 65536, 16, 2, 2, 4
     rng = np.random.default_rng(3)
-    env = _env(N, B, "lattice", True, seed=3, timestep_limit=30)
-    small = _env(N, 256, "lattice", True, seed=3, timestep_limit=30)
-    a0 = _draw(rng, 3, B, N)
+    env = T.look_env(N, B, "lattice", True, seed=3, timestep_limit=30)
+    small = T.look_env(N, 256, "lattice", True, seed=3, timestep_limit=30)
+    a0 = T.look_draw(rng, 3, B, N)
     env.rollout(torch.as_tensor(a0, device=env.device), hold=9)
     small.rollout(torch.as_tensor(a0[:, :256].copy(), device=env.device), hold=9)
-    for k in TL.STATE:     # envs are independent and the sampler is keyed by the env index: the small env IS the first 256
+    for k in H.STATE:     # envs are independent and the sampler is keyed by the env index: the small env IS the first 256
         rows = 256 * N if getattr(env, k).shape[0] == B * N else 256
         assert torch.equal(getattr(env, k)[:rows], getattr(small, k))
-    actions = torch.as_tensor(_draw(rng, M, Hn, B, N), device=env.device)
-    ref = _reference(small, actions[:, :, :256].contiguous(), K)
+    actions = torch.as_tensor(T.look_draw(rng, M, Hn, B, N), device=env.device)
+    ref = T.chained_skip_reference(small, actions[:, :, :256].contiguous(), K)
     ref.pop("seg_flags")
     assert ref["done"].any() and (ref["n_steps"] > K).any()
-    snap = _snapshot(env)
+    snap = H.snapshot(env)
     first = lambda res: {k: (v[:, :, :256] if k == "seg_reward" else v[:, :256]).contiguous().cpu() for k, v in res.items()}   # noqa: E731
     res = env.lookahead_plan(actions, K, outputs=ALL)
-    _assert_equal(first(res), ref, "full size")
+    T.assert_equal(first(res), ref, "full size")
     fast = env.lookahead_plan(actions, K, outputs=("seg_reward",))
-    _assert_equal(first(fast), ref, "full size, fast form")
-    _bytes_equal(env, snap)
+    T.assert_equal(first(fast), ref, "full size, fast form")
+    H.bytes_equal(env, snap)
     n = res["n_steps"]
     assert bool(((n >= 1) & (n <= Hn * K)).all()) and bool((n[res["done"] == 0] == Hn * K).all())
     env.close()

@@ -35,14 +35,6 @@ KS = (1, 3, 4, 8)
 FULL_SIZE = dict(B=65536, N=16, K=4, seed=5, compared=256)
 
 
-def _ragged(N):
-    """two whole workgroups plus a part (tests/test_frame_skip.py::_cases)"""
-    per = 256 // H.lane_width(N)
-    B = 2 * per + max(1, per // 3) if per > 1 else 2 * per + 1
-    assert (B * H.lane_width(N)) % 256 != 0
-    return B
-
-
 @functools.lru_cache(maxsize=None)
 def _sector():
     from envs.atc import scenarios
@@ -55,7 +47,7 @@ def _case(N, family):
     """(state, reference) of one shape-matrix case: computed once, shared by the CPU conditions and the GPU comparisons, never changed"""
     comp = _sector()[1]
     rng = np.random.default_rng(1000 * N + len(family))
-    st = R.FAMILIES[family](rng, _ragged(N), N, comp.pos_k)
+    st = R.FAMILIES[family](rng, H.ragged(N), N, comp.pos_k)
     return st, R.traffic_reference(st, comp.pos_origin, comp.pos_k)
 
 
@@ -135,7 +127,7 @@ def test_gpu_case_inputs_contain_the_edge_cases():
         for family in R.FAMILIES:
             st, ref = _case(N, family)
             act = R.active_bits(st["mask"], N)
-            assert st["x_fix"].shape == (_ragged(N), N)
+            assert st["x_fix"].shape == (H.ragged(N), N)
             counts = act.sum(1)
             assert counts.min() == 0 and counts.max() == N, "masks with no and with every bit set"
             inactive += int((~act).sum())
@@ -218,7 +210,7 @@ _ENVS = {}
 def _env_for(N, B=None):
     """one plain env per shape (traffic=0: the launches below go through the C-ABI with their own buffers)"""
     from atc_hip.vec_env import AtcVecEnv
-    key = (N, B or _ragged(N))
+    key = (N, B or H.ragged(N))
     if key not in _ENVS:
         _ENVS[key] = AtcVecEnv(key[1], N, scenario=_sector()[0], auto_reset=True, spawn="lattice", grid_cell=0.5)
     return _ENVS[key]
