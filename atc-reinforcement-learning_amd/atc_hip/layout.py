@@ -82,3 +82,7 @@ LOOKAHEAD_MAX_M, LOOKAHEAD_LAUNCH_SLOTS = 64, 7
 # record (slot = log2(W))
 PLAN_MAX_H = 16
 PLAN_LAUNCH_SLOTS = 7
+# branch and select (include/atc_step.h: atc_branch, atc_state_select): their own launch records (atc_branch_launch_counts: slot =
+# log2(W); atc_select_launch_counts: one slot)
+BRANCH_LAUNCH_SLOTS = 7
+SELECT_LAUNCH_SLOTS = 1

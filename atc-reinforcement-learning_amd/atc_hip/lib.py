@@ -69,7 +69,8 @@ EXPORTS = ("atc_abi_version", "atc_last_error", "atc_launch_counts", "atc_host_m
            "atc_query_mva_index", "atc_query_corridor", "atc_query_shaping", "atc_reset", "atc_observe", "atc_step",
            "atc_step_multi", "atc_step_packet", "atc_rollout", "atc_rollout_hold", "atc_serve_start", "atc_serve_step", "atc_serve_stop",
            "atc_step_skip", "atc_skip_launch_counts", "atc_fill_prefetch_info", "atc_observe_traffic", "atc_traffic_launch_counts",
-           "atc_lookahead", "atc_lookahead_launch_counts", "atc_lookahead_set_mapping", "atc_lookahead_plan", "atc_plan_launch_counts")
+           "atc_lookahead", "atc_lookahead_launch_counts", "atc_lookahead_set_mapping", "atc_lookahead_plan", "atc_plan_launch_counts",
+           "atc_branch", "atc_branch_launch_counts", "atc_state_select", "atc_select_launch_counts")
 
 def load():
     """Loads libatcstep.so; raises (never falls back) when it has not been built."""
@@ -118,6 +119,10 @@ def load():
     lib.atc_lookahead_set_mapping.argtypes = [ci]
     lib.atc_lookahead_plan.argtypes = [vp, ci, ci, ci, ci, ci, C.POINTER(AtcState), vp, C.POINTER(AtcPlanOut), C.POINTER(AtcParams), vp]
     lib.atc_plan_launch_counts.argtypes = [C.POINTER(C.c_uint64), ci]
+    lib.atc_branch.argtypes = [vp, ci, ci, ci, ci, C.POINTER(AtcState), vp, C.POINTER(AtcState), C.POINTER(AtcLookaheadOut), C.POINTER(AtcParams), vp]
+    lib.atc_branch_launch_counts.argtypes = [C.POINTER(C.c_uint64), ci]
+    lib.atc_state_select.argtypes = [vp, ci, ci, C.POINTER(AtcState), ci, C.POINTER(AtcState), vp, vp, vp]
+    lib.atc_select_launch_counts.argtypes = [C.POINTER(C.c_uint64), ci]
     for name in EXPORTS:
         if name not in ("atc_abi_version", "atc_last_error"):
             getattr(lib, name).restype = ci
@@ -174,6 +179,17 @@ def plan_launch_counts():
     """Launches of the plan look-ahead kernel (atc_lookahead_plan) made by the calling thread so far, by lane-group width:
     {16: n, ...}, widths with a count of zero left out.  Separate from the other launch records, which a plan call leaves as they are."""
     return _counts("atc_plan_launch_counts", L.PLAN_LAUNCH_SLOTS)
+
+
+def branch_launch_counts():
+    """Launches of the branch kernel (atc_branch) made by the calling thread so far, by lane-group width: {16: n, ...}, widths with a
+    count of zero left out.  Separate from the other launch records, which a branch call leaves as they are."""
+    return _counts("atc_branch_launch_counts", L.BRANCH_LAUNCH_SLOTS)
+
+
+def select_launch_counts():
+    """Launches of the state gather (atc_state_select) made by the calling thread so far: {"select": n}, or {} before the first."""
+    return _counts("atc_select_launch_counts", L.SELECT_LAUNCH_SLOTS, lambda i: "select")
 
 
 def lookahead_set_mapping(candidates_per_workgroup=0):

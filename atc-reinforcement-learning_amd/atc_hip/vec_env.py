@@ -435,6 +435,93 @@ class AtcVecEnv:
         self._finish()
         return res
 
+    def _check_twin(self, other, what):
+        """branch() / select(): `other` must be an AtcVecEnv of the same N and device whose sector blob and atc_params_t are byte-equal"""
+        if not isinstance(other, AtcVecEnv):
+            raise ValueError("%s must be an AtcVecEnv" % what)
+        if other is self:
+            raise ValueError("%s must be another env than this one" % what)
+        if other.N != self.N or other.device != self.device:
+            raise ValueError("%s must have this env's num_aircraft and device" % what)
+        if other.host_mapped or self.host_mapped:
+            raise ValueError("branch / select need device-resident envs (host_mapped=False)")
+        a, b = self.compiled.blob32, other.compiled.blob32
+        if a.shape != b.shape or a.tobytes() != b.tobytes():
+            raise ValueError("%s must be built on the same sector (byte-equal blob)" % what)
+        if bytes(self.params) != bytes(other.params):
+            raise ValueError("%s must have byte-equal parameters (atc_params_t)" % what)
+
+    def branch(self, actions, K, into):
+        """Branch (atc_branch, include/atc_step.h): flies each of M candidate decisions per env for up to K steps — what
+        step_skip(actions[m], K) does from the state this env is in NOW — and KEEPS every outcome: candidate m of env e becomes env
+        m * B + e of `into`, an AtcVecEnv with into.B == M * self.B, the same num_aircraft, device, sector and parameters (anything
+        else: ValueError).  actions: [M, B, N, 3] (or [M, B, N*3]), 1 <= M <= 64, 1 <= K <= 255.  One launch; this env is left
+        exactly as it is.  The results land in `into`'s own bound tensors (obs, reward, done, flags, ac_reward / min_sep where it
+        has them, frame_steps), `into.traffic` is refreshed when it has one, and (obs, reward, done, info) of `into` is returned as
+        step_skip returns it: view the tensors as [M, B, ...].  `into.raw_obs` and `into.term_obs` are NOT written (atc_lookahead_out_t has
+        neither): they keep what they held.  An env-candidate with a WIDE heading is not evaluated: frame_steps
+        == 0, zeros, and the child env is a copy of this env's.  AtcSBVecEnv and AtcGym deliberately have no such method."""
+        torch = self.torch
+        K = int(K)
+        if not 1 <= K <= L.SKIP_MAX:
+            raise ValueError("1 <= K <= %d" % L.SKIP_MAX)
+        M = int(actions.shape[0]) if hasattr(actions, "shape") else len(actions)
+        if not 1 <= M <= L.LOOKAHEAD_MAX_M:
+            raise ValueError("1 <= M (actions.shape[0]) <= %d" % L.LOOKAHEAD_MAX_M)
+        self._check_twin(into, "into")
+        if into.B != M * self.B:
+            raise ValueError("into.num_envs must be M * num_envs = %d, got %d" % (M * self.B, into.B))
+        a = self._as_actions(actions, lead=(M,))
+        if into.frame_steps is None:
+            into.frame_steps = into._new_output(into.B, torch.uint8)
+            into._frame_steps_ptr = into._ptr(into.frame_steps)
+        if into._info_skip is None:
+            into._info_skip = dict(into._info_cache, frame_steps=into.frame_steps)
+        out = _lib.AtcLookaheadOut(**{n: into._ptr(t) for n, t in (("reward", into.reward), ("done", into.done), ("n_steps", into.frame_steps),
+                                                                   ("flags", into.flags), ("ac_reward", into.ac_reward),
+                                                                   ("min_sep", into.min_sep), ("obs", into.obs))})
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.atc_branch(self.sector.handle, self.B, self.N, K, M, C.byref(self._state), self._ptr(a), C.byref(into._state),
+                                            C.byref(out), C.byref(self.params), self._stream()))
+            into._launch_traffic()
+        into._prev_actions = None   # (check_held: the child's next step() has no previous step of its own to repeat)
+        self._keep_branch = a   # the actions outlive the launch on a non-default stream (one tensor per call kind, like _keep_lookahead)
+        return into.obs, into.reward, into.done, into._info_skip
+
+    def select(self, src, index, mask=None):
+        """State gather (atc_state_select, include/atc_step.h): env e of this batch takes the state of env index[e] of `src` — commit a
+        branch()'s winner, keep a beam, restore a snapshot.  src: an AtcVecEnv of the same num_aircraft, device, sector and
+        parameters (any num_envs); index: int32 / int64 tensor [B]; mask: optional [B], only envs with mask != 0 are written.  Envs
+        masked out or with an index outside 0 .. src.B - 1 keep what they hold.  For the selected envs self.obs (and raw_obs where
+        both envs have it) is gathered from src's as well — src's rows as they are: branch() does not write a child's raw_obs, so after
+        branch(into=src) they are whatever src.raw_obs held before; self.traffic is refreshed when this env has one.  Returns self.obs."""
+        torch = self.torch
+        self._check_twin(src, "src")
+        if not torch.is_tensor(index):
+            index = torch.as_tensor(np.asarray(index))
+        if index.dtype not in (torch.int32, torch.int64) or index.numel() != self.B:
+            raise ValueError("index must be an int32 / int64 tensor of %d elements" % self.B)
+        # (the range test on the caller's own dtype: an int64 value beyond 32 bits must be refused, not wrapped into range)
+        index = index.to(device=self.device).reshape(self.B)
+        idx = torch.where((index >= 0) & (index < src.B), index, torch.full_like(index, -1)).to(torch.int32).contiguous()
+        m = self._as_mask(mask)
+        if m is not None and m.numel() != self.B:
+            raise ValueError("mask must have %d elements" % self.B)
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.atc_state_select(self.sector.handle, self.N, self.B, C.byref(self._state), src.B, C.byref(src._state),
+                                                  idx.data_ptr(), self._ptr(m), self._stream()))
+            ok = (idx >= 0) & (idx < src.B)
+            if m is not None:
+                ok &= m.reshape(self.B) != 0
+            rows = idx.clamp(0, src.B - 1).long()
+            pairs = [(self.obs, src.obs)] + ([(self.raw_obs, src.raw_obs)] if self.raw_obs is not None and src.raw_obs is not None else [])
+            for mine, theirs in pairs:
+                mine.copy_(torch.where(ok[:, None], theirs.index_select(0, rows), mine))
+            self._launch_traffic()
+        self._prev_actions = None
+        self._keep_select = (idx, m)   # (likewise: index and mask until the next select)
+        return self.obs
+
     def make_launcher(self, actions, stream=None, held=False):
         """Pre-bound `atc_step` call for FIXED buffers (this env's state / outputs, the given device action tensor, the
         given torch stream or the current one): returns a no-argument callable that only launches — host cost of a few

@@ -17,6 +17,8 @@ int atc_skip_launch_counts(uint64_t* out, int n) { return copy_counts(t_skip_lau
 int atc_traffic_launch_counts(uint64_t* out, int n) { return copy_counts(t_traffic_launches, ATC_TRAFFIC_LAUNCH_SLOTS, out, n); }
 int atc_lookahead_launch_counts(uint64_t* out, int n) { return copy_counts(t_look_launches, ATC_LOOKAHEAD_LAUNCH_SLOTS, out, n); }
 int atc_plan_launch_counts(uint64_t* out, int n) { return copy_counts(t_plan_launches, ATC_PLAN_LAUNCH_SLOTS, out, n); }
+int atc_branch_launch_counts(uint64_t* out, int n) { return copy_counts(t_branch_launches, ATC_BRANCH_LAUNCH_SLOTS, out, n); }
+int atc_select_launch_counts(uint64_t* out, int n) { return copy_counts(t_select_launches, ATC_SELECT_LAUNCH_SLOTS, out, n); }
 int atc_lookahead_set_mapping(int candidates_per_workgroup) {
     if (candidates_per_workgroup < 0 || candidates_per_workgroup > ATC_LOOKAHEAD_MAX_M) return fail_arg("candidates per workgroup must be 0 (the library's choice) .. 64");
     t_look_cpg = candidates_per_workgroup;
@@ -448,6 +450,41 @@ int atc_lookahead_plan(const atc_scenario_t* s, int B, int N, int K, int H, int 
                        const atc_plan_out_t* out, const atc_params_t* p, void* stream) {
     if (const int rc = check_candidates(s, B, N, K, &H, M, st, actions, out, p, "segment", "atc_plan_out_t", "segment")) return rc;
     return with_width(N, [&](auto w) { return launch_plan<decltype(w)::value>(s, B, N, K, H, M, st, actions, out, p, (hipStream_t)stream); });
+}
+
+int atc_branch(const atc_scenario_t* s, int B, int N, int K, int M, const atc_state_t* src, const float* actions, const atc_state_t* dst,
+               const atc_lookahead_out_t* out, const atc_params_t* p, void* stream) {
+    // K, then M, before any pointer is looked at
+    if (K < 1 || K > ATC_SKIP_MAX) return fail_arg("K (the branch length) must be 1 .. 255");
+    if (M < 1 || M > ATC_LOOKAHEAD_MAX_M) return fail_arg("M (the number of candidates) must be 1 .. 64");
+    if (!out || !out->reward || !out->done) return fail_arg("null pointer: atc_lookahead_out_t.reward and .done are required");
+    if (!dst || state_has_null(dst)) return fail_arg("null pointer: dst and its six arrays are required");
+    // (pointer values only; a src the later checks refuse has no ranges to compare)
+    if (src && B >= 1 && N >= 1 && N <= ATC_MAX_AIRCRAFT && states_overlap(dst, (unsigned long long)M * B, src, B, N))
+        return fail_arg("dst (M*B envs) overlaps src (B envs)");
+    if (B >= 1 && N >= 1 && N <= ATC_MAX_AIRCRAFT &&
+        ((unsigned long long)M * B * N * ATC_OBS_DIM * 4ull >= (1ull << 32) || (unsigned long long)M * B * 64ull >= (1ull << 32)))
+        return fail_arg("M*B is not a batch size atc_step accepts (M*B*N*40 bytes must stay below 4 GiB): split the candidates");
+    if (!actions) return fail_arg("null pointer");
+    if (const int rc = check_env_args(s, B, N, src, p)) return rc;
+    if (const int rc = check_dt(s, p)) return rc;
+    if (p->mode & ATC_M_ACTIONS_HELD) return fail_arg("ATC_M_ACTIONS_HELD is for atc_step only: every candidate's first step carries a fresh decision");
+    return with_width(N, [&](auto w) { return launch_branch<decltype(w)::value>(s, B, N, K, M, src, actions, dst, out, p, (hipStream_t)stream); });
+}
+
+int atc_state_select(const atc_scenario_t* s, int N, int B_dst, const atc_state_t* dst, int B_src, const atc_state_t* src, const int32_t* index,
+                     const uint8_t* mask, void* stream) {
+    if (N < 1 || N > ATC_MAX_AIRCRAFT || B_dst < 1 || B_src < 1) return fail_arg("need 1 <= N <= 64, B_dst >= 1 and B_src >= 1");
+    if (!index || !dst || !src || state_has_null(dst) || state_has_null(src)) return fail_arg("null pointer");
+    if (states_overlap(dst, B_dst, src, B_src, N)) return fail_arg("dst overlaps src");
+    if (!s) return fail_arg("null pointer");
+    for (const int B : {B_dst, B_src})
+        if ((unsigned long long)B * N * ATC_OBS_DIM * 4ull >= (1ull << 32) || (unsigned long long)B * 64ull >= (1ull << 32))
+            return fail_arg("B*N too large for one launch (B*N*40 bytes must stay below 4 GiB): split the batch");
+    hipLaunchKernelGGL(k_select, dim3(step_grid(B_dst, N)), dim3(kBlock), 0, (hipStream_t)stream, N, B_dst, *dst, B_src, *src, index, mask);
+    HIP_TRY(hipGetLastError());
+    ++t_select_launches[0];
+    return ATC_OK;
 }
 
 }  // extern "C"

@@ -564,7 +564,10 @@ __device__ __forceinline__ bool within(int d, int D) { return (uint32_t)d + (uin
 // ---- first half of AtcGym.step: timestep, rate limits towards the targets, kinematics, MVA floor ---------------------
 // RO ("read only", the look-ahead kernel: csrc/atc_lookahead.inc): every store to atc_state_t on the step path is compiled out — here
 // the side-record stores of WIDE headings.  Default off: every other instantiation is what it was.
-template <bool ONE, bool LAT, bool LDSG = false, bool RO = false>
+// NB ("named bases", the branch kernel: csrc/atc_branch.inc): the phi_wide and stats bases are the ones the caller hands in, as in a
+// single-step launch, while everything else keeps the multi-step form.  A kernarg re-read cannot carry a base that differs per
+// candidate.  Default = ONE: every other instantiation is what it was.
+template <bool ONE, bool LAT, bool LDSG = false, bool RO = false, bool NB = ONE>
 __device__ __forceinline__ Mid step_part_a(const float* __restrict__ grid, const QRates& q, const QKin& qk, const QGrid& qg,
                                            const LaneIds& d, uint32_t tv, double th, int tp, float act_p, LaneState& ls, EnvState& es,
                                            bool repeated, bool all_active, double* wide_named, int zk,
@@ -672,7 +675,7 @@ __device__ __forceinline__ Mid step_part_a(const float* __restrict__ grid, const
             const bool wide = d.lane_valid && (is_wide(tp) || is_wide(a.phi) || (book && is_wide(ls.la_p)));
             if (ATC_RARE(__builtin_amdgcn_ballot_w64(wide) != 0ull)) {
                 if (wide) {
-                    double* w = at<double>(wide_base<ONE>(wide_named, zk), d.i * 32u);
+                    double* w = at<double>(wide_base<NB>(wide_named, zk), d.i * 32u);
                     bool lim;
                     const double T = phi_target_wide(__builtin_fma((double)act_p, q.dec_mp, q.dec_cp), &lim);
                     const double P = is_wide(a.phi) ? w[0] : (double)a.phi;
@@ -824,7 +827,8 @@ struct StepVals {
 };
 // RO: see step_part_a — here the auto-reset path reads the episode number and writes nothing: no per-episode record update, no fences
 // around it, no terminal observation.
-template <int W, bool FULL, bool ONE, bool LAT, bool LDSG = false, bool SKIP = false, bool RO = false>
+// NB: see step_part_a — the per-episode record and the side record are addressed from the bases handed in (stp, wide_named).
+template <int W, bool FULL, bool ONE, bool LAT, bool LDSG = false, bool SKIP = false, bool RO = false, bool NB = ONE>
 __device__ __forceinline__ bool step_part_b(const float* __restrict__ K, const float* __restrict__ grid,
                                             const atc_params_t& p, const StepDerived& q, const QScan& qs, int zk, int N,
                                             const LaneIds& d, const Mid& m, LaneState& ls,
@@ -853,7 +857,7 @@ __device__ __forceinline__ bool step_part_b(const float* __restrict__ K, const f
     constexpr int kWalkBatch = (W == 1) ? 4 : ATC_MVA_BATCH;
     constexpr bool kResolveAfterScan = W >= 16 || W == 1;   // (W = 2 .. 8: the unrolled xor scan with the cell in flight costs 4 - 22 registers)
     WideWords ww = {0, 0};
-    if (LAT) ww = wide_words<ONE>(m.plain, a.phi, wide_named, zk, i);
+    if (LAT) ww = wide_words<NB>(m.plain, a.phi, wide_named, zk, i);
     float mva = 0.0f;
     int pi = 0;
     if (!kResolveAfterScan) {
@@ -1018,7 +1022,7 @@ __device__ __forceinline__ bool step_part_b(const float* __restrict__ K, const f
     if (kObsFirst) {
         // (observation word 3 first, then the heading for the angles — each its own rare look-up for a WIDE heading, before the rest
         // of the observation occupies its registers)
-        const WideWords wo = LAT ? ww : wide_words<ONE>(m.plain, a.phi, wide_named, zk, i);   // (ONE test for both words)
+        const WideWords wo = LAT ? ww : wide_words<NB>(m.plain, a.phi, wide_named, zk, i);   // (ONE test for both words)
         const float phi_f = phi_real(wo.counts), phi_o = __int_as_float(wo.obs_bits);
         ob = get_state(oc, a.x, a.y, x32, y32, hf, phi_f, phi_o, v_real(a.v), hf);   // (word 5 = h - mva follows the resolve)
         if (p.mode & ATC_M_REWARD_SHAPING) shaping = shaping_total(shaping_core(oc, ob.d_faf, ob.phi_rel_faf, ob.o[9], hf, ob.on_gp));
@@ -1078,7 +1082,7 @@ __device__ __forceinline__ bool step_part_b(const float* __restrict__ K, const f
             fl |= conflict ? (uint32_t)ATC_F_CONFLICT : 0u;
         }
         // ---- win / timeout overrides (atc_gym.py:163-173) ---------------------------------------------------------------
-        if (inside_corridor(K, qs.tri_bbox, x32, y32, hf, (double)(LAT ? ww.counts : heading_counts<ONE>(m.plain, a.phi, wide_named, zk, i)))) {
+        if (inside_corridor(K, qs.tri_bbox, x32, y32, hf, (double)(LAT ? ww.counts : heading_counts<NB>(m.plain, a.phi, wide_named, zk, i)))) {
             int bonus = (qs.timestep_limit - es.t) * 5;
             bonus = bonus < 0 ? 0 : bonus;
             r = (float)(10000 + bonus);
@@ -1101,7 +1105,7 @@ __device__ __forceinline__ bool step_part_b(const float* __restrict__ K, const f
         if (kObsFirst) {
             ob.o[5] = alt_above(a.h, mva);
         } else {
-            const WideWords wo = LAT ? ww : wide_words<ONE>(m.plain, a.phi, wide_named, zk, i);
+            const WideWords wo = LAT ? ww : wide_words<NB>(m.plain, a.phi, wide_named, zk, i);
             const float phi_f = phi_real(wo.counts), phi_o = __int_as_float(wo.obs_bits);
             ob = get_state(oc, a.x, a.y, x32, y32, hf, phi_f, phi_o, v_real(a.v), alt_above(a.h, mva));
             if (p.mode & ATC_M_REWARD_SHAPING) shaping = shaping_total(shaping_core(oc, ob.d_faf, ob.phi_rel_faf, ob.o[9], hf, ob.on_gp));
@@ -1192,7 +1196,7 @@ __device__ __forceinline__ bool step_part_b(const float* __restrict__ K, const f
         if (!RO) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
         // (multi-step launches fetch the record's base here, on the rare path: carried from the top of the step it sat in
         // vector-register lanes)
-        int32_t* stats = ONE ? stp : kernarg_reread<int32_t*>(offsetof(StepArgs, st) + offsetof(atc_state_t, stats), zk);
+        int32_t* stats = NB ? stp : kernarg_reread<int32_t*>(offsetof(StepArgs, st) + offsetof(atc_state_t, stats), zk);
         int4* sr = at<int4>(stats, (uint32_t)e * (ATC_STAT_WORDS * 4u));
         const int4 s0 = sr[0];  // episodes, ep_length, ep_return, win_bits
         const int episode = s0.x;
@@ -1726,6 +1730,7 @@ k_serve(const float* __restrict__ blob, int off_grid, atc_state_t st, atc_out_t 
 #include "atc_traffic.inc"       // k_traffic (atc_observe_traffic)
 #include "atc_lookahead.inc"     // k_lookahead (atc_lookahead)
 #include "atc_plan.inc"          // k_plan (atc_lookahead_plan)
+#include "atc_branch.inc"        // k_branch (atc_branch), k_select (atc_state_select)
 
 // ---------------------------------------------------------------------------------------------------------------
 // host side of the C-ABI
@@ -2000,6 +2005,51 @@ static int launch_plan(const atc_scenario* s, int B, int N, int K, int H, int M,
         hipLaunchKernelGGL((k_plan<W, decltype(full)::value>), dim3(g.grid), dim3(kBlock), lds_bytes(s, W >= 32, true), stream, s->d_blob, s->off_grid, B, N, K, H, M, *st, actions, out, *p, q, po->n_steps, po->seg_reward, g.cpg, g.groups, g.tiles);
         HIP_TRY(hipGetLastError());
         ++t_plan_launches[__builtin_ctz(W)];
+        return ATC_OK;
+    });
+}
+
+// ---- branch and select (include/atc_step.h: atc_branch, atc_state_select) -------------------------------------------------------
+// their own launch records (atc_branch_launch_counts: slot = log2(W), the rules of the frame-skip record; atc_select_launch_counts: one slot)
+static thread_local uint64_t t_branch_launches[ATC_BRANCH_LAUNCH_SLOTS] = {0};
+static thread_local uint64_t t_select_launches[ATC_SELECT_LAUNCH_SLOTS] = {0};
+
+// the byte ranges of the six arrays of a batch of B envs x N aircraft; true if any array of `a` shares a byte with any array of `b`.
+// Pointer VALUES only: nothing is dereferenced.
+static void state_ranges(const atc_state_t* st, unsigned long long B, unsigned long long N, uintptr_t lo[6], uintptr_t hi[6]) {
+    const void* ptr[6] = {st->ac, st->alt, st->last_act, st->env, st->stats, st->phi_wide};
+    const unsigned long long bytes[6] = {B * N * 16ull, B * N * 8ull, B * N * 16ull, B * (ATC_ENV_WORDS * 4ull), B * (ATC_STAT_WORDS * 4ull), B * N * 32ull};
+    for (int i = 0; i < 6; ++i) {
+        lo[i] = reinterpret_cast<uintptr_t>(ptr[i]);
+        hi[i] = lo[i] + (uintptr_t)bytes[i];
+    }
+}
+static bool states_overlap(const atc_state_t* a, unsigned long long Ba, const atc_state_t* b, unsigned long long Bb, unsigned long long N) {
+    uintptr_t alo[6], ahi[6], blo[6], bhi[6];
+    state_ranges(a, Ba, N, alo, ahi);
+    state_ranges(b, Bb, N, blo, bhi);
+    for (int i = 0; i < 6; ++i)
+        for (int j = 0; j < 6; ++j)
+            if (alo[i] < bhi[j] && blo[j] < ahi[i]) return true;
+    return false;
+}
+static bool state_has_null(const atc_state_t* st) {
+    return !st->ac || !st->alt || !st->last_act || !st->env || !st->stats || !st->phi_wide;
+}
+
+template <int W>
+static int launch_branch(const atc_scenario* s, int B, int N, int K, int M, const atc_state_t* src, const float* actions, const atc_state_t* dst,
+                         const atc_lookahead_out_t* lo, const atc_params_t* p, hipStream_t stream) {
+    CandGrid g;
+    if (const int rc = cand_grid(B, W, M, &g)) return rc;
+    atc_out_t out;
+    cand_out(lo, &out);
+    const bool any = lo->ac_reward || lo->min_sep;   // k_skip's rule: obs and flags are stored by both forms (csrc/atc_branch.inc)
+    const StepDerived& q = derive(*p, s, 0);
+    return with_flag(any, [&](auto full) {
+        hipLaunchKernelGGL((k_branch<W, decltype(full)::value>), dim3(g.grid), dim3(kBlock), lds_bytes(s, W >= 32, true), stream, s->d_blob, s->off_grid, B, N, K, M, *src, actions, out, *p, q, lo->n_steps, g.cpg, g.groups, g.tiles, *dst);
+        HIP_TRY(hipGetLastError());
+        ++t_branch_launches[__builtin_ctz(W)];
         return ATC_OK;
     });
 }

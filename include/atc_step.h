@@ -808,6 +808,51 @@ int atc_lookahead_plan(const atc_scenario_t* s, int B, int N, int K, int H, int 
 enum { ATC_PLAN_LAUNCH_SLOTS = 7 };
 int atc_plan_launch_counts(uint64_t* out, int n);
 
+/* BRANCH (extension): atc_lookahead that KEEPS the outcomes — M candidate action blocks per env are flown for K steps in ONE launch and
+ * each outcome becomes an env of a second batch `dst` of M*B envs, which a caller can score, expand again (beam search, MCTS expansion,
+ * restore) or commit with atc_state_select instead of flying the winner a second time.  1 <= K <= ATC_SKIP_MAX, 1 <= M <=
+ * ATC_LOOKAHEAD_MAX_M.  Candidate m of env e owns child env c = m*B + e of dst.  Defined per (m, e) as
+ *
+ *     atc_step_skip(s, B, N, K, <a bit-exact private copy of src env e>, actions[m], ..., p, stream)
+ *
+ * i.e. the copy steps with actions[m] until a step reports done or n == K.
+ * DST STATE: the rows of child c in ac, alt, last_act, env and stats are bit for bit what that call leaves behind, the per-episode
+ * record update of an auto-reset inside the call included.  A phi_wide row of dst is written only for an aircraft whose phi_fix or
+ * last_act[.][1] is saturated; every other phi_wide row of dst is unspecified (as atc_state_t allows: its contents are unspecified
+ * while the 32-bit fields are in range).
+ * OUT: atc_lookahead_out_t with atc_lookahead's meaning, word for word: reward and done are required, every other pointer may be
+ * NULL; [M][B...] is the child batch's own [M*B...] layout, so the child env's bound output tensors can be passed; a launch that asks
+ * for neither ac_reward nor min_sep runs a form with those two compiled out (obs and flags, what a child env always binds, are stored
+ * by both forms where requested, as atc_step_skip's fast form stores them).  There is no term_obs.
+ * RESET DRAWS inside the call use the SOURCE env index e and the copy's episode number, like atc_lookahead — which is what makes the
+ * call equal to atc_step_skip on a copy of src.  Afterwards dst is an ordinary batch: later resets of child c are keyed by c.
+ * SRC is read only: all six arrays are byte-identical afterwards.
+ * LIMIT — WIDE headings: atc_lookahead's rule.  An env-candidate that is WIDE at the start (phi_fix or last_act[.][1] of any aircraft
+ * saturated) or becomes WIDE in an executed step is NOT EVALUATED: n_steps = 0, done = 0, every requested output word of (m, e) is 0,
+ * and child c is a byte copy of src env e's rows — the phi_wide rows of its saturated aircraft included.
+ * ATC_ERR_ARG, in this order, the first two before any pointer is looked at: K outside 1 .. ATC_SKIP_MAX; M outside 1 ..
+ * ATC_LOOKAHEAD_MAX_M; out, out->reward or out->done NULL; dst NULL or any of its six pointers NULL; any dst array's byte range (sized
+ * for M*B envs) overlaps any src array's range (sized for B envs); M*B not a batch size atc_step accepts; the argument errors of
+ * atc_step; ATC_M_ACTIONS_HELD in p->mode.
+ * Counted by atc_branch_launch_counts only (slot = log2(W); the rules of atc_skip_launch_counts): every other launch record stays
+ * still.  atc_lookahead_set_mapping governs this call's candidates per workgroup as well; results do not depend on it. */
+int atc_branch(const atc_scenario_t* s, int B, int N, int K, int M, const atc_state_t* src, const float* actions /* [M][B*N*3] */,
+               const atc_state_t* dst /* M*B envs */, const atc_lookahead_out_t* out, const atc_params_t* p, void* stream);
+enum { ATC_BRANCH_LAUNCH_SLOTS = 7 };
+int atc_branch_launch_counts(uint64_t* out, int n);
+
+/* SELECT (extension): gather env states between batches by index — the other half of atc_branch (commit a winner, keep a beam,
+ * restore a snapshot).  For every e < B_dst with mask[e] != 0 (mask NULL: every e) and 0 <= index[e] < B_src, dst env e takes src env
+ * index[e]'s rows of ac, alt, last_act, env and stats, and the phi_wide row of each aircraft with a saturated field (phi_fix or
+ * last_act[.][1]).  Every other dst byte is untouched: envs masked out and envs with a negative or too-large index keep what they
+ * hold.  Indices may repeat.  No arithmetic, no parameters, no random numbers; index and mask are device pointers.
+ * src and dst may not overlap (atc_branch's range check).  ATC_ERR_ARG: N outside 1 .. 64 or B_dst / B_src < 1 (checked first); index
+ * NULL, a NULL state pointer, overlapping arrays.  Counted by atc_select_launch_counts only (one slot). */
+int atc_state_select(const atc_scenario_t* s, int N, int B_dst, const atc_state_t* dst, int B_src, const atc_state_t* src,
+                     const int32_t* index /* [B_dst], device */, const uint8_t* mask /* nullable [B_dst] */, void* stream);
+enum { ATC_SELECT_LAUNCH_SLOTS = 1 };
+int atc_select_launch_counts(uint64_t* out, int n);
+
 #ifdef __cplusplus
 }
 #endif
