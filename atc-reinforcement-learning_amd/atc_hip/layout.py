@@ -82,6 +82,14 @@ LOOKAHEAD_MAX_M, LOOKAHEAD_LAUNCH_SLOTS = 64, 7
 # record (slot = log2(W))
 PLAN_MAX_H = 16
 PLAN_LAUNCH_SLOTS = 7
+# drawn plans (include/atc_step.h: atc_lookahead_plan_sampled, atc_plan_draw): at most SAMPLE_MAX_M candidates drawn inside the launch;
+# DRAW_MEAN_FIRST: the flag of atc_plan_draw_t that makes candidate 0 the mean; DRAW_SCALE_BITS: the bit pattern of the fp32 factor of
+# the draw (0x1.bb67aep-16); their own launch records (sampled: slot = log2(W); draw: one slot)
+SAMPLE_MAX_M = 1024
+DRAW_MEAN_FIRST = 1
+DRAW_SCALE_BITS = 0x37DDB3D7
+PLAN_SAMPLED_LAUNCH_SLOTS = 7
+PLAN_DRAW_LAUNCH_SLOTS = 1
 # branch and select (include/atc_step.h: atc_branch, atc_state_select): their own launch records (atc_branch_launch_counts: slot =
 # log2(W); atc_select_launch_counts: one slot)
 BRANCH_LAUNCH_SLOTS = 7

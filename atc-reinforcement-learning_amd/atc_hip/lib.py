@@ -58,6 +58,14 @@ class AtcPlanOut(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in PLAN_FIELDS]
 
 
+PLAN_DRAW_FIELDS = ("seed", "iteration", "flags")
+
+
+class AtcPlanDraw(C.Structure):
+    """atc_plan_draw_t"""
+    _fields_ = [("seed", C.c_uint64), ("iteration", C.c_uint32), ("flags", C.c_uint32)]
+
+
 class AtcStepCall(C.Structure):
     """atc_step_call_t"""
     _fields_ = [("s", C.c_void_p), ("B", C.c_int32), ("N", C.c_int32), ("st", C.POINTER(AtcState)), ("actions", C.c_void_p),
@@ -70,7 +78,8 @@ EXPORTS = ("atc_abi_version", "atc_last_error", "atc_launch_counts", "atc_host_m
            "atc_step_multi", "atc_step_packet", "atc_rollout", "atc_rollout_hold", "atc_serve_start", "atc_serve_step", "atc_serve_stop",
            "atc_step_skip", "atc_skip_launch_counts", "atc_fill_prefetch_info", "atc_observe_traffic", "atc_traffic_launch_counts",
            "atc_lookahead", "atc_lookahead_launch_counts", "atc_lookahead_set_mapping", "atc_lookahead_plan", "atc_plan_launch_counts",
-           "atc_branch", "atc_branch_launch_counts", "atc_state_select", "atc_select_launch_counts")
+           "atc_branch", "atc_branch_launch_counts", "atc_state_select", "atc_select_launch_counts",
+           "atc_plan_draw", "atc_lookahead_plan_sampled", "atc_plan_sampled_launch_counts", "atc_plan_draw_launch_counts")
 
 def load():
     """Loads libatcstep.so; raises (never falls back) when it has not been built."""
@@ -119,6 +128,11 @@ def load():
     lib.atc_lookahead_set_mapping.argtypes = [ci]
     lib.atc_lookahead_plan.argtypes = [vp, ci, ci, ci, ci, ci, C.POINTER(AtcState), vp, C.POINTER(AtcPlanOut), C.POINTER(AtcParams), vp]
     lib.atc_plan_launch_counts.argtypes = [C.POINTER(C.c_uint64), ci]
+    lib.atc_plan_draw.argtypes = [vp, ci, ci, ci, ci, vp, vp, C.POINTER(AtcPlanDraw), vp, ci, vp, C.POINTER(AtcParams), vp]
+    lib.atc_lookahead_plan_sampled.argtypes = [vp, ci, ci, ci, ci, ci, C.POINTER(AtcState), vp, vp, C.POINTER(AtcPlanDraw), C.POINTER(AtcPlanOut),
+                                               C.POINTER(AtcParams), vp]
+    lib.atc_plan_sampled_launch_counts.argtypes = [C.POINTER(C.c_uint64), ci]
+    lib.atc_plan_draw_launch_counts.argtypes = [C.POINTER(C.c_uint64), ci]
     lib.atc_branch.argtypes = [vp, ci, ci, ci, ci, C.POINTER(AtcState), vp, C.POINTER(AtcState), C.POINTER(AtcLookaheadOut), C.POINTER(AtcParams), vp]
     lib.atc_branch_launch_counts.argtypes = [C.POINTER(C.c_uint64), ci]
     lib.atc_state_select.argtypes = [vp, ci, ci, C.POINTER(AtcState), ci, C.POINTER(AtcState), vp, vp, vp]
@@ -179,6 +193,17 @@ def plan_launch_counts():
     """Launches of the plan look-ahead kernel (atc_lookahead_plan) made by the calling thread so far, by lane-group width:
     {16: n, ...}, widths with a count of zero left out.  Separate from the other launch records, which a plan call leaves as they are."""
     return _counts("atc_plan_launch_counts", L.PLAN_LAUNCH_SLOTS)
+
+
+def plan_sampled_launch_counts():
+    """Launches of the drawn-plan kernel (atc_lookahead_plan_sampled) made by the calling thread so far, by lane-group width:
+    {16: n, ...}, widths with a count of zero left out.  Separate from the other launch records, which a sampled call leaves as they are."""
+    return _counts("atc_plan_sampled_launch_counts", L.PLAN_SAMPLED_LAUNCH_SLOTS)
+
+
+def plan_draw_launch_counts():
+    """Launches of the plan materialiser (atc_plan_draw) made by the calling thread so far: {"draw": n}, or {} before the first."""
+    return _counts("atc_plan_draw_launch_counts", L.PLAN_DRAW_LAUNCH_SLOTS, lambda i: "draw")
 
 
 def branch_launch_counts():

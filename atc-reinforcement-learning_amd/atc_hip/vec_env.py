@@ -416,17 +416,7 @@ class AtcVecEnv:
             raise ValueError("outputs must be a subset of %r" % (allowed,))
         outputs = tuple(n for n in allowed if n in outputs)
         a = self._as_actions(actions, lead=lead)
-        cache = self.__dict__.setdefault("_plan_cache" if plan else "_lookahead_cache", {})
-        key = lead + (outputs,)
-        if key not in cache:
-            B, N, z = self.B, self.N, self._new_output
-            shapes = {"reward": ((M, B), torch.float32), "done": ((M, B), torch.uint8), "n_steps": ((M, B), torch.int16 if plan else torch.uint8),
-                      "seg_reward": (lead + (B,), torch.float32), "flags": ((M, B, N), torch.int16), "min_sep": ((M, B), torch.float32),
-                      "ac_reward": ((M, B, N), torch.float32), "obs": ((M, B, N * L.OBS_DIM), torch.float32)}
-            res = {n: z(*shapes[n]) for n in ("reward", "done", "n_steps") + outputs}
-            out_type, fields = (_lib.AtcPlanOut, _lib.PLAN_FIELDS) if plan else (_lib.AtcLookaheadOut, _lib.LOOKAHEAD_FIELDS)
-            cache[key] = (res, out_type(*[self._ptr(res.get(n)) for n in fields]))
-        res, out = cache[key]
+        res, out = self._candidate_results("_plan_cache" if plan else "_lookahead_cache", lead, outputs, plan)
         call = self._lib.atc_lookahead_plan if plan else self._lib.atc_lookahead
         with torch.cuda.device(self.device):   # (the C argument order: K, [H,] M)
             _lib.check(call(self.sector.handle, self.B, self.N, K, *lead[::-1], C.byref(self._state), self._ptr(a), C.byref(out),
@@ -434,6 +424,120 @@ class AtcVecEnv:
         setattr(self, "_keep_plan" if plan else "_keep_lookahead", a)   # the actions outlive the launch, one tensor per call kind
         self._finish()
         return res
+
+    def _candidate_results(self, cache_name, lead, outputs, plan):
+        """The result tensors of a candidate-scoring call and the output struct that points at them, made once per (M[, H], outputs)"""
+        torch = self.torch
+        cache = self.__dict__.setdefault(cache_name, {})
+        key = lead + (outputs,)
+        if key not in cache:
+            M, B, N, z = lead[0], self.B, self.N, self._new_output
+            shapes = {"reward": ((M, B), torch.float32), "done": ((M, B), torch.uint8), "n_steps": ((M, B), torch.int16 if plan else torch.uint8),
+                      "seg_reward": (lead + (B,), torch.float32), "flags": ((M, B, N), torch.int16), "min_sep": ((M, B), torch.float32),
+                      "ac_reward": ((M, B, N), torch.float32), "obs": ((M, B, N * L.OBS_DIM), torch.float32)}
+            res = {n: z(*shapes[n]) for n in ("reward", "done", "n_steps") + outputs}
+            out_type, fields = (_lib.AtcPlanOut, _lib.PLAN_FIELDS) if plan else (_lib.AtcLookaheadOut, _lib.LOOKAHEAD_FIELDS)
+            cache[key] = (res, out_type(*[self._ptr(res.get(n)) for n in fields]))
+        return cache[key]
+
+    def _draw_h(self, mean):
+        """H of the drawn-plan calls: mean is [H, B, N, 3] or [H, B, N*3]; outside 1 .. 16: ValueError"""
+        if not hasattr(mean, "shape") or len(mean.shape) < 2:
+            raise ValueError("mean must be [H, B, N, 3] or [H, B, N*3]")
+        H = int(mean.shape[0])
+        if not 1 <= H <= L.PLAN_MAX_H:
+            raise ValueError("1 <= H (mean.shape[0]) <= %d" % L.PLAN_MAX_H)
+        return H
+
+    def _draw_source(self, H, mean, std, seed, iteration, mean_first):
+        """(mean, std, atc_plan_draw_t) as the library reads them: contiguous float32 tensors of H * B * N * 3 elements (a python float
+        for std is broadcast once into a cached tensor)"""
+        torch = self.torch
+        mu = self._as_actions(mean, lead=(H,))
+        if isinstance(std, (int, float)):
+            cache = self.__dict__.setdefault("_std_cache", {})
+            key = (H, float(std))
+            if key not in cache:
+                cache.clear()   # (one broadcast tensor at a time: a planner keeps its value from call to call)
+                cache[key] = torch.full((H, self.B, self.N * L.ACT_DIM), float(std), dtype=torch.float32, device=mu.device,
+                                        pin_memory=not mu.is_cuda)
+            sd = cache[key]
+        else:
+            sd = self._as_actions(std, lead=(H,))
+        if not 0 <= int(iteration) < 2 ** 32:
+            raise ValueError("0 <= iteration < 2**32")
+        dr = _lib.AtcPlanDraw(int(seed) & (2 ** 64 - 1), int(iteration), L.DRAW_MEAN_FIRST if mean_first else 0)
+        return mu, sd, dr
+
+    def lookahead_plan_sampled(self, mean, std, K, M, seed=0, iteration=0, mean_first=True, outputs=("seg_reward",)):
+        """Plan query with the candidates DRAWN inside the launch (atc_lookahead_plan_sampled, include/atc_step.h): lookahead_plan() on
+        the M plans draw_plans(mean, std, M, seed, iteration, mean_first) would return, bit for bit, without that [M, H, B, N, 3]
+        tensor ever existing — so M goes up to 1024.  mean, std: [H, B, N, 3] (or [H, B, N*3]) float tensors, std also a python
+        float (broadcast once into a cached tensor); every action component is clamp(mean + std * z, -1, 1) with z a function of (seed,
+        iteration, m, h, aircraft, component) alone, mean 0 and variance 1.  mean_first: candidate 0 is the (clamped) mean itself.
+        1 <= K <= 255, 1 <= H <= 16, 1 <= M <= 1024; continuous action space only.  Returns lookahead_plan()'s dict; the tensors are
+        allocated once per (M, H, outputs) and overwritten by the next such call.  The env state is left as it is.  Regenerate the few
+        plans you need (elites, the winner) with draw_plans(index=...).  AtcSBVecEnv and AtcGym deliberately have no such method."""
+        torch = self.torch
+        K = int(K)
+        if not 1 <= K <= L.SKIP_MAX:
+            raise ValueError("1 <= K <= %d" % L.SKIP_MAX)
+        H = self._draw_h(mean)
+        M = int(M)
+        if not 1 <= M <= L.SAMPLE_MAX_M:
+            raise ValueError("1 <= M <= %d" % L.SAMPLE_MAX_M)
+        mu, sd, dr = self._draw_source(H, mean, std, seed, iteration, mean_first)
+        if not set(outputs) <= set(self.PLAN_OUTPUTS):
+            raise ValueError("outputs must be a subset of %r" % (self.PLAN_OUTPUTS,))
+        outputs = tuple(n for n in self.PLAN_OUTPUTS if n in outputs)
+        if self.params.mode & L.M_DISCRETE:
+            raise ValueError("only the continuous action space is drawn (this env has discrete actions)")
+        res, out = self._candidate_results("_plan_sampled_cache", (M, H), outputs, True)
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.atc_lookahead_plan_sampled(self.sector.handle, self.B, self.N, K, H, M, C.byref(self._state), self._ptr(mu),
+                                                            self._ptr(sd), C.byref(dr), C.byref(out), C.byref(self.params), self._stream()))
+        self._keep_plan_sampled = (mu, sd)   # mean and std outlive the launch (one pair per call kind, like _keep_plan)
+        self._finish()
+        return res
+
+    def draw_plans(self, mean, std, M, seed=0, iteration=0, mean_first=True, index=None, out=None):
+        """The plans lookahead_plan_sampled() scores, as a tensor (atc_plan_draw, include/atc_step.h).  Without `index`: all M
+        candidates, [M, H, B, N, 3].  With `index` ([E, B] or [B], any integer dtype): [E, H, B, N, 3] whose row r holds, for env e,
+        candidate index[r, e] — the elites of a CEM iteration, the winner; an env whose index is outside 0 .. M-1 keeps what the row
+        holds (zeros in a fresh tensor; a value beyond 32 bits is out of range, never wrapped).  out: a float32 device tensor of
+        that many elements to write into instead of a fresh one.  mean, std, M, seed, iteration, mean_first: as in
+        lookahead_plan_sampled()."""
+        torch = self.torch
+        H = self._draw_h(mean)
+        M = int(M)
+        if not 1 <= M <= L.SAMPLE_MAX_M:
+            raise ValueError("1 <= M <= %d" % L.SAMPLE_MAX_M)
+        idx, R = None, M
+        if index is not None:
+            if not torch.is_tensor(index):
+                index = torch.as_tensor(np.asarray(index))
+            if index.dtype.is_floating_point or index.dtype is torch.bool or index.numel() < 1 or index.numel() % self.B:
+                raise ValueError("index must be an integer tensor [E, B] or [B] (B = %d)" % self.B)
+            R = index.numel() // self.B
+            # (the range test on the caller's own dtype: an int64 value beyond 32 bits must be refused, not wrapped into range)
+            index = index.to(device=self.device).reshape(R, self.B)
+            idx = torch.where((index >= 0) & (index < M), index, torch.full_like(index, -1)).to(torch.int32).contiguous()
+        mu, sd, dr = self._draw_source(H, mean, std, seed, iteration, mean_first)
+        if self.params.mode & L.M_DISCRETE:
+            raise ValueError("only the continuous action space is drawn (this env has discrete actions)")
+        shape = (R, H, self.B, self.N, L.ACT_DIM)
+        if out is None:
+            out = (torch.empty if idx is None else torch.zeros)(shape, dtype=torch.float32, device=self.device)
+        elif not (torch.is_tensor(out) and out.is_cuda and out.device == self.device and out.dtype is torch.float32 and out.is_contiguous()
+                  and out.numel() == int(np.prod(shape, dtype=np.int64))):
+            raise ValueError("out must be a contiguous float32 tensor of %s on %s" % (shape, self.device))
+        if self.host_mapped and not (mu.is_cuda and sd.is_cuda):
+            mu, sd = mu.to(self.device), sd.to(self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.atc_plan_draw(self.sector.handle, self.B, self.N, H, M, self._ptr(mu), self._ptr(sd), C.byref(dr),
+                                               None if idx is None else idx.data_ptr(), R, out.data_ptr(), C.byref(self.params), self._stream()))
+        self._keep_draw = (mu, sd, idx)
+        return out.view(shape)
 
     def _check_twin(self, other, what):
         """branch() / select(): `other` must be an AtcVecEnv of the same N and device whose sector blob and atc_params_t are byte-equal"""

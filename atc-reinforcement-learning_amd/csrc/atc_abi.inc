@@ -17,6 +17,8 @@ int atc_skip_launch_counts(uint64_t* out, int n) { return copy_counts(t_skip_lau
 int atc_traffic_launch_counts(uint64_t* out, int n) { return copy_counts(t_traffic_launches, ATC_TRAFFIC_LAUNCH_SLOTS, out, n); }
 int atc_lookahead_launch_counts(uint64_t* out, int n) { return copy_counts(t_look_launches, ATC_LOOKAHEAD_LAUNCH_SLOTS, out, n); }
 int atc_plan_launch_counts(uint64_t* out, int n) { return copy_counts(t_plan_launches, ATC_PLAN_LAUNCH_SLOTS, out, n); }
+int atc_plan_sampled_launch_counts(uint64_t* out, int n) { return copy_counts(t_plan_sampled_launches, ATC_PLAN_SAMPLED_LAUNCH_SLOTS, out, n); }
+int atc_plan_draw_launch_counts(uint64_t* out, int n) { return copy_counts(t_plan_draw_launches, ATC_PLAN_DRAW_LAUNCH_SLOTS, out, n); }
 int atc_branch_launch_counts(uint64_t* out, int n) { return copy_counts(t_branch_launches, ATC_BRANCH_LAUNCH_SLOTS, out, n); }
 int atc_select_launch_counts(uint64_t* out, int n) { return copy_counts(t_select_launches, ATC_SELECT_LAUNCH_SLOTS, out, n); }
 int atc_lookahead_set_mapping(int candidates_per_workgroup) {
@@ -450,6 +452,37 @@ int atc_lookahead_plan(const atc_scenario_t* s, int B, int N, int K, int H, int 
                        const atc_plan_out_t* out, const atc_params_t* p, void* stream) {
     if (const int rc = check_candidates(s, B, N, K, &H, M, st, actions, out, p, "segment", "atc_plan_out_t", "segment")) return rc;
     return with_width(N, [&](auto w) { return launch_plan<decltype(w)::value>(s, B, N, K, H, M, st, actions, out, p, (hipStream_t)stream); });
+}
+
+int atc_lookahead_plan_sampled(const atc_scenario_t* s, int B, int N, int K, int H, int M, const atc_state_t* st, const float* mean,
+                               const float* std, const atc_plan_draw_t* dr, const atc_plan_out_t* out, const atc_params_t* p, void* stream) {
+    const DrawSource src = {mean, std, dr};
+    if (const int rc = check_candidates(s, B, N, K, &H, M, st, nullptr, out, p, "segment", "atc_plan_out_t", "segment", &src)) return rc;
+    return with_width(N, [&](auto w) { return launch_plan_sampled<decltype(w)::value>(s, B, N, K, H, M, st, src, out, p, (hipStream_t)stream); });
+}
+
+int atc_plan_draw(const atc_scenario_t* s, int B, int N, int H, int M, const float* mean, const float* std, const atc_plan_draw_t* dr,
+                  const int32_t* index, int E, float* actions, const atc_params_t* p, void* stream) {
+    // H, then M, then E, before any pointer is looked at
+    if (H < 1 || H > ATC_PLAN_MAX_H) return fail_arg("H (the number of segments of a plan) must be 1 .. 16");
+    if (M < 1 || M > ATC_SAMPLE_MAX_M) return fail_arg("M (the number of drawn candidates) must be 1 .. 1024");
+    if (index && E < 1) return fail_arg("E (the rows of index) must be >= 1");
+    if (!s) return fail_arg("null pointer: s");
+    if (!mean) return fail_arg("null pointer: mean is required");
+    if (!std) return fail_arg("null pointer: std is required");
+    if (!dr) return fail_arg("null pointer: dr (atc_plan_draw_t) is required");
+    if (!actions) return fail_arg("null pointer: actions");
+    if (!p) return fail_arg("null pointer: p");
+    if (p->mode & ATC_M_DISCRETE) return fail_arg("ATC_M_DISCRETE: only the continuous action space is drawn");
+    if (const int rc = check_batch_range(B, N)) return rc;
+    if (const int rc = check_batch_size(B, N)) return rc;
+    const int R = index ? E : M;
+    const unsigned tiles = (unsigned)(((unsigned long long)B * N + kBlock - 1) / kBlock);
+    hipLaunchKernelGGL(k_plan_draw, dim3(tiles, (unsigned)H, (unsigned)std::min(R, 65535)), dim3(kBlock), 0, (hipStream_t)stream, B, N, H, M, R, mean, std,
+                       *dr, index, actions);
+    HIP_TRY(hipGetLastError());
+    ++t_plan_draw_launches[0];
+    return ATC_OK;
 }
 
 int atc_branch(const atc_scenario_t* s, int B, int N, int K, int M, const atc_state_t* src, const float* actions, const atc_state_t* dst,

@@ -1730,6 +1730,7 @@ k_serve(const float* __restrict__ blob, int off_grid, atc_state_t st, atc_out_t 
 #include "atc_traffic.inc"       // k_traffic (atc_observe_traffic)
 #include "atc_lookahead.inc"     // k_lookahead (atc_lookahead)
 #include "atc_plan.inc"          // k_plan (atc_lookahead_plan)
+#include "atc_plan_sampled.inc"  // k_plan_sampled (atc_lookahead_plan_sampled), k_plan_draw (atc_plan_draw)
 #include "atc_branch.inc"        // k_branch (atc_branch), k_select (atc_state_select)
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -1836,13 +1837,21 @@ static int launch_step(const atc_scenario* s, int B, int N, int T, int hold, con
 }
 
 // argument checks shared by every entry point that touches the env state
-static int check_env_args(const atc_scenario_t* s, int B, int N, const atc_state_t* st, const atc_params_t* p) {
-    if (!s || !st || !p) return fail_arg("null pointer");
+// the batch shape alone (atc_plan_draw has no state to check): the range of B and N, then the 32-bit byte offsets of one launch
+static int check_batch_range(int B, int N) {
     if (B < 1 || N < 1 || N > ATC_MAX_AIRCRAFT) return fail_arg("need B >= 1, 1 <= N <= 64");
-    if (!st->ac || !st->alt || !st->last_act || !st->env || !st->stats || !st->phi_wide) return fail_arg("atc_state_t has a null field");
+    return ATC_OK;
+}
+static int check_batch_size(int B, int N) {
     if ((unsigned long long)B * N * ATC_OBS_DIM * 4ull >= (1ull << 32) || (unsigned long long)B * 64ull >= (1ull << 32))
         return fail_arg("B*N too large for one launch (B*N*40 bytes must stay below 4 GiB): split the batch");
     return ATC_OK;
+}
+static int check_env_args(const atc_scenario_t* s, int B, int N, const atc_state_t* st, const atc_params_t* p) {
+    if (!s || !st || !p) return fail_arg("null pointer");
+    if (const int rc = check_batch_range(B, N)) return rc;
+    if (!st->ac || !st->alt || !st->last_act || !st->env || !st->stats || !st->phi_wide) return fail_arg("atc_state_t has a null field");
+    return check_batch_size(B, N);
 }
 
 // the step's time increment against the fixed-point formats of include/atc_step.h: a step's displacement (<= 512 kt) must stay below
@@ -1956,20 +1965,34 @@ static bool cand_out(const O* o, atc_out_t* out) {
     out->obs = o->obs; out->reward = o->reward; out->ac_reward = o->ac_reward; out->done = o->done; out->flags = o->flags; out->min_sep = o->min_sep;
     return o->flags || o->ac_reward || o->min_sep || o->obs;
 }
-// the argument checks of atc_lookahead (H null) and atc_lookahead_plan: K, then H, then M, before any pointer is looked at
+// where a sampled call's candidates come from, in place of an action tensor (include/atc_step.h: atc_lookahead_plan_sampled)
+struct DrawSource {
+    const float* mean;
+    const float* std;
+    const atc_plan_draw_t* dr;
+};
+// the argument checks of atc_lookahead (H null), atc_lookahead_plan and atc_lookahead_plan_sampled (`drawn` given, `actions` unused):
+// K, then H, then M, before any pointer is looked at
 template <typename O>
 static int check_candidates(const atc_scenario_t* s, int B, int N, int K, const int* H, int M, const atc_state_t* st, const float* actions,
-                            const O* out, const atc_params_t* p, const char* k_is, const char* out_type, const char* fresh_per) {
+                            const O* out, const atc_params_t* p, const char* k_is, const char* out_type, const char* fresh_per,
+                            const DrawSource* drawn = nullptr) {
     char msg[160];
     auto fail = [&](const char* fmt, const char* word) { snprintf(msg, sizeof msg, fmt, word); return fail_arg(msg); };
     if (K < 1 || K > ATC_SKIP_MAX) return fail("K (the %s length) must be 1 .. 255", k_is);
     if (H && (*H < 1 || *H > ATC_PLAN_MAX_H)) return fail_arg("H (the number of segments of a plan) must be 1 .. 16");
-    if (M < 1 || M > ATC_LOOKAHEAD_MAX_M) return fail_arg("M (the number of candidates) must be 1 .. 64");
+    if (drawn) {
+        if (M < 1 || M > ATC_SAMPLE_MAX_M) return fail_arg("M (the number of drawn candidates) must be 1 .. 1024");
+        if (!drawn->dr) return fail_arg("null pointer: dr (atc_plan_draw_t) is required");
+        if (!drawn->mean) return fail_arg("null pointer: mean is required");
+        if (!drawn->std) return fail_arg("null pointer: std is required");
+    } else if (M < 1 || M > ATC_LOOKAHEAD_MAX_M) return fail_arg("M (the number of candidates) must be 1 .. 64");
     if (!out || !out->reward || !out->done) return fail("null pointer: %s.reward and .done are required", out_type);
-    if (!actions) return fail_arg("null pointer");
+    if (!drawn && !actions) return fail_arg("null pointer");
     if (const int rc = check_env_args(s, B, N, st, p)) return rc;
     if (const int rc = check_dt(s, p)) return rc;
     if (p->mode & ATC_M_ACTIONS_HELD) return fail("ATC_M_ACTIONS_HELD is for atc_step only: every %s's first step carries a fresh decision", fresh_per);
+    if (drawn && (p->mode & ATC_M_DISCRETE)) return fail_arg("ATC_M_DISCRETE: only the continuous action space is drawn");
     return ATC_OK;
 }
 
@@ -2005,6 +2028,27 @@ static int launch_plan(const atc_scenario* s, int B, int N, int K, int H, int M,
         hipLaunchKernelGGL((k_plan<W, decltype(full)::value>), dim3(g.grid), dim3(kBlock), lds_bytes(s, W >= 32, true), stream, s->d_blob, s->off_grid, B, N, K, H, M, *st, actions, out, *p, q, po->n_steps, po->seg_reward, g.cpg, g.groups, g.tiles);
         HIP_TRY(hipGetLastError());
         ++t_plan_launches[__builtin_ctz(W)];
+        return ATC_OK;
+    });
+}
+
+// ---- drawn plans (include/atc_step.h: atc_lookahead_plan_sampled, atc_plan_draw) -----------------------------------------------
+// their own launch records (atc_plan_sampled_launch_counts: slot = log2(W), the rules of the frame-skip record; atc_plan_draw_launch_counts: one slot)
+static thread_local uint64_t t_plan_sampled_launches[ATC_PLAN_SAMPLED_LAUNCH_SLOTS] = {0};
+static thread_local uint64_t t_plan_draw_launches[ATC_PLAN_DRAW_LAUNCH_SLOTS] = {0};
+
+template <int W>
+static int launch_plan_sampled(const atc_scenario* s, int B, int N, int K, int H, int M, const atc_state_t* st, const DrawSource& src,
+                               const atc_plan_out_t* po, const atc_params_t* p, hipStream_t stream) {
+    CandGrid g;
+    if (const int rc = cand_grid(B, W, M, &g)) return rc;
+    atc_out_t out;
+    const bool any = cand_out(po, &out);
+    const StepDerived& q = derive(*p, s, 0);
+    return with_flag(any, [&](auto full) {
+        hipLaunchKernelGGL((k_plan_sampled<W, decltype(full)::value>), dim3(g.grid), dim3(kBlock), lds_bytes(s, W >= 32, true), stream, s->d_blob, s->off_grid, B, N, K, H, M, *st, src.mean, out, *p, q, po->n_steps, po->seg_reward, g.cpg, g.groups, g.tiles, src.std, *src.dr);
+        HIP_TRY(hipGetLastError());
+        ++t_plan_sampled_launches[__builtin_ctz(W)];
         return ATC_OK;
     });
 }

@@ -808,6 +808,57 @@ int atc_lookahead_plan(const atc_scenario_t* s, int B, int N, int K, int H, int 
 enum { ATC_PLAN_LAUNCH_SLOTS = 7 };
 int atc_plan_launch_counts(uint64_t* out, int n);
 
+/* DRAWN PLANS (extension): atc_lookahead_plan whose M candidates are DRAWN inside the launch from a mean, a standard deviation and a
+ * counter-based key, so that a sampling planner (CEM, MPPI) never builds the [M][H][B*N*3] candidate tensor: M H B N 12 bytes that are
+ * written, read once and thrown away.  The few plans a caller needs afterwards (the elites, the winner) are regenerated exactly from
+ * their candidate numbers by atc_plan_draw.  1 <= M <= ATC_SAMPLE_MAX_M.
+ * THE DRAW.  mean and std are [H][B*N*3] float32 (device).  For candidate m, segment h, aircraft i = e*N + k (its index in this batch)
+ * and component c in {0, 1, 2} (v, h, phi), with mix64 the 64-bit mixer of the reset draws (z += 0x9E3779B97F4A7C15; z = (z ^ z >> 30) *
+ * 0xBF58476D1CE4E5B9; z = (z ^ z >> 27) * 0x94D049BB133111EB; z ^ z >> 31, all modulo 2^64):
+ *
+ *     key = mix64( mix64(seed ^ ((u64)iteration << 32 | (u64)m)) ^ ((u64)h << 32 | (u64)i) )
+ *     w   = mix64(key ^ (u64)(c + 1))
+ *     S   = (w & 0xffff) + ((w >> 16) & 0xffff) + ((w >> 32) & 0xffff) + (w >> 48)            an exact integer 0 .. 262140
+ *     z   = (float)((int)S - 131070) * 0x1.bb67aep-16f                                        ONE fp32 multiply
+ *     a   = fminf(fmaxf(mean[h][i][c] + std[h][i][c] * z, -1.0f), 1.0f)                       two fp32 roundings, never fused
+ *
+ * z is a centred sum of four 16-bit uniforms (Irwin-Hall) scaled by the fp32 nearest to 1 / sqrt((65536^2 - 1) / 3): mean 0, variance
+ * 1, kurtosis 2.7, support +-3.46.  With ATC_DRAW_MEAN_FIRST in dr->flags candidate 0 is the mean itself, a = fminf(fmaxf(mean, -1), 1),
+ * and no key is evaluated for it.  A NaN in mean or std gives a = -1 (fmaxf returns its other operand).  The draw of (m, h, i) does
+ * not depend on M, H, B or on the other candidates; another `iteration` or `seed` gives a fresh set.  Only the continuous action space
+ * is drawn: both calls refuse ATC_M_DISCRETE in p->mode (atc_plan_draw takes p for that alone).
+ *
+ * atc_plan_draw materialises drawn plans: rows r < R of actions [R][H][B*N*3].  index == NULL: R = M and row r is candidate r.
+ * Otherwise R = E and row r of env e is candidate index[r*B + e] (device pointer; indices may repeat); an env whose index is outside
+ * 0 .. M-1 keeps what the row holds (atc_state_select's rule).  ATC_ERR_ARG, in this order: H outside 1 .. ATC_PLAN_MAX_H; M outside
+ * 1 .. ATC_SAMPLE_MAX_M; E < 1 when index is given; a NULL pointer (s, mean, std, dr, actions, p); ATC_M_DISCRETE; B or N out of range.
+ * Counted by atc_plan_draw_launch_counts only (one slot).
+ *
+ * atc_lookahead_plan_sampled is atc_lookahead_plan on the plans atc_plan_draw(index = NULL) would write — every word of every output
+ * equal, bit for bit; no action tensor exists.  The state is untouched and the WIDE rule is atc_lookahead_plan's; draws lie in
+ * [-1, 1], so no drawn action makes a heading WIDE.  ATC_ERR_ARG, in this order, the first three before any pointer is looked at: K
+ * outside 1 .. ATC_SKIP_MAX; H outside 1 .. ATC_PLAN_MAX_H; M outside 1 .. ATC_SAMPLE_MAX_M; dr, mean or std NULL; out, out->reward or
+ * out->done NULL; the argument errors of atc_step; ATC_M_ACTIONS_HELD or ATC_M_DISCRETE in p->mode.
+ * Counted by atc_plan_sampled_launch_counts only (slot = log2(W); the rules of atc_skip_launch_counts): every other launch record stays
+ * still.  atc_lookahead_set_mapping governs this call's candidates per workgroup as well; results do not depend on it. */
+#define ATC_SAMPLE_MAX_M 1024
+#define ATC_DRAW_MEAN_FIRST 1u
+typedef struct atc_plan_draw {
+    uint64_t seed;
+    uint32_t iteration;
+    uint32_t flags;      /* ATC_DRAW_MEAN_FIRST or 0 */
+} atc_plan_draw_t;
+int atc_plan_draw(const atc_scenario_t* s, int B, int N, int H, int M, const float* mean, const float* std /* [H][B*N*3] each */,
+                  const atc_plan_draw_t* dr, const int32_t* index /* nullable [E][B], device */, int E,
+                  float* actions /* [R][H][B*N*3] */, const atc_params_t* p, void* stream);
+int atc_lookahead_plan_sampled(const atc_scenario_t* s, int B, int N, int K, int H, int M, const atc_state_t* st,
+                               const float* mean, const float* std, const atc_plan_draw_t* dr,
+                               const atc_plan_out_t* out, const atc_params_t* p, void* stream);
+enum { ATC_PLAN_SAMPLED_LAUNCH_SLOTS = 7 };
+int atc_plan_sampled_launch_counts(uint64_t* out, int n);
+enum { ATC_PLAN_DRAW_LAUNCH_SLOTS = 1 };
+int atc_plan_draw_launch_counts(uint64_t* out, int n);
+
 /* BRANCH (extension): atc_lookahead that KEEPS the outcomes — M candidate action blocks per env are flown for K steps in ONE launch and
  * each outcome becomes an env of a second batch `dst` of M*B envs, which a caller can score, expand again (beam search, MCTS expansion,
  * restore) or commit with atc_state_select instead of flying the winner a second time.  1 <= K <= ATC_SKIP_MAX, 1 <= M <=
