@@ -564,7 +564,9 @@ class AtcVecEnv:
         has them, frame_steps), `into.traffic` is refreshed when it has one, and (obs, reward, done, info) of `into` is returned as
         step_skip returns it: view the tensors as [M, B, ...].  `into.raw_obs` and `into.term_obs` are NOT written (atc_lookahead_out_t has
         neither): they keep what they held.  An env-candidate with a WIDE heading is not evaluated: frame_steps
-        == 0, zeros, and the child env is a copy of this env's.  AtcSBVecEnv and AtcGym deliberately have no such method."""
+        == 0, zeros, and the child env is a copy of this env's.  For into.step(a, held=True) afterwards, the previous step of child
+        m * B + e is this call's step with actions[m]; of a child that was not evaluated, the previous step of this env's env e.
+        AtcSBVecEnv and AtcGym deliberately have no such method."""
         torch = self.torch
         K = int(K)
         if not 1 <= K <= L.SKIP_MAX:
@@ -598,7 +600,9 @@ class AtcVecEnv:
         parameters (any num_envs); index: int32 / int64 tensor [B]; mask: optional [B], only envs with mask != 0 are written.  Envs
         masked out or with an index outside 0 .. src.B - 1 keep what they hold.  For the selected envs self.obs (and raw_obs where
         both envs have it) is gathered from src's as well — src's rows as they are: branch() does not write a child's raw_obs, so after
-        branch(into=src) they are whatever src.raw_obs held before; self.traffic is refreshed when this env has one.  Returns self.obs."""
+        branch(into=src) they are whatever src.raw_obs held before; self.traffic is refreshed when this env has one.  For
+        step(a, held=True) afterwards, the previous step of a written env is the previous step of the src env it was gathered from; an
+        env that was not written keeps its own.  Returns self.obs."""
         torch = self.torch
         self._check_twin(src, "src")
         if not torch.is_tensor(index):

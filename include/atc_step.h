@@ -198,6 +198,10 @@ enum {
                                         an aircraft under control in the previous step has last_action == its accepted
                                         targets (atc_gym.py:305-311), so no action is counted and the record does not
                                         change.  Envs reset since their last step (timesteps == 0) are handled in full.
+                                        The previous step of an env that atc_branch wrote (child m*B + e) is the branch's step
+                                        with actions[m]; of a child that was not evaluated (a byte copy), src env e's previous
+                                        step; of an env that atc_state_select wrote, the previous step of the src env it was
+                                        gathered from.
                                         Set on a launch whose actions DID change, actions_taken / last_action are wrong. */
 };
 
@@ -877,6 +881,9 @@ int atc_plan_draw_launch_counts(uint64_t* out, int n);
  * by both forms where requested, as atc_step_skip's fast form stores them).  There is no term_obs.
  * RESET DRAWS inside the call use the SOURCE env index e and the copy's episode number, like atc_lookahead — which is what makes the
  * call equal to atc_step_skip on a copy of src.  Afterwards dst is an ordinary batch: later resets of child c are keyed by c.
+ * ATC_M_ACTIONS_HELD afterwards: the previous step of child c is this call's step with actions[m] — an atc_step of dst with those
+ * actions may set the bit (a child that ended and was reset inside the call has timesteps == 0 and is handled in full); the previous
+ * step of a child that was NOT EVALUATED (below) is src env e's previous step.
  * SRC is read only: all six arrays are byte-identical afterwards.
  * LIMIT — WIDE headings: atc_lookahead's rule.  An env-candidate that is WIDE at the start (phi_fix or last_act[.][1] of any aircraft
  * saturated) or becomes WIDE in an executed step is NOT EVALUATED: n_steps = 0, done = 0, every requested output word of (m, e) is 0,
@@ -897,6 +904,8 @@ int atc_branch_launch_counts(uint64_t* out, int n);
  * index[e]'s rows of ac, alt, last_act, env and stats, and the phi_wide row of each aircraft with a saturated field (phi_fix or
  * last_act[.][1]).  Every other dst byte is untouched: envs masked out and envs with a negative or too-large index keep what they
  * hold.  Indices may repeat.  No arithmetic, no parameters, no random numbers; index and mask are device pointers.
+ * ATC_M_ACTIONS_HELD afterwards: the previous step of a written dst env is the previous step of the src env it was gathered from (its
+ * last_act row came along); an env that was not written keeps its own.
  * src and dst may not overlap (atc_branch's range check).  ATC_ERR_ARG: N outside 1 .. 64 or B_dst / B_src < 1 (checked first); index
  * NULL, a NULL state pointer, overlapping arrays.  Counted by atc_select_launch_counts only (one slot). */
 int atc_state_select(const atc_scenario_t* s, int N, int B_dst, const atc_state_t* dst, int B_src, const atc_state_t* src,
