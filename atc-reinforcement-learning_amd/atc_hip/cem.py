@@ -1,6 +1,17 @@
-"""Cross-entropy-method planning on AtcVecEnv's drawn-plan calls: the candidates of every iteration are drawn and scored inside one
-launch (lookahead_plan_sampled), and only the elites are ever materialised (draw_plans(index=...))."""
+"""Sampling planners on AtcVecEnv's drawn-plan calls: the candidates of every iteration are drawn and scored inside one launch
+(lookahead_plan_sampled) and the distribution is refit from per-candidate weights in another (refit_plans), so that nothing scales with
+M * H * B * N.  cem_plan: the cross-entropy method with the elites materialised (draw_plans(index=...)); cem_plan_launch: the same
+with the refit in a launch; mppi_plan: model-predictive path integral control, a softmax-weighted refit over all M candidates."""
 import torch
+
+
+def _start(env, mean, std):
+    """mean and std of a planner's start as fresh [H, B, N, 3] float32 tensors on the env's device (std may be a python float)"""
+    H, B, N = int(mean.shape[0]), env.B, env.N
+    mean = torch.as_tensor(mean, dtype=torch.float32, device=env.device).reshape(H, B, N, 3).clone()
+    std = (torch.full_like(mean, float(std)) if isinstance(std, (int, float))
+           else torch.as_tensor(std, dtype=torch.float32, device=env.device).reshape(H, B, N, 3).clone())
+    return H, mean, std
 
 
 def cem_plan(env, mean, std, K, M, iters, elites, gamma=1.0, seed=0):
@@ -10,12 +21,22 @@ def cem_plan(env, mean, std, K, M, iters, elites, gamma=1.0, seed=0):
     python float).  K: steps a decision is held; M: plans drawn per env and iteration (1 .. 1024); elites: plans per env the refit
     keeps (1 .. M); iters >= 1 (ValueError otherwise).  gamma: discount per SEGMENT applied to seg_reward.  Iteration t draws with
     (seed, iteration=t), candidate 0 being the current mean, so an iteration never scores worse than the mean it started from.
+    The elites are materialised ([E, H, B, N, 3]) and their mean and std taken in torch; cem_plan_launch() is the same loop without
+    that tensor.
     Returns (mean, std, best_first_decision): the refit distribution [H, B, N, 3] twice, and [B, N, 3], the first decision of the
     best plan of the last iteration — what to pass to env.step_skip(..., K)."""
-    H, B, N = int(mean.shape[0]), env.B, env.N
-    mean = torch.as_tensor(mean, dtype=torch.float32, device=env.device).reshape(H, B, N, 3).clone()
-    std = (torch.full_like(mean, float(std)) if isinstance(std, (int, float))
-           else torch.as_tensor(std, dtype=torch.float32, device=env.device).reshape(H, B, N, 3).clone())
+    return _cem(env, mean, std, K, M, iters, elites, gamma, seed, "torch")
+
+
+def cem_plan_launch(env, mean, std, K, M, iters, elites, gamma=1.0, seed=0):
+    """cem_plan() with the refit done by env.refit_plans(): the elites get weight 1 and every other candidate 0, and no tensor of plans
+    exists beyond the best one's [1, H, B, N, 3].  Arguments and results as cem_plan()'s; the two agree to rounding, not bit for bit
+    (refit_plans sums about the clamped mean, in candidate order)."""
+    return _cem(env, mean, std, K, M, iters, elites, gamma, seed, "launch")
+
+
+def _cem(env, mean, std, K, M, iters, elites, gamma, seed, refit):
+    H, mean, std = _start(env, mean, std)
     if int(iters) < 1:
         raise ValueError("iters >= 1 (there is no best plan before the first iteration)")
     if not 1 <= int(elites) <= int(M):
@@ -26,8 +47,41 @@ def cem_plan(env, mean, std, K, M, iters, elites, gamma=1.0, seed=0):
         seg = env.lookahead_plan_sampled(mean, std, K, M, seed=seed, iteration=t, mean_first=True, outputs=("seg_reward",))["seg_reward"]
         score = (seg * discount[None, :, None]).sum(1)                      # [M, B]
         elite_idx = score.topk(int(elites), dim=0).indices                  # [E, B], best first
+        if refit == "launch":
+            weight = torch.zeros_like(score).scatter_(0, elite_idx, 1.0)    # [M, B]: 1 for an env's elites
+            best = env.draw_plans(mean, std, M, seed=seed, iteration=t, mean_first=True, index=elite_idx[:1])[0, 0].clone()
+            mean, std = env.refit_plans(mean, std, M, weight, seed=seed, iteration=t, mean_first=True)
+            continue
         plans = env.draw_plans(mean, std, M, seed=seed, iteration=t, mean_first=True, index=elite_idx)   # [E, H, B, N, 3]
         best = plans[0, 0].clone()
         mean = plans.mean(0)
         std = plans.std(0, unbiased=False)
+    return mean, std, best
+
+
+def mppi_plan(env, mean, std, K, M, iters, temperature, gamma=1.0, seed=0, std_min=0.0):
+    """`iters` MPPI iterations of H-segment plans from the state `env` is in now (which is left as it is): every iteration draws and
+    scores M plans per env in one launch, weighs candidate m of env e with exp((score - max over m) / temperature) — 0 where the
+    candidate was not evaluated (n_steps == 0) — and refits mean and std from ALL M candidates with env.refit_plans(); no plan is
+    materialised but the best one of the last iteration.
+
+    env, mean, std, K, M, gamma, seed: as in cem_plan().  temperature > 0 and iters >= 1 (ValueError otherwise).  std_min: lower
+    bound put on the refit std, so that a sharp softmax does not collapse the search.
+    Returns (mean, std, best_first_decision): [H, B, N, 3] twice, and [B, N, 3], the first decision of the best-scoring plan of the
+    last iteration."""
+    H, mean, std = _start(env, mean, std)
+    if int(iters) < 1:
+        raise ValueError("iters >= 1 (there is no best plan before the first iteration)")
+    if not float(temperature) > 0.0:
+        raise ValueError("temperature > 0")
+    discount = torch.tensor([float(gamma) ** h for h in range(H)], dtype=torch.float32, device=env.device)
+    best = None
+    for t in range(int(iters)):
+        res = env.lookahead_plan_sampled(mean, std, K, M, seed=seed, iteration=t, mean_first=True, outputs=("seg_reward",))   # (n_steps: always)
+        score = (res["seg_reward"] * discount[None, :, None]).sum(1)        # [M, B]
+        weight = torch.exp((score - score.max(0).values) / float(temperature))
+        weight = torch.where(res["n_steps"] == 0, torch.zeros_like(weight), weight)
+        if t == int(iters) - 1:
+            best = env.draw_plans(mean, std, M, seed=seed, iteration=t, mean_first=True, index=score.argmax(0)[None])[0, 0].clone()
+        mean, std = env.refit_plans(mean, std, M, weight, seed=seed, iteration=t, mean_first=True, std_min=std_min)
     return mean, std, best

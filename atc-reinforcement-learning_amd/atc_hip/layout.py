@@ -90,6 +90,8 @@ DRAW_MEAN_FIRST = 1
 DRAW_SCALE_BITS = 0x37DDB3D7
 PLAN_SAMPLED_LAUNCH_SLOTS = 7
 PLAN_DRAW_LAUNCH_SLOTS = 1
+# the refit on drawn plans (include/atc_step.h: atc_plan_refit): its own launch record, one slot
+PLAN_REFIT_LAUNCH_SLOTS = 1
 # branch and select (include/atc_step.h: atc_branch, atc_state_select): their own launch records (atc_branch_launch_counts: slot =
 # log2(W); atc_select_launch_counts: one slot)
 BRANCH_LAUNCH_SLOTS = 7

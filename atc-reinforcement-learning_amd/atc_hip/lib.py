@@ -79,7 +79,8 @@ EXPORTS = ("atc_abi_version", "atc_last_error", "atc_launch_counts", "atc_host_m
            "atc_step_skip", "atc_skip_launch_counts", "atc_fill_prefetch_info", "atc_observe_traffic", "atc_traffic_launch_counts",
            "atc_lookahead", "atc_lookahead_launch_counts", "atc_lookahead_set_mapping", "atc_lookahead_plan", "atc_plan_launch_counts",
            "atc_branch", "atc_branch_launch_counts", "atc_state_select", "atc_select_launch_counts",
-           "atc_plan_draw", "atc_lookahead_plan_sampled", "atc_plan_sampled_launch_counts", "atc_plan_draw_launch_counts")
+           "atc_plan_draw", "atc_lookahead_plan_sampled", "atc_plan_sampled_launch_counts", "atc_plan_draw_launch_counts",
+           "atc_plan_refit", "atc_plan_refit_launch_counts")
 
 def load():
     """Loads libatcstep.so; raises (never falls back) when it has not been built."""
@@ -133,6 +134,8 @@ def load():
                                                C.POINTER(AtcParams), vp]
     lib.atc_plan_sampled_launch_counts.argtypes = [C.POINTER(C.c_uint64), ci]
     lib.atc_plan_draw_launch_counts.argtypes = [C.POINTER(C.c_uint64), ci]
+    lib.atc_plan_refit.argtypes = [vp, ci, ci, ci, ci, vp, vp, C.POINTER(AtcPlanDraw), vp, vp, vp, C.POINTER(AtcParams), vp]
+    lib.atc_plan_refit_launch_counts.argtypes = [C.POINTER(C.c_uint64), ci]
     lib.atc_branch.argtypes = [vp, ci, ci, ci, ci, C.POINTER(AtcState), vp, C.POINTER(AtcState), C.POINTER(AtcLookaheadOut), C.POINTER(AtcParams), vp]
     lib.atc_branch_launch_counts.argtypes = [C.POINTER(C.c_uint64), ci]
     lib.atc_state_select.argtypes = [vp, ci, ci, C.POINTER(AtcState), ci, C.POINTER(AtcState), vp, vp, vp]
@@ -204,6 +207,11 @@ def plan_sampled_launch_counts():
 def plan_draw_launch_counts():
     """Launches of the plan materialiser (atc_plan_draw) made by the calling thread so far: {"draw": n}, or {} before the first."""
     return _counts("atc_plan_draw_launch_counts", L.PLAN_DRAW_LAUNCH_SLOTS, lambda i: "draw")
+
+
+def plan_refit_launch_counts():
+    """Launches of the refit on drawn plans (atc_plan_refit) made by the calling thread so far: {"refit": n}, or {} before the first."""
+    return _counts("atc_plan_refit_launch_counts", L.PLAN_REFIT_LAUNCH_SLOTS, lambda i: "refit")
 
 
 def branch_launch_counts():

@@ -539,6 +539,51 @@ class AtcVecEnv:
         self._keep_draw = (mu, sd, idx)
         return out.view(shape)
 
+    def refit_plans(self, mean, std, M, weight, seed=0, iteration=0, mean_first=True, out=None, std_min=0.0):
+        """The distribution update of a sampling planner on the plans lookahead_plan_sampled() scored, none materialised
+        (atc_plan_refit, include/atc_step.h): the weighted mean and standard deviation over the M candidates of (seed, iteration), each
+        regenerated inside the launch.  weight: [M, B] (converted to contiguous float32 on this env's device) — 0/1 for CEM elites,
+        softmax(score / temperature) for MPPI; a candidate takes part in its env iff 0 < weight <= FLT_MAX (NaN, zero, negative and
+        infinite weights leave it out; give 0 to candidates with n_steps == 0).  Returns (mean', std'), each [H, B, N, 3]: without
+        `out`, fresh tensors that start as copies of the inputs as the library reads them, so an env with no participating candidate
+        keeps its distribution; out=(mean_t, std_t) names contiguous float32 device tensors of H*B*N*3 elements to write instead — they
+        may be the inputs themselves (an in-place update), any other overlap is refused by the library.  std_min > 0 clamps the
+        returned std from below (torch, on the small result).  mean, std, M, seed, iteration, mean_first: as in
+        lookahead_plan_sampled(); continuous action space only."""
+        torch = self.torch
+        H = self._draw_h(mean)
+        M = int(M)
+        if not 1 <= M <= L.SAMPLE_MAX_M:
+            raise ValueError("1 <= M <= %d" % L.SAMPLE_MAX_M)
+        if not torch.is_tensor(weight):
+            weight = torch.as_tensor(np.asarray(weight))
+        if tuple(weight.shape) != (M, self.B):
+            raise ValueError("weight must be [M, B] = [%d, %d], got %r" % (M, self.B, tuple(weight.shape)))
+        w = weight.to(device=self.device, dtype=torch.float32).contiguous()
+        mu, sd, dr = self._draw_source(H, mean, std, seed, iteration, mean_first)
+        if self.params.mode & L.M_DISCRETE:
+            raise ValueError("only the continuous action space is drawn (this env has discrete actions)")
+        if self.host_mapped and not (mu.is_cuda and sd.is_cuda):
+            mu, sd = mu.to(self.device), sd.to(self.device)
+        shape = (H, self.B, self.N, L.ACT_DIM)
+        if out is None:
+            new_mu, new_sd = mu.clone(), sd.clone()
+        else:
+            if not (isinstance(out, (tuple, list)) and len(out) == 2):
+                raise ValueError("out must be a pair (mean_t, std_t)")
+            new_mu, new_sd = out
+            for t in (new_mu, new_sd):
+                if not (torch.is_tensor(t) and t.is_cuda and t.device == self.device and t.dtype is torch.float32 and t.is_contiguous()
+                        and t.numel() == int(np.prod(shape, dtype=np.int64))):
+                    raise ValueError("out must hold contiguous float32 tensors of %s on %s" % (shape, self.device))
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.atc_plan_refit(self.sector.handle, self.B, self.N, H, M, self._ptr(mu), self._ptr(sd), C.byref(dr),
+                                                w.data_ptr(), new_mu.data_ptr(), new_sd.data_ptr(), C.byref(self.params), self._stream()))
+        self._keep_refit = (mu, sd, w)   # the inputs outlive the launch (like _keep_draw)
+        if float(std_min) > 0.0:
+            new_sd.clamp_(min=float(std_min))
+        return new_mu.view(shape), new_sd.view(shape)
+
     def _check_twin(self, other, what):
         """branch() / select(): `other` must be an AtcVecEnv of the same N and device whose sector blob and atc_params_t are byte-equal"""
         if not isinstance(other, AtcVecEnv):

@@ -19,6 +19,7 @@ int atc_lookahead_launch_counts(uint64_t* out, int n) { return copy_counts(t_loo
 int atc_plan_launch_counts(uint64_t* out, int n) { return copy_counts(t_plan_launches, ATC_PLAN_LAUNCH_SLOTS, out, n); }
 int atc_plan_sampled_launch_counts(uint64_t* out, int n) { return copy_counts(t_plan_sampled_launches, ATC_PLAN_SAMPLED_LAUNCH_SLOTS, out, n); }
 int atc_plan_draw_launch_counts(uint64_t* out, int n) { return copy_counts(t_plan_draw_launches, ATC_PLAN_DRAW_LAUNCH_SLOTS, out, n); }
+int atc_plan_refit_launch_counts(uint64_t* out, int n) { return copy_counts(t_plan_refit_launches, ATC_PLAN_REFIT_LAUNCH_SLOTS, out, n); }
 int atc_branch_launch_counts(uint64_t* out, int n) { return copy_counts(t_branch_launches, ATC_BRANCH_LAUNCH_SLOTS, out, n); }
 int atc_select_launch_counts(uint64_t* out, int n) { return copy_counts(t_select_launches, ATC_SELECT_LAUNCH_SLOTS, out, n); }
 int atc_lookahead_set_mapping(int candidates_per_workgroup) {
@@ -482,6 +483,44 @@ int atc_plan_draw(const atc_scenario_t* s, int B, int N, int H, int M, const flo
                        *dr, index, actions);
     HIP_TRY(hipGetLastError());
     ++t_plan_draw_launches[0];
+    return ATC_OK;
+}
+
+int atc_plan_refit(const atc_scenario_t* s, int B, int N, int H, int M, const float* mean, const float* std, const atc_plan_draw_t* dr,
+                   const float* weight, float* new_mean, float* new_std, const atc_params_t* p, void* stream) {
+    // H, then M, before any pointer is looked at
+    if (H < 1 || H > ATC_PLAN_MAX_H) return fail_arg("H (the number of segments of a plan) must be 1 .. 16");
+    if (M < 1 || M > ATC_SAMPLE_MAX_M) return fail_arg("M (the number of drawn candidates) must be 1 .. 1024");
+    if (!s) return fail_arg("null pointer: s");
+    if (!mean) return fail_arg("null pointer: mean is required");
+    if (!std) return fail_arg("null pointer: std is required");
+    if (!dr) return fail_arg("null pointer: dr (atc_plan_draw_t) is required");
+    if (!weight) return fail_arg("null pointer: weight is required");
+    if (!new_mean) return fail_arg("null pointer: new_mean");
+    if (!new_std) return fail_arg("null pointer: new_std");
+    if (!p) return fail_arg("null pointer: p");
+    if (p->mode & ATC_M_DISCRETE) return fail_arg("ATC_M_DISCRETE: only the continuous action space is drawn");
+    if (const int rc = check_batch_range(B, N)) return rc;
+    if (const int rc = check_batch_size(B, N)) return rc;
+    {   // the five byte ranges (pointer VALUES only): new_mean == mean and new_std == std exactly are the in-place update, any other overlap is refused
+        const char* const name[5] = {"mean", "std", "weight", "new_mean", "new_std"};
+        const void* const ptr[5] = {mean, std, weight, new_mean, new_std};
+        const uintptr_t rows = (uintptr_t)H * (uintptr_t)B * (uintptr_t)N * 12u, wts = (uintptr_t)M * (uintptr_t)B * 4u;
+        for (int a = 0; a < 5; ++a)
+            for (int b = a + 1; b < 5; ++b) {
+                if ((a == 0 && b == 3 && mean == new_mean) || (a == 1 && b == 4 && std == new_std)) continue;
+                const uintptr_t alo = reinterpret_cast<uintptr_t>(ptr[a]), blo = reinterpret_cast<uintptr_t>(ptr[b]);
+                if (alo < blo + (b == 2 ? wts : rows) && blo < alo + (a == 2 ? wts : rows)) {
+                    char msg[160];
+                    snprintf(msg, sizeof msg, "%s overlaps %s (only new_mean == mean and new_std == std, as equal pointers, may share memory)", name[a], name[b]);
+                    return fail_arg(msg);
+                }
+            }
+    }
+    const unsigned tiles = (unsigned)(((unsigned long long)B * N + kBlock - 1) / kBlock);
+    hipLaunchKernelGGL(k_plan_refit, dim3(tiles, (unsigned)H), dim3(kBlock), 0, (hipStream_t)stream, B, N, H, M, mean, std, *dr, weight, new_mean, new_std);
+    HIP_TRY(hipGetLastError());
+    ++t_plan_refit_launches[0];
     return ATC_OK;
 }
 

@@ -863,6 +863,41 @@ int atc_plan_sampled_launch_counts(uint64_t* out, int n);
 enum { ATC_PLAN_DRAW_LAUNCH_SLOTS = 1 };
 int atc_plan_draw_launch_counts(uint64_t* out, int n);
 
+/* atc_plan_refit: the distribution update of a sampling planner on the drawn plans, none materialised — the weighted mean and standard
+ * deviation over the M candidates of one (seed, iteration), each regenerated in registers.  weight is [M][B] float32 (device): 0/1 for
+ * the elites of CEM, softmax(score / lambda) for MPPI, anything else for a reward-weighted refit.  Candidate m of env e PARTICIPATES iff
+ * 0 < weight[m*B + e] <= FLT_MAX: a NaN, zero, negative or infinite weight leaves it out (give weight 0 to a candidate that was not
+ * evaluated, n_steps == 0).  For every segment h, aircraft i = e*N + k and component c, with a_m exactly the value atc_plan_draw writes
+ * for (m, h, i, c) — same key, same ATC_DRAW_MEAN_FIRST rule, same NaN behaviour:
+ *
+ *     ctr = fminf(fmaxf(mean[h][i][c], -1), 1)
+ *     W = 0; s1 = 0; s2 = 0
+ *     for m = 0 .. M-1 ascending, participating candidates only:
+ *         w = weight[m][e];  d = a_m - ctr;  t = w * d
+ *         s1 = s1 + t;  s2 = s2 + t * d;  W = W + w
+ *     q = s1 / W
+ *     new_mean[h][i][c] = ctr + q
+ *     new_std [h][i][c] = sqrtf(fmaxf(s2 / W - q * q, 0))
+ *
+ * Every operation is fp32 and rounded once, nothing is fused, the division and the square root are correctly rounded, and the loop is
+ * sequential in m: a loop over M in any IEEE fp32 arithmetic reproduces every word (tests/plan_refit_ref.py does, in numpy).  The moments
+ * are taken about ctr because their terms then scale as std * z: E[a^2] - E[a]^2 would lose a standard deviation below about 1e-3.
+ * An env with no participating candidate is NOT WRITTEN: its new_mean / new_std rows keep what they hold (atc_state_select's rule).  If an
+ * env's participating weights sum beyond FLT_MAX its rows are unspecified; nothing faults and no other env is affected.
+ * ALIASING: new_mean == mean and new_std == std are allowed as exactly equal pointers (the in-place update: a lane reads its own words
+ * before it writes them).  Any other overlap among the byte ranges of mean, std, new_mean, new_std (H*B*N*12 bytes each) and weight
+ * (M*B*4 bytes) is ATC_ERR_ARG.
+ * ATC_ERR_ARG, in this order, the first two before any pointer is looked at: H outside 1 .. ATC_PLAN_MAX_H; M outside 1 ..
+ * ATC_SAMPLE_MAX_M; a NULL pointer (s, mean, std, dr, weight, new_mean, new_std, p); ATC_M_DISCRETE in p->mode; B or N out of range; the
+ * overlap rule.  Counted by atc_plan_refit_launch_counts only (one slot); a refused call moves no launch record. */
+int atc_plan_refit(const atc_scenario_t* s, int B, int N, int H, int M,
+                   const float* mean, const float* std /* [H][B*N*3] each */, const atc_plan_draw_t* dr,
+                   const float* weight /* [M][B], device */,
+                   float* new_mean, float* new_std /* [H][B*N*3] each */,
+                   const atc_params_t* p, void* stream);
+enum { ATC_PLAN_REFIT_LAUNCH_SLOTS = 1 };
+int atc_plan_refit_launch_counts(uint64_t* out, int n);
+
 /* BRANCH (extension): atc_lookahead that KEEPS the outcomes — M candidate action blocks per env are flown for K steps in ONE launch and
  * each outcome becomes an env of a second batch `dst` of M*B envs, which a caller can score, expand again (beam search, MCTS expansion,
  * restore) or commit with atc_state_select instead of flying the winner a second time.  1 <= K <= ATC_SKIP_MAX, 1 <= M <=
