@@ -1,7 +1,11 @@
 """Sampling planners on AtcVecEnv's drawn-plan calls: the candidates of every iteration are drawn and scored inside one launch
 (lookahead_plan_sampled) and the distribution is refit from per-candidate weights in another (refit_plans), so that nothing scales with
 M * H * B * N.  cem_plan: the cross-entropy method with the elites materialised (draw_plans(index=...)); cem_plan_launch: the same
-with the refit in a launch; mppi_plan: model-predictive path integral control, a softmax-weighted refit over all M candidates."""
+with the refit in a launch; mppi_plan: model-predictive path integral control, a softmax-weighted refit over all M candidates.
+cem_plan_scored / mppi_plan_scored: the same two planners with the glue between the scoring and the refit — discount, ranking, weights,
+winner — in a launch of its own (score_plans), so that an iteration is three launches, lookahead_plan_sampled -> score_plans ->
+refit_plans, on buffers allocated once; their ranking is defined (ties to the lower candidate number) and leaves out candidates that
+were not evaluated."""
 import torch
 
 
@@ -85,3 +89,51 @@ def mppi_plan(env, mean, std, K, M, iters, temperature, gamma=1.0, seed=0, std_m
             best = env.draw_plans(mean, std, M, seed=seed, iteration=t, mean_first=True, index=score.argmax(0)[None])[0, 0].clone()
         mean, std = env.refit_plans(mean, std, M, weight, seed=seed, iteration=t, mean_first=True, std_min=std_min)
     return mean, std, best
+
+
+def _score_buffers(env, M, B):
+    """score, weight and top of score_plans(top=1), allocated once for a whole planner call"""
+    return {"score": torch.empty((M, B), dtype=torch.float32, device=env.device),
+            "weight": torch.empty((M, B), dtype=torch.float32, device=env.device),
+            "top": torch.empty((1, B), dtype=torch.int32, device=env.device)}
+
+
+def _scored(env, mean, std, K, M, iters, gamma, seed, std_min, **how):
+    H, mean, std = _start(env, mean, std)
+    if int(iters) < 1:
+        raise ValueError("iters >= 1 (there is no best plan before the first iteration)")
+    buf = _score_buffers(env, int(M), env.B)
+    best = None
+    for t in range(int(iters)):
+        res = env.lookahead_plan_sampled(mean, std, K, M, seed=seed, iteration=t, mean_first=True, outputs=("seg_reward",))   # (n_steps: always)
+        env.score_plans(res["seg_reward"], n_steps=res["n_steps"], gamma=gamma, top=1, out=buf, **how)
+        if t == int(iters) - 1:
+            best = env.draw_plans(mean, std, M, seed=seed, iteration=t, mean_first=True, index=buf["top"][:1])[0, 0].clone()
+        mean, std = env.refit_plans(mean, std, M, buf["weight"], seed=seed, iteration=t, mean_first=True, std_min=std_min)
+    return mean, std, best
+
+
+def cem_plan_scored(env, mean, std, K, M, iters, elites, gamma=1.0, seed=0):
+    """cem_plan_launch() with everything between the scoring launch and the refit launch done by env.score_plans(): an iteration is
+    lookahead_plan_sampled -> score_plans -> refit_plans, three launches on the env's stream, and the score / weight / top buffers are
+    allocated once before the loop.  Arguments and results as cem_plan()'s.  It differs from the older loops in three ways:
+    candidates that were NOT EVALUATED (n_steps == 0, a WIDE heading) and candidates whose score is not finite are left out of the
+    elites (the older loops let their score of 0 compete); equal scores go to the LOWER candidate number (torch.topk does not say);
+    the discount of segment h is the fp32 running product gamma * gamma * ... (the older loops round float(gamma) ** h once).  So the
+    results agree with cem_plan_launch() only where none of that bites.  An env with no valid candidate keeps its mean and std, and its
+    best_first_decision row is zero."""
+    if not 1 <= int(elites) <= int(M):
+        raise ValueError("1 <= elites <= M")
+    return _scored(env, mean, std, K, M, iters, gamma, seed, 0.0, mode="elite", elites=int(elites))
+
+
+def mppi_plan_scored(env, mean, std, K, M, iters, temperature, gamma=1.0, seed=0, std_min=0.0):
+    """mppi_plan() with the softmax weights and the winner computed by env.score_plans(): an iteration is lookahead_plan_sampled ->
+    score_plans -> refit_plans, three launches on the env's stream, and the score / weight / top buffers are allocated once before the
+    loop.  Arguments and results as mppi_plan()'s.  It differs from mppi_plan() in three ways: candidates that were NOT EVALUATED or
+    whose score is not finite are left out of the maximum and of the winner as well (mppi_plan() only zeroes the weight of the
+    former); equal scores go to the LOWER candidate number; the discount of segment h is the fp32 running product (mppi_plan() rounds
+    float(gamma) ** h once).  So the results agree with mppi_plan() only where none of that bites."""
+    if not float(temperature) > 0.0:
+        raise ValueError("temperature > 0")
+    return _scored(env, mean, std, K, M, iters, gamma, seed, std_min, mode="softmax", temperature=float(temperature))

@@ -92,6 +92,11 @@ PLAN_SAMPLED_LAUNCH_SLOTS = 7
 PLAN_DRAW_LAUNCH_SLOTS = 1
 # the refit on drawn plans (include/atc_step.h: atc_plan_refit): its own launch record, one slot
 PLAN_REFIT_LAUNCH_SLOTS = 1
+# scoring and ranking of drawn plans (include/atc_step.h: atc_plan_score): at most SCORE_MAX_TOP rows of best candidate numbers; the two
+# modes of atc_plan_score_t; its own launch record, one slot
+SCORE_MAX_TOP = 64
+SCORE_ELITE, SCORE_SOFTMAX = 0, 1
+PLAN_SCORE_LAUNCH_SLOTS = 1
 # branch and select (include/atc_step.h: atc_branch, atc_state_select): their own launch records (atc_branch_launch_counts: slot =
 # log2(W); atc_select_launch_counts: one slot)
 BRANCH_LAUNCH_SLOTS = 7

@@ -66,6 +66,14 @@ class AtcPlanDraw(C.Structure):
     _fields_ = [("seed", C.c_uint64), ("iteration", C.c_uint32), ("flags", C.c_uint32)]
 
 
+PLAN_SCORE_FIELDS = ("mode", "elites", "gamma", "temperature")
+
+
+class AtcPlanScore(C.Structure):
+    """atc_plan_score_t"""
+    _fields_ = [("mode", C.c_uint32), ("elites", C.c_int32), ("gamma", C.c_float), ("temperature", C.c_float)]
+
+
 class AtcStepCall(C.Structure):
     """atc_step_call_t"""
     _fields_ = [("s", C.c_void_p), ("B", C.c_int32), ("N", C.c_int32), ("st", C.POINTER(AtcState)), ("actions", C.c_void_p),
@@ -80,7 +88,7 @@ EXPORTS = ("atc_abi_version", "atc_last_error", "atc_launch_counts", "atc_host_m
            "atc_lookahead", "atc_lookahead_launch_counts", "atc_lookahead_set_mapping", "atc_lookahead_plan", "atc_plan_launch_counts",
            "atc_branch", "atc_branch_launch_counts", "atc_state_select", "atc_select_launch_counts",
            "atc_plan_draw", "atc_lookahead_plan_sampled", "atc_plan_sampled_launch_counts", "atc_plan_draw_launch_counts",
-           "atc_plan_refit", "atc_plan_refit_launch_counts")
+           "atc_plan_refit", "atc_plan_refit_launch_counts", "atc_plan_score", "atc_plan_score_launch_counts")
 
 def load():
     """Loads libatcstep.so; raises (never falls back) when it has not been built."""
@@ -136,6 +144,8 @@ def load():
     lib.atc_plan_draw_launch_counts.argtypes = [C.POINTER(C.c_uint64), ci]
     lib.atc_plan_refit.argtypes = [vp, ci, ci, ci, ci, vp, vp, C.POINTER(AtcPlanDraw), vp, vp, vp, C.POINTER(AtcParams), vp]
     lib.atc_plan_refit_launch_counts.argtypes = [C.POINTER(C.c_uint64), ci]
+    lib.atc_plan_score.argtypes = [vp, ci, ci, ci, vp, vp, C.POINTER(AtcPlanScore), vp, vp, vp, ci, vp]
+    lib.atc_plan_score_launch_counts.argtypes = [C.POINTER(C.c_uint64), ci]
     lib.atc_branch.argtypes = [vp, ci, ci, ci, ci, C.POINTER(AtcState), vp, C.POINTER(AtcState), C.POINTER(AtcLookaheadOut), C.POINTER(AtcParams), vp]
     lib.atc_branch_launch_counts.argtypes = [C.POINTER(C.c_uint64), ci]
     lib.atc_state_select.argtypes = [vp, ci, ci, C.POINTER(AtcState), ci, C.POINTER(AtcState), vp, vp, vp]
@@ -212,6 +222,11 @@ def plan_draw_launch_counts():
 def plan_refit_launch_counts():
     """Launches of the refit on drawn plans (atc_plan_refit) made by the calling thread so far: {"refit": n}, or {} before the first."""
     return _counts("atc_plan_refit_launch_counts", L.PLAN_REFIT_LAUNCH_SLOTS, lambda i: "refit")
+
+
+def plan_score_launch_counts():
+    """Launches of the scoring and ranking of drawn plans (atc_plan_score) made by the calling thread so far: {"score": n}, or {} before the first."""
+    return _counts("atc_plan_score_launch_counts", L.PLAN_SCORE_LAUNCH_SLOTS, lambda i: "score")
 
 
 def branch_launch_counts():

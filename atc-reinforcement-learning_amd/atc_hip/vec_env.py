@@ -584,6 +584,74 @@ class AtcVecEnv:
             new_sd.clamp_(min=float(std_min))
         return new_mu.view(shape), new_sd.view(shape)
 
+    def score_plans(self, seg_reward, n_steps=None, *, mode="elite", elites=None, temperature=None, gamma=1.0, top=1, out=None):
+        """What lies between lookahead_plan_sampled() and refit_plans() in a sampling planner's iteration, in one launch on this env's
+        current stream (atc_plan_score, include/atc_step.h).  seg_reward: [M, H, B] float32 and n_steps: [M, B] int16 / uint16 or None,
+        contiguous tensors on this env's device as lookahead_plan_sampled() returns them (nothing is converted: ValueError otherwise).
+        score[m, e] = seg[m, 0, e] + seg[m, 1, e] * gamma + seg[m, 2, e] * (gamma * gamma) + ... in fp32, left to right, the discount a
+        running product.  A candidate is VALID iff it was evaluated (n_steps != 0, or n_steps is None) and its score is finite; the
+        valid candidates of an env are ordered by score descending, equal scores (+0 == -0) to the LOWER candidate number.
+        mode="elite": weight 1.0 for the first min(elites, valid) of that order, 0.0 for the rest (1 <= elites <= M).
+        mode="softmax": weight exp((score - best score) / temperature) for a valid candidate — exactly 1.0 for the best —, 0.0 for
+        an invalid one (temperature > 0 and finite).
+        Returns {"score": [M, B] float32, "weight": [M, B] float32, "top": [top, B] int32}: top[r, e] is the candidate at position r
+        of env e's order (what draw_plans(index=) takes), -1 where the env has fewer valid candidates; 0 <= top <= 64, and with top=0
+        there is no "top" entry.  An env without a valid candidate has weight 0 everywhere, which refit_plans() leaves unwritten.
+        out: a dict with contiguous device tensors of those names, shapes and dtypes to write into; with it the method allocates
+        nothing, without it exactly its results.  No two of the tensors may share memory (refused by the library).  The method reads
+        no action and no state, so it works on discrete-action envs too."""
+        torch = self.torch
+        dev = self.device
+
+        def on_device(t, dtypes, shape, what):
+            if not (torch.is_tensor(t) and t.is_cuda and t.device == dev and t.dtype in dtypes and t.is_contiguous()
+                    and (shape is None or tuple(t.shape) == shape)):
+                raise ValueError("%s must be a contiguous %s tensor%s on %s" % (
+                    what, " / ".join(str(d) for d in dtypes), "" if shape is None else " of %r" % (shape,), dev))
+            return t
+
+        on_device(seg_reward, (torch.float32,), None, "seg_reward")
+        if seg_reward.dim() != 3 or int(seg_reward.shape[2]) != self.B:
+            raise ValueError("seg_reward must be [M, H, B] with B = %d, got %r" % (self.B, tuple(seg_reward.shape)))
+        M, H = int(seg_reward.shape[0]), int(seg_reward.shape[1])
+        if not 1 <= H <= L.PLAN_MAX_H:
+            raise ValueError("1 <= H (seg_reward.shape[1]) <= %d" % L.PLAN_MAX_H)
+        if not 1 <= M <= L.SAMPLE_MAX_M:
+            raise ValueError("1 <= M (seg_reward.shape[0]) <= %d" % L.SAMPLE_MAX_M)
+        R = int(top)
+        if not 0 <= R <= L.SCORE_MAX_TOP:
+            raise ValueError("0 <= top <= %d" % L.SCORE_MAX_TOP)
+        if n_steps is not None:
+            on_device(n_steps, (torch.int16, getattr(torch, "uint16", torch.int16)), (M, self.B), "n_steps")
+        if mode not in ("elite", "softmax"):
+            raise ValueError('mode must be "elite" or "softmax"')
+        if not np.isfinite(float(gamma)) or abs(float(gamma)) > float(np.finfo(np.float32).max):
+            raise ValueError("gamma must be finite")
+        if mode == "elite":
+            if elites is None or not 1 <= int(elites) <= M:
+                raise ValueError("mode=\"elite\" needs 1 <= elites <= M")
+            sc = _lib.AtcPlanScore(L.SCORE_ELITE, int(elites), float(gamma), 0.0)
+        else:
+            t32 = np.float32(temperature) if temperature is not None else np.float32(np.nan)
+            if not (t32 > 0 and np.isfinite(t32)):
+                raise ValueError("mode=\"softmax\" needs a temperature > 0 and finite (in float32)")
+            sc = _lib.AtcPlanScore(L.SCORE_SOFTMAX, 0, float(gamma), float(t32))
+        want = {"score": ((torch.float32,), (M, self.B)), "weight": ((torch.float32,), (M, self.B))}
+        if R:
+            want["top"] = ((torch.int32,), (R, self.B))
+        if out is None:
+            res = {n: torch.empty(shape, dtype=dt[0], device=dev) for n, (dt, shape) in want.items()}
+        else:
+            if not isinstance(out, dict) or not set(want) <= set(out):
+                raise ValueError("out must be a dict with %s" % ", ".join(want))
+            res = {n: on_device(out[n], dt, shape, "out[%r]" % n) for n, (dt, shape) in want.items()}
+        with torch.cuda.device(dev):
+            _lib.check(self._lib.atc_plan_score(self.sector.handle, self.B, H, M, seg_reward.data_ptr(),
+                                                None if n_steps is None else n_steps.data_ptr(), C.byref(sc), res["score"].data_ptr(),
+                                                res["weight"].data_ptr(), res["top"].data_ptr() if R else None, R, self._stream()))
+        self._keep_score = (seg_reward, n_steps)   # the inputs outlive the launch (like _keep_refit)
+        return res
+
     def _check_twin(self, other, what):
         """branch() / select(): `other` must be an AtcVecEnv of the same N and device whose sector blob and atc_params_t are byte-equal"""
         if not isinstance(other, AtcVecEnv):

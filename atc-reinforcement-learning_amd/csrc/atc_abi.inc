@@ -20,6 +20,7 @@ int atc_plan_launch_counts(uint64_t* out, int n) { return copy_counts(t_plan_lau
 int atc_plan_sampled_launch_counts(uint64_t* out, int n) { return copy_counts(t_plan_sampled_launches, ATC_PLAN_SAMPLED_LAUNCH_SLOTS, out, n); }
 int atc_plan_draw_launch_counts(uint64_t* out, int n) { return copy_counts(t_plan_draw_launches, ATC_PLAN_DRAW_LAUNCH_SLOTS, out, n); }
 int atc_plan_refit_launch_counts(uint64_t* out, int n) { return copy_counts(t_plan_refit_launches, ATC_PLAN_REFIT_LAUNCH_SLOTS, out, n); }
+int atc_plan_score_launch_counts(uint64_t* out, int n) { return copy_counts(t_plan_score_launches, ATC_PLAN_SCORE_LAUNCH_SLOTS, out, n); }
 int atc_branch_launch_counts(uint64_t* out, int n) { return copy_counts(t_branch_launches, ATC_BRANCH_LAUNCH_SLOTS, out, n); }
 int atc_select_launch_counts(uint64_t* out, int n) { return copy_counts(t_select_launches, ATC_SELECT_LAUNCH_SLOTS, out, n); }
 int atc_lookahead_set_mapping(int candidates_per_workgroup) {
@@ -521,6 +522,47 @@ int atc_plan_refit(const atc_scenario_t* s, int B, int N, int H, int M, const fl
     hipLaunchKernelGGL(k_plan_refit, dim3(tiles, (unsigned)H), dim3(kBlock), 0, (hipStream_t)stream, B, N, H, M, mean, std, *dr, weight, new_mean, new_std);
     HIP_TRY(hipGetLastError());
     ++t_plan_refit_launches[0];
+    return ATC_OK;
+}
+
+int atc_plan_score(const atc_scenario_t* s, int B, int H, int M, const float* seg_reward, const uint16_t* n_steps, const atc_plan_score_t* sc,
+                   float* score, float* weight, int32_t* top, int R, void* stream) {
+    // H, then M, then R, before any pointer is looked at
+    if (H < 1 || H > ATC_PLAN_MAX_H) return fail_arg("H (the number of segments of a plan) must be 1 .. 16");
+    if (M < 1 || M > ATC_SAMPLE_MAX_M) return fail_arg("M (the number of drawn candidates) must be 1 .. 1024");
+    if (R < 0 || R > ATC_SCORE_MAX_TOP) return fail_arg("R (the rows of top) must be 0 .. 64");
+    if (R > 0 && !top) return fail_arg("R (the rows of top) > 0 needs top");
+    if (!s) return fail_arg("null pointer: s");
+    if (!seg_reward) return fail_arg("null pointer: seg_reward is required");
+    if (!sc) return fail_arg("null pointer: sc (atc_plan_score_t) is required");
+    if (!score) return fail_arg("null pointer: score is required (result and workspace)");
+    if (!weight) return fail_arg("null pointer: weight is required");
+    if (sc->mode != ATC_SCORE_ELITE && sc->mode != ATC_SCORE_SOFTMAX) return fail_arg("sc->mode must be ATC_SCORE_ELITE or ATC_SCORE_SOFTMAX");
+    if (sc->mode == ATC_SCORE_ELITE && (sc->elites < 1 || sc->elites > M)) return fail_arg("sc->elites must be 1 .. M");
+    if (!(fabsf(sc->gamma) <= __FLT_MAX__)) return fail_arg("sc->gamma must be finite");
+    if (sc->mode == ATC_SCORE_SOFTMAX && !(sc->temperature > 0.0f && sc->temperature <= __FLT_MAX__)) return fail_arg("sc->temperature must be > 0 and finite");
+    if (B < 1) return fail_arg("need B >= 1");
+    {   // the byte ranges (pointer VALUES only): any overlap is refused, ranges that only touch are not
+        const char* const name[5] = {"seg_reward", "n_steps", "score", "weight", "top"};
+        const void* const ptr[5] = {seg_reward, n_steps, score, weight, R > 0 ? top : nullptr};
+        const uintptr_t mb = (uintptr_t)M * (uintptr_t)B;
+        const uintptr_t bytes[5] = {mb * (uintptr_t)H * 4u, mb * 2u, mb * 4u, mb * 4u, (uintptr_t)R * (uintptr_t)B * 4u};
+        for (int a = 0; a < 5; ++a)
+            for (int b = a + 1; b < 5; ++b) {
+                if (!ptr[a] || !ptr[b]) continue;
+                const uintptr_t alo = reinterpret_cast<uintptr_t>(ptr[a]), blo = reinterpret_cast<uintptr_t>(ptr[b]);
+                if (alo < blo + bytes[b] && blo < alo + bytes[a]) {
+                    char msg[160];
+                    snprintf(msg, sizeof msg, "%s overlaps %s (no two arrays of atc_plan_score may share memory)", name[a], name[b]);
+                    return fail_arg(msg);
+                }
+            }
+    }
+    const unsigned tiles = (unsigned)(((unsigned long long)B + kScoreBlock - 1) / kScoreBlock);
+    hipLaunchKernelGGL(k_plan_score, dim3(tiles), dim3(kScoreBlock), 0, (hipStream_t)stream, B, H, M, seg_reward, n_steps, *sc, score, weight,
+                       R > 0 ? top : nullptr, R);
+    HIP_TRY(hipGetLastError());
+    ++t_plan_score_launches[0];
     return ATC_OK;
 }
 

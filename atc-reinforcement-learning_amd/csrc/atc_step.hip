@@ -1732,6 +1732,7 @@ k_serve(const float* __restrict__ blob, int off_grid, atc_state_t st, atc_out_t 
 #include "atc_plan.inc"          // k_plan (atc_lookahead_plan)
 #include "atc_plan_sampled.inc"  // k_plan_sampled (atc_lookahead_plan_sampled), k_plan_draw (atc_plan_draw)
 #include "atc_plan_refit.inc"    // k_plan_refit (atc_plan_refit)
+#include "atc_plan_score.inc"    // k_plan_score (atc_plan_score)
 #include "atc_branch.inc"        // k_branch (atc_branch), k_select (atc_state_select)
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -2038,6 +2039,7 @@ static int launch_plan(const atc_scenario* s, int B, int N, int K, int H, int M,
 static thread_local uint64_t t_plan_sampled_launches[ATC_PLAN_SAMPLED_LAUNCH_SLOTS] = {0};
 static thread_local uint64_t t_plan_draw_launches[ATC_PLAN_DRAW_LAUNCH_SLOTS] = {0};
 static thread_local uint64_t t_plan_refit_launches[ATC_PLAN_REFIT_LAUNCH_SLOTS] = {0};   // atc_plan_refit_launch_counts: one slot
+static thread_local uint64_t t_plan_score_launches[ATC_PLAN_SCORE_LAUNCH_SLOTS] = {0};   // atc_plan_score_launch_counts: one slot
 
 template <int W>
 static int launch_plan_sampled(const atc_scenario* s, int B, int N, int K, int H, int M, const atc_state_t* st, const DrawSource& src,

@@ -898,6 +898,57 @@ int atc_plan_refit(const atc_scenario_t* s, int B, int N, int H, int M,
 enum { ATC_PLAN_REFIT_LAUNCH_SLOTS = 1 };
 int atc_plan_refit_launch_counts(uint64_t* out, int n);
 
+/* atc_plan_score: what lies between the scoring launch and the refit launch of a sampling planner's iteration, in one launch — the
+ * segment rewards of the M candidates turned into a discounted score per candidate, a strict total order per env, the weights
+ * atc_plan_refit reads (elite 0/1, or softmax) and the best R candidate numbers (what atc_plan_draw's `index` takes).  `s` names the
+ * device, as in atc_plan_draw; the call reads nothing else of it.  All array pointers are device pointers.
+ * SCORE.  g_0 = 1.0f; g_h = g_{h-1} * gamma, each one fp32 multiply.  score[m][e] = seg[m][0][e] is assigned, not 0 + ...; then for
+ * h = 1 .. H-1 ascending: score = score + seg[m][h][e] * g_h.  The product and the sum are each rounded once and never fused (the file
+ * is built with -ffp-contract=off).  A score that is a NaN is stored as the quiet NaN 0x7FC00000 (IEEE 754 fixes neither the sign nor
+ * the payload of a computed NaN), so that every score word is defined.
+ * VALID.  Candidate m of env e is VALID iff both hold: n_steps == NULL or n_steps[m*B + e] != 0; fabsf(score) <= FLT_MAX, so the score
+ * is not NaN and not +-Inf.  An invalid candidate gets weight = 0 and never appears in top.  Its score word is still the computed value.
+ * ORDER.  Valid candidates of an env are ordered by score descending.  Equal scores go to the LOWER candidate number.  +0 and -0
+ * compare equal.  This is a strict total order.  Every result below is a function of it.
+ * ELITE.  The first min(elites, number of valid candidates) candidates in the order get weight = 1.0f.  All others get 0.0f.
+ * SOFTMAX.  With smax the score of the first candidate in the order:
+ *
+ *     x = (score - smax) / temperature          one fp32 subtraction and one correctly rounded fp32 division
+ *     weight = expf(x)
+ *
+ * The best candidate therefore gets exactly 1.0f, since expf(0) == 1.  expf is the device library's.  It is the only inexact step in
+ * the contract (tests/plan_score_ref.py restates everything else in numpy, bit for bit, and x exactly).
+ * TOP.  Row r < R of env e is the candidate number at position r of the order.  The entry is -1 where the env has fewer than r+1 valid
+ * candidates.  -1 is out of range for atc_plan_draw's index, so that row is kept.  R is independent of elites.  top[0] is the winner in
+ * both modes.
+ * ENV WITH NO VALID CANDIDATE.  All M weights are 0, which atc_plan_refit reads as "not written".  Every top entry is -1.
+ * score is required: it is a result and the call's workspace.  weight is required.  Results do not depend on how the launch maps envs
+ * to lanes.
+ * ALIASING.  Any overlap among the byte ranges of seg_reward (M*H*B*4 bytes), n_steps (M*B*2), score, weight (M*B*4 each) and top
+ * (R*B*4) is ATC_ERR_ARG (pointer values only, as atc_plan_refit compares them; ranges that only touch are accepted).
+ * ATC_ERR_ARG, in this order, the first three before any pointer is looked at, atc_last_error() naming the argument: H outside 1 ..
+ * ATC_PLAN_MAX_H; M outside 1 .. ATC_SAMPLE_MAX_M; R outside 0 .. ATC_SCORE_MAX_TOP, or R > 0 with top == NULL; a NULL pointer among s,
+ * seg_reward, sc, score, weight; sc->mode unknown; in ELITE mode, elites outside 1 .. M; gamma not finite; in SOFTMAX mode, temperature
+ * not > 0 and finite; B < 1; the overlap rule.
+ * Counted by atc_plan_score_launch_counts only (one slot; the rules of atc_plan_refit_launch_counts); a refused call moves no launch
+ * record. */
+#define ATC_SCORE_MAX_TOP 64
+enum { ATC_SCORE_ELITE = 0, ATC_SCORE_SOFTMAX = 1 };
+typedef struct atc_plan_score {
+    uint32_t mode;         /* ATC_SCORE_ELITE | ATC_SCORE_SOFTMAX */
+    int32_t  elites;       /* ELITE: 1 .. M */
+    float    gamma;        /* discount per SEGMENT, finite */
+    float    temperature;  /* SOFTMAX: > 0 and finite */
+} atc_plan_score_t;
+int atc_plan_score(const atc_scenario_t* s, int B, int H, int M,
+                   const float* seg_reward /* [M][H][B] */, const uint16_t* n_steps /* nullable [M][B] */,
+                   const atc_plan_score_t* sc,
+                   float* score /* [M][B], required: result and workspace */,
+                   float* weight /* [M][B], required */,
+                   int32_t* top /* nullable [R][B] */, int R, void* stream);
+enum { ATC_PLAN_SCORE_LAUNCH_SLOTS = 1 };
+int atc_plan_score_launch_counts(uint64_t* out, int n);
+
 /* BRANCH (extension): atc_lookahead that KEEPS the outcomes — M candidate action blocks per env are flown for K steps in ONE launch and
  * each outcome becomes an env of a second batch `dst` of M*B envs, which a caller can score, expand again (beam search, MCTS expansion,
  * restore) or commit with atc_state_select instead of flying the winner a second time.  1 <= K <= ATC_SKIP_MAX, 1 <= M <=
