@@ -14,6 +14,7 @@ import plan_draw_ref as P
 F32 = np.float32
 FLT_MAX = np.finfo(np.float32).max
 U = 2.0 ** -24          # the unit roundoff of float32
+ETA = 2.0 ** -149       # the smallest positive float32: what a product or quotient that underflows may be off by, absolutely
 
 
 def participates(weight):
@@ -59,19 +60,22 @@ def refit(mean, std, M, weight, seed=0, iteration=0, mean_first=True, into=None,
     return np.where(some, new_mean, keep_mean).astype(F32), np.where(some, new_std, keep_std).astype(F32)
 
 
-def refit64(mean, std, M, weight, seed=0, iteration=0, mean_first=True):
+def refit64(mean, std, M, weight, seed=0, iteration=0, mean_first=True, draws=None):
     """The weighted mean and standard deviation of the float32 draws in float64 (envs with no participant: NaN), and A1 = sum |w d| / W,
-    A2 = sum w d^2 / W with d = a - ctr: what the float32 loop's rounding errors are proportional to."""
+    A2 = sum w d^2 / W with d = a - ctr: what the float32 loop's rounding errors are proportional to.  draws: as in refit()."""
     mean, std, weight = _inputs(mean, std, M, weight)
     part = participates(weight)
     w = np.where(part, weight, 0).astype(np.float64)[:, None, :, None, None]                    # [M, 1, B, 1, 1]
-    a = P.draw(mean, std, M, seed=seed, iteration=iteration, mean_first=mean_first).astype(np.float64)
+    a = P.draw(mean, std, M, seed=seed, iteration=iteration, mean_first=mean_first) if draws is None else np.asarray(draws, F32)
+    assert a.shape == (M,) + mean.shape, a.shape
+    a = a.astype(np.float64)
     d = a - P.clamp(mean).astype(np.float64)[None]
     with np.errstate(all="ignore"):
         Wt = w.sum(0)
         mu = (w * a).sum(0) / Wt
         sd = np.sqrt((w * (a - mu[None]) ** 2).sum(0) / Wt)
-        return dict(mean=mu, std=sd, A1=(w * np.abs(d)).sum(0) / Wt, A2=(w * d * d).sum(0) / Wt, q=(w * d).sum(0) / Wt)
+        return dict(mean=mu, std=sd, A1=(w * np.abs(d)).sum(0) / Wt, A2=(w * d * d).sum(0) / Wt, q=(w * d).sum(0) / Wt,
+                    W=np.broadcast_to(Wt, mu.shape))
 
 
 def gamma(n):
@@ -83,11 +87,19 @@ def bounds(M, r64):
     a term of s1 carries the roundings of d, of t and of at most M additions, W those of at most M additions, the quotient one more:
     |q^ - q| <= gamma(2 M + 3) A1 =: eq, and the mean adds the rounding of ctr + q.  A term of s2 carries one rounding more than one of
     s1 (all terms >= 0), so |s2/W^ - A2| <= gamma(2 M + 4) A2; q q carries 2 |q| eq + eq^2 and its own rounding; the subtraction one
-    more.  With ev the sum of these, |sqrt(v^) - sqrt(v)| <= min(sqrt(ev), ev / sqrt(v)), and the square root rounds once."""
+    more.  With ev the sum of these, |sqrt(v^) - sqrt(v)| <= min(sqrt(ev), ev / sqrt(v)), and the square root rounds once.
+    UNDERFLOW.  Weights down to the smallest subnormal participate (a softmax gives them), and then w d and (w d) d lie among the
+    subnormals, where that model does not hold: a product or quotient there is fl(x op y) = (x op y)(1 + delta) + eta with
+    |eta| <= ETA (sums and differences of float32 numbers are exact where they underflow, and a square root never underflows).  Each of
+    the at most M terms of s1 carries one eta, and the quotient one more: eq grows by (M ETA / W)(1 + gamma(2 M + 3)) + ETA.  A term
+    (w d) d of s2 carries |d| <= 2 times the eta of w d and one of its own, 3 ETA, and the quotient one more: ev grows by
+    (3 M ETA / W)(1 + gamma(2 M + 4)) + ETA, and by one more ETA for the product q q."""
     A1, A2, q, sd = r64["A1"], r64["A2"], np.abs(r64["q"]), r64["std"]
-    eq = gamma(2 * M + 3) * A1
-    e_mean = eq + U * (np.abs(r64["mean"]) + eq)
-    ev = gamma(2 * M + 4) * A2 + 2 * q * eq + eq * eq + U * (q * q + 2 * q * eq + eq * eq) + U * (A2 + q * q) * (1 + gamma(2 * M + 6))
+    W = r64["W"]
     with np.errstate(all="ignore"):
+        eq = gamma(2 * M + 3) * A1 + (M * ETA / W) * (1 + gamma(2 * M + 3)) + ETA
+        e_mean = eq + U * (np.abs(r64["mean"]) + eq)
+        ev = gamma(2 * M + 4) * A2 + 2 * q * eq + eq * eq + U * (q * q + 2 * q * eq + eq * eq) + U * (A2 + q * q) * (1 + gamma(2 * M + 6)) \
+            + (3 * M * ETA / W) * (1 + gamma(2 * M + 4)) + 2 * ETA
         e_std = np.minimum(np.sqrt(ev), np.where(sd > 0, ev / sd, np.inf))
     return e_mean, e_std + U * (sd + e_std)

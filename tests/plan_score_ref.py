@@ -8,6 +8,10 @@ FLT_MAX = np.finfo(np.float32).max
 FLT_MIN = np.finfo(np.float32).tiny
 MAX_TOP = 64
 QUIET_NAN = np.array([0x7FC00000], np.uint32).view(np.float32)[0]
+# THE SOFTMAX BAR (derived in tests/test_plan_score.py's docstring): twice the largest ulp distance of the device's expf measured over
+# that file's softmax inputs on an MI355X.  One bar for every test that holds a softmax weight.
+MEASURED_MAX_ULP = 1
+SOFTMAX_ULP_BAR = 2 * MEASURED_MAX_ULP
 
 
 def score(seg, gamma):

@@ -33,6 +33,13 @@ tensor of the env are byte-equal to a snapshot taken before, the held bookkeepin
     ("plan", K, H, "fast" | "all")          env.lookahead_plan          skip_ref.plan_references
     ("plan_sampled", K, H, mean_first)      env.lookahead_plan_sampled  plan_draw_ref.draw, then skip_ref.plan_references; bit for bit
                                                                         env.lookahead_plan on env.draw_plans(...)
+    ("plan_iter", mode, M, H)               one iteration of a scored planner by the public calls: env.lookahead_plan_sampled -> score_plans
+                                            -> refit_plans -> draw_plans(index=top[:1]); tests/planner_ref.py::check_iteration against the
+                                            oracle's flight of the numpy-drawn plans.  mode: "elite" | "softmax"; K, the scoring arguments,
+                                            the seed and the iteration follow from the operation's index.  The batch keeps the decision:
+    ("step", "decision")                    the last plan_iter's decision of this batch flown for its K steps: one fresh step with the
+                                            device's own decision tensor (the numpy row of the same candidate on the oracle, zeros where the
+                                            env has no valid candidate), then K - 1 held steps
 The state-moving calls:
     ("branch", src, K)                      src.branch(cand, K, into=child)   branch_ref.oracle_branch: every candidate flown on the SOURCE
                                             oracle from a snapshot (resets inside the call keyed by e), its rows copied into rows m B + e of
@@ -70,7 +77,9 @@ SELECT_KINDS = ("commit", "beam", "stash", "restore", "edge", "zero")
 SCORE_M = 3                # candidates of ("lookahead", ...) and ("plan", ...)
 TREE_WILD_ENVS = 0.2       # tree sessions: the share of ENVS whose heading components take part in the wild draws (see Session)
 BOUND = ("obs", "raw_obs", "reward", "done", "flags", "ac_reward", "min_sep", "term_obs", "traffic", "frame_steps")
-BATCH_OPS = ("step", "skip", "rollout", "reset", "observe", "traffic", "set_state", "set_last_action", "lookahead", "plan", "plan_sampled")
+BATCH_OPS = ("step", "skip", "rollout", "reset", "observe", "traffic", "set_state", "set_last_action", "lookahead", "plan", "plan_sampled",
+             "plan_iter")
+ITER_KS = (2, 4, 5)        # K of ("plan_iter", ...), by the operation's index
 
 Case = collections.namedtuple("Case", "N B auto_reset normalize dt keep_active spawn timestep_limit sep_nm seed")
 
@@ -128,6 +137,7 @@ class Batch:
         self.win_pending = []         # (env, slot) placed on the winning state: the next fresh actions fly them into the corridor
         self.branch_actions = None    # [B, N, 3]: the candidates of the last branch into this batch, child by child
         self.hi_from = B + 1          # child: root's B (envs c >= B: their reset key is not a source env's)
+        self.decision = None          # (numpy [B, N, 3], the device's tensor or None, K) of the last plan_iter on this batch
 
     def stepped(self, a):
         self.prev_actions = np.ascontiguousarray(np.asarray(a, np.float32).reshape(self.prev_actions.shape)).copy()
@@ -383,6 +393,10 @@ class Session:
             if bt.branch_actions is None:
                 raise IllegalScript("%s: no branch into this batch" % here)
             a = bt.branch_actions
+        elif mode == "decision":
+            if bt.decision is None:
+                raise IllegalScript("%s: no plan_iter on this batch" % here)
+            return self._fly_decision(bt)
         else:
             if not bt.has_prev.all():
                 raise IllegalScript("%s: no step to repeat" % here)
@@ -404,6 +418,30 @@ class Session:
         bt.stepped(a)
         rec["done"] = int(orc.done.sum())
         self._ended(rec, bt, ep, orc.done)
+        return rec
+
+    def _fly_decision(self, bt):
+        """("step", "decision"): K steps with the last plan_iter's decision, the first in full, the others held; every step compared"""
+        env, orc = bt.env, bt.orc
+        a, dev, K = bt.decision
+        rec = {"t0_envs": int((orc.timesteps == 0).sum()), "wide_active": self._wide_active(bt), "wide_envs": int(skip_ref.wide_envs(orc).sum()),
+               "batch": bt.name, "K": K, "held_steps": K - 1, "nonzero_rows": int(a.reshape(bt.B, -1).any(1).sum()), "done": 0, "_out": []}
+        for j in range(K):
+            if j > 0:       # the held promise, by the one rule every scripted held step goes through
+                ok, why = held_is_legal(bt.prev_actions, bt.la_touched, a, bt.has_prev)
+                if not ok:
+                    raise IllegalScript("operation %d: held step %d of a decision: %s" % (len(self.done_ops), j, why))
+            ep = orc.episodes.copy()
+            orc.step(a)
+            if env is not None:
+                env.step(dev, held=j > 0)
+                got = self._step_outputs(bt)
+                bars.check_step(got, orc, self.case.normalize, self.half, ("decision", j))
+                bars.check_state(env, orc)
+                rec["_out"] += self._written(got) + ([self._cpu(env.traffic)] if env.traffic_k else [])
+            bt.stepped(a)
+            rec["done"] += int(orc.done.sum())
+            self._ended(rec, bt, ep, orc.done)
         return rec
 
     def _op_skip(self, rng, bt, K):
@@ -622,6 +660,60 @@ class Session:
             return res
         rec = self._score(bt, refs, ok, K, call, Hn, ("plan_sampled", K, Hn, M))
         rec["shape"] = ("plan_sampled", M, Hn, outputs)
+        return rec
+
+    def _op_plan_iter(self, rng, bt, mode, M, Hn):
+        """mean and std tensors drawn (std 0.3 .. 1.5 per component), K = ITER_KS[index % 3]; elites, temperature, gamma and top rotate
+        with the index.  Without a device the stand-in of tests/planner_ref.py takes the device's place, so that the oracle-only record
+        holds a decision too."""
+        import held_tools
+        import plan_draw_ref
+        import planner_ref
+        self._scoring_batch(bt, "plan_iter")
+        verify = self._untouched_before
+        N, idx, B = self.case.N, self._index, bt.B
+        K = ITER_KS[idx % 3]
+        how = dict(gamma=(1.0, 0.9, 0.0)[(idx // 2) % 3], top=(1, 5)[idx % 2], mode=mode)
+        if mode == "elite":
+            how["elites"] = (1, min(3, M), M)[idx % 3]
+        else:
+            how["temperature"] = (0.5, 5.0)[(idx // 3) % 2]
+        mean = (held_tools.look_draw(rng, Hn, B, N) * np.float32(0.8)).astype(np.float32)
+        std = rng.uniform(0.3, 1.5, (Hn, B, N, 3)).astype(np.float32)
+        key = dict(seed=self.case.seed * 1000 + idx, iteration=1 + idx, mean_first=True)
+        plans = plan_draw_ref.draw(mean, std, M, **key)
+        ok = ~skip_ref.wide_envs(bt.orc)
+        refs = skip_ref.plan_references(bt.orc, plans, K)
+        n = np.stack([r["n_steps"].astype(np.int64) for r in refs])[:, ok]
+        done = np.stack([r["done"].astype(bool) for r in refs])[:, ok]
+        rec = {"batch": bt.name, "pairs": M * B, "evaluated": M * int(ok.sum()), "evaluated_per_candidate": [int(ok.sum())] * M, "K": K,
+               "early": int((done & (n < K * Hn)).sum()), "ran_all": int((n == K * Hn).sum()), "t0_envs": int((bt.orc.timesteps == 0).sum()),
+               "shape": ("plan_iter", M, Hn, mode), "how": how}
+        dev = None
+        if bt.env is not None:
+            env = bt.env
+            mu, sd = self._dev(bt, mean), self._dev(bt, std)
+            res = env.lookahead_plan_sampled(mu, sd, K, M, outputs=("seg_reward",), **key)
+            sc = env.score_plans(res["seg_reward"], res["n_steps"], **how)
+            new_mean, new_std = env.refit_plans(mu, sd, M, sc["weight"], **key)
+            dev = env.draw_plans(mu, sd, M, index=sc["top"][:1], **key)[0, 0].clone()
+            got = {k: self._cpu(v) for k, v in dict(res, **sc).items()}
+            got.update(new_mean=self._cpu(new_mean), new_std=self._cpu(new_std), decision=self._cpu(dev))
+            for m, r in enumerate(refs):
+                bars.check_candidate_outputs({k: got[k][m] for k in ("reward", "done", "n_steps")}, r, ok, self.half, tag=("plan_iter", m))
+                bars.check_plan_segments(got["seg_reward"][m], r, ok, K, tag=("plan_iter", m))
+            ref = planner_ref.reference(refs, ok, seg32=got["seg_reward"], **how)
+            rec["_out"] = [got[k] for k in sorted(got)]
+        else:
+            ref = planner_ref.reference(refs, ok, **how)
+            got = planner_ref.stand_in(refs, ok, plans, mean, std, **how)
+        rec["stats"] = planner_ref.check_iteration(got, ref, plans, mean, std, tag=("plan_iter", idx, mode, M, Hn))
+        ev, ndw, asked, nde = planner_ref.shares(ref)
+        rec.update(evaluated_envs=ev, none_valid=B - ev, non_decisive_winner=ndw, non_decisive_boundary=nde)
+        t0 = np.asarray(got["top"])[0].astype(np.int64)
+        row = np.where((t0 >= 0)[:, None, None], plans[np.maximum(t0, 0), 0, np.arange(B)], np.float32(0)).astype(np.float32)
+        verify()
+        bt.decision = (np.ascontiguousarray(row), dev, K)
         return rec
 
     # -------------------------------------------------------------------------------------------------------- state-moving calls
@@ -932,3 +1024,30 @@ def make_tree_script(case):
             touched[dst] = touched[src] or (touched[dst] and not whole)
         script.append(op)
     return script
+
+
+# ---------------------------------------------------------------------------------------------------------------- planner scripts
+def mixed_skip_k(case):
+    """K of the planner scripts' step_skip that must leave early AND full envs behind: 20 — envs reset two steps before run all 20 under a
+    time limit of 22 or more, the others meet it inside the block —, but 12 with 64 aircraft, where within 20 steps every env of the
+    batch ends on something else than its time limit"""
+    return 12 if case.N == 64 else 20
+
+
+def make_planner_script(case):
+    """A tree script around ("plan_iter", ...): the operation between two held steps; directly after a step_skip with early and full envs
+    (mixed_skip_k); after a masked reset of some envs; directly before ("step", "decision"), which flies the decision, and a held step
+    that holds it on; on the beam after a select, decision flown there.  The two modes, M in {3, 5, 8} and H in {1, 2, 3} rotate; one
+    shape comes twice.  The case seeds the operations' inputs and sets that one K; the rest of the script is fixed."""
+    return [
+        ("step", "fresh"), ("step", "held"), ("plan_iter", "elite", 8, 3), ("step", "held"),
+        ("skip", 5), ("reset", "random"), ("step", "fresh"), ("step", "held"), ("skip", mixed_skip_k(case)), ("plan_iter", "softmax", 5, 2),
+        ("step", "held"),
+        ("reset", "random"), ("plan_iter", "elite", 3, 1), ("step", "held"),
+        ("plan_iter", "softmax", 8, 3), ("step", "decision"), ("step", "held"),
+        ("plan_iter", "elite", 5, 2), ("step", "decision"), ("step", "held"), ("plan_iter", "elite", 8, 3), ("step", "held"),
+        ("reset", "random"), ("step", "tame"), ("step", "held"), ("branch", "root", 5), ("select", "beam", "child", "beam"),
+        ("plan_iter", "elite", 8, 2, "beam"), ("step", "decision", "beam"), ("step", "held", "beam"),
+        ("select", "beam", "root", "stash"), ("plan_iter", "softmax", 3, 3, "beam"), ("step", "decision", "beam"),
+        ("select", "root", "beam", "restore"), ("step", "held"),
+    ]

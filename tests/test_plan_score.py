@@ -35,8 +35,8 @@ from held_tools import GUARD, HEADER, LIB
 NAMES = ("atc_plan_score", "atc_plan_score_launch_counts")
 FAKE = C.c_void_p(0x100000)     # a made-up pointer: a call that is refused never follows it
 PATTERN = 0xA5                  # the byte output buffers hold before a call
-MEASURED_MAX_ULP = 1            # largest distance seen over this file's softmax inputs on an MI355X
-SOFTMAX_ULP_BAR = 2 * MEASURED_MAX_ULP
+MEASURED_MAX_ULP = S.MEASURED_MAX_ULP        # largest distance seen over this file's softmax inputs on an MI355X
+SOFTMAX_ULP_BAR = S.SOFTMAX_ULP_BAR          # (both kept in tests/plan_score_ref.py, where tests/planner_ref.py takes the same bar from)
 
 
 # ---------------------------------------------------------------------------------------------------------------- CPU: the ABI
