@@ -61,6 +61,17 @@ def look_ragged(N):
     return 256 // W + 3    # B * W = 256 + 3 W: two workgroups, the last one partial
 
 
+def look_tiles(N, tiles, partial):
+    """B whose B * W slots fill `tiles` 256-slot workgroups: tiles - 1 whole ones and a last one that is whole (partial=False) or holds
+    3 envs (1 env at W = 64: a tile holds 4).  From 9 tiles on the candidate kernels' launch has more than one chunk of 8 tiles
+    (csrc/atc_lookahead.inc: look_tile)."""
+    W = H.lane_width(N)
+    per = 256 // W
+    B = (tiles - 1) * per + ((1 if W == 64 else 3) if partial else per)
+    assert -(-B * W // 256) == tiles and (B * W % 256 != 0) == bool(partial)    # step_grid's count (csrc/atc_step.hip)
+    return B
+
+
 def look_scenario():
     from envs.atc import scenarios
     return scenarios.LOWWDense()

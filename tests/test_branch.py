@@ -395,7 +395,8 @@ def test_branches_between_calls_change_nothing():
 @pytest.mark.timeout(300)
 def test_full_size_batch():
     """65 536 x 16, M = 2, K = 2 in one call: the first 256 envs of each candidate against step_skip on copies, the rest through properties
-    (1 <= n_steps <= K, n_steps == K unless done, the child's timestep and episode records consistent with them) and the src bytes."""
+    (1 <= n_steps <= K, n_steps == K unless done, the child's timestep and episode records consistent with them) and the src bytes.
+    (The exact check of the tile decode past one chunk, on every env: tests/test_candidate_tiles.py.)"""
     import torch
     B, N, M, K = 65536, 16, 2, 2
     rng = np.random.default_rng(3)

@@ -266,7 +266,8 @@ def test_lookaheads_between_calls_change_nothing():
 @pytest.mark.gpu
 @pytest.mark.timeout(300)
 def test_full_size_batch():
-    """65 536 x 16, M = 4, K = 4: the first 256 envs against step_skip on copies, the state bytes of all of them."""
+    """65 536 x 16, M = 4, K = 4: the first 256 envs against step_skip on copies, the state bytes of all of them; the envs beyond 256 by
+    properties.  (The exact check of the tile decode past one chunk, on every env: tests/test_candidate_tiles.py.)"""
     import torch
     B, N, M, K = 65536, 16, 4, 4
     rng = np.random.default_rng(3)

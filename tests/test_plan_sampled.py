@@ -659,7 +659,8 @@ def test_cem_plan_equals_the_loop_on_tensors():
 @pytest.mark.timeout(300)
 def test_full_size_batch():
     """65 536 x 16, M = 4, H = 2, K = 2, once: the first 256 envs of each candidate against the tensor route on a 256-env twin (the
-    draw is keyed by the aircraft's index in the batch, the resets by the env's: the twin IS the first 256), the rest by properties."""
+    draw is keyed by the aircraft's index in the batch, the resets by the env's: the twin IS the first 256), the rest by properties.
+    (The exact check of the tile decode past one chunk, on every env: tests/test_candidate_tiles.py.)"""
     import torch
     B, N, M, Hn, K = 65536, 16, 4, 2, 2
     rng = np.random.default_rng(3)
