@@ -22,11 +22,12 @@ from fuzz_space import Mismatch, make_env, make_oracle
 SEEDS = range(5000, 5040)     # the first 40 cases of tests/test_fuzz_held.py's default sweep
 
 
-def run(seed, device=True):
-    """Returns dict(seed, kw, pairs, excluded (pairs not evaluated: WIDE at the start, on the oracle), events (held_fuzz's counters on the oracle's
+def run(seed, device=True, case=None, watch=None):
+    """case: (scn, comp, kw) shaped like held_fuzz.case(seed)'s, flown in its place (tests/noise_sectors.py::noise_case); watch:
+    held_fuzz._add_block's, for the branch's blocks.  Returns dict(seed, kw, pairs, excluded (pairs not evaluated: WIDE at the start, on the oracle), events (held_fuzz's counters on the oracle's
     results)) and, on the device, launches (what the branch launch record gained) and not_evaluated (pairs the device returned n_steps == 0
     for; asserted equal to excluded)."""
-    scn, comp, kw = F.case(seed)
+    scn, comp, kw = case if case is not None else F.case(seed)
     ctx = {"seed": int(seed), "call": "setup", "kw": kw}
     B, N, discrete, wild = kw["B"], kw["N"], kw["discrete"], kw["wild"]
     c = kw["lookahead"]
@@ -83,7 +84,7 @@ def run(seed, device=True):
         if n.size:
             rec["events"]["differ"] += int((n.min(0) != n.max(0)).sum())
         for r in refs:
-            F._add_block(rec["events"], r, K, ok, auto_reset)
+            F._add_block(rec["events"], r, K, ok, auto_reset, watch)
         if device:
             ctx.update(call="the parent afterwards")
             bars.check_state(env, orc)

@@ -59,6 +59,9 @@ def case(seed):
     return scn, comp, kw
 
 
+_drawn_case = case     # (run() has an argument of that name)
+
+
 def draw_flown(rng, B, N, discrete, wild):
     """The actions of a flown step_skip call: fuzz_space.draw_actions, with the HEADING components taking part in the `wild` share in
     HEADING_WILD_ENVS of the envs (env 0 never does)."""
@@ -92,7 +95,7 @@ def properties(scn, kw):
 # ---------------------------------------------------------------------------------------------------------------- events
 def _new_events():
     return dict(pairs=0, n_hist={}, early=0, differ=0, done=0, reset_in_block=0, conflict=0, below_mva=0, inactive=0, refused=0,
-                refused_repeated=0, late_stop=0, late_reset=0)
+                refused_repeated=0, late_stop=0, late_reset=0, noise=0)
 
 
 def _add_n(ev, n, done, limit):
@@ -104,12 +107,16 @@ def _add_n(ev, n, done, limit):
     ev["done"] += int(done.sum())
 
 
-def _add_block(ev, ref, K, mask, auto_reset):
-    """one skip_reference result, the envs of mask [B]: what its executed steps' flag words show, and resets with steps of the block left"""
+def _add_block(ev, ref, K, mask, auto_reset, watch=None):
+    """one skip_reference result, the envs of mask [B]: what its executed steps' flag words show, and resets with steps of the block left.
+    watch(ref, executed [K, B], auto_reset): a caller's own count on the same steps (tests/noise_sectors.py::Coverage.add_block)"""
     n = ref["n_steps"].astype(int)
     executed = (np.arange(K)[:, None] < n[None, :]) & mask[None, :]
+    if watch is not None:
+        watch(ref, executed, auto_reset)
     sf = np.where(executed[:, :, None], ref["step_flags"], 0)
-    for name, bit in (("conflict", H.F_CONFLICT), ("below_mva", H.F_BELOW_MVA), ("inactive", H.F_INACTIVE), ("refused", REFUSED)):
+    for name, bit in (("conflict", H.F_CONFLICT), ("below_mva", H.F_BELOW_MVA), ("inactive", H.F_INACTIVE), ("refused", REFUSED),
+                      ("noise", H.F_NOISE)):
         ev[name] += int((sf & bit != 0).any(axis=(0, 2)).sum())
     ev["refused_repeated"] += int((sf[1:] & REFUSED != 0).any(axis=(0, 2)).sum())
     if auto_reset:
@@ -145,15 +152,16 @@ def _skip_outputs(env, ret, full):
     return got
 
 
-def run(seed, device=True):
-    """Flies case(seed).  device=True: on the GPU against the oracle (raises Mismatch at the first comparison that fails); device=False:
+def run(seed, device=True, case=None, watch=None):
+    """Flies case(seed) — or the given case=(scn, comp, kw) of the same shape (tests/noise_sectors.py::noise_case).  watch: {kernel: _add_block's
+    watch}.  device=True: on the GPU against the oracle (raises Mismatch at the first comparison that fails); device=False:
     the oracle alone.  Returns the case's record: seed, kw, props (properties()), events {kernel: counts} on the oracle's results —
     pairs (evaluated (candidate, env) pairs), n_hist, early, differ (envs whose candidates stop at different n), done, reset_in_block
-    (auto-reset with steps of the block left), conflict / below_mva / inactive / refused / refused_repeated (a refused target on a step
+    (auto-reset with steps of the block left), conflict / below_mva / inactive / noise / refused / refused_repeated (a refused target on a step
     j >= 1 of a block), late_stop / late_reset (a plan that ends in a segment h >= 1; with auto-reset on) —, wide {kernel: (pairs excluded
     as WIDE at the start, pairs)}, traffic_short (aircraft under control with fewer than K others) and, on the device, launches (what each
     launch record gained)."""
-    scn, comp, kw = case(seed)
+    scn, comp, kw = case if case is not None else _drawn_case(seed)
     ctx = {"seed": int(seed), "call": "setup", "kw": kw}
     rec = dict(seed=int(seed), kw=kw, props=properties(scn, kw), events={k: _new_events() for k in KERNELS}, wide={}, traffic_short=0)
     env = None
@@ -161,7 +169,7 @@ def run(seed, device=True):
         start = _counters() if device else None
         orc = make_oracle(comp, kw, auto_reset=True)
         env = make_env(scn, kw, auto_reset=True) if device else None
-        _fly(env, orc, comp, kw, rec, ctx)
+        _fly(env, orc, comp, kw, rec, ctx, watch or {})
         if device:
             rec["launches"] = _gained(start, _counters())
     except AssertionError as e:
@@ -176,7 +184,7 @@ def run(seed, device=True):
     return rec
 
 
-def _fly(env, orc, comp, kw, rec, ctx):
+def _fly(env, orc, comp, kw, rec, ctx, watch):
     B, N, full, discrete, wild = kw["B"], kw["N"], kw["full"], kw["discrete"], kw["wild"]
     half = bars.half_range(comp)
     rng = np.random.default_rng([kw["seed"], 0x464C59])
@@ -193,7 +201,7 @@ def _fly(env, orc, comp, kw, rec, ctx):
         a = draw_flown(rng, B, N, discrete, wild)
         ref = R.skip_reference(orc, a, K)
         _add_n(ev["skip"], ref["n_steps"].astype(int), ref["done"].astype(bool), K)
-        _add_block(ev["skip"], ref, K, np.ones(B, bool), auto_reset)
+        _add_block(ev["skip"], ref, K, np.ones(B, bool), auto_reset, watch.get("skip"))
         if env is not None:
             got = _skip_outputs(env, env.step_skip(a, K), full)
             ctx.update(call=tag, K=K, got=got, ref=ref, records=None, cand=None)
@@ -240,10 +248,10 @@ def _fly(env, orc, comp, kw, rec, ctx):
             ev[kernel]["differ"] += int((n.min(0) != n.max(0)).sum())
         for m in range(M):
             if Hn is None:
-                _add_block(ev[kernel], refs[m], K, ok, auto_reset)
+                _add_block(ev[kernel], refs[m], K, ok, auto_reset, watch.get(kernel))
             else:
                 for alive, r in records[m]:
-                    _add_block(ev[kernel], r, K, ok & alive, auto_reset)
+                    _add_block(ev[kernel], r, K, ok & alive, auto_reset, watch.get(kernel))
         if Hn is not None:
             late = done & (n > K)
             ev[kernel]["late_stop"] += int(late.sum())

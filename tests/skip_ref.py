@@ -56,7 +56,8 @@ def skip_reference(orc, actions, K):
     """Runs one frame-skip call of length K on the oracle env `orc` (left in the state after the call) and returns a dict:
     obs, raw_obs, reward, ac_reward, done, flags, min_sep, term_obs, n_steps as the call defines them, plus
     reward_scale [B] / ac_reward_scale [B, N] = sum over the executed steps of max(1, |r_j|) (the per-step 1e-5 bar, added up),
-    step_done [K, B], step_flags [K, B, N] (the oracle's own per-step record, for event checks) and n_steps.
+    step_done [K, B], step_flags [K, B, N], step_pos [K, 3, B N] (x, y [nm] and altitude [ft] after each step: the oracle's own
+    per-step record, for event checks) and n_steps.
     The sums and the minimum are taken in the oracle's dtype: a float64 OracleEnv gives the float64-built reference."""
     B, N = orc.B, orc.N
     actions = np.ascontiguousarray(np.asarray(actions, np.float32).reshape(B, N, 3))
@@ -89,6 +90,7 @@ def skip_reference(orc, actions, K):
         "flags": np.bitwise_or.reduce(np.where(executed[:, :, None], flags, 0).astype(np.uint16), axis=0),
         "min_sep": np.where(executed, np.stack([o["min_sep"] for o in outs]), np.inf).min(axis=0).astype(orc.dtype),
         "step_done": done, "step_flags": flags,
+        "step_pos": np.stack([np.stack([orc._nm(s["px"], 0), orc._nm(s["py"], 1), s["h"]]) for s in states]),
     }
     # the terminal observation is written by the terminating step of envs that are auto-reset in this call; untouched otherwise
     ended = done[last, env_rows]

@@ -691,6 +691,12 @@ def test_batched_n64_noise_vs_oracle():
     scn = scenarios.LOWWDense()
     n_done, seen = run_vs_oracle(scn, scenarios.compile_scenario(scn, grid_cell=0.5), B=128, N=64, steps=240, seed=33)
     assert n_done > 20 and (seen & H.F_CONFLICT)
+    # The oracle alone shows that the run above never reaches an area (0 of 1 966 080 aircraft-steps carry F_NOISE: aircraft spawn at
+    # FL130 and above, the ceilings are 6 000 - 8 000 ft) — a second run on a sector of tests/noise_sectors.py that does
+    import noise_sectors as NS
+    scn = NS.noise_sector(4, 16, "LOWW")
+    n_done, seen = run_vs_oracle(scn, scenarios.compile_scenario(scn, grid_cell=0.5), B=32, N=64, steps=120, seed=34, sep_nm=0.0)
+    assert seen & H.F_NOISE
 
 
 def test_batched_odd_n_and_short_timeout_vs_oracle():

@@ -7,46 +7,8 @@ import pytest
 import helpers as H  # noqa: F401
 from atc_hip import layout as L
 from atc_hip import scenario as S
+from noise_sectors import probe_points, random_sector
 from test_scenario_compile import _walk_grid
-
-
-def random_sector(seed, n_poly):
-    rng = np.random.default_rng(seed)
-    mvas = []
-    for p in range(n_poly):
-        cx, cy = rng.uniform(10, 50, 2)
-        n = int(rng.integers(3, 12))
-        ang = np.sort(rng.uniform(0, 2 * np.pi, n))
-        rad = rng.uniform(3, 18, n)               # star-shaped (generally concave) ring
-        pts = np.stack([cx + rad * np.cos(ang), cy + rad * np.sin(ang)], 1)
-        if rng.random() < 0.4:                    # snap some vertices to a coarse lattice: shared / axis-aligned edges
-            pts = np.round(pts / 2.0) * 2.0
-            keep = [0]
-            for k in range(1, len(pts)):
-                if not np.array_equal(pts[k], pts[keep[-1]]):
-                    keep.append(k)
-            pts = pts[keep]
-            if len(pts) >= 2 and np.array_equal(pts[0], pts[-1]):
-                pts = pts[:-1]
-            if len(pts) < 3:
-                pts = np.array([[cx, cy], [cx + 6, cy], [cx + 6, cy + 6]])
-        mvas.append((pts, float(rng.integers(20, 90)) * 100.0))
-    # two exact rectangles sharing an edge (the classic tie-break case)
-    mvas.append(([(20, 20), (30, 20), (30, 30), (20, 30)], 2500.0))
-    mvas.append(([(30, 20), (40, 20), (40, 30), (30, 30)], 3500.0))
-    return mvas, (30.0, 30.0, 500.0, float(rng.integers(0, 360))), [(12.0, 12.0, 45.0, [150])]
-
-
-def probe_points(comp, rng, n_random=2500):
-    bb = comp.bbox
-    pts = [np.stack([rng.uniform(bb[0] - 1, bb[2] + 1, n_random), rng.uniform(bb[1] - 1, bb[3] + 1, n_random)], 1)]
-    for ring in comp.mva_rings:
-        for k in range(len(ring) - 1):
-            t = rng.uniform(0, 1, 6)[:, None]
-            pts.append(ring[k][None, :] * (1 - t) + ring[k + 1][None, :] * t + rng.normal(0, 3e-4, (6, 2)))
-            pts.append(ring[k][None, :] + rng.normal(0, 1e-5, (2, 2)))
-            pts.append(ring[k][None, :])          # exact vertices
-    return np.concatenate(pts)
 
 
 @pytest.mark.parametrize("seed,n_poly,cell", [(1, 3, 0.5), (2, 8, 0.5), (3, 14, 1.0), (4, 20, 0.25), (5, 6, 4.0), (6, 11, 0.5)])
