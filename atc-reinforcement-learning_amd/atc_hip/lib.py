@@ -107,7 +107,6 @@ def load():
         raise RuntimeError("libatcstep.so lacks %s — rebuild" % ", ".join(missing))
     lib.atc_abi_version.restype = ci
     lib.atc_last_error.restype = C.c_char_p
-    lib.atc_launch_counts.argtypes = [C.POINTER(C.c_uint64), ci]
     lib.atc_host_mapped_ptr.argtypes = [vp, C.POINTER(vp)]
     lib.atc_scenario_create.argtypes = [vp, C.c_size_t, ci, C.POINTER(vp)]
     lib.atc_scenario_destroy.argtypes = [vp]
@@ -128,28 +127,20 @@ def load():
     lib.atc_rollout.argtypes = [vp, ci, ci, ci, C.POINTER(AtcState), vp, C.POINTER(AtcOut), C.POINTER(AtcParams), vp]
     lib.atc_rollout_hold.argtypes = [vp, ci, ci, ci, ci, C.POINTER(AtcState), vp, C.POINTER(AtcOut), C.POINTER(AtcParams), vp]
     lib.atc_step_skip.argtypes = [vp, ci, ci, ci, C.POINTER(AtcState), vp, C.POINTER(AtcOut), vp, C.POINTER(AtcParams), vp]
-    lib.atc_skip_launch_counts.argtypes = [C.POINTER(C.c_uint64), ci]
     lib.atc_fill_prefetch_info.argtypes = [vp, ci, ci, C.POINTER(ci), C.POINTER(ci)]
     lib.atc_observe_traffic.argtypes = [vp, ci, ci, ci, C.POINTER(AtcState), vp, C.POINTER(AtcParams), vp]
-    lib.atc_traffic_launch_counts.argtypes = [C.POINTER(C.c_uint64), ci]
     lib.atc_lookahead.argtypes = [vp, ci, ci, ci, ci, C.POINTER(AtcState), vp, C.POINTER(AtcLookaheadOut), C.POINTER(AtcParams), vp]
-    lib.atc_lookahead_launch_counts.argtypes = [C.POINTER(C.c_uint64), ci]
     lib.atc_lookahead_set_mapping.argtypes = [ci]
     lib.atc_lookahead_plan.argtypes = [vp, ci, ci, ci, ci, ci, C.POINTER(AtcState), vp, C.POINTER(AtcPlanOut), C.POINTER(AtcParams), vp]
-    lib.atc_plan_launch_counts.argtypes = [C.POINTER(C.c_uint64), ci]
     lib.atc_plan_draw.argtypes = [vp, ci, ci, ci, ci, vp, vp, C.POINTER(AtcPlanDraw), vp, ci, vp, C.POINTER(AtcParams), vp]
     lib.atc_lookahead_plan_sampled.argtypes = [vp, ci, ci, ci, ci, ci, C.POINTER(AtcState), vp, vp, C.POINTER(AtcPlanDraw), C.POINTER(AtcPlanOut),
                                                C.POINTER(AtcParams), vp]
-    lib.atc_plan_sampled_launch_counts.argtypes = [C.POINTER(C.c_uint64), ci]
-    lib.atc_plan_draw_launch_counts.argtypes = [C.POINTER(C.c_uint64), ci]
     lib.atc_plan_refit.argtypes = [vp, ci, ci, ci, ci, vp, vp, C.POINTER(AtcPlanDraw), vp, vp, vp, C.POINTER(AtcParams), vp]
-    lib.atc_plan_refit_launch_counts.argtypes = [C.POINTER(C.c_uint64), ci]
     lib.atc_plan_score.argtypes = [vp, ci, ci, ci, vp, vp, C.POINTER(AtcPlanScore), vp, vp, vp, ci, vp]
-    lib.atc_plan_score_launch_counts.argtypes = [C.POINTER(C.c_uint64), ci]
     lib.atc_branch.argtypes = [vp, ci, ci, ci, ci, C.POINTER(AtcState), vp, C.POINTER(AtcState), C.POINTER(AtcLookaheadOut), C.POINTER(AtcParams), vp]
-    lib.atc_branch_launch_counts.argtypes = [C.POINTER(C.c_uint64), ci]
     lib.atc_state_select.argtypes = [vp, ci, ci, C.POINTER(AtcState), ci, C.POINTER(AtcState), vp, vp, vp]
-    lib.atc_select_launch_counts.argtypes = [C.POINTER(C.c_uint64), ci]
+    for getter in LAUNCH_RECORDS:
+        getattr(lib, getter).argtypes = [C.POINTER(C.c_uint64), ci]
     for name in EXPORTS:
         if name not in ("atc_abi_version", "atc_last_error"):
             getattr(lib, name).restype = ci
@@ -171,73 +162,101 @@ def launch_name(slot):
     return "%d/%s" % (1 << (slot // L.LF_FORMS), L.LF_NAMES[slot % L.LF_FORMS])
 
 
-def _counts(getter, slots, name=lambda i: 1 << i):
-    """{name(slot): count} of one of the library's launch records (`getter`: its atc_*_launch_counts), zero counts left out."""
+def _width(slot):
+    return 1 << slot
+
+
+# The library's launch records (include/atc_step.h): getter -> (slots, name of a slot: a function of the slot number, or the one
+# slot's name).  load() gives every getter its argtypes from this table; each has a wrapper below, and launch_records() reads all.
+LAUNCH_RECORDS = {
+    "atc_launch_counts": (L.LAUNCH_SLOTS, launch_name),
+    "atc_skip_launch_counts": (L.SKIP_LAUNCH_SLOTS, _width),
+    "atc_traffic_launch_counts": (L.TRAFFIC_LAUNCH_SLOTS, _width),
+    "atc_lookahead_launch_counts": (L.LOOKAHEAD_LAUNCH_SLOTS, _width),
+    "atc_plan_launch_counts": (L.PLAN_LAUNCH_SLOTS, _width),
+    "atc_plan_sampled_launch_counts": (L.PLAN_SAMPLED_LAUNCH_SLOTS, _width),
+    "atc_plan_draw_launch_counts": (L.PLAN_DRAW_LAUNCH_SLOTS, "draw"),
+    "atc_plan_refit_launch_counts": (L.PLAN_REFIT_LAUNCH_SLOTS, "refit"),
+    "atc_plan_score_launch_counts": (L.PLAN_SCORE_LAUNCH_SLOTS, "score"),
+    "atc_branch_launch_counts": (L.BRANCH_LAUNCH_SLOTS, _width),
+    "atc_select_launch_counts": (L.SELECT_LAUNCH_SLOTS, "select"),
+}
+
+
+def _counts(getter):
+    """{name of slot: count} of one of the library's launch records (`getter`: a key of LAUNCH_RECORDS), zero counts left out."""
+    slots, name = LAUNCH_RECORDS[getter]
     buf = (C.c_uint64 * slots)()
     check(getattr(load(), getter)(buf, slots))
-    return {name(i): int(v) for i, v in enumerate(buf) if v}
+    return {name(i) if callable(name) else name: int(v) for i, v in enumerate(buf) if v}
+
+
+def launch_records():
+    """Every launch record of the calling thread in one dict, keyed by getter name: {"atc_launch_counts": launch_counts(), ...,
+    "atc_select_launch_counts": select_launch_counts()}.  Equal before and after a block of code: nothing in it launched."""
+    return {getter: _counts(getter) for getter in LAUNCH_RECORDS}
 
 
 def launch_counts():
     """Launches made by the calling thread so far, per kernel instantiation: {"16/allv-multi": n, ..., "serve": n}, names with a
     count of zero left out.  The counters only grow; take the difference of two calls around a block of code."""
-    return _counts("atc_launch_counts", L.LAUNCH_SLOTS, launch_name)
+    return _counts("atc_launch_counts")
 
 
 def skip_launch_counts():
     """Launches of the frame-skip kernel (atc_step_skip) made by the calling thread so far, by lane-group width: {16: n, ...},
     widths with a count of zero left out.  Separate from launch_counts(), which a skip call leaves as it is."""
-    return _counts("atc_skip_launch_counts", L.SKIP_LAUNCH_SLOTS)
+    return _counts("atc_skip_launch_counts")
 
 
 def traffic_launch_counts():
     """Launches of the traffic-observation kernel (atc_observe_traffic) made by the calling thread so far, by lane-group width:
     {16: n, ...}, widths with a count of zero left out.  Separate from launch_counts() and skip_launch_counts()."""
-    return _counts("atc_traffic_launch_counts", L.TRAFFIC_LAUNCH_SLOTS)
+    return _counts("atc_traffic_launch_counts")
 
 
 def lookahead_launch_counts():
     """Launches of the look-ahead kernel (atc_lookahead) made by the calling thread so far, by lane-group width: {16: n, ...},
     widths with a count of zero left out.  Separate from the other launch records, which a look-ahead leaves as they are."""
-    return _counts("atc_lookahead_launch_counts", L.LOOKAHEAD_LAUNCH_SLOTS)
+    return _counts("atc_lookahead_launch_counts")
 
 
 def plan_launch_counts():
     """Launches of the plan look-ahead kernel (atc_lookahead_plan) made by the calling thread so far, by lane-group width:
     {16: n, ...}, widths with a count of zero left out.  Separate from the other launch records, which a plan call leaves as they are."""
-    return _counts("atc_plan_launch_counts", L.PLAN_LAUNCH_SLOTS)
+    return _counts("atc_plan_launch_counts")
 
 
 def plan_sampled_launch_counts():
     """Launches of the drawn-plan kernel (atc_lookahead_plan_sampled) made by the calling thread so far, by lane-group width:
     {16: n, ...}, widths with a count of zero left out.  Separate from the other launch records, which a sampled call leaves as they are."""
-    return _counts("atc_plan_sampled_launch_counts", L.PLAN_SAMPLED_LAUNCH_SLOTS)
+    return _counts("atc_plan_sampled_launch_counts")
 
 
 def plan_draw_launch_counts():
     """Launches of the plan materialiser (atc_plan_draw) made by the calling thread so far: {"draw": n}, or {} before the first."""
-    return _counts("atc_plan_draw_launch_counts", L.PLAN_DRAW_LAUNCH_SLOTS, lambda i: "draw")
+    return _counts("atc_plan_draw_launch_counts")
 
 
 def plan_refit_launch_counts():
     """Launches of the refit on drawn plans (atc_plan_refit) made by the calling thread so far: {"refit": n}, or {} before the first."""
-    return _counts("atc_plan_refit_launch_counts", L.PLAN_REFIT_LAUNCH_SLOTS, lambda i: "refit")
+    return _counts("atc_plan_refit_launch_counts")
 
 
 def plan_score_launch_counts():
     """Launches of the scoring and ranking of drawn plans (atc_plan_score) made by the calling thread so far: {"score": n}, or {} before the first."""
-    return _counts("atc_plan_score_launch_counts", L.PLAN_SCORE_LAUNCH_SLOTS, lambda i: "score")
+    return _counts("atc_plan_score_launch_counts")
 
 
 def branch_launch_counts():
     """Launches of the branch kernel (atc_branch) made by the calling thread so far, by lane-group width: {16: n, ...}, widths with a
     count of zero left out.  Separate from the other launch records, which a branch call leaves as they are."""
-    return _counts("atc_branch_launch_counts", L.BRANCH_LAUNCH_SLOTS)
+    return _counts("atc_branch_launch_counts")
 
 
 def select_launch_counts():
     """Launches of the state gather (atc_state_select) made by the calling thread so far: {"select": n}, or {} before the first."""
-    return _counts("atc_select_launch_counts", L.SELECT_LAUNCH_SLOTS, lambda i: "select")
+    return _counts("atc_select_launch_counts")
 
 
 def lookahead_set_mapping(candidates_per_workgroup=0):

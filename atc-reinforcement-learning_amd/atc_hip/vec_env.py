@@ -449,6 +449,37 @@ class AtcVecEnv:
             raise ValueError("1 <= H (mean.shape[0]) <= %d" % L.PLAN_MAX_H)
         return H
 
+    @staticmethod
+    def _drawn_m(M, name="M"):
+        """M of the drawn-plan calls as an int; outside 1 .. 1024: ValueError"""
+        M = int(M)
+        if not 1 <= M <= L.SAMPLE_MAX_M:
+            raise ValueError("1 <= %s <= %d" % (name, L.SAMPLE_MAX_M))
+        return M
+
+    def _refuse_discrete(self):
+        if self.params.mode & L.M_DISCRETE:
+            raise ValueError("only the continuous action space is drawn (this env has discrete actions)")
+
+    def _as_tensor(self, v):
+        return v if self.torch.is_tensor(v) else self.torch.as_tensor(np.asarray(v))
+
+    def _to_device(self, mu, sd):
+        """mean and std for a call that takes device tensors only: a host-mapped env's pinned pair is copied to the device"""
+        if self.host_mapped and not (mu.is_cuda and sd.is_cuda):
+            return mu.to(self.device), sd.to(self.device)
+        return mu, sd
+
+    def _on_device(self, t, dtypes, shape, what=None, text=None, elements=False):
+        """`t` if it is a contiguous tensor of one of `dtypes` on this env's device and, where `shape` is given, of that shape (elements=True:
+        of that many elements); ValueError otherwise — `text % (shape, device)` in the caller's words, or in terms of `what`"""
+        torch = self.torch
+        if not (torch.is_tensor(t) and t.is_cuda and t.device == self.device and t.dtype in dtypes and t.is_contiguous()
+                and (shape is None or (t.numel() == int(np.prod(shape, dtype=np.int64)) if elements else tuple(t.shape) == shape))):
+            raise ValueError(text % (shape, self.device) if text else "%s must be a contiguous %s tensor%s on %s" % (
+                what, " / ".join(str(d) for d in dtypes), "" if shape is None else " of %r" % (shape,), self.device))
+        return t
+
     def _draw_source(self, H, mean, std, seed, iteration, mean_first):
         """(mean, std, atc_plan_draw_t) as the library reads them: contiguous float32 tensors of H * B * N * 3 elements (a python float
         for std is broadcast once into a cached tensor)"""
@@ -483,15 +514,12 @@ class AtcVecEnv:
         if not 1 <= K <= L.SKIP_MAX:
             raise ValueError("1 <= K <= %d" % L.SKIP_MAX)
         H = self._draw_h(mean)
-        M = int(M)
-        if not 1 <= M <= L.SAMPLE_MAX_M:
-            raise ValueError("1 <= M <= %d" % L.SAMPLE_MAX_M)
+        M = self._drawn_m(M)
         mu, sd, dr = self._draw_source(H, mean, std, seed, iteration, mean_first)
         if not set(outputs) <= set(self.PLAN_OUTPUTS):
             raise ValueError("outputs must be a subset of %r" % (self.PLAN_OUTPUTS,))
         outputs = tuple(n for n in self.PLAN_OUTPUTS if n in outputs)
-        if self.params.mode & L.M_DISCRETE:
-            raise ValueError("only the continuous action space is drawn (this env has discrete actions)")
+        self._refuse_discrete()
         res, out = self._candidate_results("_plan_sampled_cache", (M, H), outputs, True)
         with torch.cuda.device(self.device):
             _lib.check(self._lib.atc_lookahead_plan_sampled(self.sector.handle, self.B, self.N, K, H, M, C.byref(self._state), self._ptr(mu),
@@ -509,13 +537,10 @@ class AtcVecEnv:
         lookahead_plan_sampled()."""
         torch = self.torch
         H = self._draw_h(mean)
-        M = int(M)
-        if not 1 <= M <= L.SAMPLE_MAX_M:
-            raise ValueError("1 <= M <= %d" % L.SAMPLE_MAX_M)
+        M = self._drawn_m(M)
         idx, R = None, M
         if index is not None:
-            if not torch.is_tensor(index):
-                index = torch.as_tensor(np.asarray(index))
+            index = self._as_tensor(index)
             if index.dtype.is_floating_point or index.dtype is torch.bool or index.numel() < 1 or index.numel() % self.B:
                 raise ValueError("index must be an integer tensor [E, B] or [B] (B = %d)" % self.B)
             R = index.numel() // self.B
@@ -523,16 +548,13 @@ class AtcVecEnv:
             index = index.to(device=self.device).reshape(R, self.B)
             idx = torch.where((index >= 0) & (index < M), index, torch.full_like(index, -1)).to(torch.int32).contiguous()
         mu, sd, dr = self._draw_source(H, mean, std, seed, iteration, mean_first)
-        if self.params.mode & L.M_DISCRETE:
-            raise ValueError("only the continuous action space is drawn (this env has discrete actions)")
+        self._refuse_discrete()
         shape = (R, H, self.B, self.N, L.ACT_DIM)
         if out is None:
             out = (torch.empty if idx is None else torch.zeros)(shape, dtype=torch.float32, device=self.device)
-        elif not (torch.is_tensor(out) and out.is_cuda and out.device == self.device and out.dtype is torch.float32 and out.is_contiguous()
-                  and out.numel() == int(np.prod(shape, dtype=np.int64))):
-            raise ValueError("out must be a contiguous float32 tensor of %s on %s" % (shape, self.device))
-        if self.host_mapped and not (mu.is_cuda and sd.is_cuda):
-            mu, sd = mu.to(self.device), sd.to(self.device)
+        else:
+            self._on_device(out, (torch.float32,), shape, text="out must be a contiguous float32 tensor of %s on %s", elements=True)
+        mu, sd = self._to_device(mu, sd)
         with torch.cuda.device(self.device):
             _lib.check(self._lib.atc_plan_draw(self.sector.handle, self.B, self.N, H, M, self._ptr(mu), self._ptr(sd), C.byref(dr),
                                                None if idx is None else idx.data_ptr(), R, out.data_ptr(), C.byref(self.params), self._stream()))
@@ -552,19 +574,14 @@ class AtcVecEnv:
         lookahead_plan_sampled(); continuous action space only."""
         torch = self.torch
         H = self._draw_h(mean)
-        M = int(M)
-        if not 1 <= M <= L.SAMPLE_MAX_M:
-            raise ValueError("1 <= M <= %d" % L.SAMPLE_MAX_M)
-        if not torch.is_tensor(weight):
-            weight = torch.as_tensor(np.asarray(weight))
+        M = self._drawn_m(M)
+        weight = self._as_tensor(weight)
         if tuple(weight.shape) != (M, self.B):
             raise ValueError("weight must be [M, B] = [%d, %d], got %r" % (M, self.B, tuple(weight.shape)))
         w = weight.to(device=self.device, dtype=torch.float32).contiguous()
         mu, sd, dr = self._draw_source(H, mean, std, seed, iteration, mean_first)
-        if self.params.mode & L.M_DISCRETE:
-            raise ValueError("only the continuous action space is drawn (this env has discrete actions)")
-        if self.host_mapped and not (mu.is_cuda and sd.is_cuda):
-            mu, sd = mu.to(self.device), sd.to(self.device)
+        self._refuse_discrete()
+        mu, sd = self._to_device(mu, sd)
         shape = (H, self.B, self.N, L.ACT_DIM)
         if out is None:
             new_mu, new_sd = mu.clone(), sd.clone()
@@ -573,9 +590,7 @@ class AtcVecEnv:
                 raise ValueError("out must be a pair (mean_t, std_t)")
             new_mu, new_sd = out
             for t in (new_mu, new_sd):
-                if not (torch.is_tensor(t) and t.is_cuda and t.device == self.device and t.dtype is torch.float32 and t.is_contiguous()
-                        and t.numel() == int(np.prod(shape, dtype=np.int64))):
-                    raise ValueError("out must hold contiguous float32 tensors of %s on %s" % (shape, self.device))
+                self._on_device(t, (torch.float32,), shape, text="out must hold contiguous float32 tensors of %s on %s", elements=True)
         with torch.cuda.device(self.device):
             _lib.check(self._lib.atc_plan_refit(self.sector.handle, self.B, self.N, H, M, self._ptr(mu), self._ptr(sd), C.byref(dr),
                                                 w.data_ptr(), new_mu.data_ptr(), new_sd.data_ptr(), C.byref(self.params), self._stream()))
@@ -602,22 +617,14 @@ class AtcVecEnv:
         no action and no state, so it works on discrete-action envs too."""
         torch = self.torch
         dev = self.device
-
-        def on_device(t, dtypes, shape, what):
-            if not (torch.is_tensor(t) and t.is_cuda and t.device == dev and t.dtype in dtypes and t.is_contiguous()
-                    and (shape is None or tuple(t.shape) == shape)):
-                raise ValueError("%s must be a contiguous %s tensor%s on %s" % (
-                    what, " / ".join(str(d) for d in dtypes), "" if shape is None else " of %r" % (shape,), dev))
-            return t
-
+        on_device = self._on_device
         on_device(seg_reward, (torch.float32,), None, "seg_reward")
         if seg_reward.dim() != 3 or int(seg_reward.shape[2]) != self.B:
             raise ValueError("seg_reward must be [M, H, B] with B = %d, got %r" % (self.B, tuple(seg_reward.shape)))
         M, H = int(seg_reward.shape[0]), int(seg_reward.shape[1])
         if not 1 <= H <= L.PLAN_MAX_H:
             raise ValueError("1 <= H (seg_reward.shape[1]) <= %d" % L.PLAN_MAX_H)
-        if not 1 <= M <= L.SAMPLE_MAX_M:
-            raise ValueError("1 <= M (seg_reward.shape[0]) <= %d" % L.SAMPLE_MAX_M)
+        self._drawn_m(M, "M (seg_reward.shape[0])")
         R = int(top)
         if not 0 <= R <= L.SCORE_MAX_TOP:
             raise ValueError("0 <= top <= %d" % L.SCORE_MAX_TOP)
@@ -718,8 +725,7 @@ class AtcVecEnv:
         env that was not written keeps its own.  Returns self.obs."""
         torch = self.torch
         self._check_twin(src, "src")
-        if not torch.is_tensor(index):
-            index = torch.as_tensor(np.asarray(index))
+        index = self._as_tensor(index)
         if index.dtype not in (torch.int32, torch.int64) or index.numel() != self.B:
             raise ValueError("index must be an int32 / int64 tensor of %d elements" % self.B)
         # (the range test on the caller's own dtype: an int64 value beyond 32 bits must be refused, not wrapped into range)

@@ -7,22 +7,22 @@ extern "C" {
 int atc_abi_version(void) { return ATC_ABI_VERSION; }
 
 // every launch record's getter: the first min(n, slots) counters of the calling thread
-static int copy_counts(const uint64_t* record, int slots, uint64_t* out, int n) {
+static int copy_counts(Record rec, uint64_t* out, int n) {
     if (!out || n < 0) return fail_arg("null pointer");
-    for (int i = 0; i < n && i < slots; ++i) out[i] = record[i];
+    for (int i = 0; i < n && i < kRecordSlots[rec]; ++i) out[i] = record(rec)[i];
     return ATC_OK;
 }
-int atc_launch_counts(uint64_t* out, int n) { return copy_counts(t_launches, ATC_LAUNCH_SLOTS, out, n); }
-int atc_skip_launch_counts(uint64_t* out, int n) { return copy_counts(t_skip_launches, ATC_SKIP_LAUNCH_SLOTS, out, n); }
-int atc_traffic_launch_counts(uint64_t* out, int n) { return copy_counts(t_traffic_launches, ATC_TRAFFIC_LAUNCH_SLOTS, out, n); }
-int atc_lookahead_launch_counts(uint64_t* out, int n) { return copy_counts(t_look_launches, ATC_LOOKAHEAD_LAUNCH_SLOTS, out, n); }
-int atc_plan_launch_counts(uint64_t* out, int n) { return copy_counts(t_plan_launches, ATC_PLAN_LAUNCH_SLOTS, out, n); }
-int atc_plan_sampled_launch_counts(uint64_t* out, int n) { return copy_counts(t_plan_sampled_launches, ATC_PLAN_SAMPLED_LAUNCH_SLOTS, out, n); }
-int atc_plan_draw_launch_counts(uint64_t* out, int n) { return copy_counts(t_plan_draw_launches, ATC_PLAN_DRAW_LAUNCH_SLOTS, out, n); }
-int atc_plan_refit_launch_counts(uint64_t* out, int n) { return copy_counts(t_plan_refit_launches, ATC_PLAN_REFIT_LAUNCH_SLOTS, out, n); }
-int atc_plan_score_launch_counts(uint64_t* out, int n) { return copy_counts(t_plan_score_launches, ATC_PLAN_SCORE_LAUNCH_SLOTS, out, n); }
-int atc_branch_launch_counts(uint64_t* out, int n) { return copy_counts(t_branch_launches, ATC_BRANCH_LAUNCH_SLOTS, out, n); }
-int atc_select_launch_counts(uint64_t* out, int n) { return copy_counts(t_select_launches, ATC_SELECT_LAUNCH_SLOTS, out, n); }
+int atc_launch_counts(uint64_t* out, int n) { return copy_counts(REC_STEP, out, n); }
+int atc_skip_launch_counts(uint64_t* out, int n) { return copy_counts(REC_SKIP, out, n); }
+int atc_traffic_launch_counts(uint64_t* out, int n) { return copy_counts(REC_TRAFFIC, out, n); }
+int atc_lookahead_launch_counts(uint64_t* out, int n) { return copy_counts(REC_LOOKAHEAD, out, n); }
+int atc_plan_launch_counts(uint64_t* out, int n) { return copy_counts(REC_PLAN, out, n); }
+int atc_plan_sampled_launch_counts(uint64_t* out, int n) { return copy_counts(REC_PLAN_SAMPLED, out, n); }
+int atc_plan_draw_launch_counts(uint64_t* out, int n) { return copy_counts(REC_PLAN_DRAW, out, n); }
+int atc_plan_refit_launch_counts(uint64_t* out, int n) { return copy_counts(REC_PLAN_REFIT, out, n); }
+int atc_plan_score_launch_counts(uint64_t* out, int n) { return copy_counts(REC_PLAN_SCORE, out, n); }
+int atc_branch_launch_counts(uint64_t* out, int n) { return copy_counts(REC_BRANCH, out, n); }
+int atc_select_launch_counts(uint64_t* out, int n) { return copy_counts(REC_SELECT, out, n); }
 int atc_lookahead_set_mapping(int candidates_per_workgroup) {
     if (candidates_per_workgroup < 0 || candidates_per_workgroup > ATC_LOOKAHEAD_MAX_M) return fail_arg("candidates per workgroup must be 0 (the library's choice) .. 64");
     t_look_cpg = candidates_per_workgroup;
@@ -343,7 +343,7 @@ int atc_serve_start(const atc_scenario_t* s, const atc_state_t* st, const atc_ou
     hipLaunchKernelGGL(k_serve, dim3(1), dim3(64), lds_bytes(s, false, true), (hipStream_t)stream, s->d_blob, s->off_grid, *st, *out, *p,
                        derive(*p, s, 0), mb_dev, seq, (unsigned long long)lease_us * 100ull);
     HIP_TRY(hipGetLastError());
-    ++t_launches[ATC_LAUNCH_SERVE];
+    ++record(REC_STEP)[ATC_LAUNCH_SERVE];
     return ATC_OK;
 }
 
@@ -447,122 +447,84 @@ int atc_observe_traffic(const atc_scenario_t* s, int B, int N, int K, const atc_
 int atc_lookahead(const atc_scenario_t* s, int B, int N, int K, int M, const atc_state_t* st, const float* actions,
                   const atc_lookahead_out_t* out, const atc_params_t* p, void* stream) {
     if (const int rc = check_candidates(s, B, N, K, nullptr, M, st, actions, out, p, "look-ahead", "atc_lookahead_out_t", "candidate")) return rc;
-    return with_width(N, [&](auto w) { return launch_lookahead<decltype(w)::value>(s, B, N, K, M, st, actions, out, p, (hipStream_t)stream); });
+    return launch_candidates(REC_LOOKAHEAD, s, B, N, M, out, cand_any(out), p, [&](auto w, auto full, const CandGrid& g, size_t lds, const atc_out_t& o, const StepDerived& q) {
+        hipLaunchKernelGGL((k_lookahead<decltype(w)::value, decltype(full)::value>), dim3(g.grid), dim3(kBlock), lds, (hipStream_t)stream, s->d_blob, s->off_grid, B, N, K, M, *st, actions, o, *p, q, out->n_steps, g.cpg, g.groups, g.tiles);
+    });
 }
 
 int atc_lookahead_plan(const atc_scenario_t* s, int B, int N, int K, int H, int M, const atc_state_t* st, const float* actions,
                        const atc_plan_out_t* out, const atc_params_t* p, void* stream) {
     if (const int rc = check_candidates(s, B, N, K, &H, M, st, actions, out, p, "segment", "atc_plan_out_t", "segment")) return rc;
-    return with_width(N, [&](auto w) { return launch_plan<decltype(w)::value>(s, B, N, K, H, M, st, actions, out, p, (hipStream_t)stream); });
+    return launch_candidates(REC_PLAN, s, B, N, M, out, cand_any(out), p, [&](auto w, auto full, const CandGrid& g, size_t lds, const atc_out_t& o, const StepDerived& q) {
+        hipLaunchKernelGGL((k_plan<decltype(w)::value, decltype(full)::value>), dim3(g.grid), dim3(kBlock), lds, (hipStream_t)stream, s->d_blob, s->off_grid, B, N, K, H, M, *st, actions, o, *p, q, out->n_steps, out->seg_reward, g.cpg, g.groups, g.tiles);
+    });
 }
 
 int atc_lookahead_plan_sampled(const atc_scenario_t* s, int B, int N, int K, int H, int M, const atc_state_t* st, const float* mean,
                                const float* std, const atc_plan_draw_t* dr, const atc_plan_out_t* out, const atc_params_t* p, void* stream) {
-    const DrawSource src = {mean, std, dr};
-    if (const int rc = check_candidates(s, B, N, K, &H, M, st, nullptr, out, p, "segment", "atc_plan_out_t", "segment", &src)) return rc;
-    return with_width(N, [&](auto w) { return launch_plan_sampled<decltype(w)::value>(s, B, N, K, H, M, st, src, out, p, (hipStream_t)stream); });
+    if (const int rc = check_candidates(s, B, N, K, &H, M, st, nullptr, out, p, "segment", "atc_plan_out_t", "segment", {need_dr(dr), need_mean(mean), need_std(std)}))
+        return rc;
+    return launch_candidates(REC_PLAN_SAMPLED, s, B, N, M, out, cand_any(out), p, [&](auto w, auto full, const CandGrid& g, size_t lds, const atc_out_t& o, const StepDerived& q) {
+        hipLaunchKernelGGL((k_plan_sampled<decltype(w)::value, decltype(full)::value>), dim3(g.grid), dim3(kBlock), lds, (hipStream_t)stream, s->d_blob, s->off_grid, B, N, K, H, M, *st, mean, o, *p, q, out->n_steps, out->seg_reward, g.cpg, g.groups, g.tiles, std, *dr);
+    });
 }
 
 int atc_plan_draw(const atc_scenario_t* s, int B, int N, int H, int M, const float* mean, const float* std, const atc_plan_draw_t* dr,
                   const int32_t* index, int E, float* actions, const atc_params_t* p, void* stream) {
     // H, then M, then E, before any pointer is looked at
-    if (H < 1 || H > ATC_PLAN_MAX_H) return fail_arg("H (the number of segments of a plan) must be 1 .. 16");
-    if (M < 1 || M > ATC_SAMPLE_MAX_M) return fail_arg("M (the number of drawn candidates) must be 1 .. 1024");
-    if (index && E < 1) return fail_arg("E (the rows of index) must be >= 1");
-    if (!s) return fail_arg("null pointer: s");
-    if (!mean) return fail_arg("null pointer: mean is required");
-    if (!std) return fail_arg("null pointer: std is required");
-    if (!dr) return fail_arg("null pointer: dr (atc_plan_draw_t) is required");
-    if (!actions) return fail_arg("null pointer: actions");
-    if (!p) return fail_arg("null pointer: p");
-    if (p->mode & ATC_M_DISCRETE) return fail_arg("ATC_M_DISCRETE: only the continuous action space is drawn");
-    if (const int rc = check_batch_range(B, N)) return rc;
-    if (const int rc = check_batch_size(B, N)) return rc;
+    if (const int rc = check_drawn_plan(H, M, index && E < 1 ? "E (the rows of index) must be >= 1" : nullptr,
+                                        {{s, "null pointer: s"}, need_mean(mean), need_std(std), need_dr(dr), {actions, "null pointer: actions"}, {p, "null pointer: p"}},
+                                        p, B, N))
+        return rc;
     const int R = index ? E : M;
-    const unsigned tiles = (unsigned)(((unsigned long long)B * N + kBlock - 1) / kBlock);
-    hipLaunchKernelGGL(k_plan_draw, dim3(tiles, (unsigned)H, (unsigned)std::min(R, 65535)), dim3(kBlock), 0, (hipStream_t)stream, B, N, H, M, R, mean, std,
+    hipLaunchKernelGGL(k_plan_draw, dim3(flat_tiles(B, N), (unsigned)H, (unsigned)std::min(R, 65535)), dim3(kBlock), 0, (hipStream_t)stream, B, N, H, M, R, mean, std,
                        *dr, index, actions);
     HIP_TRY(hipGetLastError());
-    ++t_plan_draw_launches[0];
+    ++record(REC_PLAN_DRAW)[0];
     return ATC_OK;
 }
 
 int atc_plan_refit(const atc_scenario_t* s, int B, int N, int H, int M, const float* mean, const float* std, const atc_plan_draw_t* dr,
                    const float* weight, float* new_mean, float* new_std, const atc_params_t* p, void* stream) {
     // H, then M, before any pointer is looked at
-    if (H < 1 || H > ATC_PLAN_MAX_H) return fail_arg("H (the number of segments of a plan) must be 1 .. 16");
-    if (M < 1 || M > ATC_SAMPLE_MAX_M) return fail_arg("M (the number of drawn candidates) must be 1 .. 1024");
-    if (!s) return fail_arg("null pointer: s");
-    if (!mean) return fail_arg("null pointer: mean is required");
-    if (!std) return fail_arg("null pointer: std is required");
-    if (!dr) return fail_arg("null pointer: dr (atc_plan_draw_t) is required");
-    if (!weight) return fail_arg("null pointer: weight is required");
-    if (!new_mean) return fail_arg("null pointer: new_mean");
-    if (!new_std) return fail_arg("null pointer: new_std");
-    if (!p) return fail_arg("null pointer: p");
-    if (p->mode & ATC_M_DISCRETE) return fail_arg("ATC_M_DISCRETE: only the continuous action space is drawn");
-    if (const int rc = check_batch_range(B, N)) return rc;
-    if (const int rc = check_batch_size(B, N)) return rc;
-    {   // the five byte ranges (pointer VALUES only): new_mean == mean and new_std == std exactly are the in-place update, any other overlap is refused
-        const char* const name[5] = {"mean", "std", "weight", "new_mean", "new_std"};
-        const void* const ptr[5] = {mean, std, weight, new_mean, new_std};
-        const uintptr_t rows = (uintptr_t)H * (uintptr_t)B * (uintptr_t)N * 12u, wts = (uintptr_t)M * (uintptr_t)B * 4u;
-        for (int a = 0; a < 5; ++a)
-            for (int b = a + 1; b < 5; ++b) {
-                if ((a == 0 && b == 3 && mean == new_mean) || (a == 1 && b == 4 && std == new_std)) continue;
-                const uintptr_t alo = reinterpret_cast<uintptr_t>(ptr[a]), blo = reinterpret_cast<uintptr_t>(ptr[b]);
-                if (alo < blo + (b == 2 ? wts : rows) && blo < alo + (a == 2 ? wts : rows)) {
-                    char msg[160];
-                    snprintf(msg, sizeof msg, "%s overlaps %s (only new_mean == mean and new_std == std, as equal pointers, may share memory)", name[a], name[b]);
-                    return fail_arg(msg);
-                }
-            }
-    }
-    const unsigned tiles = (unsigned)(((unsigned long long)B * N + kBlock - 1) / kBlock);
-    hipLaunchKernelGGL(k_plan_refit, dim3(tiles, (unsigned)H), dim3(kBlock), 0, (hipStream_t)stream, B, N, H, M, mean, std, *dr, weight, new_mean, new_std);
+    if (const int rc = check_drawn_plan(H, M, nullptr,
+                                        {{s, "null pointer: s"}, need_mean(mean), need_std(std), need_dr(dr), need_weight(weight), {new_mean, "null pointer: new_mean"},
+                                         {new_std, "null pointer: new_std"}, {p, "null pointer: p"}},
+                                        p, B, N))
+        return rc;
+    // new_mean == mean and new_std == std exactly are the in-place update, any other overlap is refused
+    const uintptr_t rows = (uintptr_t)H * (uintptr_t)B * (uintptr_t)N * 12u, wts = (uintptr_t)M * (uintptr_t)B * 4u;
+    const ByteRange ranges[5] = {{mean, rows, "mean"}, {std, rows, "std"}, {weight, wts, "weight"}, {new_mean, rows, "new_mean"}, {new_std, rows, "new_std"}};
+    if (const int rc = check_disjoint(ranges, 5, {{0, 3}, {1, 4}}, "only new_mean == mean and new_std == std, as equal pointers, may share memory")) return rc;
+    hipLaunchKernelGGL(k_plan_refit, dim3(flat_tiles(B, N), (unsigned)H), dim3(kBlock), 0, (hipStream_t)stream, B, N, H, M, mean, std, *dr, weight, new_mean, new_std);
     HIP_TRY(hipGetLastError());
-    ++t_plan_refit_launches[0];
+    ++record(REC_PLAN_REFIT)[0];
     return ATC_OK;
 }
 
 int atc_plan_score(const atc_scenario_t* s, int B, int H, int M, const float* seg_reward, const uint16_t* n_steps, const atc_plan_score_t* sc,
                    float* score, float* weight, int32_t* top, int R, void* stream) {
     // H, then M, then R, before any pointer is looked at
-    if (H < 1 || H > ATC_PLAN_MAX_H) return fail_arg("H (the number of segments of a plan) must be 1 .. 16");
-    if (M < 1 || M > ATC_SAMPLE_MAX_M) return fail_arg("M (the number of drawn candidates) must be 1 .. 1024");
-    if (R < 0 || R > ATC_SCORE_MAX_TOP) return fail_arg("R (the rows of top) must be 0 .. 64");
-    if (R > 0 && !top) return fail_arg("R (the rows of top) > 0 needs top");
-    if (!s) return fail_arg("null pointer: s");
-    if (!seg_reward) return fail_arg("null pointer: seg_reward is required");
-    if (!sc) return fail_arg("null pointer: sc (atc_plan_score_t) is required");
-    if (!score) return fail_arg("null pointer: score is required (result and workspace)");
-    if (!weight) return fail_arg("null pointer: weight is required");
+    const char* const r_refusal = R < 0 || R > ATC_SCORE_MAX_TOP ? "R (the rows of top) must be 0 .. 64" : R > 0 && !top ? "R (the rows of top) > 0 needs top" : nullptr;
+    if (const int rc = check_drawn_plan(H, M, r_refusal,
+                                        {{s, "null pointer: s"}, {seg_reward, "null pointer: seg_reward is required"}, {sc, "null pointer: sc (atc_plan_score_t) is required"},
+                                         {score, "null pointer: score is required (result and workspace)"}, need_weight(weight)}))
+        return rc;
     if (sc->mode != ATC_SCORE_ELITE && sc->mode != ATC_SCORE_SOFTMAX) return fail_arg("sc->mode must be ATC_SCORE_ELITE or ATC_SCORE_SOFTMAX");
     if (sc->mode == ATC_SCORE_ELITE && (sc->elites < 1 || sc->elites > M)) return fail_arg("sc->elites must be 1 .. M");
     if (!(fabsf(sc->gamma) <= __FLT_MAX__)) return fail_arg("sc->gamma must be finite");
     if (sc->mode == ATC_SCORE_SOFTMAX && !(sc->temperature > 0.0f && sc->temperature <= __FLT_MAX__)) return fail_arg("sc->temperature must be > 0 and finite");
     if (B < 1) return fail_arg("need B >= 1");
-    {   // the byte ranges (pointer VALUES only): any overlap is refused, ranges that only touch are not
-        const char* const name[5] = {"seg_reward", "n_steps", "score", "weight", "top"};
-        const void* const ptr[5] = {seg_reward, n_steps, score, weight, R > 0 ? top : nullptr};
-        const uintptr_t mb = (uintptr_t)M * (uintptr_t)B;
-        const uintptr_t bytes[5] = {mb * (uintptr_t)H * 4u, mb * 2u, mb * 4u, mb * 4u, (uintptr_t)R * (uintptr_t)B * 4u};
-        for (int a = 0; a < 5; ++a)
-            for (int b = a + 1; b < 5; ++b) {
-                if (!ptr[a] || !ptr[b]) continue;
-                const uintptr_t alo = reinterpret_cast<uintptr_t>(ptr[a]), blo = reinterpret_cast<uintptr_t>(ptr[b]);
-                if (alo < blo + bytes[b] && blo < alo + bytes[a]) {
-                    char msg[160];
-                    snprintf(msg, sizeof msg, "%s overlaps %s (no two arrays of atc_plan_score may share memory)", name[a], name[b]);
-                    return fail_arg(msg);
-                }
-            }
-    }
+    // any overlap is refused (n_steps may be absent, and top with R == 0)
+    const uintptr_t mb = (uintptr_t)M * (uintptr_t)B;
+    const ByteRange ranges[5] = {{seg_reward, mb * (uintptr_t)H * 4u, "seg_reward"}, {n_steps, mb * 2u, "n_steps"}, {score, mb * 4u, "score"}, {weight, mb * 4u, "weight"},
+                                 {R > 0 ? top : nullptr, (uintptr_t)R * (uintptr_t)B * 4u, "top"}};
+    if (const int rc = check_disjoint(ranges, 5, {}, "no two arrays of atc_plan_score may share memory")) return rc;
     const unsigned tiles = (unsigned)(((unsigned long long)B + kScoreBlock - 1) / kScoreBlock);
     hipLaunchKernelGGL(k_plan_score, dim3(tiles), dim3(kScoreBlock), 0, (hipStream_t)stream, B, H, M, seg_reward, n_steps, *sc, score, weight,
                        R > 0 ? top : nullptr, R);
     HIP_TRY(hipGetLastError());
-    ++t_plan_score_launches[0];
+    ++record(REC_PLAN_SCORE)[0];
     return ATC_OK;
 }
 
@@ -576,14 +538,17 @@ int atc_branch(const atc_scenario_t* s, int B, int N, int K, int M, const atc_st
     // (pointer values only; a src the later checks refuse has no ranges to compare)
     if (src && B >= 1 && N >= 1 && N <= ATC_MAX_AIRCRAFT && states_overlap(dst, (unsigned long long)M * B, src, B, N))
         return fail_arg("dst (M*B envs) overlaps src (B envs)");
-    if (B >= 1 && N >= 1 && N <= ATC_MAX_AIRCRAFT &&
-        ((unsigned long long)M * B * N * ATC_OBS_DIM * 4ull >= (1ull << 32) || (unsigned long long)M * B * 64ull >= (1ull << 32)))
-        return fail_arg("M*B is not a batch size atc_step accepts (M*B*N*40 bytes must stay below 4 GiB): split the candidates");
+    if (B >= 1 && N >= 1 && N <= ATC_MAX_AIRCRAFT)
+        if (const int rc = check_batch_size((unsigned long long)M * B, N, "M*B is not a batch size atc_step accepts (M*B*N*40 bytes must stay below 4 GiB): split the candidates"))
+            return rc;
     if (!actions) return fail_arg("null pointer");
     if (const int rc = check_env_args(s, B, N, src, p)) return rc;
     if (const int rc = check_dt(s, p)) return rc;
     if (p->mode & ATC_M_ACTIONS_HELD) return fail_arg("ATC_M_ACTIONS_HELD is for atc_step only: every candidate's first step carries a fresh decision");
-    return with_width(N, [&](auto w) { return launch_branch<decltype(w)::value>(s, B, N, K, M, src, actions, dst, out, p, (hipStream_t)stream); });
+    // k_skip's rule for the form: obs and flags are stored by both (csrc/atc_branch.inc)
+    return launch_candidates(REC_BRANCH, s, B, N, M, out, out->ac_reward || out->min_sep, p, [&](auto w, auto full, const CandGrid& g, size_t lds, const atc_out_t& o, const StepDerived& q) {
+        hipLaunchKernelGGL((k_branch<decltype(w)::value, decltype(full)::value>), dim3(g.grid), dim3(kBlock), lds, (hipStream_t)stream, s->d_blob, s->off_grid, B, N, K, M, *src, actions, o, *p, q, out->n_steps, g.cpg, g.groups, g.tiles, *dst);
+    });
 }
 
 int atc_state_select(const atc_scenario_t* s, int N, int B_dst, const atc_state_t* dst, int B_src, const atc_state_t* src, const int32_t* index,
@@ -593,11 +558,10 @@ int atc_state_select(const atc_scenario_t* s, int N, int B_dst, const atc_state_
     if (states_overlap(dst, B_dst, src, B_src, N)) return fail_arg("dst overlaps src");
     if (!s) return fail_arg("null pointer");
     for (const int B : {B_dst, B_src})
-        if ((unsigned long long)B * N * ATC_OBS_DIM * 4ull >= (1ull << 32) || (unsigned long long)B * 64ull >= (1ull << 32))
-            return fail_arg("B*N too large for one launch (B*N*40 bytes must stay below 4 GiB): split the batch");
+        if (const int rc = check_batch_size(B, N)) return rc;
     hipLaunchKernelGGL(k_select, dim3(step_grid(B_dst, N)), dim3(kBlock), 0, (hipStream_t)stream, N, B_dst, *dst, B_src, *src, index, mask);
     HIP_TRY(hipGetLastError());
-    ++t_select_launches[0];
+    ++record(REC_SELECT)[0];
     return ATC_OK;
 }
 

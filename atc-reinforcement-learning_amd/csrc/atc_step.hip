@@ -1738,6 +1738,8 @@ k_serve(const float* __restrict__ blob, int off_grid, atc_state_t st, atc_out_t 
 // ---------------------------------------------------------------------------------------------------------------
 // host side of the C-ABI
 // ---------------------------------------------------------------------------------------------------------------
+#include <initializer_list>
+#include <utility>
 static int grid_for(const atc_scenario* s, long long threads) {
     long long blocks = (threads + kBlock - 1) / kBlock;
     const long long cap = (long long)s->n_cu * ATC_GRID_CAP;
@@ -1747,6 +1749,8 @@ static int grid_for(const atc_scenario* s, long long threads) {
 }
 // the step kernels (k_step, k_skip): one workgroup per 256 slots of W per env, no grid-stride loop
 static int step_grid(int B, int W) { return (int)(((long long)B * W + kBlock - 1) / kBlock); }
+// ... and the kernels over the flat B*N aircraft of a plan (k_plan_draw, k_plan_refit): the same tiles of 256, no padding to W
+static unsigned flat_tiles(int B, int N) { return (unsigned)step_grid(B, N); }
 static size_t lds_bytes(const atc_scenario*, bool pair_scan, bool step_kernel = false) {
     size_t w = 0;  // the sector is not staged: LDS only holds the obs transpose stage and the pair-scan staging
     if (step_kernel) w += (size_t)(kBlock / 64) * 64 * ATC_OBS_DIM;
@@ -1754,9 +1758,21 @@ static size_t lds_bytes(const atc_scenario*, bool pair_scan, bool step_kernel = 
     return w * sizeof(float);
 }
 
-// the launch record (include/atc_step.h: atc_launch_counts): launches of each k_step instantiation and k_serve starts made by the
-// calling thread — a plain thread-local counter that nothing in the library reads back
-static thread_local uint64_t t_launches[ATC_LAUNCH_SLOTS] = {0};
+// the launch records (include/atc_step.h: the atc_*_launch_counts getters): launches made by the calling thread, every record's
+// counters in one table — plain thread-local counters that nothing in the library reads back.  REC_STEP has a slot for each k_step
+// instantiation and one for k_serve starts; a record of 7 slots counts by lane-group width (slot = log2(W)); a record of one slot
+// counts its entry point's launches.  A call moves its own record only.
+enum Record { REC_STEP, REC_SKIP, REC_TRAFFIC, REC_LOOKAHEAD, REC_PLAN, REC_PLAN_SAMPLED, REC_PLAN_DRAW, REC_PLAN_REFIT, REC_PLAN_SCORE, REC_BRANCH, REC_SELECT, REC_COUNT };
+constexpr int kRecordSlots[REC_COUNT] = {ATC_LAUNCH_SLOTS, ATC_SKIP_LAUNCH_SLOTS, ATC_TRAFFIC_LAUNCH_SLOTS, ATC_LOOKAHEAD_LAUNCH_SLOTS, ATC_PLAN_LAUNCH_SLOTS,
+                                         ATC_PLAN_SAMPLED_LAUNCH_SLOTS, ATC_PLAN_DRAW_LAUNCH_SLOTS, ATC_PLAN_REFIT_LAUNCH_SLOTS, ATC_PLAN_SCORE_LAUNCH_SLOTS,
+                                         ATC_BRANCH_LAUNCH_SLOTS, ATC_SELECT_LAUNCH_SLOTS};
+constexpr int record_offset(int id) {
+    int o = 0;
+    for (int i = 0; i < id; ++i) o += kRecordSlots[i];
+    return o;
+}
+static thread_local uint64_t t_records[record_offset(REC_COUNT)] = {0};
+static uint64_t* record(int id) { return t_records + record_offset(id); }
 
 // Fill-phase prefetch of the fast single-step launches (k_step): `stride` = the workgroups the device holds at once = the first
 // round of the launch, from the runtime's occupancy for the instantiation (asked once per thread, instantiation and device) and the
@@ -1807,7 +1823,7 @@ static int launch_step2(const atc_scenario* s, int B, int N, int T, int hold, co
     HIP_TRY(hipGetLastError());
     constexpr int form = LDSG ? ATC_LF_LDSG : LAT ? ATC_LF_LAT : FULL ? (ONE ? ATC_LF_FULL_ONE : ATC_LF_FULL_MULTI)
                          : ONE ? (ALLV ? ATC_LF_ALLV_ONE : ATC_LF_GEN_ONE) : (ALLV ? ATC_LF_ALLV_MULTI : ATC_LF_GEN_MULTI);
-    ++t_launches[__builtin_ctz(W) * ATC_LF_FORMS + form];
+    ++record(REC_STEP)[__builtin_ctz(W) * ATC_LF_FORMS + form];
     return ATC_OK;
 }
 template <int W>
@@ -1839,20 +1855,24 @@ static int launch_step(const atc_scenario* s, int B, int N, int T, int hold, con
 }
 
 // argument checks shared by every entry point that touches the env state
-// the batch shape alone (atc_plan_draw has no state to check): the range of B and N, then the 32-bit byte offsets of one launch
+// the batch shape alone (atc_plan_draw has no state to check): the range of B and N, then the 32-bit byte offsets of one launch over
+// B envs (atc_branch: the M*B envs it writes; atc_state_select: either batch), refused in the caller's words
 static int check_batch_range(int B, int N) {
     if (B < 1 || N < 1 || N > ATC_MAX_AIRCRAFT) return fail_arg("need B >= 1, 1 <= N <= 64");
     return ATC_OK;
 }
-static int check_batch_size(int B, int N) {
-    if ((unsigned long long)B * N * ATC_OBS_DIM * 4ull >= (1ull << 32) || (unsigned long long)B * 64ull >= (1ull << 32))
-        return fail_arg("B*N too large for one launch (B*N*40 bytes must stay below 4 GiB): split the batch");
+static int check_batch_size(unsigned long long B, int N,
+                            const char* refusal = "B*N too large for one launch (B*N*40 bytes must stay below 4 GiB): split the batch") {
+    if (B * N * ATC_OBS_DIM * 4ull >= (1ull << 32) || B * 64ull >= (1ull << 32)) return fail_arg(refusal);
     return ATC_OK;
+}
+static bool state_has_null(const atc_state_t* st) {
+    return !st->ac || !st->alt || !st->last_act || !st->env || !st->stats || !st->phi_wide;
 }
 static int check_env_args(const atc_scenario_t* s, int B, int N, const atc_state_t* st, const atc_params_t* p) {
     if (!s || !st || !p) return fail_arg("null pointer");
     if (const int rc = check_batch_range(B, N)) return rc;
-    if (!st->ac || !st->alt || !st->last_act || !st->env || !st->stats || !st->phi_wide) return fail_arg("atc_state_t has a null field");
+    if (state_has_null(st)) return fail_arg("atc_state_t has a null field");
     return check_batch_size(B, N);
 }
 
@@ -1900,9 +1920,6 @@ static int step_common(const atc_scenario_t* s, int B, int N, int T, int hold, c
 }
 
 // ---- frame skip (include/atc_step.h: atc_step_skip) ------------------------------------------------------------------------------
-// its own launch record (atc_skip_launch_counts): slot = log2(W); the step kernel's record and its slots stay as they are
-static thread_local uint64_t t_skip_launches[ATC_SKIP_LAUNCH_SLOTS] = {0};
-
 template <int W>
 static int launch_skip(const atc_scenario* s, int B, int N, int K, const atc_state_t* st, const float* actions, const atc_out_t* out,
                        uint8_t* n_steps, const atc_params_t* p, hipStream_t stream) {
@@ -1913,20 +1930,17 @@ static int launch_skip(const atc_scenario* s, int B, int N, int K, const atc_sta
     return with_flag(out->raw_obs || out->ac_reward || out->min_sep || out->term_obs, [&](auto full) {
         hipLaunchKernelGGL((k_skip<W, decltype(full)::value>), dim3(grid), dim3(kBlock), lds, stream, s->d_blob, s->off_grid, B, N, K, 0, *st, actions, *out, *p, q, n_steps);
         HIP_TRY(hipGetLastError());
-        ++t_skip_launches[__builtin_ctz(W)];
+        ++record(REC_SKIP)[__builtin_ctz(W)];
         return ATC_OK;
     });
 }
 
 // ---- traffic observation (include/atc_step.h: atc_observe_traffic) -------------------------------------------------------------
-// its own launch record (atc_traffic_launch_counts): slot = log2(W), the rules of the frame-skip record
-static thread_local uint64_t t_traffic_launches[ATC_TRAFFIC_LAUNCH_SLOTS] = {0};
-
 template <int W, int KT>
 static int launch_traffic2(int B, int N, const atc_state_t* st, float* traffic, const TrafficArgs& q, hipStream_t stream) {
     hipLaunchKernelGGL((k_traffic<W, KT>), dim3(step_grid(B, W)), dim3(kBlock), 0, stream, B, N, *st, traffic, q);
     HIP_TRY(hipGetLastError());
-    ++t_traffic_launches[__builtin_ctz(W)];
+    ++record(REC_TRAFFIC)[__builtin_ctz(W)];
     return ATC_OK;
 }
 // the compiled list lengths are 1, 2, 4, 8: a K in between runs the next one and stores its first K records
@@ -1938,9 +1952,7 @@ static int launch_traffic(int B, int N, const atc_state_t* st, float* traffic, c
     return launch_traffic2<W, 8>(B, N, st, traffic, q, stream);
 }
 
-// ---- what-if look-ahead (include/atc_step.h: atc_lookahead) ---------------------------------------------------------------------
-// its own launch record (atc_lookahead_launch_counts): slot = log2(W), the rules of the frame-skip record
-static thread_local uint64_t t_look_launches[ATC_LOOKAHEAD_LAUNCH_SLOTS] = {0};
+// ---- the candidate kernels (include/atc_step.h: atc_lookahead, atc_lookahead_plan, atc_lookahead_plan_sampled, atc_branch) ----------
 // candidates per workgroup (csrc/atc_lookahead.inc) asked for by atc_lookahead_set_mapping; 0: the library's choice
 static thread_local int t_look_cpg = 0;
 #define ATC_LOOKAHEAD_CPG_DEFAULT 1   // one workgroup per (tile, candidate): measured against the in-workgroup loop in DESIGN.md, section 3c
@@ -1959,147 +1971,140 @@ static int cand_grid(int B, int W, int M, CandGrid* g) {
     g->grid = (unsigned)grid;
     return ATC_OK;
 }
-// the kernels' atc_out_t from the six fields atc_lookahead_out_t and atc_plan_out_t name alike; true: one of the four optional outputs
-// is asked for (the fast form has them compiled out)
+// the kernels' atc_out_t from the six fields atc_lookahead_out_t and atc_plan_out_t name alike
 template <typename O>
-static bool cand_out(const O* o, atc_out_t* out) {
-    memset(out, 0, sizeof *out);
-    out->obs = o->obs; out->reward = o->reward; out->ac_reward = o->ac_reward; out->done = o->done; out->flags = o->flags; out->min_sep = o->min_sep;
+static atc_out_t cand_out(const O* o) {
+    atc_out_t out;
+    memset(&out, 0, sizeof out);
+    out.obs = o->obs; out.reward = o->reward; out.ac_reward = o->ac_reward; out.done = o->done; out.flags = o->flags; out.min_sep = o->min_sep;
+    return out;
+}
+// true: one of the four optional outputs is asked for (the look-ahead kernels' fast form has them compiled out)
+template <typename O>
+static bool cand_any(const O* o) {
     return o->flags || o->ac_reward || o->min_sep || o->obs;
 }
-// where a sampled call's candidates come from, in place of an action tensor (include/atc_step.h: atc_lookahead_plan_sampled)
-struct DrawSource {
-    const float* mean;
-    const float* std;
-    const atc_plan_draw_t* dr;
-};
-// the argument checks of atc_lookahead (H null), atc_lookahead_plan and atc_lookahead_plan_sampled (`drawn` given, `actions` unused):
-// K, then H, then M, before any pointer is looked at
+// The one launch of the candidate kernels (k_lookahead, k_plan, k_plan_sampled, k_branch): the grid, the kernels' atc_out_t, the derived
+// constants, then `launch(w, full, g, lds, out, q)` — the caller's generic lambda, which names the kernel instantiation
+// <decltype(w)::value, decltype(full)::value> and its argument list — and the count in record `rec`, slot log2(W).  `any` picks the
+// form with the optional outputs compiled in: cand_any(o), or atc_branch's own rule.
+template <typename O, typename L>
+static int launch_candidates(Record rec, const atc_scenario* s, int B, int N, int M, const O* o, bool any, const atc_params_t* p, L launch) {
+    return with_width(N, [&](auto w) {
+        constexpr int W = decltype(w)::value;
+        CandGrid g;
+        if (const int rc = cand_grid(B, W, M, &g)) return rc;
+        const atc_out_t out = cand_out(o);
+        const StepDerived& q = derive(*p, s, 0);
+        return with_flag(any, [&](auto full) {
+            launch(w, full, g, lds_bytes(s, W >= 32, true), out, q);
+            HIP_TRY(hipGetLastError());
+            ++record(rec)[__builtin_ctz(W)];
+            return ATC_OK;
+        });
+    });
+}
+
+// ---- argument checks of the candidate and drawn-plan calls ----------------------------------------------------------------------
+static int check_plan_h(int H) {
+    if (H < 1 || H > ATC_PLAN_MAX_H) return fail_arg("H (the number of segments of a plan) must be 1 .. 16");
+    return ATC_OK;
+}
+static int check_drawn_m(int M) {
+    if (M < 1 || M > ATC_SAMPLE_MAX_M) return fail_arg("M (the number of drawn candidates) must be 1 .. 1024");
+    return ATC_OK;
+}
+static int check_continuous(const atc_params_t* p) {
+    if (p->mode & ATC_M_DISCRETE) return fail_arg("ATC_M_DISCRETE: only the continuous action space is drawn");
+    return ATC_OK;
+}
+// a pointer a call requires and the words it is refused in when null; a list of them is looked at in its order
+struct Required { const void* ptr; const char* refusal; };
+static int check_required(std::initializer_list<Required> list) {
+    for (const Required& r : list)
+        if (!r.ptr) return fail_arg(r.refusal);
+    return ATC_OK;
+}
+// the pointers more than one drawn-plan call requires: the three sources of a drawn plan (include/atc_step.h:
+// atc_lookahead_plan_sampled) and the candidates' weights
+static Required need_mean(const float* mean) { return {mean, "null pointer: mean is required"}; }
+static Required need_std(const float* std) { return {std, "null pointer: std is required"}; }
+static Required need_dr(const atc_plan_draw_t* dr) { return {dr, "null pointer: dr (atc_plan_draw_t) is required"}; }
+static Required need_weight(const float* weight) { return {weight, "null pointer: weight is required"}; }
+// The checks of atc_plan_draw, atc_plan_refit and atc_plan_score up to the batch shape: H, then M, then the call's further count
+// (`count_refusal`: null, or what is wrong with E / R), all before any pointer is looked at; then the required pointers in the caller's
+// order; then, for a call that has parameters (`p`, itself among `required`; atc_plan_score has neither p nor N, and goes on with
+// checks of its own), the continuous action space and the batch shape.
+static int check_drawn_plan(int H, int M, const char* count_refusal, std::initializer_list<Required> required, const atc_params_t* p = nullptr,
+                            int B = 0, int N = 0) {
+    if (const int rc = check_plan_h(H)) return rc;
+    if (const int rc = check_drawn_m(M)) return rc;
+    if (count_refusal) return fail_arg(count_refusal);
+    if (const int rc = check_required(required)) return rc;
+    if (!p) return ATC_OK;
+    if (const int rc = check_continuous(p)) return rc;
+    if (const int rc = check_batch_range(B, N)) return rc;
+    return check_batch_size(B, N);
+}
+// the argument checks of atc_lookahead (H null), atc_lookahead_plan and atc_lookahead_plan_sampled (`drawn`: dr, mean, std in place of
+// `actions`): K, then H, then M, before any pointer is looked at
 template <typename O>
 static int check_candidates(const atc_scenario_t* s, int B, int N, int K, const int* H, int M, const atc_state_t* st, const float* actions,
                             const O* out, const atc_params_t* p, const char* k_is, const char* out_type, const char* fresh_per,
-                            const DrawSource* drawn = nullptr) {
+                            std::initializer_list<Required> drawn = {}) {
     char msg[160];
     auto fail = [&](const char* fmt, const char* word) { snprintf(msg, sizeof msg, fmt, word); return fail_arg(msg); };
+    const bool is_drawn = drawn.size() != 0;
     if (K < 1 || K > ATC_SKIP_MAX) return fail("K (the %s length) must be 1 .. 255", k_is);
-    if (H && (*H < 1 || *H > ATC_PLAN_MAX_H)) return fail_arg("H (the number of segments of a plan) must be 1 .. 16");
-    if (drawn) {
-        if (M < 1 || M > ATC_SAMPLE_MAX_M) return fail_arg("M (the number of drawn candidates) must be 1 .. 1024");
-        if (!drawn->dr) return fail_arg("null pointer: dr (atc_plan_draw_t) is required");
-        if (!drawn->mean) return fail_arg("null pointer: mean is required");
-        if (!drawn->std) return fail_arg("null pointer: std is required");
+    if (H) if (const int rc = check_plan_h(*H)) return rc;
+    if (is_drawn) {
+        if (const int rc = check_drawn_m(M)) return rc;
+        if (const int rc = check_required(drawn)) return rc;
     } else if (M < 1 || M > ATC_LOOKAHEAD_MAX_M) return fail_arg("M (the number of candidates) must be 1 .. 64");
     if (!out || !out->reward || !out->done) return fail("null pointer: %s.reward and .done are required", out_type);
-    if (!drawn && !actions) return fail_arg("null pointer");
+    if (!is_drawn && !actions) return fail_arg("null pointer");
     if (const int rc = check_env_args(s, B, N, st, p)) return rc;
     if (const int rc = check_dt(s, p)) return rc;
     if (p->mode & ATC_M_ACTIONS_HELD) return fail("ATC_M_ACTIONS_HELD is for atc_step only: every %s's first step carries a fresh decision", fresh_per);
-    if (drawn && (p->mode & ATC_M_DISCRETE)) return fail_arg("ATC_M_DISCRETE: only the continuous action space is drawn");
+    return is_drawn ? check_continuous(p) : ATC_OK;
+}
+
+// ---- byte ranges that must not share memory (atc_plan_refit, atc_plan_score, atc_branch, atc_state_select) ----------------------
+// Pointer VALUES only: nothing is dereferenced.  Ranges that only touch do not overlap.
+struct ByteRange { const void* ptr; uintptr_t bytes; const char* name; };
+static bool ranges_overlap(const ByteRange& a, const ByteRange& b) {
+    const uintptr_t alo = reinterpret_cast<uintptr_t>(a.ptr), blo = reinterpret_cast<uintptr_t>(b.ptr);
+    return alo < blo + b.bytes && blo < alo + a.bytes;
+}
+// every pair of r[0 .. n-1], null entries left out; a pair listed in `may_equal` (first < second) is let through as EQUAL pointers (an
+// in-place update).  Refused as "<name> overlaps <name> (<tail>)".
+static int check_disjoint(const ByteRange* r, int n, std::initializer_list<std::pair<int, int>> may_equal, const char* tail) {
+    for (int a = 0; a < n; ++a)
+        for (int b = a + 1; b < n; ++b) {
+            if (!r[a].ptr || !r[b].ptr || !ranges_overlap(r[a], r[b])) continue;
+            bool in_place = false;
+            for (const auto& pair : may_equal) in_place |= pair.first == a && pair.second == b && r[a].ptr == r[b].ptr;
+            if (in_place) continue;
+            char msg[160];
+            snprintf(msg, sizeof msg, "%s overlaps %s (%s)", r[a].name, r[b].name, tail);
+            return fail_arg(msg);
+        }
     return ATC_OK;
 }
-
-template <int W>
-static int launch_lookahead(const atc_scenario* s, int B, int N, int K, int M, const atc_state_t* st, const float* actions,
-                            const atc_lookahead_out_t* lo, const atc_params_t* p, hipStream_t stream) {
-    CandGrid g;
-    if (const int rc = cand_grid(B, W, M, &g)) return rc;
-    atc_out_t out;
-    const bool any = cand_out(lo, &out);
-    const StepDerived& q = derive(*p, s, 0);
-    return with_flag(any, [&](auto full) {
-        hipLaunchKernelGGL((k_lookahead<W, decltype(full)::value>), dim3(g.grid), dim3(kBlock), lds_bytes(s, W >= 32, true), stream, s->d_blob, s->off_grid, B, N, K, M, *st, actions, out, *p, q, lo->n_steps, g.cpg, g.groups, g.tiles);
-        HIP_TRY(hipGetLastError());
-        ++t_look_launches[__builtin_ctz(W)];
-        return ATC_OK;
-    });
-}
-
-// ---- plan look-ahead (include/atc_step.h: atc_lookahead_plan) -------------------------------------------------------------------
-// its own launch record (atc_plan_launch_counts): slot = log2(W), the rules of the frame-skip record
-static thread_local uint64_t t_plan_launches[ATC_PLAN_LAUNCH_SLOTS] = {0};
-
-template <int W>
-static int launch_plan(const atc_scenario* s, int B, int N, int K, int H, int M, const atc_state_t* st, const float* actions,
-                       const atc_plan_out_t* po, const atc_params_t* p, hipStream_t stream) {
-    CandGrid g;
-    if (const int rc = cand_grid(B, W, M, &g)) return rc;
-    atc_out_t out;
-    const bool any = cand_out(po, &out);
-    const StepDerived& q = derive(*p, s, 0);
-    return with_flag(any, [&](auto full) {
-        hipLaunchKernelGGL((k_plan<W, decltype(full)::value>), dim3(g.grid), dim3(kBlock), lds_bytes(s, W >= 32, true), stream, s->d_blob, s->off_grid, B, N, K, H, M, *st, actions, out, *p, q, po->n_steps, po->seg_reward, g.cpg, g.groups, g.tiles);
-        HIP_TRY(hipGetLastError());
-        ++t_plan_launches[__builtin_ctz(W)];
-        return ATC_OK;
-    });
-}
-
-// ---- drawn plans (include/atc_step.h: atc_lookahead_plan_sampled, atc_plan_draw) -----------------------------------------------
-// their own launch records (atc_plan_sampled_launch_counts: slot = log2(W), the rules of the frame-skip record; atc_plan_draw_launch_counts: one slot)
-static thread_local uint64_t t_plan_sampled_launches[ATC_PLAN_SAMPLED_LAUNCH_SLOTS] = {0};
-static thread_local uint64_t t_plan_draw_launches[ATC_PLAN_DRAW_LAUNCH_SLOTS] = {0};
-static thread_local uint64_t t_plan_refit_launches[ATC_PLAN_REFIT_LAUNCH_SLOTS] = {0};   // atc_plan_refit_launch_counts: one slot
-static thread_local uint64_t t_plan_score_launches[ATC_PLAN_SCORE_LAUNCH_SLOTS] = {0};   // atc_plan_score_launch_counts: one slot
-
-template <int W>
-static int launch_plan_sampled(const atc_scenario* s, int B, int N, int K, int H, int M, const atc_state_t* st, const DrawSource& src,
-                               const atc_plan_out_t* po, const atc_params_t* p, hipStream_t stream) {
-    CandGrid g;
-    if (const int rc = cand_grid(B, W, M, &g)) return rc;
-    atc_out_t out;
-    const bool any = cand_out(po, &out);
-    const StepDerived& q = derive(*p, s, 0);
-    return with_flag(any, [&](auto full) {
-        hipLaunchKernelGGL((k_plan_sampled<W, decltype(full)::value>), dim3(g.grid), dim3(kBlock), lds_bytes(s, W >= 32, true), stream, s->d_blob, s->off_grid, B, N, K, H, M, *st, src.mean, out, *p, q, po->n_steps, po->seg_reward, g.cpg, g.groups, g.tiles, src.std, *src.dr);
-        HIP_TRY(hipGetLastError());
-        ++t_plan_sampled_launches[__builtin_ctz(W)];
-        return ATC_OK;
-    });
-}
-
-// ---- branch and select (include/atc_step.h: atc_branch, atc_state_select) -------------------------------------------------------
-// their own launch records (atc_branch_launch_counts: slot = log2(W), the rules of the frame-skip record; atc_select_launch_counts: one slot)
-static thread_local uint64_t t_branch_launches[ATC_BRANCH_LAUNCH_SLOTS] = {0};
-static thread_local uint64_t t_select_launches[ATC_SELECT_LAUNCH_SLOTS] = {0};
-
-// the byte ranges of the six arrays of a batch of B envs x N aircraft; true if any array of `a` shares a byte with any array of `b`.
-// Pointer VALUES only: nothing is dereferenced.
-static void state_ranges(const atc_state_t* st, unsigned long long B, unsigned long long N, uintptr_t lo[6], uintptr_t hi[6]) {
-    const void* ptr[6] = {st->ac, st->alt, st->last_act, st->env, st->stats, st->phi_wide};
-    const unsigned long long bytes[6] = {B * N * 16ull, B * N * 8ull, B * N * 16ull, B * (ATC_ENV_WORDS * 4ull), B * (ATC_STAT_WORDS * 4ull), B * N * 32ull};
-    for (int i = 0; i < 6; ++i) {
-        lo[i] = reinterpret_cast<uintptr_t>(ptr[i]);
-        hi[i] = lo[i] + (uintptr_t)bytes[i];
-    }
-}
+// true if any of the six arrays of `a` (Ba envs x N aircraft) shares a byte with any array of `b` (Bb envs)
 static bool states_overlap(const atc_state_t* a, unsigned long long Ba, const atc_state_t* b, unsigned long long Bb, unsigned long long N) {
-    uintptr_t alo[6], ahi[6], blo[6], bhi[6];
-    state_ranges(a, Ba, N, alo, ahi);
-    state_ranges(b, Bb, N, blo, bhi);
+    auto ranges = [N](const atc_state_t* st, unsigned long long B, ByteRange r[6]) {
+        const void* ptr[6] = {st->ac, st->alt, st->last_act, st->env, st->stats, st->phi_wide};
+        const unsigned long long bytes[6] = {B * N * 16ull, B * N * 8ull, B * N * 16ull, B * (ATC_ENV_WORDS * 4ull), B * (ATC_STAT_WORDS * 4ull), B * N * 32ull};
+        for (int i = 0; i < 6; ++i) r[i] = ByteRange{ptr[i], (uintptr_t)bytes[i], nullptr};
+    };
+    ByteRange ra[6], rb[6];
+    ranges(a, Ba, ra);
+    ranges(b, Bb, rb);
     for (int i = 0; i < 6; ++i)
         for (int j = 0; j < 6; ++j)
-            if (alo[i] < bhi[j] && blo[j] < ahi[i]) return true;
+            if (ranges_overlap(ra[i], rb[j])) return true;
     return false;
-}
-static bool state_has_null(const atc_state_t* st) {
-    return !st->ac || !st->alt || !st->last_act || !st->env || !st->stats || !st->phi_wide;
-}
-
-template <int W>
-static int launch_branch(const atc_scenario* s, int B, int N, int K, int M, const atc_state_t* src, const float* actions, const atc_state_t* dst,
-                         const atc_lookahead_out_t* lo, const atc_params_t* p, hipStream_t stream) {
-    CandGrid g;
-    if (const int rc = cand_grid(B, W, M, &g)) return rc;
-    atc_out_t out;
-    cand_out(lo, &out);
-    const bool any = lo->ac_reward || lo->min_sep;   // k_skip's rule: obs and flags are stored by both forms (csrc/atc_branch.inc)
-    const StepDerived& q = derive(*p, s, 0);
-    return with_flag(any, [&](auto full) {
-        hipLaunchKernelGGL((k_branch<W, decltype(full)::value>), dim3(g.grid), dim3(kBlock), lds_bytes(s, W >= 32, true), stream, s->d_blob, s->off_grid, B, N, K, M, *src, actions, out, *p, q, lo->n_steps, g.cpg, g.groups, g.tiles, *dst);
-        HIP_TRY(hipGetLastError());
-        ++t_branch_launches[__builtin_ctz(W)];
-        return ATC_OK;
-    });
 }
 
 #include "atc_abi.inc"   // the extern "C" entry points (host side)

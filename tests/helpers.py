@@ -25,6 +25,15 @@ def launches():
             gained[name] = n - before.get(name, 0)
 
 
+def launch_records(*first):
+    """Every launch record of the calling thread (atc_hip.lib.launch_records) as a tuple to compare or index: the records named in
+    `first` ("plan_score" for atc_plan_score_launch_counts, "" for atc_launch_counts) in that order, then all the others."""
+    from atc_hip import lib
+    recs = lib.launch_records()
+    named = ["atc_%s_launch_counts" % n if n else "atc_launch_counts" for n in first]
+    return tuple(recs[n] for n in named) + tuple(r for n, r in recs.items() if n not in named)
+
+
 def lane_width(N):
     """W of k_step<W, ...>: the aircraft count rounded up to a power of two."""
     return 1 << max(0, (int(N) - 1).bit_length())

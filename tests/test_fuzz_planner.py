@@ -238,11 +238,8 @@ def test_check_refit_holds_subnormal_softmax_weights():
 _device = {}      # seed -> (the case's reference with the device's own segment words, what check_iteration measured)
 
 
-def _records():
-    from atc_hip import lib
-    return (lib.plan_score_launch_counts(), lib.plan_refit_launch_counts(), lib.plan_sampled_launch_counts(), lib.plan_draw_launch_counts(),
-            lib.plan_launch_counts(), lib.lookahead_launch_counts(), lib.skip_launch_counts(), lib.launch_counts(), lib.traffic_launch_counts(),
-            lib.branch_launch_counts(), lib.select_launch_counts())
+# every launch record of the library (helpers.launch_records), the ones this module indexes first
+_records = functools.partial(H.launch_records, "plan_score", "plan_refit", "plan_sampled", "plan_draw")
 
 
 def _same_words(got, want, what, tag):

@@ -11,6 +11,7 @@ the launch records; M = 1024; cem_plan_launch and mppi_plan against the same loo
 
 The grid's inputs are valid only if the REFERENCE shows a component whose new_std == 0 and one whose mean moved away from ctr."""
 import ctypes as C
+import functools
 import inspect
 import re
 import shutil
@@ -64,11 +65,8 @@ def test_header_constant_and_argtypes():
     assert callable(lib.plan_refit_launch_counts)
 
 
-def _records():
-    from atc_hip import lib
-    return (lib.plan_refit_launch_counts(), lib.plan_sampled_launch_counts(), lib.plan_draw_launch_counts(), lib.plan_launch_counts(),
-            lib.lookahead_launch_counts(), lib.skip_launch_counts(), lib.launch_counts(), lib.traffic_launch_counts(), lib.branch_launch_counts(),
-            lib.select_launch_counts())
+# every launch record of the library (helpers.launch_records), the ones this module indexes first
+_records = functools.partial(H.launch_records, "plan_refit")
 
 
 ARGS = ("s", "mean", "std", "d", "weight", "new_mean", "new_std", "p")

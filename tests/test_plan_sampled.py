@@ -11,6 +11,7 @@ mapping; the prefix property, independence of M, iteration, mean_first; M = 1024
 
 Inputs are valid only if the REFERENCE shows the events of _check_events; the test fails otherwise."""
 import ctypes as C
+import functools
 import inspect
 import re
 import shutil
@@ -96,10 +97,8 @@ def test_header_constants_match_layout():
     assert np.float32(1.0 / np.sqrt((65536.0 ** 2 - 1.0) / 3.0)).view(np.uint32) == 0x37DDB3D7      # the fp32 nearest to 1 / sigma
 
 
-def _records():
-    from atc_hip import lib
-    return (lib.plan_sampled_launch_counts(), lib.plan_draw_launch_counts(), lib.plan_launch_counts(), lib.lookahead_launch_counts(),
-            lib.skip_launch_counts(), lib.launch_counts(), lib.traffic_launch_counts(), lib.branch_launch_counts(), lib.select_launch_counts())
+# every launch record of the library (helpers.launch_records), the ones this module indexes first
+_records = functools.partial(H.launch_records, "plan_sampled", "plan_draw")
 
 
 FAKE = C.c_void_p(0x1000)     # a made-up pointer: a call that is refused never follows it

@@ -16,6 +16,7 @@ softmax inputs in one device run — printed by test_softmax_weight_within_the_b
 is twice that.  Weights whose reference is below FLT_MIN are compared by absolute difference <= FLT_MIN; the best candidate's weight
 must be exactly 1."""
 import ctypes as C
+import functools
 import inspect
 import re
 import shutil
@@ -79,11 +80,8 @@ def test_header_constants_struct_and_argtypes():
     assert callable(lib.plan_score_launch_counts)
 
 
-def _records():
-    from atc_hip import lib
-    return (lib.plan_score_launch_counts(), lib.plan_refit_launch_counts(), lib.plan_sampled_launch_counts(), lib.plan_draw_launch_counts(),
-            lib.plan_launch_counts(), lib.lookahead_launch_counts(), lib.skip_launch_counts(), lib.launch_counts(), lib.traffic_launch_counts(),
-            lib.branch_launch_counts(), lib.select_launch_counts())
+# every launch record of the library (helpers.launch_records), the ones this module indexes first
+_records = functools.partial(H.launch_records, "plan_score", "plan_refit", "plan_sampled", "plan_draw")
 
 
 ARGS = ("s", "seg_reward", "sc", "score", "weight")      # the pointers that may not be NULL, in the order they are looked at
