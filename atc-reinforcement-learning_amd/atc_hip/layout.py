@@ -101,3 +101,9 @@ PLAN_SCORE_LAUNCH_SLOTS = 1
 # log2(W); atc_select_launch_counts: one slot)
 BRANCH_LAUNCH_SLOTS = 7
 SELECT_LAUNCH_SLOTS = 1
+# policy rollout (include/atc_step.h: atc_rollout_policy): the MLP is POLICY_IN -> POLICY_HIDDEN -> POLICY_HIDDEN -> ACT_DIM, POLICY_WORDS
+# floats in one array (W1, b1, W2, b2, W3, b3, log_std; weights row-major [out][in]); POLICY_DETERMINISTIC: the flag of atc_policy_t that
+# flies the mean; its own launch record (slot = log2(W))
+POLICY_IN, POLICY_HIDDEN, POLICY_WORDS = 10, 64, 5062
+POLICY_DETERMINISTIC = 1
+ROLLOUT_POLICY_LAUNCH_SLOTS = 7

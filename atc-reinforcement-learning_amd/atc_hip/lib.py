@@ -74,6 +74,23 @@ class AtcPlanScore(C.Structure):
     _fields_ = [("mode", C.c_uint32), ("elites", C.c_int32), ("gamma", C.c_float), ("temperature", C.c_float)]
 
 
+POLICY_FIELDS = ("w", "n_hidden", "flags", "seed", "decision0", "reserved")
+
+
+class AtcPolicy(C.Structure):
+    """atc_policy_t"""
+    _fields_ = [("w", C.c_void_p), ("n_hidden", C.c_int32), ("flags", C.c_uint32), ("seed", C.c_uint64), ("decision0", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+POLICY_OUT_FIELDS = ("obs", "reward", "done", "flags", "action", "logp")
+
+
+class AtcPolicyOut(C.Structure):
+    """atc_policy_out_t"""
+    _fields_ = [(n, C.c_void_p) for n in POLICY_OUT_FIELDS]
+
+
 class AtcStepCall(C.Structure):
     """atc_step_call_t"""
     _fields_ = [("s", C.c_void_p), ("B", C.c_int32), ("N", C.c_int32), ("st", C.POINTER(AtcState)), ("actions", C.c_void_p),
@@ -88,7 +105,8 @@ EXPORTS = ("atc_abi_version", "atc_last_error", "atc_launch_counts", "atc_host_m
            "atc_lookahead", "atc_lookahead_launch_counts", "atc_lookahead_set_mapping", "atc_lookahead_plan", "atc_plan_launch_counts",
            "atc_branch", "atc_branch_launch_counts", "atc_state_select", "atc_select_launch_counts",
            "atc_plan_draw", "atc_lookahead_plan_sampled", "atc_plan_sampled_launch_counts", "atc_plan_draw_launch_counts",
-           "atc_plan_refit", "atc_plan_refit_launch_counts", "atc_plan_score", "atc_plan_score_launch_counts")
+           "atc_plan_refit", "atc_plan_refit_launch_counts", "atc_plan_score", "atc_plan_score_launch_counts",
+           "atc_rollout_policy", "atc_rollout_policy_launch_counts")
 
 def load():
     """Loads libatcstep.so; raises (never falls back) when it has not been built."""
@@ -139,6 +157,7 @@ def load():
     lib.atc_plan_score.argtypes = [vp, ci, ci, ci, vp, vp, C.POINTER(AtcPlanScore), vp, vp, vp, ci, vp]
     lib.atc_branch.argtypes = [vp, ci, ci, ci, ci, C.POINTER(AtcState), vp, C.POINTER(AtcState), C.POINTER(AtcLookaheadOut), C.POINTER(AtcParams), vp]
     lib.atc_state_select.argtypes = [vp, ci, ci, C.POINTER(AtcState), ci, C.POINTER(AtcState), vp, vp, vp]
+    lib.atc_rollout_policy.argtypes = [vp, ci, ci, ci, ci, C.POINTER(AtcState), vp, C.POINTER(AtcPolicy), C.POINTER(AtcPolicyOut), C.POINTER(AtcParams), vp]
     for getter in LAUNCH_RECORDS:
         getattr(lib, getter).argtypes = [C.POINTER(C.c_uint64), ci]
     for name in EXPORTS:
@@ -180,6 +199,7 @@ LAUNCH_RECORDS = {
     "atc_plan_score_launch_counts": (L.PLAN_SCORE_LAUNCH_SLOTS, "score"),
     "atc_branch_launch_counts": (L.BRANCH_LAUNCH_SLOTS, _width),
     "atc_select_launch_counts": (L.SELECT_LAUNCH_SLOTS, "select"),
+    "atc_rollout_policy_launch_counts": (L.ROLLOUT_POLICY_LAUNCH_SLOTS, _width),
 }
 
 
@@ -257,6 +277,12 @@ def branch_launch_counts():
 def select_launch_counts():
     """Launches of the state gather (atc_state_select) made by the calling thread so far: {"select": n}, or {} before the first."""
     return _counts("atc_select_launch_counts")
+
+
+def rollout_policy_launch_counts():
+    """Launches of the policy rollout (atc_rollout_policy) made by the calling thread so far, by lane-group width: {16: n, ...}, widths
+    with a count of zero left out.  Separate from the other launch records, which a policy rollout leaves as they are."""
+    return _counts("atc_rollout_policy_launch_counts")
 
 
 def lookahead_set_mapping(candidates_per_workgroup=0):

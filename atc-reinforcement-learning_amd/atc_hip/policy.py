@@ -1,0 +1,52 @@
+"""The policy of AtcVecEnv.rollout_policy (include/atc_step.h: atc_rollout_policy) as the library reads it: one float32 array of
+POLICY_WORDS words — W1[64][10], b1[64], W2[64][64], b2[64], W3[3][64], b3[3], log_std[3], every weight matrix row-major [out][in],
+i.e. torch.nn.Linear.weight as it lies in memory.  No value head: values come from one batched forward over the stored observations."""
+from . import layout as L
+
+SHAPES = (("W1", (L.POLICY_HIDDEN, L.POLICY_IN)), ("b1", (L.POLICY_HIDDEN,)), ("W2", (L.POLICY_HIDDEN, L.POLICY_HIDDEN)), ("b2", (L.POLICY_HIDDEN,)),
+          ("W3", (L.ACT_DIM, L.POLICY_HIDDEN)), ("b3", (L.ACT_DIM,)), ("log_std", (L.ACT_DIM,)))
+
+
+def offsets():
+    """{name: (first word, shape)} of the seven parts of the packed array"""
+    out, at = {}, 0
+    for name, shape in SHAPES:
+        n = 1
+        for s in shape:
+            n *= s
+        out[name] = (at, shape)
+        at += n
+    assert at == L.POLICY_WORDS
+    return out
+
+
+def pack_mlp(W1, b1, W2, b2, W3, b3, log_std, device=None):
+    """The POLICY_WORDS-word float32 tensor of a 10 -> 64 -> 64 -> 3 MLP with weights [out, in] (tensors or arrays; shapes are
+    checked, nothing is transposed or broadcast).  On `device` (default: the first part's device if it is a tensor, else the CPU):
+    rollout_policy needs it on the env's device."""
+    import torch
+    parts = []
+    for (name, shape), v in zip(SHAPES, (W1, b1, W2, b2, W3, b3, log_std)):
+        t = torch.as_tensor(v).detach()
+        if tuple(t.shape) != shape:
+            raise ValueError("%s must have shape %s (weights are [out, in]), got %s" % (name, shape, tuple(t.shape)))
+        if device is None and t.is_cuda:
+            device = t.device
+        parts.append(t)
+    flat = torch.cat([t.to(device=device or "cpu", dtype=torch.float32).reshape(-1) for t in parts]).contiguous()
+    assert flat.numel() == L.POLICY_WORDS
+    return flat
+
+
+def from_torch(module, log_std, device=None):
+    """pack_mlp of an nn.Sequential(Linear(10, 64), Tanh(), Linear(64, 64), Tanh(), Linear(64, 3)) — biases required — and a
+    log_std of 3 values (a parameter of the trainer's, not of the module)."""
+    from torch import nn
+    layers = list(module)
+    kinds = (nn.Linear, nn.Tanh, nn.Linear, nn.Tanh, nn.Linear)
+    if len(layers) != len(kinds) or not all(isinstance(m, k) for m, k in zip(layers, kinds)):
+        raise ValueError("need nn.Sequential(Linear, Tanh, Linear, Tanh, Linear)")
+    lin = layers[0::2]
+    if any(m.bias is None for m in lin):
+        raise ValueError("every Linear layer needs a bias")
+    return pack_mlp(lin[0].weight, lin[0].bias, lin[1].weight, lin[1].bias, lin[2].weight, lin[2].bias, log_std, device=device)

@@ -830,6 +830,45 @@ class AtcVecEnv:
         self._finish()
         return out
 
+    def rollout_policy(self, weights, T, hold=1, seed=0, decision0=0, deterministic=False, obs0=None, out=None):
+        """T consecutive steps in one launch with the decisions of a 10 -> 64 -> 64 -> 3 tanh MLP and a diagonal Gaussian taken inside
+        it (include/atc_step.h: atc_rollout_policy) — the on-policy collection loop: observation -> policy -> sample -> clamp -> step.
+        weights: the POLICY_WORDS-word float32 tensor of atc_hip.policy.pack_mlp / from_torch, on this env's device.  One decision per
+        `hold` steps, each from the observation the step before it stored; decision 0 from `obs0` (default: the env's bound
+        observation tensor, what the last reset / step left).  Successive calls pass decision0 += T // hold for fresh noise and the last
+        row of the previous call's obs as obs0; deterministic=True flies the mean (logp = 0).
+        Returns a dict of device tensors: obs / reward / done / flags [T, ...] as rollout() returns them, action [T // hold, B, N, 3] —
+        the UNCLAMPED sample, what logp is about; its clamp to [-1, 1] is what was flown — and logp [T // hold, B, N].  Values are not
+        computed: run the value network once over the stored obs.  Like rollout(), it produces no traffic observation."""
+        torch = self.torch
+        T, hold = int(T), int(hold)
+        B, N, dev = self.B, self.N, self.device
+        w = weights
+        if not (torch.is_tensor(w) and w.dtype == torch.float32 and w.device == dev and w.is_contiguous() and w.numel() == L.POLICY_WORDS):
+            raise ValueError("weights must be the contiguous float32 tensor of %d words (atc_hip.policy.pack_mlp) on %s" % (L.POLICY_WORDS, dev))
+        x0 = self.obs if obs0 is None else obs0
+        if not (torch.is_tensor(x0) and x0.dtype == torch.float32 and x0.is_contiguous() and x0.numel() == B * N * L.OBS_DIM):
+            raise ValueError("obs0 must be a contiguous float32 tensor of B*N*%d words" % L.OBS_DIM)
+        n_dec = T // hold if hold >= 1 else 0     # (a T or hold the library refuses is refused by it, below)
+        if out is None:
+            out = {
+                "obs": torch.empty((T, B, N * L.OBS_DIM), dtype=torch.float32, device=dev),
+                "reward": torch.empty((T, B), dtype=torch.float32, device=dev),
+                "done": torch.empty((T, B), dtype=torch.uint8, device=dev),
+                "flags": torch.empty((T, B, N), dtype=torch.int16, device=dev),
+                "action": torch.empty((n_dec, B, N, L.ACT_DIM), dtype=torch.float32, device=dev),
+                "logp": torch.empty((n_dec, B, N), dtype=torch.float32, device=dev),
+            }
+        o = _lib.AtcPolicyOut(*[self._ptr(out.get(k)) for k in _lib.POLICY_OUT_FIELDS])
+        pol = _lib.AtcPolicy(self._ptr(w), L.POLICY_HIDDEN, L.POLICY_DETERMINISTIC if deterministic else 0, int(seed) & (2 ** 64 - 1),
+                             int(decision0) & 0xffffffff, 0)
+        with torch.cuda.device(dev):
+            _lib.check(self._lib.atc_rollout_policy(self.sector.handle, B, N, T, hold, C.byref(self._state), self._ptr(x0), C.byref(pol),
+                                                    C.byref(o), C.byref(self.params), self._stream()))
+        self._keep = (w, x0)
+        self._finish()
+        return out
+
     def get_attr(self, name, indices=None):
         """VecEnv.get_attr for the attributes the reference's trainer reads (learning/atc-gym-stable-baselines.py:34,36)
         and the episode counters."""

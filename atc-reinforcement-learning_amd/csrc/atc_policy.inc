@@ -1,0 +1,237 @@
+// atc_policy.inc — atc_rollout_policy (include/atc_step.h): T steps with the decisions of a 10 -> 64 -> 64 -> 3 tanh MLP and a diagonal
+// Gaussian taken INSIDE the launch.  Included by atc_step.hip behind atc_branch.inc.
+//   k_rollout_policy is the multi-step k_step's loop — state loaded once, step_part_a / step_part_b per step, state written once — as
+//   a copy of the text, not a flag on k_step (the precedent of k_plan_sampled: k_step's instances keep their machine code).  The step
+//   runs in its SKIP form, which hands the step's values back in registers (StepVals), and this kernel stores them per step the way
+//   the tail of step_part_b does: observation rows through store_obs_rows, then the flag word, reward and done.  The observation
+//   registers of a step are carried over the loop's back edge (nothing else of the step is live there) and the first step of the
+//   next block evaluates the policy on them; decision 0 reads obs0.  One evaluation site, so one copy of the MLP's code.
+//   THE MLP.  One lane per aircraft slot evaluates its own row: layer 1 unrolled (640 fmaf — in float64 where a wavefront holds an input
+//   above 4 in magnitude, see there —, 64 activations kept in vector registers),
+//   layer 2 as a loop over the 64 output neurons with the 64 inputs unrolled — four partial sums, so that no fmaf waits for the one
+//   before it — and layer 3 folded into that loop (each tanh(h2_j) goes straight into the three output sums; h2 is never stored).
+//   WEIGHTS are read through the constant address space at wave-uniform indices: scalar loads (s_load_dwordx8 / x16 into scalar
+//   registers, which the fmaf takes as an operand), 20 KB per decision and wavefront out of the scalar cache / L2.  Why not LDS
+//   broadcasts: a wave-uniform ds_read_b128 costs 4 LDS cycles for 4 weights = 16 VALU cycles of fmaf per SIMD, and the four SIMDs of a
+//   CU share one LDS — the pipe would be exactly saturated before the step's own LDS stages (pair scan, observation transpose) ask
+//   for anything; the scalar path leaves LDS and the vector registers alone.  Why not v_mfma_f32_32x32x2f32: its rate is the packed
+//   fp32 VALU's (twice the plain fmaf's), but its A / B operands want activation k of aircraft l in lane l + 32 (k & 1): the
+//   activations of a lane-per-aircraft layout would have to cross lane halves before and after each layer (DESIGN.md section 3k).
+//   The base pointer goes through the block's opaque zero, or the (invariant) weight loads are hoisted out of the step loop and the
+//   scalar registers holding them spilled to vector-register lanes.
+//   THE DRAW: integers, key, u1, u2 exact; logf / cosf / sqrtf / expf / tanhf are the device library's (the file is built without
+//   fast-math and with -ffp-contract=off).  tests/policy_ref.py restates everything in numpy.
+enum { ATC_POL_W1 = 0, ATC_POL_B1 = 640, ATC_POL_W2 = 704, ATC_POL_B2 = 4800, ATC_POL_W3 = 4864, ATC_POL_B3 = 5056, ATC_POL_LOGSTD = 5059 };
+static_assert(ATC_POL_LOGSTD + 3 == ATC_POLICY_WORDS && ATC_POLICY_IN == ATC_OBS_DIM && ATC_POLICY_HIDDEN == 64, "atc_policy_t.w layout");
+#define ATC_POL_TWO_PI 6.2831853071795864769f
+#define ATC_POL_LOGP_C 2.7568155996140185f   // 1.5 log(2 pi)
+
+typedef __attribute__((address_space(4))) const float* pol_wptr;   // constant address space: uniform indices become scalar loads
+
+struct PolicyDecision {
+    Float3 u;      // the unclamped sample (atc_policy_out_t.action)
+    Float3 a;      // what is flown: plan_draw_clamp(u)
+    float logp;
+};
+
+// one standard normal by Box-Muller from 64 mixed bits: u1 in (0, 1] from the top 24 bits, u2 in [0, 1) from bits 16..39
+__device__ __forceinline__ float policy_z(uint64_t key, uint32_t c) {
+    const uint64_t w = mix64(key ^ (uint64_t)(c + 1u));
+    const float u1 = (float)((uint32_t)(w >> 40) + 1u) * 0x1p-24f;
+    const float u2 = (float)((uint32_t)(w >> 16) & 0xffffffu) * 0x1p-24f;
+    return sqrtf(-2.0f * logf(u1)) * cosf(ATC_POL_TWO_PI * u2);
+}
+
+__device__ __forceinline__ PolicyDecision policy_decide(const float* w_arg, int zk, const float* x, uint64_t seed, uint32_t decision, uint32_t i,
+                                                        bool deterministic) {
+    pol_wptr w = (pol_wptr)(uintptr_t)w_arg;
+    asm volatile("" : "+s"(w) : "s"(zk));
+    // Layer 1.  Normalised observations lie in [-1, 1] and the fp32 sum is good to 1e-7.  Unnormalised ones reach 1.5e4 (the altitude
+    // words, and the raw reset observation behind an auto-reset): the fp32 partial sums then round by up to 1e-3, and a neuron whose
+    // sum happens to land near 0 — one in 10^4 — hands an error of that size through tanh's slope to the outputs.  A wavefront that
+    // holds such an input sums this layer in float64 (the products are exact there); the choice is wave-uniform.
+    float h1[ATC_POLICY_HIDDEN];
+    float xmax = 0.0f;
+#pragma unroll
+    for (int c = 0; c < ATC_POLICY_IN; ++c) xmax = fmaxf(xmax, fabsf(x[c]));
+    if (ATC_RARE(__builtin_amdgcn_ballot_w64(!(xmax <= 4.0f)) != 0ull)) {
+        double xd[ATC_POLICY_IN];
+#pragma unroll
+        for (int c = 0; c < ATC_POLICY_IN; ++c) xd[c] = (double)x[c];
+#pragma unroll
+        for (int j = 0; j < ATC_POLICY_HIDDEN; ++j) {
+            double s = (double)w[ATC_POL_B1 + j];
+#pragma unroll
+            for (int c = 0; c < ATC_POLICY_IN; ++c) s = __builtin_fma((double)w[ATC_POL_W1 + j * ATC_POLICY_IN + c], xd[c], s);
+            h1[j] = (float)s;
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < ATC_POLICY_HIDDEN; ++j) {
+            float s = w[ATC_POL_B1 + j];
+#pragma unroll
+            for (int c = 0; c < ATC_POLICY_IN; ++c) s = fmaf(w[ATC_POL_W1 + j * ATC_POLICY_IN + c], x[c], s);
+            h1[j] = s;
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < ATC_POLICY_HIDDEN; ++j) h1[j] = tanhf(h1[j]);
+    float mu[3] = {w[ATC_POL_B3 + 0], w[ATC_POL_B3 + 1], w[ATC_POL_B3 + 2]};
+#pragma unroll 1
+    for (int j = 0; j < ATC_POLICY_HIDDEN; ++j) {
+        pol_wptr row = w + ATC_POL_W2 + j * ATC_POLICY_HIDDEN;
+        float s0 = w[ATC_POL_B2 + j], s1 = 0.0f, s2 = 0.0f, s3 = 0.0f;
+#pragma unroll
+        for (int c = 0; c < ATC_POLICY_HIDDEN; c += 4) {
+            s0 = fmaf(row[c + 0], h1[c + 0], s0);
+            s1 = fmaf(row[c + 1], h1[c + 1], s1);
+            s2 = fmaf(row[c + 2], h1[c + 2], s2);
+            s3 = fmaf(row[c + 3], h1[c + 3], s3);
+        }
+        const float h2 = tanhf((s0 + s1) + (s2 + s3));
+#pragma unroll
+        for (int c = 0; c < 3; ++c) mu[c] = fmaf(w[ATC_POL_W3 + c * ATC_POLICY_HIDDEN + j], h2, mu[c]);
+    }
+    PolicyDecision dec;
+    dec.logp = 0.0f;
+    if (deterministic) {
+        dec.u = Float3{mu[0], mu[1], mu[2]};
+    } else {
+        const uint64_t key = mix64(mix64(seed ^ (uint64_t)decision) ^ (uint64_t)i);
+        float u[3], lp = 0.0f;
+#pragma unroll
+        for (uint32_t c = 0; c < 3u; ++c) {
+            const float ls = w[ATC_POL_LOGSTD + c];
+            const float z = policy_z(key, c);
+            u[c] = mu[c] + expf(ls) * z;
+            lp += -0.5f * (z * z) - ls;
+        }
+        dec.u = Float3{u[0], u[1], u[2]};
+        dec.logp = lp - ATC_POL_LOGP_C;
+    }
+    dec.a = Float3{plan_draw_clamp(dec.u.a), plan_draw_clamp(dec.u.b), plan_draw_clamp(dec.u.c)};   // (a NaN gives -1)
+    return dec;
+}
+
+struct PolicyArgs {
+    const float* blob;
+    int off_grid, B, N, T, hold;
+    atc_state_t st;
+    const float* obs0;
+    atc_out_t out;      // obs, reward, done, flags of atc_policy_out_t; the other fields null
+    atc_params_t p;
+    StepDerived q;
+    const float* w;
+    uint64_t seed;
+    uint32_t decision0, pflags;
+    float* action;
+    float* logp;
+};
+static_assert(offsetof(PolicyArgs, hold) == offsetof(StepArgs, hold) && offsetof(PolicyArgs, st) == offsetof(StepArgs, st) &&
+              offsetof(PolicyArgs, out) == offsetof(StepArgs, out) && offsetof(PolicyArgs, q) == offsetof(StepArgs, q),
+              "k_rollout_policy's kernel arguments must lie where k_step's do: the step re-reads them by StepArgs offsets");
+
+// wavefronts per SIMD k_rollout_policy is register-budgeted for (<= 168 VGPRs): the 64 hidden activations are live next to what the
+// step carries across its loop, which the step's own 5 - 6 do not hold.  -DATC_POLICY_WAVES=n: A/B builds.
+#ifndef ATC_POLICY_WAVES
+#define ATC_POLICY_WAVES 3
+#endif
+template <int W>
+__global__ void __launch_bounds__(kBlock, ATC_POLICY_WAVES)
+k_rollout_policy(const float* __restrict__ blob, int off_grid, int B, int N, int T, int hold, atc_state_t st, const float* __restrict__ obs0,
+                 atc_out_t out, atc_params_t p, StepDerived q, const float* __restrict__ pw, uint64_t seed, uint32_t decision0, uint32_t pflags,
+                 float* __restrict__ action, float* __restrict__ logp) {
+    constexpr bool ONE = false, LAT = false, FULL = false;   // (QGET: the multi-step form — kernarg re-reads inside the step)
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    float4* pos = reinterpret_cast<float4*>(smem);                    // [2 kBlock] pair-scan staging (W >= 32)
+    float* obs_stage = smem + (W >= 32 ? 2 * kBlock * 4 : 0);  // [4 waves][64 x 10] obs transpose
+    const float* __restrict__ K = blob;
+    const float* __restrict__ grid = off_grid ? blob + off_grid : nullptr;
+    const uint32_t BN = (uint32_t)B * (uint32_t)N;
+    const LaneIds d = make_ids<W, false>(blockIdx.x * kBlock, B, N);
+
+    const int4 e0 = *at<int4>(st.env, (uint32_t)d.e * (ATC_ENV_WORDS * 4u));
+    const uint32_t hi0 = (W == 64) ? *at<uint32_t>(st.stats, (uint32_t)d.e * (ATC_STAT_WORDS * 4u) + ATC_STAT_MASK_HI * 4u) : 0u;
+    EnvState es = {e0.x, e0.y, __int_as_float(e0.z), (uint64_t)(uint32_t)e0.w | ((uint64_t)hi0 << 32)};
+    const int4 ps = *at<int4>(st.ac, d.i * 16u);
+    const double h0 = *at<double>(st.alt, d.i * 8u);
+    const int4 la0 = *at<int4>(st.last_act, d.i * 16u);
+    LaneState ls = {{ps.x, ps.y, h0, ps.z, (uint32_t)ps.w}, (uint32_t)la0.x, __hiloint2double(la0.w, la0.z), la0.y, false};
+    // what decision 0 sees: the lane's row of obs0 (an idle lane reads the last aircraft's row: in bounds, its decision is never stored)
+    float x[ATC_OBS_DIM];
+    {
+        const float2* r0 = at<float2>(obs0, times40(d.i));
+#pragma unroll
+        for (int c = 0; c < ATC_OBS_DIM / 2; ++c) {
+            const float2 v = r0[c];
+            x[2 * c] = v.x;
+            x[2 * c + 1] = v.y;
+        }
+    }
+
+    Float3 act = {0.0f, 0.0f, 0.0f};   // the clamped action of the current block
+    Targets tg = {0u, 0.0f, 0};
+    uint64_t refused_blk = 0ull;
+    bool refused_known = false;
+    bool all_active = false, mask_dirty = true;
+    int left = 0;                 // steps the current block is still flown for
+    uint32_t blk = 0u;            // the number of the coming decision
+    QRates qr_next = kernarg_reread<QRates>(offsetof(StepArgs, q) + offsetof(StepDerived, r), opaque_zero());
+    settle_state(ls, es);
+#pragma unroll
+    for (int c = 0; c < ATC_OBS_DIM; ++c) asm volatile("" : "+v"(x[c]));   // (waited for here, like the state: see settle_state)
+    for (int step = 0; step < T; ++step) {
+        const size_t sBN = (size_t)step * BN, sB = (size_t)step * (uint32_t)B;
+        LaneIds dl = d;
+        atc_params_t pl = p;
+        const int zk = opaque_zero();   // this step's opaque zero (see k_step)
+        pl.mode += (uint32_t)zk;
+        const StepOut so = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // (the step stores nothing itself)
+        const QRates qr = qr_next;
+        const QScan qs = QGET(s);
+        const bool first = left == 0;   // this step opens a block: a fresh decision, from the observation the step before it stored
+        if (ATC_RARE(first)) {
+            left = kernarg_reread<int>(offsetof(StepArgs, hold), zk);
+            const PolicyDecision dec = policy_decide(pw, zk, x, seed, decision0 + blk, dl.i, (pflags & ATC_POLICY_DETERMINISTIC) != 0u);
+            if (dl.lane_valid) {
+                *at<Float3>(action + (size_t)blk * BN * 3u, times12(dl.i)) = dec.u;
+                if (logp) *at<float>(logp + (size_t)blk * BN, dl.i * 4u) = dec.logp;
+            }
+            act = dec.a;
+            tg = decode_targets(qr, act);
+            refused_known = false;
+            ++blk;
+        }
+        --left;
+        const bool repeated = !first && __builtin_amdgcn_ballot_w64(es.t == 0) == 0ull;
+        if (ATC_RARE(mask_dirty)) {
+            all_active = (__builtin_amdgcn_ballot_w64(!(dl.lane_valid && ((dl.k < 32 ? ((uint32_t)es.amask >> dl.k) : ((uint32_t)(es.amask >> 32) >> (dl.k - 32))) & 1u))) |
+                          __builtin_amdgcn_ballot_w64(max(ls.a.phi, ls.la_p) == INT32_MAX) | __builtin_amdgcn_ballot_w64(min(ls.a.phi, ls.la_p) == INT32_MIN)) == 0ull;
+            mask_dirty = false;
+        }
+        const Mid m = step_part_a<false, false>(grid, qr, QGET(k), QGET(g), dl, tg.v, altitude_target(qr, tg.ah), tg.p, act.c, ls, es, repeated, all_active,
+                                                st.phi_wide, zk, refused_blk, refused_known ATC_TRACE_PASS(nullptr));
+        refused_known = true;
+        StepVals sv;
+        Float3 nxt = act;
+        int scan_skip = 0;
+        uint32_t scan_mask = 0u;
+        const bool quiet = step_part_b<W, FULL, false, false, false, true>(K, grid, pl, q, qs, zk, N, dl, m, ls, es, so, st.stats, st.phi_wide, pos, obs_stage,
+                                                                            nullptr, nxt, qr_next, scan_skip, scan_mask, nullptr, nullptr, &sv);
+        if (ATC_RARE(!quiet)) mask_dirty = true;
+        // ---- this step's row of the [T][...] outputs: the tail of step_part_b (observation first, the three small stores last) ----
+        const atc_out_t o_t = kernarg_reread<atc_out_t>(offsetof(StepArgs, out), zk);
+        store_obs_rows(o_t.obs + sBN * ATC_OBS_DIM, dl, sv.o, obs_stage);
+        if (dl.lane_valid) stream_store(at<uint16_t>(o_t.flags + sBN, dl.i * 2u), (uint16_t)sv.fl);
+        if (dl.env_valid && dl.k == 0) {
+            *at<float>(o_t.reward + sB, (uint32_t)dl.e * 4u) = sv.env_r;
+            *at<uint8_t>(o_t.done + sB, (uint32_t)dl.e) = sv.done ? 1 : 0;
+        }
+        // what the next decision sees, if the next step opens a block: the observation as stored
+#pragma unroll
+        for (int c = 0; c < ATC_OBS_DIM; ++c) x[c] = sv.o[c];
+    }
+    const atc_state_t st_end = kernarg_reread<atc_state_t>(offsetof(StepArgs, st), opaque_zero());
+    store_lane_state(st_end, d, ls, true);
+    store_env_state<W>(st_end, d, es, hi0);
+}

@@ -1734,6 +1734,7 @@ k_serve(const float* __restrict__ blob, int off_grid, atc_state_t st, atc_out_t 
 #include "atc_plan_refit.inc"    // k_plan_refit (atc_plan_refit)
 #include "atc_plan_score.inc"    // k_plan_score (atc_plan_score)
 #include "atc_branch.inc"        // k_branch (atc_branch), k_select (atc_state_select)
+#include "atc_policy.inc"        // k_rollout_policy (atc_rollout_policy)
 
 // ---------------------------------------------------------------------------------------------------------------
 // host side of the C-ABI
@@ -1762,10 +1763,10 @@ static size_t lds_bytes(const atc_scenario*, bool pair_scan, bool step_kernel = 
 // counters in one table — plain thread-local counters that nothing in the library reads back.  REC_STEP has a slot for each k_step
 // instantiation and one for k_serve starts; a record of 7 slots counts by lane-group width (slot = log2(W)); a record of one slot
 // counts its entry point's launches.  A call moves its own record only.
-enum Record { REC_STEP, REC_SKIP, REC_TRAFFIC, REC_LOOKAHEAD, REC_PLAN, REC_PLAN_SAMPLED, REC_PLAN_DRAW, REC_PLAN_REFIT, REC_PLAN_SCORE, REC_BRANCH, REC_SELECT, REC_COUNT };
+enum Record { REC_STEP, REC_SKIP, REC_TRAFFIC, REC_LOOKAHEAD, REC_PLAN, REC_PLAN_SAMPLED, REC_PLAN_DRAW, REC_PLAN_REFIT, REC_PLAN_SCORE, REC_BRANCH, REC_SELECT, REC_POLICY, REC_COUNT };
 constexpr int kRecordSlots[REC_COUNT] = {ATC_LAUNCH_SLOTS, ATC_SKIP_LAUNCH_SLOTS, ATC_TRAFFIC_LAUNCH_SLOTS, ATC_LOOKAHEAD_LAUNCH_SLOTS, ATC_PLAN_LAUNCH_SLOTS,
                                          ATC_PLAN_SAMPLED_LAUNCH_SLOTS, ATC_PLAN_DRAW_LAUNCH_SLOTS, ATC_PLAN_REFIT_LAUNCH_SLOTS, ATC_PLAN_SCORE_LAUNCH_SLOTS,
-                                         ATC_BRANCH_LAUNCH_SLOTS, ATC_SELECT_LAUNCH_SLOTS};
+                                         ATC_BRANCH_LAUNCH_SLOTS, ATC_SELECT_LAUNCH_SLOTS, ATC_ROLLOUT_POLICY_LAUNCH_SLOTS};
 constexpr int record_offset(int id) {
     int o = 0;
     for (int i = 0; i < id; ++i) o += kRecordSlots[i];
@@ -2105,6 +2106,26 @@ static bool states_overlap(const atc_state_t* a, unsigned long long Ba, const at
         for (int j = 0; j < 6; ++j)
             if (ranges_overlap(ra[i], rb[j])) return true;
     return false;
+}
+
+// ---- policy rollout (include/atc_step.h: atc_rollout_policy) ---------------------------------------------------------------------
+template <int W>
+static int launch_policy(const atc_scenario* s, int B, int N, int T, int hold, const atc_state_t* st, const float* obs0, const atc_policy_t* pol,
+                         const atc_policy_out_t* o, const atc_params_t* p, hipStream_t stream) {
+    const size_t lds = lds_bytes(s, W >= 32, true);
+    const int grid = step_grid(B, W);
+    const StepDerived& q = derive(*p, s, 0);
+    atc_out_t out;
+    memset(&out, 0, sizeof(out));
+    out.obs = o->obs;
+    out.reward = o->reward;
+    out.done = o->done;
+    out.flags = o->flags;
+    hipLaunchKernelGGL((k_rollout_policy<W>), dim3(grid), dim3(kBlock), lds, stream, s->d_blob, s->off_grid, B, N, T, hold, *st, obs0, out, *p, q, pol->w, pol->seed,
+                       pol->decision0, pol->flags, o->action, o->logp);
+    HIP_TRY(hipGetLastError());
+    ++record(REC_POLICY)[__builtin_ctz(W)];
+    return ATC_OK;
 }
 
 #include "atc_abi.inc"   // the extern "C" entry points (host side)

@@ -999,6 +999,68 @@ int atc_state_select(const atc_scenario_t* s, int N, int B_dst, const atc_state_
 enum { ATC_SELECT_LAUNCH_SLOTS = 1 };
 int atc_select_launch_counts(uint64_t* out, int n);
 
+/* POLICY ROLLOUT (extension): the on-policy collection loop of the reference's trainer — PPO2 with MlpPolicy, two tanh layers of 64 and
+ * a diagonal Gaussian, n_steps transitions per update (learning/atc-gym-stable-baselines.py:112-122) — in ONE launch: observation ->
+ * MLP -> Gaussian sample -> clamp -> step, T times, the state in registers throughout like atc_rollout_hold.  The action of step t + 1
+ * depends on the observation of step t, so a caller of atc_step pays a launch boundary (and half a dozen framework launches) inside
+ * every step.  The policy is 10 -> 64 -> 64 -> 3: ATC_POLICY_WORDS floats in one device array, each weight matrix row-major
+ * [out][in], i.e. torch.nn.Linear.weight as it lies in memory.  A value head is not part of it: values come from one batched forward
+ * over the stored observations.
+ * DECISIONS.  Decision b, for b = 0 .. T / hold - 1, is taken for every aircraft slot i = e*N + k from the ten words x that the step
+ * before it stored for that slot: obs0 for b = 0, out->obs of step b*hold - 1 otherwise — exactly what a caller of atc_step would feed
+ * its policy (normalised or not per ATC_M_NORMALIZE, the raw reset observation right after an auto-reset, zeros for an aircraft that
+ * is not under control).  With mix64 the mixer of the reset draws (see atc_plan_draw):
+ *
+ *     h1 = tanh(W1 x + b1);  h2 = tanh(W2 h1 + b2);  mu = W3 h2 + b3;  sigma_c = expf(log_std_c)
+ *     key = mix64( mix64(seed ^ (u64)(decision0 + b)) ^ (u64)i )         decision0 + b wraps modulo 2^32
+ *     w_c = mix64(key ^ (u64)(c + 1))                                    c = 0, 1, 2 (v, h, phi)
+ *     u1  = ((w_c >> 40) + 1) * 2^-24   in (0, 1];    u2 = ((w_c >> 16) & 0xffffff) * 2^-24   in [0, 1)
+ *     z_c = sqrtf(-2 logf(u1)) * cosf(2 pi u2)                           Box-Muller: a true Gaussian, |z| <= 5.77; 2 pi u2 is ONE fp32
+ *                                                                        product with the fp32 nearest to 2 pi
+ *     u_c = mu_c + sigma_c * z_c                                         ATC_POLICY_DETERMINISTIC: u_c = mu_c, no key is evaluated, logp = 0
+ *     a_c = fminf(fmaxf(u_c, -1), 1)                                     a NaN (a diverged network) gives -1: no NaN reaches the env
+ *     logp = sum_c (-0.5 z_c^2 - log_std_c) - 1.5 log(2 pi)              the log-density of u under N(mu, sigma)
+ *
+ * action[b] = u, the UNCLAMPED sample (what logp is about), and logp[b] as above; steps b*hold .. b*hold + hold - 1 are flown with a.
+ * Successive launches pass decision0 += T / hold for fresh noise, and the last observation of one launch as the obs0 of the next: two
+ * launches of T / 2 then reproduce one launch of T bit for bit.
+ * DYNAMICS.  Everything else — the per-step outputs, the state afterwards, stepping through auto-resets inside a held block, the
+ * last-action record, WIDE headings — is atc_rollout_hold(T, hold) on the tensor of the clamped actions a, bit for bit.
+ * EXACT AND INEXACT.  The integers, the key, u1 and u2 are exact.  The dot products may be summed in any order and by any unit; tanh,
+ * expf, logf and cosf are the device library's, not the fast intrinsics: mu, z, u and logp are values (tests/policy_ref.py restates them
+ * in float64 and states the bars), a is exactly the clamp of the stored u.
+ * ATC_ERR_ARG, in this order, the first before any pointer is looked at, atc_last_error() naming the argument: T < 1, hold < 1 or T not
+ * a multiple of hold; a NULL among pol, pol->w, obs0, out, out's four step outputs, out->action; n_hidden != ATC_POLICY_HIDDEN or
+ * unknown flag bits; the argument errors of atc_rollout_hold; ATC_M_DISCRETE (a Gaussian policy draws the continuous space only) or
+ * ATC_M_ACTIONS_HELD in p->mode; obs0 (B*N*40 bytes) overlapping out->obs (T*B*N*40 bytes).
+ * Counted by atc_rollout_policy_launch_counts only (slot = log2(W); the rules of atc_skip_launch_counts): every other launch record
+ * stays still, and a refused call moves none. */
+#define ATC_POLICY_IN 10            /* = ATC_OBS_DIM: the policy sees one aircraft's own observation row */
+#define ATC_POLICY_HIDDEN 64
+#define ATC_POLICY_WORDS 5062
+#define ATC_POLICY_DETERMINISTIC 1u
+typedef struct atc_policy {
+    const float* w;      /* device, ATC_POLICY_WORDS floats: W1[64][10], b1[64], W2[64][64], b2[64], W3[3][64], b3[3], log_std[3] */
+    int32_t n_hidden;    /* must be ATC_POLICY_HIDDEN (refused otherwise; the field is there so a later width needs no new struct) */
+    uint32_t flags;      /* ATC_POLICY_DETERMINISTIC or 0 */
+    uint64_t seed;
+    uint32_t decision0;  /* number of the launch's first decision */
+    uint32_t reserved;
+} atc_policy_t;
+typedef struct atc_policy_out {
+    float* obs;          /* [T][B*N*10]     required: atc_rollout's per-step outputs */
+    float* reward;       /* [T][B]          required */
+    uint8_t* done;       /* [T][B]          required */
+    uint16_t* flags;     /* [T][B*N]        required */
+    float* action;       /* [T/hold][B*N*3] required: the UNCLAMPED sample u */
+    float* logp;         /* [T/hold][B*N]   nullable */
+} atc_policy_out_t;
+int atc_rollout_policy(const atc_scenario_t* s, int B, int N, int T, int hold, const atc_state_t* st,
+                       const float* obs0 /* [B*N*10] */, const atc_policy_t* pol, const atc_policy_out_t* out,
+                       const atc_params_t* p, void* stream);
+enum { ATC_ROLLOUT_POLICY_LAUNCH_SLOTS = 7 };
+int atc_rollout_policy_launch_counts(uint64_t* out, int n);
+
 #ifdef __cplusplus
 }
 #endif
