@@ -107,3 +107,19 @@ SELECT_LAUNCH_SLOTS = 1
 POLICY_IN, POLICY_HIDDEN, POLICY_WORDS = 10, 64, 5062
 POLICY_DETERMINISTIC = 1
 ROLLOUT_POLICY_LAUNCH_SLOTS = 7
+# policy rollout with traffic (include/atc_step.h: atc_rollout_policy_traffic): the first layer is policy_in(K) = 10 + 7 K wide — the own row,
+# then words 0..6 of each of the K records — and the array policy_words(K) floats, laid out like POLICY_WORDS; K is one of POLICY_TRAFFIC_K; its
+# own launch record (slot = 3 log2(W) + log2(K))
+POLICY_TRAFFIC_K = (1, 2, 4)
+POLICY_TRAFFIC_WORDS_PER_RECORD = 7
+ROLLOUT_POLICY_TRAFFIC_LAUNCH_SLOTS = 21
+
+
+def policy_in(traffic=0):
+    """width of the policy's input row: POLICY_IN own words + 7 per traffic record (ATC_POLICY_TRAFFIC_IN)"""
+    return POLICY_IN + POLICY_TRAFFIC_WORDS_PER_RECORD * int(traffic)
+
+
+def policy_words(traffic=0):
+    """floats in the packed weight array (ATC_POLICY_WORDS; ATC_POLICY_TRAFFIC_WORDS(K))"""
+    return POLICY_WORDS + POLICY_HIDDEN * POLICY_TRAFFIC_WORDS_PER_RECORD * int(traffic)

@@ -91,6 +91,22 @@ class AtcPolicyOut(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in POLICY_OUT_FIELDS]
 
 
+POLICY_TRAFFIC_FIELDS = POLICY_FIELDS + ("traffic_k",)
+
+
+class AtcPolicyTraffic(C.Structure):
+    """atc_policy_traffic_t"""
+    _fields_ = AtcPolicy._fields_ + [("traffic_k", C.c_int32)]
+
+
+POLICY_TRAFFIC_OUT_FIELDS = POLICY_OUT_FIELDS + ("traffic",)
+
+
+class AtcPolicyTrafficOut(C.Structure):
+    """atc_policy_traffic_out_t"""
+    _fields_ = [(n, C.c_void_p) for n in POLICY_TRAFFIC_OUT_FIELDS]
+
+
 class AtcStepCall(C.Structure):
     """atc_step_call_t"""
     _fields_ = [("s", C.c_void_p), ("B", C.c_int32), ("N", C.c_int32), ("st", C.POINTER(AtcState)), ("actions", C.c_void_p),
@@ -106,7 +122,7 @@ EXPORTS = ("atc_abi_version", "atc_last_error", "atc_launch_counts", "atc_host_m
            "atc_branch", "atc_branch_launch_counts", "atc_state_select", "atc_select_launch_counts",
            "atc_plan_draw", "atc_lookahead_plan_sampled", "atc_plan_sampled_launch_counts", "atc_plan_draw_launch_counts",
            "atc_plan_refit", "atc_plan_refit_launch_counts", "atc_plan_score", "atc_plan_score_launch_counts",
-           "atc_rollout_policy", "atc_rollout_policy_launch_counts")
+           "atc_rollout_policy", "atc_rollout_policy_launch_counts", "atc_rollout_policy_traffic", "atc_rollout_policy_traffic_launch_counts")
 
 def load():
     """Loads libatcstep.so; raises (never falls back) when it has not been built."""
@@ -158,6 +174,8 @@ def load():
     lib.atc_branch.argtypes = [vp, ci, ci, ci, ci, C.POINTER(AtcState), vp, C.POINTER(AtcState), C.POINTER(AtcLookaheadOut), C.POINTER(AtcParams), vp]
     lib.atc_state_select.argtypes = [vp, ci, ci, C.POINTER(AtcState), ci, C.POINTER(AtcState), vp, vp, vp]
     lib.atc_rollout_policy.argtypes = [vp, ci, ci, ci, ci, C.POINTER(AtcState), vp, C.POINTER(AtcPolicy), C.POINTER(AtcPolicyOut), C.POINTER(AtcParams), vp]
+    lib.atc_rollout_policy_traffic.argtypes = [vp, ci, ci, ci, ci, C.POINTER(AtcState), vp, C.POINTER(AtcPolicyTraffic), C.POINTER(AtcPolicyTrafficOut),
+                                               C.POINTER(AtcParams), vp]
     for getter in LAUNCH_RECORDS:
         getattr(lib, getter).argtypes = [C.POINTER(C.c_uint64), ci]
     for name in EXPORTS:
@@ -185,6 +203,11 @@ def _width(slot):
     return 1 << slot
 
 
+def _width_k(slot):
+    """(W, K) of a slot of the traffic policy rollout's record: slot = 3 log2(W) + log2(K)"""
+    return (1 << (slot // 3), 1 << (slot % 3))
+
+
 # The library's launch records (include/atc_step.h): getter -> (slots, name of a slot: a function of the slot number, or the one
 # slot's name).  load() gives every getter its argtypes from this table; each has a wrapper below, and launch_records() reads all.
 LAUNCH_RECORDS = {
@@ -200,6 +223,7 @@ LAUNCH_RECORDS = {
     "atc_branch_launch_counts": (L.BRANCH_LAUNCH_SLOTS, _width),
     "atc_select_launch_counts": (L.SELECT_LAUNCH_SLOTS, "select"),
     "atc_rollout_policy_launch_counts": (L.ROLLOUT_POLICY_LAUNCH_SLOTS, _width),
+    "atc_rollout_policy_traffic_launch_counts": (L.ROLLOUT_POLICY_TRAFFIC_LAUNCH_SLOTS, _width_k),
 }
 
 
@@ -283,6 +307,12 @@ def rollout_policy_launch_counts():
     """Launches of the policy rollout (atc_rollout_policy) made by the calling thread so far, by lane-group width: {16: n, ...}, widths
     with a count of zero left out.  Separate from the other launch records, which a policy rollout leaves as they are."""
     return _counts("atc_rollout_policy_launch_counts")
+
+
+def rollout_policy_traffic_launch_counts():
+    """Launches of the policy rollout with traffic (atc_rollout_policy_traffic) made by the calling thread so far, by lane-group width and
+    records per aircraft: {(16, 4): n, ...}, zero counts left out.  Separate from the other launch records, rollout_policy's included."""
+    return _counts("atc_rollout_policy_traffic_launch_counts")
 
 
 def lookahead_set_mapping(candidates_per_workgroup=0):

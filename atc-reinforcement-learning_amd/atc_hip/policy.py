@@ -1,32 +1,41 @@
 """The policy of AtcVecEnv.rollout_policy (include/atc_step.h: atc_rollout_policy) as the library reads it: one float32 array of
 POLICY_WORDS words — W1[64][10], b1[64], W2[64][64], b2[64], W3[3][64], b3[3], log_std[3], every weight matrix row-major [out][in],
-i.e. torch.nn.Linear.weight as it lies in memory.  No value head: values come from one batched forward over the stored observations."""
+i.e. torch.nn.Linear.weight as it lies in memory.  No value head: values come from one batched forward over the stored observations.
+With traffic=K (AtcVecEnv.rollout_policy_traffic; atc_rollout_policy_traffic) the first layer is W1[64][10 + 7 K]: the own row, then words
+0..6 of each of the K traffic records (word 7, the slot, is not an input); everything else lies as before, behind it."""
 from . import layout as L
 
 SHAPES = (("W1", (L.POLICY_HIDDEN, L.POLICY_IN)), ("b1", (L.POLICY_HIDDEN,)), ("W2", (L.POLICY_HIDDEN, L.POLICY_HIDDEN)), ("b2", (L.POLICY_HIDDEN,)),
           ("W3", (L.ACT_DIM, L.POLICY_HIDDEN)), ("b3", (L.ACT_DIM,)), ("log_std", (L.ACT_DIM,)))
 
 
-def offsets():
+def shapes(traffic=0):
+    """SHAPES with the first layer of a policy that sees `traffic` records per aircraft"""
+    if traffic not in (0,) + L.POLICY_TRAFFIC_K:
+        raise ValueError("traffic must be 0 or one of %s records per aircraft" % (L.POLICY_TRAFFIC_K,))
+    return (("W1", (L.POLICY_HIDDEN, L.policy_in(traffic))),) + SHAPES[1:]
+
+
+def offsets(traffic=0):
     """{name: (first word, shape)} of the seven parts of the packed array"""
     out, at = {}, 0
-    for name, shape in SHAPES:
+    for name, shape in shapes(traffic):
         n = 1
         for s in shape:
             n *= s
         out[name] = (at, shape)
         at += n
-    assert at == L.POLICY_WORDS
+    assert at == L.policy_words(traffic)
     return out
 
 
-def pack_mlp(W1, b1, W2, b2, W3, b3, log_std, device=None):
-    """The POLICY_WORDS-word float32 tensor of a 10 -> 64 -> 64 -> 3 MLP with weights [out, in] (tensors or arrays; shapes are
-    checked, nothing is transposed or broadcast).  On `device` (default: the first part's device if it is a tensor, else the CPU):
-    rollout_policy needs it on the env's device."""
+def pack_mlp(W1, b1, W2, b2, W3, b3, log_std, device=None, traffic=0):
+    """The policy_words(traffic)-word float32 tensor of an IN -> 64 -> 64 -> 3 MLP, IN = 10 + 7 traffic, with weights [out, in] (tensors or
+    arrays; shapes are checked, nothing is transposed or broadcast).  On `device` (default: the first part's device if it is a tensor,
+    else the CPU): rollout_policy needs it on the env's device."""
     import torch
     parts = []
-    for (name, shape), v in zip(SHAPES, (W1, b1, W2, b2, W3, b3, log_std)):
+    for (name, shape), v in zip(shapes(traffic), (W1, b1, W2, b2, W3, b3, log_std)):
         t = torch.as_tensor(v).detach()
         if tuple(t.shape) != shape:
             raise ValueError("%s must have shape %s (weights are [out, in]), got %s" % (name, shape, tuple(t.shape)))
@@ -34,12 +43,12 @@ def pack_mlp(W1, b1, W2, b2, W3, b3, log_std, device=None):
             device = t.device
         parts.append(t)
     flat = torch.cat([t.to(device=device or "cpu", dtype=torch.float32).reshape(-1) for t in parts]).contiguous()
-    assert flat.numel() == L.POLICY_WORDS
+    assert flat.numel() == L.policy_words(traffic)
     return flat
 
 
-def from_torch(module, log_std, device=None):
-    """pack_mlp of an nn.Sequential(Linear(10, 64), Tanh(), Linear(64, 64), Tanh(), Linear(64, 3)) — biases required — and a
+def from_torch(module, log_std, device=None, traffic=0):
+    """pack_mlp of an nn.Sequential(Linear(10 + 7 traffic, 64), Tanh(), Linear(64, 64), Tanh(), Linear(64, 3)) — biases required — and a
     log_std of 3 values (a parameter of the trainer's, not of the module)."""
     from torch import nn
     layers = list(module)
@@ -49,4 +58,22 @@ def from_torch(module, log_std, device=None):
     lin = layers[0::2]
     if any(m.bias is None for m in lin):
         raise ValueError("every Linear layer needs a bias")
-    return pack_mlp(lin[0].weight, lin[0].bias, lin[1].weight, lin[1].bias, lin[2].weight, lin[2].bias, log_std, device=device)
+    return pack_mlp(lin[0].weight, lin[0].bias, lin[1].weight, lin[1].bias, lin[2].weight, lin[2].bias, log_std, device=device, traffic=traffic)
+
+
+def input_rows(obs_rows, traffic_records):
+    """The rows a decision of rollout_policy_traffic saw, [..., N, 10 + 7 K]: stored observation rows [..., N, 10] (obs0, or obs of the step
+    before the decision; [..., N * 10] is taken as well) next to words 0..6 of the stored records [..., N, K, 8].  Tensors or arrays; a
+    trainer's update recomputes logp on these."""
+    tr = traffic_records
+    N, K = tr.shape[-3], tr.shape[-2]
+    if tr.shape[-1] != L.TRAFFIC_DIM:
+        raise ValueError("traffic_records must be [..., N, K, %d]" % L.TRAFFIC_DIM)
+    lead = tuple(tr.shape[:-3])
+    own = obs_rows.reshape(lead + (N, L.OBS_DIM))
+    seen = tr[..., :L.POLICY_TRAFFIC_WORDS_PER_RECORD].reshape(lead + (N, K * L.POLICY_TRAFFIC_WORDS_PER_RECORD))
+    if hasattr(own, "numpy") and hasattr(own, "device"):
+        import torch
+        return torch.cat([own, seen], dim=-1)
+    import numpy as np
+    return np.concatenate([own, seen], axis=-1)

@@ -839,7 +839,8 @@ class AtcVecEnv:
         row of the previous call's obs as obs0; deterministic=True flies the mean (logp = 0).
         Returns a dict of device tensors: obs / reward / done / flags [T, ...] as rollout() returns them, action [T // hold, B, N, 3] —
         the UNCLAMPED sample, what logp is about; its clamp to [-1, 1] is what was flown — and logp [T // hold, B, N].  Values are not
-        computed: run the value network once over the stored obs.  Like rollout(), it produces no traffic observation."""
+        computed: run the value network once over the stored obs.  Like rollout(), it produces no traffic observation: a policy that sees
+        traffic is rolled out by rollout_policy_traffic()."""
         torch = self.torch
         T, hold = int(T), int(hold)
         B, N, dev = self.B, self.N, self.device
@@ -865,6 +866,52 @@ class AtcVecEnv:
         with torch.cuda.device(dev):
             _lib.check(self._lib.atc_rollout_policy(self.sector.handle, B, N, T, hold, C.byref(self._state), self._ptr(x0), C.byref(pol),
                                                     C.byref(o), C.byref(self.params), self._stream()))
+        self._keep = (w, x0)
+        self._finish()
+        return out
+
+    def rollout_policy_traffic(self, weights, T, traffic, hold=1, seed=0, decision0=0, deterministic=False, obs0=None, out=None):
+        """rollout_policy with a policy that also sees traffic (include/atc_step.h: atc_rollout_policy_traffic): at every decision each
+        aircraft's `traffic` = K nearest intruders (1, 2 or 4) are found inside the launch, on the state as it is then, and words 0..6 of
+        each record widen the input row to 10 + 7 K — exactly what observe_traffic() would return there, the convention of info["traffic"].
+        weights: the L.policy_words(K)-word tensor of atc_hip.policy.pack_mlp / from_torch (traffic=K).  traffic=0 is rollout_policy itself.
+        Returns rollout_policy's dict plus "traffic" [T // hold, B, N, K, 8], the records each decision saw (atc_hip.policy.input_rows builds
+        the rows from them for the trainer's update); `out` may carry the buffers, "traffic" left out or None stores no records.
+        Independent of the env's own traffic= setting: self.traffic is neither read nor written."""
+        torch = self.torch
+        K = int(traffic)
+        if K == 0:
+            return self.rollout_policy(weights, T, hold=hold, seed=seed, decision0=decision0, deterministic=deterministic, obs0=obs0, out=out)
+        if K not in L.POLICY_TRAFFIC_K:
+            raise ValueError("traffic must be 0 or one of %s records per aircraft" % (L.POLICY_TRAFFIC_K,))
+        T, hold = int(T), int(hold)
+        B, N, dev = self.B, self.N, self.device
+        w, words = weights, L.policy_words(K)
+        if not (torch.is_tensor(w) and w.dtype == torch.float32 and w.device == dev and w.is_contiguous() and w.numel() == words):
+            raise ValueError("weights must be the contiguous float32 tensor of %d words (atc_hip.policy.pack_mlp(traffic=%d)) on %s" % (words, K, dev))
+        x0 = self.obs if obs0 is None else obs0
+        if not (torch.is_tensor(x0) and x0.dtype == torch.float32 and x0.is_contiguous() and x0.numel() == B * N * L.OBS_DIM):
+            raise ValueError("obs0 must be a contiguous float32 tensor of B*N*%d words" % L.OBS_DIM)
+        n_dec = T // hold if hold >= 1 else 0     # (a T or hold the library refuses is refused by it, below)
+        if out is None:
+            out = {
+                "obs": torch.empty((T, B, N * L.OBS_DIM), dtype=torch.float32, device=dev),
+                "reward": torch.empty((T, B), dtype=torch.float32, device=dev),
+                "done": torch.empty((T, B), dtype=torch.uint8, device=dev),
+                "flags": torch.empty((T, B, N), dtype=torch.int16, device=dev),
+                "action": torch.empty((n_dec, B, N, L.ACT_DIM), dtype=torch.float32, device=dev),
+                "logp": torch.empty((n_dec, B, N), dtype=torch.float32, device=dev),
+                "traffic": torch.empty((n_dec, B, N, K, L.TRAFFIC_DIM), dtype=torch.float32, device=dev),
+            }
+        tr = out.get("traffic")
+        if tr is not None and not (torch.is_tensor(tr) and tr.dtype == torch.float32 and tr.is_contiguous() and tr.numel() == n_dec * B * N * K * L.TRAFFIC_DIM):
+            raise ValueError("out['traffic'] must be a contiguous float32 tensor of [T // hold, B, N, %d, %d]" % (K, L.TRAFFIC_DIM))
+        o = _lib.AtcPolicyTrafficOut(*[self._ptr(out.get(k)) for k in _lib.POLICY_TRAFFIC_OUT_FIELDS])
+        pol = _lib.AtcPolicyTraffic(self._ptr(w), L.POLICY_HIDDEN, L.POLICY_DETERMINISTIC if deterministic else 0, int(seed) & (2 ** 64 - 1),
+                                    int(decision0) & 0xffffffff, 0, K)
+        with torch.cuda.device(dev):
+            _lib.check(self._lib.atc_rollout_policy_traffic(self.sector.handle, B, N, T, hold, C.byref(self._state), self._ptr(x0), C.byref(pol),
+                                                            C.byref(o), C.byref(self.params), self._stream()))
         self._keep = (w, x0)
         self._finish()
         return out

@@ -24,6 +24,7 @@ int atc_plan_score_launch_counts(uint64_t* out, int n) { return copy_counts(REC_
 int atc_branch_launch_counts(uint64_t* out, int n) { return copy_counts(REC_BRANCH, out, n); }
 int atc_select_launch_counts(uint64_t* out, int n) { return copy_counts(REC_SELECT, out, n); }
 int atc_rollout_policy_launch_counts(uint64_t* out, int n) { return copy_counts(REC_POLICY, out, n); }
+int atc_rollout_policy_traffic_launch_counts(uint64_t* out, int n) { return copy_counts(REC_POLICY_TRAFFIC, out, n); }
 int atc_lookahead_set_mapping(int candidates_per_workgroup) {
     if (candidates_per_workgroup < 0 || candidates_per_workgroup > ATC_LOOKAHEAD_MAX_M) return fail_arg("candidates per workgroup must be 0 (the library's choice) .. 64");
     t_look_cpg = candidates_per_workgroup;
@@ -433,15 +434,7 @@ int atc_observe_traffic(const atc_scenario_t* s, int B, int N, int K, const atc_
     if (K < 1 || K > ATC_TRAFFIC_MAX_K) return fail_arg("K (traffic records per aircraft) must be 1 .. 8");
     if (!traffic) return fail_arg("null pointer");
     if (const int rc = check_env_args(s, B, N, st, p)) return rc;
-    TrafficArgs q;
-    q.pos_inv = (double)s->consts[ATC_C_POS_INV];
-    q.x0 = (double)s->consts[ATC_C_POS_X0];
-    q.y0 = (double)s->consts[ATC_C_POS_Y0];
-    const bool nrm = (p->mode & ATC_M_NORMALIZE) != 0;
-    q.s_pos = nrm ? 1.0f / s->consts[ATC_C_WORLD_DIAG] : 1.0f;
-    q.h_div = nrm ? s->consts[ATC_C_H_MAX] : 1.0f;
-    q.s_v = nrm ? 1.0f / (2.0f * s->consts[ATC_C_V_MAX]) : 1.0f;
-    q.K = K;
+    const TrafficArgs q = traffic_common(s, p, K);
     return with_width(N, [&](auto w) { return launch_traffic<decltype(w)::value>(B, N, st, traffic, q, (hipStream_t)stream); });
 }
 
@@ -568,24 +561,16 @@ int atc_state_select(const atc_scenario_t* s, int N, int B_dst, const atc_state_
 
 int atc_rollout_policy(const atc_scenario_t* s, int B, int N, int T, int hold, const atc_state_t* st, const float* obs0, const atc_policy_t* pol,
                        const atc_policy_out_t* out, const atc_params_t* p, void* stream) {
-    // T and hold first, before any pointer is looked at
-    if (T < 1 || hold < 1) return fail_arg("need T >= 1 and hold >= 1");
-    if (T % hold != 0) return fail_arg("T must be a multiple of hold (the launch takes T / hold decisions)");
-    if (const int rc = check_required({{pol, "null pointer: pol (atc_policy_t) is required"}, {pol ? pol->w : nullptr, "null pointer: pol->w (the policy's weights) is required"},
-                                       {obs0, "null pointer: obs0 is required"}, {out, "null pointer: out (atc_policy_out_t) is required"}}))
-        return rc;
-    if (!out->obs || !out->reward || !out->done || !out->flags) return fail_arg("null pointer: atc_policy_out_t.obs, .reward, .done and .flags are required");
-    if (!out->action) return fail_arg("null pointer: atc_policy_out_t.action is required");
-    if (pol->n_hidden != ATC_POLICY_HIDDEN) return fail_arg("pol->n_hidden must be 64 (ATC_POLICY_HIDDEN)");
-    if (pol->flags & ~ATC_POLICY_DETERMINISTIC) return fail_arg("pol->flags has unknown bits (ATC_POLICY_DETERMINISTIC or 0)");
-    if (const int rc = check_env_args(s, B, N, st, p)) return rc;
-    if (const int rc = check_dt(s, p)) return rc;
-    if (p->mode & ATC_M_DISCRETE) return fail_arg("ATC_M_DISCRETE: a Gaussian policy draws the continuous action space only");
-    if (p->mode & ATC_M_ACTIONS_HELD) return fail_arg("ATC_M_ACTIONS_HELD is for atc_step only: every block's first step carries a fresh decision");
-    const uintptr_t row = (uintptr_t)B * (uintptr_t)N * (ATC_OBS_DIM * 4u);
-    const ByteRange ranges[2] = {{obs0, row, "obs0"}, {out->obs, row * (uintptr_t)T, "out->obs"}};
-    if (const int rc = check_disjoint(ranges, 2, {}, "decision 0 reads obs0 while the steps write out->obs")) return rc;
+    if (const int rc = check_policy_call(s, B, N, T, hold, st, obs0, pol, out, p, "atc_policy_t", "atc_policy_out_t", nullptr, nullptr)) return rc;
     return with_width(N, [&](auto w) { return launch_policy<decltype(w)::value>(s, B, N, T, hold, st, obs0, pol, out, p, (hipStream_t)stream); });
+}
+
+int atc_rollout_policy_traffic(const atc_scenario_t* s, int B, int N, int T, int hold, const atc_state_t* st, const float* obs0,
+                               const atc_policy_traffic_t* pol, const atc_policy_traffic_out_t* out, const atc_params_t* p, void* stream) {
+    if (const int rc = check_policy_call(s, B, N, T, hold, st, obs0, pol, out, p, "atc_policy_traffic_t", "atc_policy_traffic_out_t", pol ? &pol->traffic_k : nullptr,
+                                         out ? out->traffic : nullptr))
+        return rc;
+    return with_width(N, [&](auto w) { return launch_policy_traffic<decltype(w)::value>(s, B, N, T, hold, st, obs0, pol, out, p, (hipStream_t)stream); });
 }
 
 }  // extern "C"

@@ -21,8 +21,18 @@
 //   scalar registers holding them spilled to vector-register lanes.
 //   THE DRAW: integers, key, u1, u2 exact; logf / cosf / sqrtf / expf / tanhf are the device library's (the file is built without
 //   fast-math and with -ffp-contract=off).  tests/policy_ref.py restates everything in numpy.
-enum { ATC_POL_W1 = 0, ATC_POL_B1 = 640, ATC_POL_W2 = 704, ATC_POL_B2 = 4800, ATC_POL_W3 = 4864, ATC_POL_B3 = 5056, ATC_POL_LOGSTD = 5059 };
-static_assert(ATC_POL_LOGSTD + 3 == ATC_POLICY_WORDS && ATC_POLICY_IN == ATC_OBS_DIM && ATC_POLICY_HIDDEN == 64, "atc_policy_t.w layout");
+//   TRAFFIC (atc_rollout_policy_traffic, k_rollout_policy_traffic<W, KT>): the same loop with one more stage at the decision site — the
+//   query of atc_observe_traffic(KT) on the state in registers, through the device functions k_traffic itself calls (atc_traffic.inc),
+//   stored and fed to a first layer of 10 + 7 KT inputs.  See rollout_policy_body.
+// the seven parts of the packed array for an input row of IN words (10: atc_policy_t.w; 10 + 7 K: atc_policy_traffic_t.w)
+template <int IN>
+struct PolOff {
+    enum { W1 = 0, B1 = ATC_POLICY_HIDDEN * IN, W2 = B1 + ATC_POLICY_HIDDEN, B2 = W2 + ATC_POLICY_HIDDEN * ATC_POLICY_HIDDEN, W3 = B2 + ATC_POLICY_HIDDEN,
+           B3 = W3 + 3 * ATC_POLICY_HIDDEN, LOGSTD = B3 + 3, WORDS = LOGSTD + 3 };
+};
+static_assert(PolOff<ATC_POLICY_IN>::WORDS == ATC_POLICY_WORDS && ATC_POLICY_IN == ATC_OBS_DIM && ATC_POLICY_HIDDEN == 64, "atc_policy_t.w layout");
+static_assert(PolOff<ATC_POLICY_TRAFFIC_IN(1)>::WORDS == ATC_POLICY_TRAFFIC_WORDS(1) && PolOff<ATC_POLICY_TRAFFIC_IN(4)>::WORDS == ATC_POLICY_TRAFFIC_WORDS(4) &&
+              ATC_POLICY_TRAFFIC_WORDS(1) == 5510 && ATC_POLICY_TRAFFIC_WORDS(2) == 5958 && ATC_POLICY_TRAFFIC_WORDS(4) == 6854, "atc_policy_traffic_t.w layout");
 #define ATC_POL_TWO_PI 6.2831853071795864769f
 #define ATC_POL_LOGP_C 2.7568155996140185f   // 1.5 log(2 pi)
 
@@ -42,8 +52,10 @@ __device__ __forceinline__ float policy_z(uint64_t key, uint32_t c) {
     return sqrtf(-2.0f * logf(u1)) * cosf(ATC_POL_TWO_PI * u2);
 }
 
+template <int IN>
 __device__ __forceinline__ PolicyDecision policy_decide(const float* w_arg, int zk, const float* x, uint64_t seed, uint32_t decision, uint32_t i,
                                                         bool deterministic) {
+    typedef PolOff<IN> O;
     pol_wptr w = (pol_wptr)(uintptr_t)w_arg;
     asm volatile("" : "+s"(w) : "s"(zk));
     // Layer 1.  Normalised observations lie in [-1, 1] and the fp32 sum is good to 1e-7.  Unnormalised ones reach 1.5e4 (the altitude
@@ -53,34 +65,34 @@ __device__ __forceinline__ PolicyDecision policy_decide(const float* w_arg, int 
     float h1[ATC_POLICY_HIDDEN];
     float xmax = 0.0f;
 #pragma unroll
-    for (int c = 0; c < ATC_POLICY_IN; ++c) xmax = fmaxf(xmax, fabsf(x[c]));
+    for (int c = 0; c < IN; ++c) xmax = fmaxf(xmax, fabsf(x[c]));
     if (ATC_RARE(__builtin_amdgcn_ballot_w64(!(xmax <= 4.0f)) != 0ull)) {
-        double xd[ATC_POLICY_IN];
+        double xd[IN];
 #pragma unroll
-        for (int c = 0; c < ATC_POLICY_IN; ++c) xd[c] = (double)x[c];
+        for (int c = 0; c < IN; ++c) xd[c] = (double)x[c];
 #pragma unroll
         for (int j = 0; j < ATC_POLICY_HIDDEN; ++j) {
-            double s = (double)w[ATC_POL_B1 + j];
+            double s = (double)w[O::B1 + j];
 #pragma unroll
-            for (int c = 0; c < ATC_POLICY_IN; ++c) s = __builtin_fma((double)w[ATC_POL_W1 + j * ATC_POLICY_IN + c], xd[c], s);
+            for (int c = 0; c < IN; ++c) s = __builtin_fma((double)w[O::W1 + j * IN + c], xd[c], s);
             h1[j] = (float)s;
         }
     } else {
 #pragma unroll
         for (int j = 0; j < ATC_POLICY_HIDDEN; ++j) {
-            float s = w[ATC_POL_B1 + j];
+            float s = w[O::B1 + j];
 #pragma unroll
-            for (int c = 0; c < ATC_POLICY_IN; ++c) s = fmaf(w[ATC_POL_W1 + j * ATC_POLICY_IN + c], x[c], s);
+            for (int c = 0; c < IN; ++c) s = fmaf(w[O::W1 + j * IN + c], x[c], s);
             h1[j] = s;
         }
     }
 #pragma unroll
     for (int j = 0; j < ATC_POLICY_HIDDEN; ++j) h1[j] = tanhf(h1[j]);
-    float mu[3] = {w[ATC_POL_B3 + 0], w[ATC_POL_B3 + 1], w[ATC_POL_B3 + 2]};
+    float mu[3] = {w[O::B3 + 0], w[O::B3 + 1], w[O::B3 + 2]};
 #pragma unroll 1
     for (int j = 0; j < ATC_POLICY_HIDDEN; ++j) {
-        pol_wptr row = w + ATC_POL_W2 + j * ATC_POLICY_HIDDEN;
-        float s0 = w[ATC_POL_B2 + j], s1 = 0.0f, s2 = 0.0f, s3 = 0.0f;
+        pol_wptr row = w + O::W2 + j * ATC_POLICY_HIDDEN;
+        float s0 = w[O::B2 + j], s1 = 0.0f, s2 = 0.0f, s3 = 0.0f;
 #pragma unroll
         for (int c = 0; c < ATC_POLICY_HIDDEN; c += 4) {
             s0 = fmaf(row[c + 0], h1[c + 0], s0);
@@ -90,7 +102,7 @@ __device__ __forceinline__ PolicyDecision policy_decide(const float* w_arg, int 
         }
         const float h2 = tanhf((s0 + s1) + (s2 + s3));
 #pragma unroll
-        for (int c = 0; c < 3; ++c) mu[c] = fmaf(w[ATC_POL_W3 + c * ATC_POLICY_HIDDEN + j], h2, mu[c]);
+        for (int c = 0; c < 3; ++c) mu[c] = fmaf(w[O::W3 + c * ATC_POLICY_HIDDEN + j], h2, mu[c]);
     }
     PolicyDecision dec;
     dec.logp = 0.0f;
@@ -101,7 +113,7 @@ __device__ __forceinline__ PolicyDecision policy_decide(const float* w_arg, int 
         float u[3], lp = 0.0f;
 #pragma unroll
         for (uint32_t c = 0; c < 3u; ++c) {
-            const float ls = w[ATC_POL_LOGSTD + c];
+            const float ls = w[O::LOGSTD + c];
             const float z = policy_z(key, c);
             u[c] = mu[c] + expf(ls) * z;
             lp += -0.5f * (z * z) - ls;
@@ -131,16 +143,47 @@ static_assert(offsetof(PolicyArgs, hold) == offsetof(StepArgs, hold) && offsetof
               offsetof(PolicyArgs, out) == offsetof(StepArgs, out) && offsetof(PolicyArgs, q) == offsetof(StepArgs, q),
               "k_rollout_policy's kernel arguments must lie where k_step's do: the step re-reads them by StepArgs offsets");
 
+// k_rollout_policy_traffic's arguments: k_rollout_policy's, then what the traffic stage reads — by kernarg re-read at the decision, so that
+// nothing of it is carried across the step loop
+struct PolicyTrafficTail {
+    TrafficArgs tq;     // the host's traffic_common: the uniform terms of atc_observe_traffic
+    float* traffic;     // atc_policy_traffic_out_t.traffic, nullable
+};
+struct PolicyTrafficArgs {   // FLAT, like the kernel's argument list: a nested PolicyArgs would be padded to its own alignment (64), the kernarg segment is not
+    const float* blob;
+    int off_grid, B, N, T, hold;
+    atc_state_t st;
+    const float* obs0;
+    atc_out_t out;
+    atc_params_t p;
+    StepDerived q;
+    const float* w;
+    uint64_t seed;
+    uint32_t decision0, pflags;
+    float* action;
+    float* logp;
+    PolicyTrafficTail tt;
+};
+static_assert(offsetof(PolicyTrafficArgs, hold) == offsetof(StepArgs, hold) && offsetof(PolicyTrafficArgs, st) == offsetof(StepArgs, st) &&
+              offsetof(PolicyTrafficArgs, out) == offsetof(StepArgs, out) && offsetof(PolicyTrafficArgs, q) == offsetof(StepArgs, q) &&
+              offsetof(PolicyTrafficArgs, logp) == offsetof(PolicyArgs, logp) && alignof(PolicyTrafficTail) == 8 &&
+              offsetof(PolicyTrafficArgs, tt) == offsetof(PolicyArgs, logp) + sizeof(float*),
+              "k_rollout_policy_traffic's arguments are k_rollout_policy's with the traffic terms directly behind logp");
+
 // wavefronts per SIMD k_rollout_policy is register-budgeted for (<= 168 VGPRs): the 64 hidden activations are live next to what the
 // step carries across its loop, which the step's own 5 - 6 do not hold.  -DATC_POLICY_WAVES=n: A/B builds.
 #ifndef ATC_POLICY_WAVES
 #define ATC_POLICY_WAVES 3
 #endif
-template <int W>
-__global__ void __launch_bounds__(kBlock, ATC_POLICY_WAVES)
-k_rollout_policy(const float* __restrict__ blob, int off_grid, int B, int N, int T, int hold, atc_state_t st, const float* __restrict__ obs0,
-                 atc_out_t out, atc_params_t p, StepDerived q, const float* __restrict__ pw, uint64_t seed, uint32_t decision0, uint32_t pflags,
-                 float* __restrict__ action, float* __restrict__ logp) {
+// The loop of both kernels.  KT = 0: k_rollout_policy, the policy sees the ten own words.  KT = 1, 2, 4: k_rollout_policy_traffic — at a
+// block's first step the traffic query of atc_observe_traffic(KT) is evaluated on the state in registers (traffic_self / traffic_select /
+// traffic_record of atc_traffic.inc: k_traffic's arithmetic, so the same bits), stored, and its words 0..6 per record widen the input row.
+// An env never leaves its wavefront: W = 32 / 64 stage (x, y, tag) in the wavefront's own quarter of the pair-scan staging area (idle
+// between steps), ordered by wave-level waits — no workgroup barrier anywhere in the decision.
+template <int W, int KT>
+__device__ __forceinline__ void rollout_policy_body(const float* __restrict__ blob, int off_grid, int B, int N, int T, atc_state_t st, const float* __restrict__ obs0,
+                                                    atc_params_t p, StepDerived q, const float* __restrict__ pw, uint64_t seed, uint32_t decision0, uint32_t pflags,
+                                                    float* __restrict__ action, float* __restrict__ logp) {
     constexpr bool ONE = false, LAT = false, FULL = false;   // (QGET: the multi-step form — kernarg re-reads inside the step)
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float4* pos = reinterpret_cast<float4*>(smem);                    // [2 kBlock] pair-scan staging (W >= 32)
@@ -192,7 +235,52 @@ k_rollout_policy(const float* __restrict__ blob, int off_grid, int B, int N, int
         const bool first = left == 0;   // this step opens a block: a fresh decision, from the observation the step before it stored
         if (ATC_RARE(first)) {
             left = kernarg_reread<int>(offsetof(StepArgs, hold), zk);
-            const PolicyDecision dec = policy_decide(pw, zk, x, seed, decision0 + blk, dl.i, (pflags & ATC_POLICY_DETERMINISTIC) != 0u);
+            PolicyDecision dec;
+            if constexpr (KT == 0) {
+                dec = policy_decide<ATC_POLICY_IN>(pw, zk, x, seed, decision0 + blk, dl.i, (pflags & ATC_POLICY_DETERMINISTIC) != 0u);
+            } else {
+                // ---- the traffic query on the state the env is in now: what step b hold - 1 left, or the fresh spawn after an auto-reset ----
+                const PolicyTrafficTail tt = kernarg_reread<PolicyTrafficTail>(offsetof(PolicyTrafficArgs, tt), zk);
+                int phi = ls.a.phi;
+                if (ATC_RARE(is_wide(phi))) phi = phi_wrap(*at<double>(wide_base<false>(st.phi_wide, zk), dl.i * 32u));   // the exact counts, as the step reads them
+                const TrafficSelf me = traffic_self(ls.a.x, ls.a.y, ls.a.h, phi, ls.a.v, tt.tq);
+                const bool under = dl.lane_valid && ((dl.k < 32 ? ((uint32_t)es.amask >> dl.k) : ((uint32_t)(es.amask >> 32) >> (dl.k - 32))) & 1u);
+                const int tag = under ? dl.k : -1;
+                uint64_t best[KT];
+                if constexpr (W >= 32) {
+                    float* sl = reinterpret_cast<float*>(pos) + 8 * (dl.tid & ~63);   // this wavefront's quarter: [64] x | [64] y | [64] tag
+                    sl[dl.lane] = me.x;
+                    sl[64 + dl.lane] = me.y;
+                    reinterpret_cast<int*>(sl)[128 + dl.lane] = tag;
+                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                    __builtin_amdgcn_wave_barrier();
+                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                    const int gb = dl.lane & ~(W - 1);
+                    traffic_select<W, KT>(best, me.x, me.y, tag, dl.k, N, sl + gb, sl + 64 + gb, reinterpret_cast<const int*>(sl) + 128 + gb);
+                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");   // (the reads above, before the next step's pair scan stages over them)
+                    __builtin_amdgcn_wave_barrier();
+                } else {
+                    traffic_select<W, KT>(best, me.x, me.y, tag, dl.k, N, nullptr, nullptr, nullptr);
+                }
+                constexpr int IN = ATC_POLICY_TRAFFIC_IN(KT);
+                float xin[IN];
+#pragma unroll
+                for (int c = 0; c < ATC_OBS_DIM; ++c) xin[c] = x[c];
+                float4* dst = reinterpret_cast<float4*>(tt.traffic + ((size_t)blk * BN + dl.i) * (size_t)(KT * ATC_TRAFFIC_DIM));   // (64-bit: 32 K bytes per aircraft)
+#pragma unroll
+                for (int r = 0; r < KT; ++r) {
+                    float4 ra, rb;
+                    traffic_record<W>(best[r], under, dl.lane, me, tt.tq, ra, rb);
+                    if (tt.traffic && dl.lane_valid) {
+                        dst[2 * r] = ra;
+                        dst[2 * r + 1] = rb;
+                    }
+                    float* xr = xin + ATC_OBS_DIM + 7 * r;   // words 0..6: word 7 (the slot) is stored, not an input
+                    xr[0] = ra.x; xr[1] = ra.y; xr[2] = ra.z; xr[3] = ra.w;
+                    xr[4] = rb.x; xr[5] = rb.y; xr[6] = rb.z;
+                }
+                dec = policy_decide<IN>(pw, zk, xin, seed, decision0 + blk, dl.i, (pflags & ATC_POLICY_DETERMINISTIC) != 0u);
+            }
             if (dl.lane_valid) {
                 *at<Float3>(action + (size_t)blk * BN * 3u, times12(dl.i)) = dec.u;
                 if (logp) *at<float>(logp + (size_t)blk * BN, dl.i * 4u) = dec.logp;
@@ -234,4 +322,21 @@ k_rollout_policy(const float* __restrict__ blob, int off_grid, int B, int N, int
     const atc_state_t st_end = kernarg_reread<atc_state_t>(offsetof(StepArgs, st), opaque_zero());
     store_lane_state(st_end, d, ls, true);
     store_env_state<W>(st_end, d, es, hi0);
+}
+
+template <int W>
+__global__ void __launch_bounds__(kBlock, ATC_POLICY_WAVES)
+k_rollout_policy(const float* __restrict__ blob, int off_grid, int B, int N, int T, int hold, atc_state_t st, const float* __restrict__ obs0,
+                 atc_out_t out, atc_params_t p, StepDerived q, const float* __restrict__ pw, uint64_t seed, uint32_t decision0, uint32_t pflags,
+                 float* __restrict__ action, float* __restrict__ logp) {
+    rollout_policy_body<W, 0>(blob, off_grid, B, N, T, st, obs0, p, q, pw, seed, decision0, pflags, action, logp);   // (hold, out: kernarg re-reads)
+}
+
+// KT: the compiled list length = atc_policy_traffic_t.traffic_k (1, 2, 4)
+template <int W, int KT>
+__global__ void __launch_bounds__(kBlock, ATC_POLICY_WAVES)
+k_rollout_policy_traffic(const float* __restrict__ blob, int off_grid, int B, int N, int T, int hold, atc_state_t st, const float* __restrict__ obs0,
+                         atc_out_t out, atc_params_t p, StepDerived q, const float* __restrict__ pw, uint64_t seed, uint32_t decision0, uint32_t pflags,
+                         float* __restrict__ action, float* __restrict__ logp, PolicyTrafficTail tt) {
+    rollout_policy_body<W, KT>(blob, off_grid, B, N, T, st, obs0, p, q, pw, seed, decision0, pflags, action, logp);   // (tt: a kernarg re-read at the decision)
 }

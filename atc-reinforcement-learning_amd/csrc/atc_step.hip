@@ -1734,7 +1734,7 @@ k_serve(const float* __restrict__ blob, int off_grid, atc_state_t st, atc_out_t 
 #include "atc_plan_refit.inc"    // k_plan_refit (atc_plan_refit)
 #include "atc_plan_score.inc"    // k_plan_score (atc_plan_score)
 #include "atc_branch.inc"        // k_branch (atc_branch), k_select (atc_state_select)
-#include "atc_policy.inc"        // k_rollout_policy (atc_rollout_policy)
+#include "atc_policy.inc"        // k_rollout_policy (atc_rollout_policy), k_rollout_policy_traffic (atc_rollout_policy_traffic)
 
 // ---------------------------------------------------------------------------------------------------------------
 // host side of the C-ABI
@@ -1762,11 +1762,13 @@ static size_t lds_bytes(const atc_scenario*, bool pair_scan, bool step_kernel = 
 // the launch records (include/atc_step.h: the atc_*_launch_counts getters): launches made by the calling thread, every record's
 // counters in one table — plain thread-local counters that nothing in the library reads back.  REC_STEP has a slot for each k_step
 // instantiation and one for k_serve starts; a record of 7 slots counts by lane-group width (slot = log2(W)); a record of one slot
-// counts its entry point's launches.  A call moves its own record only.
-enum Record { REC_STEP, REC_SKIP, REC_TRAFFIC, REC_LOOKAHEAD, REC_PLAN, REC_PLAN_SAMPLED, REC_PLAN_DRAW, REC_PLAN_REFIT, REC_PLAN_SCORE, REC_BRANCH, REC_SELECT, REC_POLICY, REC_COUNT };
+// counts its entry point's launches; REC_POLICY_TRAFFIC counts by width and list length (slot = 3 log2(W) + log2(K)).  A call moves its
+// own record only.
+enum Record { REC_STEP, REC_SKIP, REC_TRAFFIC, REC_LOOKAHEAD, REC_PLAN, REC_PLAN_SAMPLED, REC_PLAN_DRAW, REC_PLAN_REFIT, REC_PLAN_SCORE, REC_BRANCH, REC_SELECT, REC_POLICY, REC_POLICY_TRAFFIC, REC_COUNT };
 constexpr int kRecordSlots[REC_COUNT] = {ATC_LAUNCH_SLOTS, ATC_SKIP_LAUNCH_SLOTS, ATC_TRAFFIC_LAUNCH_SLOTS, ATC_LOOKAHEAD_LAUNCH_SLOTS, ATC_PLAN_LAUNCH_SLOTS,
                                          ATC_PLAN_SAMPLED_LAUNCH_SLOTS, ATC_PLAN_DRAW_LAUNCH_SLOTS, ATC_PLAN_REFIT_LAUNCH_SLOTS, ATC_PLAN_SCORE_LAUNCH_SLOTS,
-                                         ATC_BRANCH_LAUNCH_SLOTS, ATC_SELECT_LAUNCH_SLOTS, ATC_ROLLOUT_POLICY_LAUNCH_SLOTS};
+                                         ATC_BRANCH_LAUNCH_SLOTS, ATC_SELECT_LAUNCH_SLOTS, ATC_ROLLOUT_POLICY_LAUNCH_SLOTS,
+                                         ATC_ROLLOUT_POLICY_TRAFFIC_LAUNCH_SLOTS};
 constexpr int record_offset(int id) {
     int o = 0;
     for (int i = 0; i < id; ++i) o += kRecordSlots[i];
@@ -1937,6 +1939,19 @@ static int launch_skip(const atc_scenario* s, int B, int N, int K, const atc_sta
 }
 
 // ---- traffic observation (include/atc_step.h: atc_observe_traffic) -------------------------------------------------------------
+// the uniform terms of a traffic query (TrafficArgs): atc_observe_traffic's, and the policy rollout's that takes the query inside its launch
+static TrafficArgs traffic_common(const atc_scenario* s, const atc_params_t* p, int K) {
+    TrafficArgs q;
+    q.pos_inv = (double)s->consts[ATC_C_POS_INV];
+    q.x0 = (double)s->consts[ATC_C_POS_X0];
+    q.y0 = (double)s->consts[ATC_C_POS_Y0];
+    const bool nrm = (p->mode & ATC_M_NORMALIZE) != 0;
+    q.s_pos = nrm ? 1.0f / s->consts[ATC_C_WORLD_DIAG] : 1.0f;
+    q.h_div = nrm ? s->consts[ATC_C_H_MAX] : 1.0f;
+    q.s_v = nrm ? 1.0f / (2.0f * s->consts[ATC_C_V_MAX]) : 1.0f;
+    q.K = K;
+    return q;
+}
 template <int W, int KT>
 static int launch_traffic2(int B, int N, const atc_state_t* st, float* traffic, const TrafficArgs& q, hipStream_t stream) {
     hipLaunchKernelGGL((k_traffic<W, KT>), dim3(step_grid(B, W)), dim3(kBlock), 0, stream, B, N, *st, traffic, q);
@@ -2108,23 +2123,97 @@ static bool states_overlap(const atc_state_t* a, unsigned long long Ba, const at
     return false;
 }
 
-// ---- policy rollout (include/atc_step.h: atc_rollout_policy) ---------------------------------------------------------------------
-template <int W>
-static int launch_policy(const atc_scenario* s, int B, int N, int T, int hold, const atc_state_t* st, const float* obs0, const atc_policy_t* pol,
-                         const atc_policy_out_t* o, const atc_params_t* p, hipStream_t stream) {
-    const size_t lds = lds_bytes(s, W >= 32, true);
-    const int grid = step_grid(B, W);
-    const StepDerived& q = derive(*p, s, 0);
+// ---- policy rollout (include/atc_step.h: atc_rollout_policy, atc_rollout_policy_traffic) ----------------------------------------------
+// the kernels' atc_out_t from the four step outputs atc_policy_out_t and atc_policy_traffic_out_t name alike
+template <typename O>
+static atc_out_t policy_out(const O* o) {
     atc_out_t out;
     memset(&out, 0, sizeof(out));
     out.obs = o->obs;
     out.reward = o->reward;
     out.done = o->done;
     out.flags = o->flags;
-    hipLaunchKernelGGL((k_rollout_policy<W>), dim3(grid), dim3(kBlock), lds, stream, s->d_blob, s->off_grid, B, N, T, hold, *st, obs0, out, *p, q, pol->w, pol->seed,
+    return out;
+}
+template <int W>
+static int launch_policy(const atc_scenario* s, int B, int N, int T, int hold, const atc_state_t* st, const float* obs0, const atc_policy_t* pol,
+                         const atc_policy_out_t* o, const atc_params_t* p, hipStream_t stream) {
+    const size_t lds = lds_bytes(s, W >= 32, true);
+    const int grid = step_grid(B, W);
+    const StepDerived& q = derive(*p, s, 0);
+    hipLaunchKernelGGL((k_rollout_policy<W>), dim3(grid), dim3(kBlock), lds, stream, s->d_blob, s->off_grid, B, N, T, hold, *st, obs0, policy_out(o), *p, q, pol->w, pol->seed,
                        pol->decision0, pol->flags, o->action, o->logp);
     HIP_TRY(hipGetLastError());
     ++record(REC_POLICY)[__builtin_ctz(W)];
+    return ATC_OK;
+}
+template <int W, int KT>
+static int launch_policy_traffic2(const atc_scenario* s, int B, int N, int T, int hold, const atc_state_t* st, const float* obs0, const atc_policy_traffic_t* pol,
+                                  const atc_policy_traffic_out_t* o, const atc_params_t* p, hipStream_t stream) {
+    const size_t lds = lds_bytes(s, W >= 32, true);   // (W >= 32: the selection borrows the pair-scan staging area between steps)
+    const int grid = step_grid(B, W);
+    const StepDerived& q = derive(*p, s, 0);
+    const PolicyTrafficTail tt = {traffic_common(s, p, KT), o->traffic};
+    hipLaunchKernelGGL((k_rollout_policy_traffic<W, KT>), dim3(grid), dim3(kBlock), lds, stream, s->d_blob, s->off_grid, B, N, T, hold, *st, obs0, policy_out(o), *p, q, pol->w,
+                       pol->seed, pol->decision0, pol->flags, o->action, o->logp, tt);
+    HIP_TRY(hipGetLastError());
+    ++record(REC_POLICY_TRAFFIC)[3 * __builtin_ctz(W) + __builtin_ctz(KT)];
+    return ATC_OK;
+}
+template <int W>
+static int launch_policy_traffic(const atc_scenario* s, int B, int N, int T, int hold, const atc_state_t* st, const float* obs0, const atc_policy_traffic_t* pol,
+                                 const atc_policy_traffic_out_t* o, const atc_params_t* p, hipStream_t stream) {
+    if (pol->traffic_k == 1) return launch_policy_traffic2<W, 1>(s, B, N, T, hold, st, obs0, pol, o, p, stream);
+    if (pol->traffic_k == 2) return launch_policy_traffic2<W, 2>(s, B, N, T, hold, st, obs0, pol, o, p, stream);
+    return launch_policy_traffic2<W, 4>(s, B, N, T, hold, st, obs0, pol, o, p, stream);
+}
+
+// The argument checks of both policy rollouts, in the header's order.  `out_type` names the output struct in the refusals; traffic_k is
+// null for atc_rollout_policy, and `traffic` is atc_policy_traffic_out_t.traffic (its range joins the overlap rule).
+template <typename P, typename O>
+static int check_policy_call(const atc_scenario_t* s, int B, int N, int T, int hold, const atc_state_t* st, const float* obs0, const P* pol, const O* out,
+                             const atc_params_t* p, const char* pol_type, const char* out_type, const int32_t* traffic_k, const float* traffic) {
+    char msg[160];
+    // T and hold first, before any pointer is looked at
+    if (T < 1 || hold < 1) return fail_arg("need T >= 1 and hold >= 1");
+    if (T % hold != 0) return fail_arg("T must be a multiple of hold (the launch takes T / hold decisions)");
+    if (!pol) {
+        snprintf(msg, sizeof msg, "null pointer: pol (%s) is required", pol_type);
+        return fail_arg(msg);
+    }
+    if (const int rc = check_required({{pol->w, "null pointer: pol->w (the policy's weights) is required"}, {obs0, "null pointer: obs0 is required"}})) return rc;
+    if (!out) {
+        snprintf(msg, sizeof msg, "null pointer: out (%s) is required", out_type);
+        return fail_arg(msg);
+    }
+    if (!out->obs || !out->reward || !out->done || !out->flags) {
+        snprintf(msg, sizeof msg, "null pointer: %s.obs, .reward, .done and .flags are required", out_type);
+        return fail_arg(msg);
+    }
+    if (!out->action) {
+        snprintf(msg, sizeof msg, "null pointer: %s.action is required", out_type);
+        return fail_arg(msg);
+    }
+    if (pol->n_hidden != ATC_POLICY_HIDDEN) return fail_arg("pol->n_hidden must be 64 (ATC_POLICY_HIDDEN)");
+    if (traffic_k && *traffic_k != 1 && *traffic_k != 2 && *traffic_k != 4) return fail_arg("pol->traffic_k must be 1, 2 or 4 (the compiled list lengths)");
+    if (pol->flags & ~ATC_POLICY_DETERMINISTIC) return fail_arg("pol->flags has unknown bits (ATC_POLICY_DETERMINISTIC or 0)");
+    if (const int rc = check_env_args(s, B, N, st, p)) return rc;
+    if (const int rc = check_dt(s, p)) return rc;
+    if (p->mode & ATC_M_DISCRETE) return fail_arg("ATC_M_DISCRETE: a Gaussian policy draws the continuous action space only");
+    if (p->mode & ATC_M_ACTIONS_HELD) return fail_arg("ATC_M_ACTIONS_HELD is for atc_step only: every block's first step carries a fresh decision");
+    const uintptr_t bn = (uintptr_t)B * (uintptr_t)N, row = bn * (ATC_OBS_DIM * 4u);
+    const ByteRange ranges[2] = {{obs0, row, "obs0"}, {out->obs, row * (uintptr_t)T, "out->obs"}};
+    if (const int rc = check_disjoint(ranges, 2, {}, "decision 0 reads obs0 while the steps write out->obs")) return rc;
+    if (traffic) {   // ... and the records written at every decision: against what the launch reads or writes next to them
+        const ByteRange tr = {traffic, (uintptr_t)(T / hold) * bn * (uintptr_t)*traffic_k * (ATC_TRAFFIC_DIM * 4u), "out->traffic"};
+        const ByteRange others[8] = {ranges[0], ranges[1], {st->ac, bn * 16u, "st->ac"}, {st->alt, bn * 8u, "st->alt"}, {st->last_act, bn * 16u, "st->last_act"},
+                                     {st->env, (uintptr_t)B * (ATC_ENV_WORDS * 4u), "st->env"}, {st->stats, (uintptr_t)B * (ATC_STAT_WORDS * 4u), "st->stats"},
+                                     {st->phi_wide, bn * 32u, "st->phi_wide"}};
+        for (const ByteRange& o : others) {
+            const ByteRange pair[2] = {tr, o};
+            if (const int rc = check_disjoint(pair, 2, {}, "the records are written while the launch reads and writes the other")) return rc;
+        }
+    }
     return ATC_OK;
 }
 

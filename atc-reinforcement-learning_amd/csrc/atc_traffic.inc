@@ -1,7 +1,8 @@
 // atc_traffic.inc — k_traffic, the kernel of atc_observe_traffic (include/atc_step.h: "Traffic observation"): for every aircraft the
 // K nearest other aircraft under control in its env, nearest first, as 8-word records in the observing aircraft's own frame.
 // Included by atc_step.hip next to atc_aux_kernels.inc (one translation unit, the per-lane device functions of atc_device.h and the
-// DPP helpers of atc_wave.h).  Reads state only; the step kernels know nothing of it.
+// DPP helpers of atc_wave.h).  Reads state only; the step kernels know nothing of it.  The arithmetic behind its loads (traffic_self,
+// traffic_select, traffic_record) is shared with k_rollout_policy_traffic (atc_policy.inc), which evaluates it on the state in registers.
 //
 // Mapping: one lane per aircraft slot, groups of W = next_pow2(N) lanes per env, 256 slots per workgroup — k_step's.  An env never
 // straddles a wavefront (W <= 64), so every partner of a lane lives in its own wavefront:
@@ -89,48 +90,36 @@ struct TrafficRow16<KT, 16> {
     static __device__ __forceinline__ void run(uint64_t (&)[KT], float, float, int) {}
 };
 
+// ---- the arithmetic behind the loads, shared by k_traffic and k_rollout_policy_traffic (atc_policy.inc): the file is built with
+// -ffp-contract=off, so both callers produce the same bits ---------------------------------------------------------------------------
+struct TrafficSelf {      // what a lane offers its partners and rotates their records with
+    float x, y, h, vx, vy, sn, cs;
+};
+// from the state words of one aircraft; `phi` is the heading's counts, a WIDE one already wrapped (phi_wrap of the side record)
+__device__ __forceinline__ TrafficSelf traffic_self(int px, int py, double alt, int phi, uint32_t v_fix, const TrafficArgs& q) {
+    TrafficSelf me;
+    me.x = (float)__builtin_fma((double)px, q.pos_inv, q.x0);
+    me.y = (float)__builtin_fma((double)py, q.pos_inv, q.y0);
+    me.h = (float)alt;
+    heading_sincos(phi, me.sn, me.cs);
+    const float v = v_real(v_fix);
+    me.vx = v * me.sn;
+    me.vy = v * me.cs;
+    return me;
+}
+
+// selection: the KT best keys of lane k (tag = k under control, -1 otherwise) over the other slots of its group of W lanes.  W >= 32
+// reads the partners from LDS: sx / sy / stag point at the GROUP's first slot, written by every lane of the group and ordered by the
+// caller (k_traffic: a workgroup barrier; the policy rollout: wave-level waits on its wavefront's own slice); unused below 32.
 template <int W, int KT>
-__global__ void __launch_bounds__(kBlock)
-k_traffic(int B, int N, atc_state_t st, float* __restrict__ traffic, TrafficArgs q) {
-    const int tid = threadIdx.x, lane = tid & 63;
-    const uint32_t slot = blockIdx.x * (uint32_t)kBlock + (uint32_t)tid;
-    const int k = (int)(slot % W);
-    const bool env_valid = slot < (uint32_t)B * (uint32_t)W;
-    const int e = env_valid ? (int)(slot / W) : B - 1;   // clamped: loads stay in bounds, nothing is stored
-    const bool lane_valid = env_valid && k < N;
-    const uint32_t i = lane_valid ? (uint32_t)e * (uint32_t)N + (uint32_t)k : (uint32_t)B * (uint32_t)N - 1u;
-
-    const int4 ps = reinterpret_cast<const int4*>(st.ac)[i];
-    const double alt = st.alt[i];
-    uint32_t mask = (uint32_t)st.env[(size_t)e * ATC_ENV_WORDS + ATC_ENV_MASK_LO];
-    if (W == 64 && k >= 32) mask = (uint32_t)st.stats[(size_t)e * ATC_STAT_WORDS + ATC_STAT_MASK_HI];
-    const bool active = lane_valid && ((mask >> (k & 31)) & 1u);
-
-    const float x = (float)__builtin_fma((double)ps.x, q.pos_inv, q.x0), y = (float)__builtin_fma((double)ps.y, q.pos_inv, q.y0);
-    const float h = (float)alt;
-    int phi = ps.z;
-    if (is_wide(phi)) phi = phi_wrap(st.phi_wide[4 * (size_t)i]);   // (include/atc_step.h, ABI 19: the exact counts are in the side record)
-    float sn, cs;
-    heading_sincos(phi, sn, cs);
-    const float v = v_real((uint32_t)ps.w);
-    const float vx = v * sn, vy = v * cs;
-    const int tag = active ? k : -1;
-
-    // ---- selection ------------------------------------------------------------------------------------------------------
-    uint64_t best[KT];
+__device__ __forceinline__ void traffic_select(uint64_t (&best)[KT], float x, float y, int tag, int k, int N, const float* sx, const float* sy,
+                                               const int* stag) {
 #pragma unroll
     for (int r = 0; r < KT; ++r) best[r] = kTrafficNone;
     if constexpr (W >= 32) {
-        __shared__ float sx[kBlock], sy[kBlock];
-        __shared__ int stag[kBlock];
-        sx[tid] = x;
-        sy[tid] = y;
-        stag[tid] = tag;
-        __syncthreads();
-        const int base = tid & ~(W - 1);
         for (int j = 0; j < N; ++j) {
-            const int pt = stag[base + j];
-            traffic_offer<KT>(best, x, y, sx[base + j], sy[base + j], pt == k ? -1 : pt);
+            const int pt = stag[j];
+            traffic_offer<KT>(best, x, y, sx[j], sy[j], pt == k ? -1 : pt);
         }
     } else if constexpr (W == 16) {
         TrafficRow16<KT, 1>::run(best, x, y, tag);
@@ -150,29 +139,74 @@ k_traffic(int B, int N, atc_state_t st, float* __restrict__ traffic, TrafficArgs
             traffic_offer_dpp<KT, X1>(best, x, y, mx, my, mt);    // k ^ 6
         }
     }
+}
+
+// features: the record of one kept key — the winner's (x, y, h, vx, vy) fetched by lane index from its group (every lane of the wavefront
+// calls this together) and rotated into the observer's frame; `a` words 0..3, `b` words 4..7
+template <int W>
+__device__ __forceinline__ void traffic_record(uint64_t key, bool active, int lane, const TrafficSelf& me, const TrafficArgs& q, float4& a, float4& b) {
+    const bool present = active && key != kTrafficNone;
+    const int j = (int)((uint32_t)key & (uint32_t)(W - 1));
+    const int src = (lane & ~(W - 1)) + j;
+    const float xj = __shfl(me.x, src, 64), yj = __shfl(me.y, src, 64), hj = __shfl(me.h, src, 64);
+    const float vxj = __shfl(me.vx, src, 64), vyj = __shfl(me.vy, src, 64);
+    const float dx = xj - me.x, dy = yj - me.y;
+    const float d = sqrtf(__uint_as_float((uint32_t)(key >> 32)));
+    const float ahead = dx * me.sn + dy * me.cs, right = dx * me.cs - dy * me.sn;
+    const float dh = hj - me.h;
+    const float dvx = vxj - me.vx, dvy = vyj - me.vy;
+    const float dva = dvx * me.sn + dvy * me.cs, dvr = dvx * me.cs - dvy * me.sn;
+    a = make_float4(1.0f, d * q.s_pos, ahead * q.s_pos, right * q.s_pos);
+    b = make_float4(dh / q.h_div, dva * q.s_v, dvr * q.s_v, (float)j);
+    if (!present) {
+        a = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        b = make_float4(0.0f, 0.0f, 0.0f, -1.0f);
+    }
+}
+
+template <int W, int KT>
+__global__ void __launch_bounds__(kBlock)
+k_traffic(int B, int N, atc_state_t st, float* __restrict__ traffic, TrafficArgs q) {
+    const int tid = threadIdx.x, lane = tid & 63;
+    const uint32_t slot = blockIdx.x * (uint32_t)kBlock + (uint32_t)tid;
+    const int k = (int)(slot % W);
+    const bool env_valid = slot < (uint32_t)B * (uint32_t)W;
+    const int e = env_valid ? (int)(slot / W) : B - 1;   // clamped: loads stay in bounds, nothing is stored
+    const bool lane_valid = env_valid && k < N;
+    const uint32_t i = lane_valid ? (uint32_t)e * (uint32_t)N + (uint32_t)k : (uint32_t)B * (uint32_t)N - 1u;
+
+    const int4 ps = reinterpret_cast<const int4*>(st.ac)[i];
+    const double alt = st.alt[i];
+    uint32_t mask = (uint32_t)st.env[(size_t)e * ATC_ENV_WORDS + ATC_ENV_MASK_LO];
+    if (W == 64 && k >= 32) mask = (uint32_t)st.stats[(size_t)e * ATC_STAT_WORDS + ATC_STAT_MASK_HI];
+    const bool active = lane_valid && ((mask >> (k & 31)) & 1u);
+
+    int phi = ps.z;
+    if (is_wide(phi)) phi = phi_wrap(st.phi_wide[4 * (size_t)i]);   // (include/atc_step.h, ABI 19: the exact counts are in the side record)
+    const TrafficSelf me = traffic_self(ps.x, ps.y, alt, phi, (uint32_t)ps.w, q);
+    const int tag = active ? k : -1;
+
+    // ---- selection ------------------------------------------------------------------------------------------------------
+    uint64_t best[KT];
+    if constexpr (W >= 32) {
+        __shared__ float sx[kBlock], sy[kBlock];
+        __shared__ int stag[kBlock];
+        sx[tid] = me.x;
+        sy[tid] = me.y;
+        stag[tid] = tag;
+        __syncthreads();
+        const int base = tid & ~(W - 1);
+        traffic_select<W, KT>(best, me.x, me.y, tag, k, N, sx + base, sy + base, stag + base);
+    } else {
+        traffic_select<W, KT>(best, me.x, me.y, tag, k, N, nullptr, nullptr, nullptr);
+    }
 
     // ---- features and store -------------------------------------------------------------------------------------------------
     float4* dst = reinterpret_cast<float4*>(traffic + (size_t)i * (size_t)q.K * ATC_TRAFFIC_DIM);
-    const int group = lane & ~(W - 1);
 #pragma unroll
     for (int r = 0; r < KT; ++r) {
-        const bool present = active && best[r] != kTrafficNone;
-        const int j = (int)((uint32_t)best[r] & (uint32_t)(W - 1));
-        const int src = group + j;
-        const float xj = __shfl(x, src, 64), yj = __shfl(y, src, 64), hj = __shfl(h, src, 64);
-        const float vxj = __shfl(vx, src, 64), vyj = __shfl(vy, src, 64);
-        const float dx = xj - x, dy = yj - y;
-        const float d = sqrtf(__uint_as_float((uint32_t)(best[r] >> 32)));
-        const float ahead = dx * sn + dy * cs, right = dx * cs - dy * sn;
-        const float dh = hj - h;
-        const float dvx = vxj - vx, dvy = vyj - vy;
-        const float dva = dvx * sn + dvy * cs, dvr = dvx * cs - dvy * sn;
-        float4 a = make_float4(1.0f, d * q.s_pos, ahead * q.s_pos, right * q.s_pos);
-        float4 b = make_float4(dh / q.h_div, dva * q.s_v, dvr * q.s_v, (float)j);
-        if (!present) {
-            a = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-            b = make_float4(0.0f, 0.0f, 0.0f, -1.0f);
-        }
+        float4 a, b;
+        traffic_record<W>(best[r], active, lane, me, q, a, b);
         if (lane_valid && r < q.K) {
             if (ATC_TRAFFIC_NT_STORES) {
                 typedef float v4f __attribute__((ext_vector_type(4)));

@@ -1061,6 +1061,55 @@ int atc_rollout_policy(const atc_scenario_t* s, int B, int N, int T, int hold, c
 enum { ATC_ROLLOUT_POLICY_LAUNCH_SLOTS = 7 };
 int atc_rollout_policy_launch_counts(uint64_t* out, int n);
 
+/* POLICY ROLLOUT WITH TRAFFIC (extension): atc_rollout_policy whose policy also sees the traffic observation — the multi-aircraft
+ * envs punish lost separation that none of the ten own words shows.  The traffic query of atc_observe_traffic(K) is evaluated INSIDE the
+ * launch, at every decision, on the state the loop holds; it feeds a wider first layer, IN -> 64 -> 64 -> 3 with IN = 10 + 7 K
+ * (ATC_POLICY_TRAFFIC_IN), and the records each decision saw are stored so that a trainer can recompute logp in its update.
+ * K = traffic_k is 1, 2 or 4 (the compiled list lengths).  The weights are ONE device array of ATC_POLICY_TRAFFIC_WORDS(K) = 4422 + 64 IN
+ * floats (5510, 5958, 6854), laid out exactly like ATC_POLICY_WORDS with W1[64][IN] row-major.
+ * INPUT ROW.  Aircraft slot i at decision b sees  x = [ own ten words | record 0 words 0..6 | ... | record K-1 words 0..6 ]:
+ *   - the own words are exactly atc_rollout_policy's: obs0 for b = 0, the observation step b*hold - 1 stored otherwise;
+ *   - the records are exactly what atc_observe_traffic(K) returns for the state the env is in when the decision is taken: the state at
+ *     launch for b = 0, otherwise the state step b*hold - 1 left — the fresh spawn after an auto-reset (the convention of
+ *     AtcVecEnv's info["traffic"]); normalised or not per ATC_M_NORMALIZE, like the own words;
+ *   - word 7 of a record (the slot) is stored but is not an input.
+ * THE TRAFFIC HALF IS EXACT.  out->traffic[b] equals atc_observe_traffic(K) on that state bit for bit: selection by
+ * (bits(d^2) << 32 | slot), ABSENT ranks, WIDE headings wrapped — everything stated under TRAFFIC OBSERVATION.
+ * EVERYTHING ELSE is atc_rollout_policy's contract, unchanged: the same key, Box-Muller and logp; action is the unclamped sample; the
+ * dynamics are atc_rollout_hold on the clamped actions bit for bit; two launches of T / 2 with decision0 += T / (2 hold) and obs0
+ * chained reproduce one launch of T bit for bit, `traffic` included.
+ * FLOAT64 LAYER 1.  A wavefront that holds an input above 4 in magnitude, or a NaN, sums layer 1 in float64; the rule is applied over
+ * the whole widened row, so unnormalised records (nm, ft, kt) take it.
+ * ATC_ERR_ARG: the refusals of atc_rollout_policy in its order; traffic_k outside {1, 2, 4} is refused behind n_hidden, naming the
+ * field; the overlap rule also refuses out->traffic (T/hold * B*N*K*32 bytes) sharing memory with obs0, out->obs or one of the six
+ * state arrays.
+ * Counted by atc_rollout_policy_traffic_launch_counts only: slot = 3 log2(W) + log2(K). */
+#define ATC_POLICY_TRAFFIC_IN(K) (10 + 7 * (K))                  /* own row + words 0..6 of K records */
+#define ATC_POLICY_TRAFFIC_WORDS(K) (4422 + 64 * ATC_POLICY_TRAFFIC_IN(K))
+typedef struct atc_policy_traffic {
+    const float* w;      /* device, ATC_POLICY_TRAFFIC_WORDS(traffic_k) floats: W1[64][IN], b1[64], W2[64][64], b2[64], W3[3][64], b3[3], log_std[3] */
+    int32_t n_hidden;    /* must be ATC_POLICY_HIDDEN */
+    uint32_t flags;      /* ATC_POLICY_DETERMINISTIC or 0 */
+    uint64_t seed;
+    uint32_t decision0;  /* number of the launch's first decision */
+    uint32_t reserved;
+    int32_t traffic_k;   /* K: 1, 2 or 4 records per aircraft */
+} atc_policy_traffic_t;
+typedef struct atc_policy_traffic_out {
+    float* obs;          /* [T][B*N*10]     required: atc_rollout's per-step outputs */
+    float* reward;       /* [T][B]          required */
+    uint8_t* done;       /* [T][B]          required */
+    uint16_t* flags;     /* [T][B*N]        required */
+    float* action;       /* [T/hold][B*N*3] required: the UNCLAMPED sample u */
+    float* logp;         /* [T/hold][B*N]   nullable */
+    float* traffic;      /* [T/hold][B*N*K*8] nullable: the records decision b saw, in atc_observe_traffic's layout */
+} atc_policy_traffic_out_t;
+int atc_rollout_policy_traffic(const atc_scenario_t* s, int B, int N, int T, int hold, const atc_state_t* st,
+                               const float* obs0 /* [B*N*10] */, const atc_policy_traffic_t* pol, const atc_policy_traffic_out_t* out,
+                               const atc_params_t* p, void* stream);
+enum { ATC_ROLLOUT_POLICY_TRAFFIC_LAUNCH_SLOTS = 21 };
+int atc_rollout_policy_traffic_launch_counts(uint64_t* out, int n);
+
 #ifdef __cplusplus
 }
 #endif
