@@ -113,6 +113,11 @@ ROLLOUT_POLICY_LAUNCH_SLOTS = 7
 POLICY_TRAFFIC_K = (1, 2, 4)
 POLICY_TRAFFIC_WORDS_PER_RECORD = 7
 ROLLOUT_POLICY_TRAFFIC_LAUNCH_SLOTS = 21
+# advantages and returns of a collection (include/atc_step.h: atc_gae): the two flags of atc_gae_t; at most GAE_MAX_NV value columns per env;
+# its own launch record, one slot
+GAE_PER_DECISION, GAE_REWARD_PER_COLUMN = 1, 2
+GAE_MAX_NV = 64
+GAE_LAUNCH_SLOTS = 1
 
 
 def policy_in(traffic=0):

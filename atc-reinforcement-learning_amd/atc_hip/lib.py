@@ -107,6 +107,22 @@ class AtcPolicyTrafficOut(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in POLICY_TRAFFIC_OUT_FIELDS]
 
 
+GAE_FIELDS = ("gamma", "lam", "flags", "_pad")
+
+
+class AtcGae(C.Structure):
+    """atc_gae_t"""
+    _fields_ = [("gamma", C.c_float), ("lam", C.c_float), ("flags", C.c_uint32), ("_pad", C.c_uint32)]
+
+
+GAE_OUT_FIELDS = ("adv", "ret", "block_reward", "block_done", "block_steps")
+
+
+class AtcGaeOut(C.Structure):
+    """atc_gae_out_t"""
+    _fields_ = [(n, C.c_void_p) for n in GAE_OUT_FIELDS]
+
+
 class AtcStepCall(C.Structure):
     """atc_step_call_t"""
     _fields_ = [("s", C.c_void_p), ("B", C.c_int32), ("N", C.c_int32), ("st", C.POINTER(AtcState)), ("actions", C.c_void_p),
@@ -122,7 +138,8 @@ EXPORTS = ("atc_abi_version", "atc_last_error", "atc_launch_counts", "atc_host_m
            "atc_branch", "atc_branch_launch_counts", "atc_state_select", "atc_select_launch_counts",
            "atc_plan_draw", "atc_lookahead_plan_sampled", "atc_plan_sampled_launch_counts", "atc_plan_draw_launch_counts",
            "atc_plan_refit", "atc_plan_refit_launch_counts", "atc_plan_score", "atc_plan_score_launch_counts",
-           "atc_rollout_policy", "atc_rollout_policy_launch_counts", "atc_rollout_policy_traffic", "atc_rollout_policy_traffic_launch_counts")
+           "atc_rollout_policy", "atc_rollout_policy_launch_counts", "atc_rollout_policy_traffic", "atc_rollout_policy_traffic_launch_counts",
+           "atc_gae", "atc_gae_launch_counts")
 
 def load():
     """Loads libatcstep.so; raises (never falls back) when it has not been built."""
@@ -176,6 +193,7 @@ def load():
     lib.atc_rollout_policy.argtypes = [vp, ci, ci, ci, ci, C.POINTER(AtcState), vp, C.POINTER(AtcPolicy), C.POINTER(AtcPolicyOut), C.POINTER(AtcParams), vp]
     lib.atc_rollout_policy_traffic.argtypes = [vp, ci, ci, ci, ci, C.POINTER(AtcState), vp, C.POINTER(AtcPolicyTraffic), C.POINTER(AtcPolicyTrafficOut),
                                                C.POINTER(AtcParams), vp]
+    lib.atc_gae.argtypes = [vp, ci, ci, ci, ci, vp, vp, vp, vp, C.POINTER(AtcGae), C.POINTER(AtcGaeOut), vp]
     for getter in LAUNCH_RECORDS:
         getattr(lib, getter).argtypes = [C.POINTER(C.c_uint64), ci]
     for name in EXPORTS:
@@ -224,6 +242,7 @@ LAUNCH_RECORDS = {
     "atc_select_launch_counts": (L.SELECT_LAUNCH_SLOTS, "select"),
     "atc_rollout_policy_launch_counts": (L.ROLLOUT_POLICY_LAUNCH_SLOTS, _width),
     "atc_rollout_policy_traffic_launch_counts": (L.ROLLOUT_POLICY_TRAFFIC_LAUNCH_SLOTS, _width_k),
+    "atc_gae_launch_counts": (L.GAE_LAUNCH_SLOTS, "gae"),
 }
 
 
@@ -313,6 +332,11 @@ def rollout_policy_traffic_launch_counts():
     """Launches of the policy rollout with traffic (atc_rollout_policy_traffic) made by the calling thread so far, by lane-group width and
     records per aircraft: {(16, 4): n, ...}, zero counts left out.  Separate from the other launch records, rollout_policy's included."""
     return _counts("atc_rollout_policy_traffic_launch_counts")
+
+
+def gae_launch_counts():
+    """Launches of the advantages and returns of a collection (atc_gae) made by the calling thread so far: {"gae": n}, or {} before the first."""
+    return _counts("atc_gae_launch_counts")
 
 
 def lookahead_set_mapping(candidates_per_workgroup=0):

@@ -1,0 +1,52 @@
+"""A PPO collection in three calls on fixed shapes: AtcVecEnv.rollout_policy (or rollout_policy_traffic) -> one value forward ->
+AtcVecEnv.gae.  The collection loop and the advantage recurrence each run inside one launch (include/atc_step.h: atc_rollout_policy,
+atc_gae); the value network is the trainer's own and runs as one batched forward over the rows the decisions saw.
+Not covered, the trainer's: bootstrapping a time-limit done (rollout_policy does not store the terminal observation), masking aircraft
+that are not under control, advantage normalisation."""
+from . import layout as L
+from . import policy as _policy
+
+
+def value_rows(env, rollout, obs0, hold=1, traffic=0):
+    """The value network's input, [D + 1, B, N, IN]: row d < D is the row decision d saw — obs0 for d = 0, the observation step
+    d * hold - 1 stored otherwise, widened by the stored traffic records with traffic=K (atc_hip.policy.input_rows) — and row D the last
+    stored observation, with traffic the records of the state the env is in NOW, obtained with observe_traffic()."""
+    torch = env.torch
+    obs = rollout["obs"]
+    T, B, N = int(obs.shape[0]), env.B, env.N
+    D = T // hold
+    own = torch.empty((D + 1, B, N, L.OBS_DIM), dtype=obs.dtype, device=obs.device)
+    own[0] = obs0.reshape(B, N, L.OBS_DIM)
+    own[1:] = obs.reshape(D, hold, B, N, L.OBS_DIM)[:, hold - 1]
+    if not traffic:
+        return own
+    records = torch.cat([rollout["traffic"], env.observe_traffic().reshape((1,) + tuple(rollout["traffic"].shape[1:]))], dim=0)
+    return _policy.input_rows(own, records)
+
+
+def collect(env, weights, value_fn, T, hold=1, traffic=0, gamma=0.99, lam=0.95, seed=0, decision0=0, obs0=None, per_decision=False):
+    """One on-policy collection of T steps, D = T // hold decisions, in three calls, in this order:
+      1. env.rollout_policy(weights, T, hold, seed, decision0, obs0=obs0) — env.rollout_policy_traffic with traffic=K;
+      2. values = value_fn(x): ONE forward over x = value_rows(...), [D + 1, B, N, IN] float32 with IN = 10 + 7 K — the stacked input
+         rows of the D decisions plus the last observation; it returns [D + 1, B, NV] or [D + 1, B] (made contiguous float32 here);
+      3. env.gae(reward, done, values, hold, gamma, lam, per_decision=per_decision).
+    With traffic=K the value input of rows 0 .. D - 1 is atc_hip.policy.input_rows of what the decisions saw; the final state's row takes
+    the own words of the last stored observation, and its traffic records are obtained with observe_traffic() on the state the rollout
+    left, so the env must have been made with AtcVecEnv(traffic=K); which of the columns the critic reads is value_fn's choice.
+    obs0 defaults to the env's bound observation tensor, as in rollout_policy; a copy is taken before the launch overwrites it.
+    Returns the rollout's dict plus "values", "adv", "ret", "block_reward", "block_done" and "block_steps" (AtcVecEnv.gae)."""
+    torch = env.torch
+    K = int(traffic)
+    if K and env.traffic_k != K:
+        raise ValueError("collect(traffic=%d) needs an env made with AtcVecEnv(traffic=%d): the last row's records come from observe_traffic()" % (K, K))
+    x0 = (env.obs if obs0 is None else obs0).clone()
+    if K:
+        out = env.rollout_policy_traffic(weights, T, K, hold=hold, seed=seed, decision0=decision0, obs0=x0)
+    else:
+        out = env.rollout_policy(weights, T, hold=hold, seed=seed, decision0=decision0, obs0=x0)
+    with torch.no_grad():
+        values = value_fn(value_rows(env, out, x0, hold=hold, traffic=K))
+    values = values.to(dtype=torch.float32).contiguous()
+    res = dict(out, values=values)
+    res.update(env.gae(out["reward"], out["done"], values, hold=hold, gamma=gamma, lam=lam, per_decision=per_decision))
+    return res

@@ -916,6 +916,73 @@ class AtcVecEnv:
         self._finish()
         return out
 
+    def gae(self, reward, done, values, hold=1, gamma=0.99, lam=0.95, *, per_decision=False, adv_next=None, out=None):
+        """Advantages and returns of a collection in one launch on this env's current stream (atc_gae, include/atc_step.h): what lies
+        between rollout_policy() plus one value forward and the update.  reward: [T, B] float32 and done: [T, B] uint8 as rollout_policy()
+        returns them, values: [D + 1, B, NV] float32 ([D + 1, B] means NV = 1) with T = D * hold — row d the value of the state decision d
+        was taken in, row D the value of the state after the last step; 1 <= NV <= 64.  All contiguous tensors on this env's device
+        (nothing is converted: ValueError otherwise).  reward [T, B, NV] gives every value column its own reward (a per-aircraft reward).
+        A decision's `hold` steps become ONE transition: R = r_0 + r_1 gamma + r_2 gamma^2 + ... (fp32, left to right, the discount a
+        running product) up to and including the block's first done — the steps behind it belong to the next episode and are not read
+        into anything — and the decisions are discounted with G = gamma^hold.  per_decision=True: R is the plain sum and G = gamma, what
+        a frame-skipping env in front of a trainer computes.  Then, d descending, with A_next = adv_next ([B, NV], default zeros):
+        a block that ended its episode has A = R - V[d], any other A = (R + G V[d+1]) - V[d] + (G lam) A_next; ret = A + V[d].
+        Returns {"adv", "ret": [D, B, NV] float32, "block_reward": [D, B] float32 ([D, B, NV] with a per-column reward), "block_done",
+        "block_steps": [D, B] uint8} (the [.., NV] axis is left out where values has none).  out: a dict with contiguous device tensors of
+        those names, shapes and dtypes to write into — "adv" and "ret" required, the three block outputs stored only where it names
+        them; with it the method allocates nothing.  No two of the tensors may share memory (refused by the library).  Two calls split
+        at D / 2, the later half first and its adv[0] as the earlier half's adv_next, equal one call bit for bit.
+        Not covered, the trainer's: bootstrapping a time-limit done (the terminal observation is not stored by rollout_policy), masking
+        aircraft that are not under control, advantage normalisation.  The method reads no action and no state."""
+        torch = self.torch
+        dev = self.device
+
+        def need(t, what, dtype, shapes):
+            if not (torch.is_tensor(t) and t.dtype == dtype and t.device == dev and t.is_contiguous() and tuple(t.shape) in shapes):
+                raise ValueError("%s must be a contiguous %s tensor of %s on %s" % (what, dtype, " or ".join(repr(s) for s in shapes), dev))
+            return t
+
+        hold = int(hold)
+        if not 1 <= hold <= L.SKIP_MAX:
+            raise ValueError("1 <= hold <= %d" % L.SKIP_MAX)
+        if not (torch.is_tensor(values) and values.dim() in (2, 3) and int(values.shape[0]) >= 2 and int(values.shape[1]) == self.B):
+            raise ValueError("values must be [D + 1, B, NV] or [D + 1, B] with D >= 1 and B = %d" % self.B)
+        D = int(values.shape[0]) - 1
+        NV = int(values.shape[2]) if values.dim() == 3 else 1
+        if not 1 <= NV <= L.GAE_MAX_NV:
+            raise ValueError("1 <= NV (values.shape[-1]) <= %d" % L.GAE_MAX_NV)
+        cols = tuple(values.shape[1:])
+        need(values, "values", torch.float32, [(D + 1,) + cols])
+        T = D * hold
+        if not torch.is_tensor(reward) or reward.dim() not in (2, 3):
+            raise ValueError("reward must be [T, B] or [T, B, NV]")
+        per_column = reward.dim() == 3
+        need(reward, "reward", torch.float32, [(T, self.B, NV)] if per_column else [(T, self.B)])
+        need(done, "done", torch.uint8, [(T, self.B)])
+        for name, v in (("gamma", gamma), ("lam", lam)):
+            with np.errstate(over="ignore"):
+                if not np.isfinite(np.float32(v)):
+                    raise ValueError("%s must be finite (in float32)" % name)
+        if adv_next is not None:
+            need(adv_next, "adv_next", torch.float32, [cols])
+        want = {"adv": (torch.float32, (D,) + cols), "ret": (torch.float32, (D,) + cols),
+                "block_reward": (torch.float32, (D,) + (cols if per_column else (self.B,))),
+                "block_done": (torch.uint8, (D, self.B)), "block_steps": (torch.uint8, (D, self.B))}
+        if out is None:
+            res = {n: torch.empty(shape, dtype=dt, device=dev) for n, (dt, shape) in want.items()}
+        else:
+            if not isinstance(out, dict) or not {"adv", "ret"} <= set(out) or not set(out) <= set(want):
+                raise ValueError("out must be a dict with adv and ret, and any of block_reward, block_done, block_steps")
+            res = {n: need(t, "out[%r]" % n, want[n][0], [want[n][1]]) for n, t in out.items()}
+        g = _lib.AtcGae(float(gamma), float(lam), (L.GAE_PER_DECISION if per_decision else 0) | (L.GAE_REWARD_PER_COLUMN if per_column else 0), 0)
+        o = _lib.AtcGaeOut(*[res[n].data_ptr() if n in res else None for n in _lib.GAE_OUT_FIELDS])
+        fn = self._lib.atc_gae
+        with torch.cuda.device(dev):
+            _lib.check(fn(self.sector.handle, self.B, NV, D, hold, reward.data_ptr(), done.data_ptr(), values.data_ptr(),
+                          None if adv_next is None else adv_next.data_ptr(), C.byref(g), C.byref(o), self._stream()))
+        self._keep_gae = (reward, done, values, adv_next)   # the inputs outlive the launch (like _keep_score)
+        return res
+
     def get_attr(self, name, indices=None):
         """VecEnv.get_attr for the attributes the reference's trainer reads (learning/atc-gym-stable-baselines.py:34,36)
         and the episode counters."""

@@ -1735,6 +1735,7 @@ k_serve(const float* __restrict__ blob, int off_grid, atc_state_t st, atc_out_t 
 #include "atc_plan_score.inc"    // k_plan_score (atc_plan_score)
 #include "atc_branch.inc"        // k_branch (atc_branch), k_select (atc_state_select)
 #include "atc_policy.inc"        // k_rollout_policy (atc_rollout_policy), k_rollout_policy_traffic (atc_rollout_policy_traffic)
+#include "atc_gae.inc"           // k_gae (atc_gae)
 
 // ---------------------------------------------------------------------------------------------------------------
 // host side of the C-ABI
@@ -1764,11 +1765,11 @@ static size_t lds_bytes(const atc_scenario*, bool pair_scan, bool step_kernel = 
 // instantiation and one for k_serve starts; a record of 7 slots counts by lane-group width (slot = log2(W)); a record of one slot
 // counts its entry point's launches; REC_POLICY_TRAFFIC counts by width and list length (slot = 3 log2(W) + log2(K)).  A call moves its
 // own record only.
-enum Record { REC_STEP, REC_SKIP, REC_TRAFFIC, REC_LOOKAHEAD, REC_PLAN, REC_PLAN_SAMPLED, REC_PLAN_DRAW, REC_PLAN_REFIT, REC_PLAN_SCORE, REC_BRANCH, REC_SELECT, REC_POLICY, REC_POLICY_TRAFFIC, REC_COUNT };
+enum Record { REC_STEP, REC_SKIP, REC_TRAFFIC, REC_LOOKAHEAD, REC_PLAN, REC_PLAN_SAMPLED, REC_PLAN_DRAW, REC_PLAN_REFIT, REC_PLAN_SCORE, REC_BRANCH, REC_SELECT, REC_POLICY, REC_POLICY_TRAFFIC, REC_GAE, REC_COUNT };
 constexpr int kRecordSlots[REC_COUNT] = {ATC_LAUNCH_SLOTS, ATC_SKIP_LAUNCH_SLOTS, ATC_TRAFFIC_LAUNCH_SLOTS, ATC_LOOKAHEAD_LAUNCH_SLOTS, ATC_PLAN_LAUNCH_SLOTS,
                                          ATC_PLAN_SAMPLED_LAUNCH_SLOTS, ATC_PLAN_DRAW_LAUNCH_SLOTS, ATC_PLAN_REFIT_LAUNCH_SLOTS, ATC_PLAN_SCORE_LAUNCH_SLOTS,
                                          ATC_BRANCH_LAUNCH_SLOTS, ATC_SELECT_LAUNCH_SLOTS, ATC_ROLLOUT_POLICY_LAUNCH_SLOTS,
-                                         ATC_ROLLOUT_POLICY_TRAFFIC_LAUNCH_SLOTS};
+                                         ATC_ROLLOUT_POLICY_TRAFFIC_LAUNCH_SLOTS, ATC_GAE_LAUNCH_SLOTS};
 constexpr int record_offset(int id) {
     int o = 0;
     for (int i = 0; i < id; ++i) o += kRecordSlots[i];
@@ -2085,7 +2086,7 @@ static int check_candidates(const atc_scenario_t* s, int B, int N, int K, const 
     return is_drawn ? check_continuous(p) : ATC_OK;
 }
 
-// ---- byte ranges that must not share memory (atc_plan_refit, atc_plan_score, atc_branch, atc_state_select) ----------------------
+// ---- byte ranges that must not share memory (atc_plan_refit, atc_plan_score, atc_branch, atc_state_select, atc_gae) ---------------------
 // Pointer VALUES only: nothing is dereferenced.  Ranges that only touch do not overlap.
 struct ByteRange { const void* ptr; uintptr_t bytes; const char* name; };
 static bool ranges_overlap(const ByteRange& a, const ByteRange& b) {

@@ -1110,6 +1110,72 @@ int atc_rollout_policy_traffic(const atc_scenario_t* s, int B, int N, int T, int
 enum { ATC_ROLLOUT_POLICY_TRAFFIC_LAUNCH_SLOTS = 21 };
 int atc_rollout_policy_traffic_launch_counts(uint64_t* out, int n);
 
+/* GAE (extension): what lies between the collection launch and the update of an on-policy trainer, in one launch — the per-step
+ * rewards and dones of a rollout (atc_rollout_policy's reward [T][B] and done [T][B]) and the values of one batched forward turned into
+ * generalised advantage estimates and returns, one transition per DECISION.  A pure function of its arrays: `s` names the device only,
+ * as in atc_plan_score; no state, no parameters and no random numbers are read.  All array pointers are device pointers.
+ * SIZES.  D >= 1 decisions of `hold` steps each (1 .. ATC_SKIP_MAX), T = D * hold steps.  NV = 1 .. 64 value columns per env (a
+ * per-aircraft critic has N, a centralised one 1); C = B * NV columns, column i = e * NV + k.  values is [D + 1][C]: row d is the value
+ * of the state decision d was taken in, row D that of the state after the last step.
+ * Every operation below is fp32, rounded once and never fused (the file is built with -ffp-contract=off).
+ * BLOCK.  Decision d owns steps t0 = d * hold .. t0 + hold - 1; r_t is reward[t][e], or reward[t][i] under ATC_GAE_REWARD_PER_COLUMN.
+ *
+ *     g = 1.0f;  R = r_{t0}  (assigned, not 0 + ...);  n = 1;  term = done[t0][e] != 0
+ *     for j = 1 .. hold - 1 while !term:
+ *         default:               g = g * gamma;  R = R + (r_{t0+j} * g)
+ *         ATC_GAE_PER_DECISION:  R = R + r_{t0+j}
+ *         n = n + 1;  term = done[t0+j][e] != 0
+ *
+ * Rewards and dones BEHIND THE FIRST DONE of a block are not read into anything: they belong to the next episode, flown under the old
+ * decision — atc_step_skip's rule ("a transition never spans two episodes") applied to a rollout's arrays.  Any word may stand there, a
+ * NaN included, without changing an output word.
+ * CONSTANTS.  G = g_{hold-1} * gamma with g_j the running product above (g_0 = 1.0f, g_j = g_{j-1} * gamma), so G is exactly gamma for
+ * hold == 1; under ATC_GAE_PER_DECISION G = gamma: summed rewards with the discount per decision, what a frame-skipping env in front
+ * of a trainer computes.  c = G * lam, one product.
+ * RECURRENCE.  d descends from D - 1.  A_next starts as adv_next[i], or +0.0f where adv_next == NULL (the operations are carried out
+ * all the same).  With V = values:
+ *
+ *     term:   delta = R - V[d][i];                       A = delta
+ *     else:   delta = (R + (G * V[d+1][i])) - V[d][i];   A = delta + (c * A_next)
+ *     adv[d][i] = A;  ret[d][i] = A + V[d][i];  A_next = A
+ *
+ * block_reward[d] = R, block_done[d] = term, block_steps[d] = n, each stored only where its pointer is given.  A NaN is stored as the
+ * quiet NaN 0x7FC00000 in adv, ret and block_reward (atc_plan_score's rule: IEEE 754 fixes neither the sign nor the payload of a
+ * computed NaN).  Results do not depend on how the launch maps columns to lanes; a loop in any IEEE fp32 arithmetic reproduces every
+ * word (tests/gae_ref.py does, in numpy).
+ * SPLITTING.  A call on decisions D/2 .. D-1 (values + (D/2) * C, the later half of reward and done), then a call on decisions
+ * 0 .. D/2 - 1 with adv_next = the first call's adv row 0, equal one call of D bit for bit.
+ * NOT COVERED (the trainer's): bootstrapping a time-limit done needs the terminal observation, which atc_rollout_policy does not
+ * store; masking aircraft that are not under control; advantage normalisation.
+ * ATC_ERR_ARG, in this order, the first four before any pointer is looked at, atc_last_error() naming the argument: D < 1; hold
+ * outside 1 .. ATC_SKIP_MAX; NV outside 1 .. 64; B < 1; a NULL among s, reward, done, values, g, out, out->adv, out->ret; unknown flag
+ * bits; gamma or lam not finite; any overlap among the byte ranges of reward (T*B*4 bytes, T*C*4 per column), done (T*B), values
+ * ((D+1)*C*4), adv_next (C*4), adv, ret (D*C*4 each), block_reward (D*B*4, D*C*4 per column), block_done and block_steps (D*B each) —
+ * pointer values only, ranges that only touch are accepted; B * NV beyond what one launch covers (2^31 - 1 workgroups of 64 columns).
+ * Counted by atc_gae_launch_counts only (one slot; the rules of atc_plan_refit_launch_counts); a refused call moves no launch record. */
+#define ATC_GAE_PER_DECISION 1u        /* block reward = plain sum, G = gamma */
+#define ATC_GAE_REWARD_PER_COLUMN 2u   /* reward is [T][C]; block_reward is [D][C] */
+#define ATC_GAE_MAX_NV 64
+typedef struct atc_gae {
+    float    gamma;   /* finite */
+    float    lam;     /* finite */
+    uint32_t flags;   /* ATC_GAE_PER_DECISION | ATC_GAE_REWARD_PER_COLUMN; unknown bits refused */
+    uint32_t _pad;
+} atc_gae_t;
+typedef struct atc_gae_out {
+    float*   adv;           /* [D][C] required */
+    float*   ret;           /* [D][C] required */
+    float*   block_reward;  /* nullable: [D][B], or [D][C] under ATC_GAE_REWARD_PER_COLUMN */
+    uint8_t* block_done;    /* nullable [D][B] */
+    uint8_t* block_steps;   /* nullable [D][B] */
+} atc_gae_out_t;
+int atc_gae(const atc_scenario_t* s, int B, int NV, int D, int hold,
+            const float* reward /* [T][B], or [T][C] per column */, const uint8_t* done /* [T][B] */,
+            const float* values /* [D+1][C] */, const float* adv_next /* nullable [C] */,
+            const atc_gae_t* g, const atc_gae_out_t* out, void* stream);
+enum { ATC_GAE_LAUNCH_SLOTS = 1 };
+int atc_gae_launch_counts(uint64_t* out, int n);
+
 #ifdef __cplusplus
 }
 #endif
