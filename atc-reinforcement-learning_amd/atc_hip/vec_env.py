@@ -211,6 +211,14 @@ class AtcVecEnv:
         self._info_cache = self._info()
         self._info_skip = None
 
+    def _bind_frame_steps(self):
+        """What step_skip() and branch(into=self) need on their first call (and again after _bind_outputs): frame_steps, [B] uint8, allocated
+        once, and the info dict that carries it.  _info_skip is not None only behind this."""
+        if self.frame_steps is None:
+            self.frame_steps = self._new_output(self.B, self.torch.uint8)
+            self._frame_steps_ptr = self._ptr(self.frame_steps)
+        self._info_skip = dict(self._info_cache, frame_steps=self.frame_steps)
+
     def _finish(self):
         if self.host_mapped:  # results live in host memory: valid only once the stream has drained
             self.torch.cuda.current_stream(self.device).synchronize()
@@ -342,11 +350,8 @@ class AtcVecEnv:
         skip = int(skip)
         if not 1 <= skip <= L.SKIP_MAX:
             raise ValueError("1 <= skip <= %d" % L.SKIP_MAX)
-        if self.frame_steps is None:
-            self.frame_steps = self._new_output(self.B, torch.uint8)
-            self._frame_steps_ptr = self._ptr(self.frame_steps)
         if self._info_skip is None:
-            self._info_skip = dict(self._info_cache, frame_steps=self.frame_steps)
+            self._bind_frame_steps()
         self._prev_actions = None   # (check_held: the block's last step is not a step() call to repeat)
         if (torch.is_tensor(actions) and actions.is_cuda and actions.dtype is torch.float32 and actions.is_contiguous()
                 and actions.numel() == self._n_act and actions.device == self.device
@@ -400,9 +405,7 @@ class AtcVecEnv:
         """lookahead() (plan=False: actions [M, ...]) and lookahead_plan() (plan=True: actions [M, H, ...]): the argument checks in
         their order, the result tensors and output struct cached per (M[, H], outputs), the launch"""
         torch = self.torch
-        K = int(K)
-        if not 1 <= K <= L.SKIP_MAX:
-            raise ValueError("1 <= K <= %d" % L.SKIP_MAX)
+        K = self._held_k(K)
         if plan and (not hasattr(actions, "shape") or len(actions.shape) < 2):
             raise ValueError("actions must be [M, H, B, N, 3] or [M, H, B, N*3]")
         M = int(actions.shape[0]) if hasattr(actions, "shape") else len(actions)
@@ -440,6 +443,14 @@ class AtcVecEnv:
             cache[key] = (res, out_type(*[self._ptr(res.get(n)) for n in fields]))
         return cache[key]
 
+    @staticmethod
+    def _held_k(K):
+        """K of the candidate calls (the steps a decision is held for) as an int; outside 1 .. 255: ValueError"""
+        K = int(K)
+        if not 1 <= K <= L.SKIP_MAX:
+            raise ValueError("1 <= K <= %d" % L.SKIP_MAX)
+        return K
+
     def _draw_h(self, mean):
         """H of the drawn-plan calls: mean is [H, B, N, 3] or [H, B, N*3]; outside 1 .. 16: ValueError"""
         if not hasattr(mean, "shape") or len(mean.shape) < 2:
@@ -464,6 +475,12 @@ class AtcVecEnv:
     def _as_tensor(self, v):
         return v if self.torch.is_tensor(v) else self.torch.as_tensor(np.asarray(v))
 
+    def _as_index(self, index, shape, n):
+        """An integer tensor as the contiguous int32 device tensor of `shape` the library reads: -1 where the value is outside 0 .. n-1
+        (the range test on the caller's own dtype: an int64 value beyond 32 bits must be refused, not wrapped into range)"""
+        index = index.to(device=self.device).reshape(shape)
+        return self.torch.where((index >= 0) & (index < n), index, self.torch.full_like(index, -1)).to(self.torch.int32).contiguous()
+
     def _to_device(self, mu, sd):
         """mean and std for a call that takes device tensors only: a host-mapped env's pinned pair is copied to the device"""
         if self.host_mapped and not (mu.is_cuda and sd.is_cuda):
@@ -474,11 +491,21 @@ class AtcVecEnv:
         """`t` if it is a contiguous tensor of one of `dtypes` on this env's device and, where `shape` is given, of that shape (elements=True:
         of that many elements); ValueError otherwise — `text % (shape, device)` in the caller's words, or in terms of `what`"""
         torch = self.torch
-        if not (torch.is_tensor(t) and t.is_cuda and t.device == self.device and t.dtype in dtypes and t.is_contiguous()
-                and (shape is None or (t.numel() == int(np.prod(shape, dtype=np.int64)) if elements else tuple(t.shape) == shape))):
+        if not (torch.is_tensor(t) and t.device == self.device and t.dtype in dtypes and t.is_contiguous()
+                and (shape is None or (t.numel() == int(np.prod(shape, dtype=np.int64)) if elements else t.shape == shape))):
             raise ValueError(text % (shape, self.device) if text else "%s must be a contiguous %s tensor%s on %s" % (
                 what, " / ".join(str(d) for d in dtypes), "" if shape is None else " of %r" % (shape,), self.device))
         return t
+
+    def _results(self, out, want, required, refusal=None, others=False):
+        """The result tensors of a call with an out= dict.  want: {name: (dtypes, shape)}.  Without `out`: fresh tensors of every name.  With
+        it: out's own — every `required` name there and, unless `others`, none that `want` does not know (ValueError otherwise: `refusal`,
+        or "out must be a dict with" want's names), each checked by _on_device as "out['name']" — and nothing is allocated."""
+        if out is None:
+            return {n: self.torch.empty(shape, dtype=dt[0], device=self.device) for n, (dt, shape) in want.items()}
+        if not isinstance(out, dict) or not required <= out.keys() or not (others or out.keys() <= want.keys()):
+            raise ValueError(refusal or "out must be a dict with %s" % ", ".join(want))
+        return {n: AtcVecEnv._on_device(self, out[n], dt, shape, "out[%r]" % n) for n, (dt, shape) in want.items() if n in out}
 
     def _draw_source(self, H, mean, std, seed, iteration, mean_first):
         """(mean, std, atc_plan_draw_t) as the library reads them: contiguous float32 tensors of H * B * N * 3 elements (a python float
@@ -510,9 +537,7 @@ class AtcVecEnv:
         allocated once per (M, H, outputs) and overwritten by the next such call.  The env state is left as it is.  Regenerate the few
         plans you need (elites, the winner) with draw_plans(index=...).  AtcSBVecEnv and AtcGym deliberately have no such method."""
         torch = self.torch
-        K = int(K)
-        if not 1 <= K <= L.SKIP_MAX:
-            raise ValueError("1 <= K <= %d" % L.SKIP_MAX)
+        K = self._held_k(K)
         H = self._draw_h(mean)
         M = self._drawn_m(M)
         mu, sd, dr = self._draw_source(H, mean, std, seed, iteration, mean_first)
@@ -544,9 +569,7 @@ class AtcVecEnv:
             if index.dtype.is_floating_point or index.dtype is torch.bool or index.numel() < 1 or index.numel() % self.B:
                 raise ValueError("index must be an integer tensor [E, B] or [B] (B = %d)" % self.B)
             R = index.numel() // self.B
-            # (the range test on the caller's own dtype: an int64 value beyond 32 bits must be refused, not wrapped into range)
-            index = index.to(device=self.device).reshape(R, self.B)
-            idx = torch.where((index >= 0) & (index < M), index, torch.full_like(index, -1)).to(torch.int32).contiguous()
+            idx = self._as_index(index, (R, self.B), M)
         mu, sd, dr = self._draw_source(H, mean, std, seed, iteration, mean_first)
         self._refuse_discrete()
         shape = (R, H, self.B, self.N, L.ACT_DIM)
@@ -646,12 +669,7 @@ class AtcVecEnv:
         want = {"score": ((torch.float32,), (M, self.B)), "weight": ((torch.float32,), (M, self.B))}
         if R:
             want["top"] = ((torch.int32,), (R, self.B))
-        if out is None:
-            res = {n: torch.empty(shape, dtype=dt[0], device=dev) for n, (dt, shape) in want.items()}
-        else:
-            if not isinstance(out, dict) or not set(want) <= set(out):
-                raise ValueError("out must be a dict with %s" % ", ".join(want))
-            res = {n: on_device(out[n], dt, shape, "out[%r]" % n) for n, (dt, shape) in want.items()}
+        res = self._results(out, want, want.keys(), others=True)   # (other names in `out`: let through, unread)
         with torch.cuda.device(dev):
             _lib.check(self._lib.atc_plan_score(self.sector.handle, self.B, H, M, seg_reward.data_ptr(),
                                                 None if n_steps is None else n_steps.data_ptr(), C.byref(sc), res["score"].data_ptr(),
@@ -688,9 +706,7 @@ class AtcVecEnv:
         m * B + e is this call's step with actions[m]; of a child that was not evaluated, the previous step of this env's env e.
         AtcSBVecEnv and AtcGym deliberately have no such method."""
         torch = self.torch
-        K = int(K)
-        if not 1 <= K <= L.SKIP_MAX:
-            raise ValueError("1 <= K <= %d" % L.SKIP_MAX)
+        K = self._held_k(K)
         M = int(actions.shape[0]) if hasattr(actions, "shape") else len(actions)
         if not 1 <= M <= L.LOOKAHEAD_MAX_M:
             raise ValueError("1 <= M (actions.shape[0]) <= %d" % L.LOOKAHEAD_MAX_M)
@@ -698,11 +714,8 @@ class AtcVecEnv:
         if into.B != M * self.B:
             raise ValueError("into.num_envs must be M * num_envs = %d, got %d" % (M * self.B, into.B))
         a = self._as_actions(actions, lead=(M,))
-        if into.frame_steps is None:
-            into.frame_steps = into._new_output(into.B, torch.uint8)
-            into._frame_steps_ptr = into._ptr(into.frame_steps)
         if into._info_skip is None:
-            into._info_skip = dict(into._info_cache, frame_steps=into.frame_steps)
+            into._bind_frame_steps()
         out = _lib.AtcLookaheadOut(**{n: into._ptr(t) for n, t in (("reward", into.reward), ("done", into.done), ("n_steps", into.frame_steps),
                                                                    ("flags", into.flags), ("ac_reward", into.ac_reward),
                                                                    ("min_sep", into.min_sep), ("obs", into.obs))})
@@ -728,9 +741,7 @@ class AtcVecEnv:
         index = self._as_tensor(index)
         if index.dtype not in (torch.int32, torch.int64) or index.numel() != self.B:
             raise ValueError("index must be an int32 / int64 tensor of %d elements" % self.B)
-        # (the range test on the caller's own dtype: an int64 value beyond 32 bits must be refused, not wrapped into range)
-        index = index.to(device=self.device).reshape(self.B)
-        idx = torch.where((index >= 0) & (index < src.B), index, torch.full_like(index, -1)).to(torch.int32).contiguous()
+        idx = self._as_index(index, (self.B,), src.B)
         m = self._as_mask(mask)
         if m is not None and m.numel() != self.B:
             raise ValueError("mask must have %d elements" % self.B)
@@ -815,12 +826,7 @@ class AtcVecEnv:
         a = self._as_actions(actions, lead=(n_blocks,))
         B, N, dev = self.B, self.N, self.device
         if out is None:
-            out = {
-                "obs": torch.empty((T, B, N * L.OBS_DIM), dtype=torch.float32, device=dev),
-                "reward": torch.empty((T, B), dtype=torch.float32, device=dev),
-                "done": torch.empty((T, B), dtype=torch.uint8, device=dev),
-                "flags": torch.empty((T, B, N), dtype=torch.int16, device=dev),
-            }
+            out = self._step_rows(T)
         o = self._make_out(out["obs"], out.get("raw_obs"), out["reward"], out.get("ac_reward"), out["done"],
                            out["flags"], out.get("min_sep"), out.get("term_obs"), None)
         with torch.cuda.device(dev):
@@ -829,6 +835,14 @@ class AtcVecEnv:
         self._keep = a
         self._finish()
         return out
+
+    def _step_rows(self, T):
+        """fresh [T, ...] tensors for the four required outputs of T steps in one launch"""
+        torch, B, N, dev = self.torch, self.B, self.N, self.device
+        return {"obs": torch.empty((T, B, N * L.OBS_DIM), dtype=torch.float32, device=dev),
+                "reward": torch.empty((T, B), dtype=torch.float32, device=dev),
+                "done": torch.empty((T, B), dtype=torch.uint8, device=dev),
+                "flags": torch.empty((T, B, N), dtype=torch.int16, device=dev)}
 
     def rollout_policy(self, weights, T, hold=1, seed=0, decision0=0, deterministic=False, obs0=None, out=None):
         """T consecutive steps in one launch with the decisions of a 10 -> 64 -> 64 -> 3 tanh MLP and a diagonal Gaussian taken inside
@@ -841,34 +855,7 @@ class AtcVecEnv:
         the UNCLAMPED sample, what logp is about; its clamp to [-1, 1] is what was flown — and logp [T // hold, B, N].  Values are not
         computed: run the value network once over the stored obs.  Like rollout(), it produces no traffic observation: a policy that sees
         traffic is rolled out by rollout_policy_traffic()."""
-        torch = self.torch
-        T, hold = int(T), int(hold)
-        B, N, dev = self.B, self.N, self.device
-        w = weights
-        if not (torch.is_tensor(w) and w.dtype == torch.float32 and w.device == dev and w.is_contiguous() and w.numel() == L.POLICY_WORDS):
-            raise ValueError("weights must be the contiguous float32 tensor of %d words (atc_hip.policy.pack_mlp) on %s" % (L.POLICY_WORDS, dev))
-        x0 = self.obs if obs0 is None else obs0
-        if not (torch.is_tensor(x0) and x0.dtype == torch.float32 and x0.is_contiguous() and x0.numel() == B * N * L.OBS_DIM):
-            raise ValueError("obs0 must be a contiguous float32 tensor of B*N*%d words" % L.OBS_DIM)
-        n_dec = T // hold if hold >= 1 else 0     # (a T or hold the library refuses is refused by it, below)
-        if out is None:
-            out = {
-                "obs": torch.empty((T, B, N * L.OBS_DIM), dtype=torch.float32, device=dev),
-                "reward": torch.empty((T, B), dtype=torch.float32, device=dev),
-                "done": torch.empty((T, B), dtype=torch.uint8, device=dev),
-                "flags": torch.empty((T, B, N), dtype=torch.int16, device=dev),
-                "action": torch.empty((n_dec, B, N, L.ACT_DIM), dtype=torch.float32, device=dev),
-                "logp": torch.empty((n_dec, B, N), dtype=torch.float32, device=dev),
-            }
-        o = _lib.AtcPolicyOut(*[self._ptr(out.get(k)) for k in _lib.POLICY_OUT_FIELDS])
-        pol = _lib.AtcPolicy(self._ptr(w), L.POLICY_HIDDEN, L.POLICY_DETERMINISTIC if deterministic else 0, int(seed) & (2 ** 64 - 1),
-                             int(decision0) & 0xffffffff, 0)
-        with torch.cuda.device(dev):
-            _lib.check(self._lib.atc_rollout_policy(self.sector.handle, B, N, T, hold, C.byref(self._state), self._ptr(x0), C.byref(pol),
-                                                    C.byref(o), C.byref(self.params), self._stream()))
-        self._keep = (w, x0)
-        self._finish()
-        return out
+        return AtcVecEnv._rollout_policy(self, 0, weights, T, hold, seed, decision0, deterministic, obs0, out)
 
     def rollout_policy_traffic(self, weights, T, traffic, hold=1, seed=0, decision0=0, deterministic=False, obs0=None, out=None):
         """rollout_policy with a policy that also sees traffic (include/atc_step.h: atc_rollout_policy_traffic): at every decision each
@@ -884,36 +871,48 @@ class AtcVecEnv:
             return self.rollout_policy(weights, T, hold=hold, seed=seed, decision0=decision0, deterministic=deterministic, obs0=obs0, out=out)
         if K not in L.POLICY_TRAFFIC_K:
             raise ValueError("traffic must be 0 or one of %s records per aircraft" % (L.POLICY_TRAFFIC_K,))
+        return AtcVecEnv._rollout_policy(self, K, weights, T, hold, seed, decision0, deterministic, obs0, out)   # (through the class: see gae)
+
+    def _rollout_policy(self, K, weights, T, hold, seed, decision0, deterministic, obs0, out):
+        """rollout_policy (K = 0) and rollout_policy_traffic (K = 1, 2, 4): the checks of weights and obs0, the result tensors, the two
+        structs, the launch"""
+        torch = self.torch
         T, hold = int(T), int(hold)
         B, N, dev = self.B, self.N, self.device
-        w, words = weights, L.policy_words(K)
+        w, words = weights, L.policy_words(K) if K else L.POLICY_WORDS
         if not (torch.is_tensor(w) and w.dtype == torch.float32 and w.device == dev and w.is_contiguous() and w.numel() == words):
-            raise ValueError("weights must be the contiguous float32 tensor of %d words (atc_hip.policy.pack_mlp(traffic=%d)) on %s" % (words, K, dev))
+            raise ValueError("weights must be the contiguous float32 tensor of %d words (atc_hip.policy.pack_mlp%s) on %s" % (
+                words, "(traffic=%d)" % K if K else "", dev))
         x0 = self.obs if obs0 is None else obs0
         if not (torch.is_tensor(x0) and x0.dtype == torch.float32 and x0.is_contiguous() and x0.numel() == B * N * L.OBS_DIM):
             raise ValueError("obs0 must be a contiguous float32 tensor of B*N*%d words" % L.OBS_DIM)
-        n_dec = T // hold if hold >= 1 else 0     # (a T or hold the library refuses is refused by it, below)
+        if out is None or K:
+            n_dec = T // hold if hold >= 1 else 0     # (a T or hold the library refuses is refused by it, below)
         if out is None:
-            out = {
-                "obs": torch.empty((T, B, N * L.OBS_DIM), dtype=torch.float32, device=dev),
-                "reward": torch.empty((T, B), dtype=torch.float32, device=dev),
-                "done": torch.empty((T, B), dtype=torch.uint8, device=dev),
-                "flags": torch.empty((T, B, N), dtype=torch.int16, device=dev),
-                "action": torch.empty((n_dec, B, N, L.ACT_DIM), dtype=torch.float32, device=dev),
-                "logp": torch.empty((n_dec, B, N), dtype=torch.float32, device=dev),
-                "traffic": torch.empty((n_dec, B, N, K, L.TRAFFIC_DIM), dtype=torch.float32, device=dev),
-            }
-        tr = out.get("traffic")
-        if tr is not None and not (torch.is_tensor(tr) and tr.dtype == torch.float32 and tr.is_contiguous() and tr.numel() == n_dec * B * N * K * L.TRAFFIC_DIM):
-            raise ValueError("out['traffic'] must be a contiguous float32 tensor of [T // hold, B, N, %d, %d]" % (K, L.TRAFFIC_DIM))
-        o = _lib.AtcPolicyTrafficOut(*[self._ptr(out.get(k)) for k in _lib.POLICY_TRAFFIC_OUT_FIELDS])
-        pol = _lib.AtcPolicyTraffic(self._ptr(w), L.POLICY_HIDDEN, L.POLICY_DETERMINISTIC if deterministic else 0, int(seed) & (2 ** 64 - 1),
-                                    int(decision0) & 0xffffffff, 0, K)
+            out = self._step_rows(T)
+            out["action"] = torch.empty((n_dec, B, N, L.ACT_DIM), dtype=torch.float32, device=dev)
+            out["logp"] = torch.empty((n_dec, B, N), dtype=torch.float32, device=dev)
+            if K:
+                out["traffic"] = torch.empty((n_dec, B, N, K, L.TRAFFIC_DIM), dtype=torch.float32, device=dev)
+        if K:
+            tr = out.get("traffic")
+            if tr is not None and not (torch.is_tensor(tr) and tr.dtype == torch.float32 and tr.is_contiguous() and tr.numel() == n_dec * B * N * K * L.TRAFFIC_DIM):
+                raise ValueError("out['traffic'] must be a contiguous float32 tensor of [T // hold, B, N, %d, %d]" % (K, L.TRAFFIC_DIM))
+            call, pol_type, out_type, fields = self._lib.atc_rollout_policy_traffic, _lib.AtcPolicyTraffic, _lib.AtcPolicyTrafficOut, _lib.POLICY_TRAFFIC_OUT_FIELDS
+        else:
+            call, pol_type, out_type, fields = self._lib.atc_rollout_policy, _lib.AtcPolicy, _lib.AtcPolicyOut, _lib.POLICY_OUT_FIELDS
+        o = out_type(*[self._ptr(out.get(k)) for k in fields])
+        pol = pol_type(self._ptr(w), L.POLICY_HIDDEN, L.POLICY_DETERMINISTIC if deterministic else 0, int(seed) & (2 ** 64 - 1),
+                       int(decision0) & 0xffffffff, 0)     # (traffic_k, where the struct has it, is zero so far)
+        if K:
+            pol.traffic_k = K
         with torch.cuda.device(dev):
-            _lib.check(self._lib.atc_rollout_policy_traffic(self.sector.handle, B, N, T, hold, C.byref(self._state), self._ptr(x0), C.byref(pol),
-                                                            C.byref(o), C.byref(self.params), self._stream()))
+            rc = call(self.sector.handle, B, N, T, hold, C.byref(self._state), self._ptr(x0), C.byref(pol), C.byref(o), C.byref(self.params), self._stream())
+            if rc:
+                _lib.check(rc)
         self._keep = (w, x0)
-        self._finish()
+        if self.host_mapped:
+            self._finish()
         return out
 
     def gae(self, reward, done, values, hold=1, gamma=0.99, lam=0.95, *, per_decision=False, adv_next=None, out=None):
@@ -935,13 +934,9 @@ class AtcVecEnv:
         Not covered, the trainer's: bootstrapping a time-limit done (the terminal observation is not stored by rollout_policy), masking
         aircraft that are not under control, advantage normalisation.  The method reads no action and no state."""
         torch = self.torch
-        dev = self.device
-
-        def need(t, what, dtype, shapes):
-            if not (torch.is_tensor(t) and t.dtype == dtype and t.device == dev and t.is_contiguous() and tuple(t.shape) in shapes):
-                raise ValueError("%s must be a contiguous %s tensor of %s on %s" % (what, dtype, " or ".join(repr(s) for s in shapes), dev))
-            return t
-
+        dev, f32 = self.device, (self.torch.float32,)
+        # (the helpers through the class: these refusals are also tested on a stand-in env that has none of the class's methods)
+        need = AtcVecEnv._on_device.__get__(self)
         hold = int(hold)
         if not 1 <= hold <= L.SKIP_MAX:
             raise ValueError("1 <= hold <= %d" % L.SKIP_MAX)
@@ -952,34 +947,30 @@ class AtcVecEnv:
         if not 1 <= NV <= L.GAE_MAX_NV:
             raise ValueError("1 <= NV (values.shape[-1]) <= %d" % L.GAE_MAX_NV)
         cols = tuple(values.shape[1:])
-        need(values, "values", torch.float32, [(D + 1,) + cols])
+        need(values, f32, (D + 1,) + cols, "values")
         T = D * hold
         if not torch.is_tensor(reward) or reward.dim() not in (2, 3):
             raise ValueError("reward must be [T, B] or [T, B, NV]")
         per_column = reward.dim() == 3
-        need(reward, "reward", torch.float32, [(T, self.B, NV)] if per_column else [(T, self.B)])
-        need(done, "done", torch.uint8, [(T, self.B)])
+        need(reward, f32, (T, self.B, NV) if per_column else (T, self.B), "reward")
+        need(done, (torch.uint8,), (T, self.B), "done")
         for name, v in (("gamma", gamma), ("lam", lam)):
             with np.errstate(over="ignore"):
                 if not np.isfinite(np.float32(v)):
                     raise ValueError("%s must be finite (in float32)" % name)
         if adv_next is not None:
-            need(adv_next, "adv_next", torch.float32, [cols])
-        want = {"adv": (torch.float32, (D,) + cols), "ret": (torch.float32, (D,) + cols),
-                "block_reward": (torch.float32, (D,) + (cols if per_column else (self.B,))),
-                "block_done": (torch.uint8, (D, self.B)), "block_steps": (torch.uint8, (D, self.B))}
-        if out is None:
-            res = {n: torch.empty(shape, dtype=dt, device=dev) for n, (dt, shape) in want.items()}
-        else:
-            if not isinstance(out, dict) or not {"adv", "ret"} <= set(out) or not set(out) <= set(want):
-                raise ValueError("out must be a dict with adv and ret, and any of block_reward, block_done, block_steps")
-            res = {n: need(t, "out[%r]" % n, want[n][0], [want[n][1]]) for n, t in out.items()}
+            need(adv_next, f32, cols, "adv_next")
+        want = {"adv": (f32, (D,) + cols), "ret": (f32, (D,) + cols), "block_reward": (f32, (D,) + (cols if per_column else (self.B,))),
+                "block_done": ((torch.uint8,), (D, self.B)), "block_steps": ((torch.uint8,), (D, self.B))}
+        res = AtcVecEnv._results(self, out, want, {"adv", "ret"}, "out must be a dict with adv and ret, and any of block_reward, block_done, block_steps")
         g = _lib.AtcGae(float(gamma), float(lam), (L.GAE_PER_DECISION if per_decision else 0) | (L.GAE_REWARD_PER_COLUMN if per_column else 0), 0)
         o = _lib.AtcGaeOut(*[res[n].data_ptr() if n in res else None for n in _lib.GAE_OUT_FIELDS])
         fn = self._lib.atc_gae
         with torch.cuda.device(dev):
-            _lib.check(fn(self.sector.handle, self.B, NV, D, hold, reward.data_ptr(), done.data_ptr(), values.data_ptr(),
-                          None if adv_next is None else adv_next.data_ptr(), C.byref(g), C.byref(o), self._stream()))
+            rc = fn(self.sector.handle, self.B, NV, D, hold, reward.data_ptr(), done.data_ptr(), values.data_ptr(),
+                    None if adv_next is None else adv_next.data_ptr(), C.byref(g), C.byref(o), self._stream())
+            if rc:
+                _lib.check(rc)
         self._keep_gae = (reward, done, values, adv_next)   # the inputs outlive the launch (like _keep_score)
         return res
 

@@ -11,7 +11,8 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "csrc", "atc_step.hip")
-DEPS = [SRC, os.path.join(HERE, "csrc", "atc_device.h"), os.path.join(HERE, "csrc", "atc_abi.inc"), os.path.join(HERE, "csrc", "atc_wave.h"),
+DEPS = [SRC, os.path.join(HERE, "csrc", "atc_device.h"), os.path.join(HERE, "csrc", "atc_kernarg.h"), os.path.join(HERE, "csrc", "atc_abi.inc"),
+        os.path.join(HERE, "csrc", "atc_wave.h"),
         os.path.join(HERE, "csrc", "atc_aux_kernels.inc"), os.path.join(HERE, "csrc", "atc_traffic.inc"),
         os.path.join(HERE, "csrc", "atc_lookahead.inc"), os.path.join(HERE, "csrc", "atc_plan.inc"),
         os.path.join(HERE, "csrc", "atc_plan_sampled.inc"), os.path.join(HERE, "csrc", "atc_plan_refit.inc"),

@@ -563,7 +563,7 @@ int atc_state_select(const atc_scenario_t* s, int N, int B_dst, const atc_state_
 int atc_rollout_policy(const atc_scenario_t* s, int B, int N, int T, int hold, const atc_state_t* st, const float* obs0, const atc_policy_t* pol,
                        const atc_policy_out_t* out, const atc_params_t* p, void* stream) {
     if (const int rc = check_policy_call(s, B, N, T, hold, st, obs0, pol, out, p, "atc_policy_t", "atc_policy_out_t", nullptr, nullptr)) return rc;
-    return with_width(N, [&](auto w) { return launch_policy<decltype(w)::value>(s, B, N, T, hold, st, obs0, pol, out, p, (hipStream_t)stream); });
+    return with_width(N, [&](auto w) { return launch_policy<decltype(w)::value, 0>(s, B, N, T, hold, st, obs0, pol, out, p, (hipStream_t)stream); });
 }
 
 int atc_rollout_policy_traffic(const atc_scenario_t* s, int B, int N, int T, int hold, const atc_state_t* st, const float* obs0,
@@ -571,7 +571,11 @@ int atc_rollout_policy_traffic(const atc_scenario_t* s, int B, int N, int T, int
     if (const int rc = check_policy_call(s, B, N, T, hold, st, obs0, pol, out, p, "atc_policy_traffic_t", "atc_policy_traffic_out_t", pol ? &pol->traffic_k : nullptr,
                                          out ? out->traffic : nullptr))
         return rc;
-    return with_width(N, [&](auto w) { return launch_policy_traffic<decltype(w)::value>(s, B, N, T, hold, st, obs0, pol, out, p, (hipStream_t)stream); });
+    return with_width(N, [&](auto w) {
+        return with_traffic_k(pol->traffic_k, [&](auto kt) {
+            return launch_policy<decltype(w)::value, decltype(kt)::value>(s, B, N, T, hold, st, obs0, pol, out, p, (hipStream_t)stream);
+        });
+    });
 }
 
 int atc_gae(const atc_scenario_t* s, int B, int NV, int D, int hold, const float* reward, const uint8_t* done, const float* values,

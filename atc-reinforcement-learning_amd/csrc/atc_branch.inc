@@ -15,30 +15,9 @@
 //   out of the other form).  obs and flags are what a child env's bound outputs always hold, as atc_step_skip's required outputs: both
 //   forms store them behind a run-time null test, like k_skip's fast form does — k_lookahead's FULL (any of the four) would send every
 //   AtcVecEnv.branch through the heavy form (measured at 65 536 x 16, K = 4, M = 4: 420 us against 183 us without the two outputs).
-struct BranchArgs {
-    const float* blob;
-    int off_grid, B, N, K, M;
-    atc_state_t st;     // the SOURCE batch: read only
-    const float* actions;
-    atc_out_t out;      // obs, reward, ac_reward, done, flags, min_sep of atc_lookahead_out_t; the other fields null
-    atc_params_t p;
-    StepDerived q;
-    uint8_t* n_steps;
-    int cpg, groups, tiles;
-    atc_state_t dst;    // the CHILD batch of M B envs
-};
-static_assert(offsetof(BranchArgs, st) == offsetof(StepArgs, st) && offsetof(BranchArgs, out) == offsetof(StepArgs, out) &&
-              offsetof(BranchArgs, q) == offsetof(StepArgs, q),
-              "k_branch's kernel arguments must lie where k_step's do: the step re-reads them by StepArgs offsets");
-// k_branch also re-reads `dst`, its LAST parameter, by offsetof(BranchArgs, dst): BranchArgs must list every kernel parameter in order.
-// last_kernarg_offset lays a kernel's parameter list out by the kernarg rules (each at its natural alignment); the static_assert behind
-// k_branch holds the struct to it, so a parameter added to one of the two alone does not compile.
-template <typename... A>
-constexpr size_t last_kernarg_offset(void (*)(A...)) {
-    size_t off = 0, last = 0;
-    ((off = (off + alignof(A) - 1) / alignof(A) * alignof(A), last = off, off += sizeof(A)), ...);
-    return last;
-}
+//   ARGUMENTS: k_lookahead's, then `dst`, the CHILD batch of M B envs; `st` is the SOURCE batch, read only.  The step halves re-read st, out
+//   and q from the kernarg segment by StepArgs offsets, and the kernel re-reads dst, its LAST parameter, at the offset its own parameter
+//   list gives (KernArgs, atc_kernarg.h); the static_assert behind the kernel holds that list to StepArgs.
 
 // candidate m's rows of a batch of M B envs: every array advanced by m B envs, so that the source's env and aircraft ids index them
 __device__ __forceinline__ atc_state_t child_rows(const atc_state_t& dst, size_t mB, size_t mBN) {
@@ -58,6 +37,7 @@ k_branch(const float* __restrict__ blob, int off_grid, int B, int N, int K_steps
          const float* __restrict__ actions, atc_out_t out, atc_params_t p, StepDerived q, uint8_t* n_steps, int cpg, int groups, int tiles,
          atc_state_t dst) {
     constexpr bool ONE = false, LAT = false;   // (QGET: the multi-step form — kernarg re-reads inside the step)
+    constexpr size_t dst_off = KernArgs<decltype(k_branch<W, FULL>)>::last();   // where `dst` lies: re-read at an env's last step
     static_assert(ATC_STAT_WORDS == 8, "the per-episode record is copied as two 16-byte pieces");
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float4* pos = reinterpret_cast<float4*>(smem);                    // [2 kBlock] pair-scan staging (W >= 32)
@@ -164,7 +144,7 @@ k_branch(const float* __restrict__ blob, int off_grid, int B, int N, int K_steps
                 int n = step + 1;
                 float ms = (min_d2 >= 1e30f) ? 1e30f : sqrtf(min_d2);
                 const int zs = opaque_zero();
-                const atc_state_t ch = child_rows(kernarg_reread<atc_state_t>(offsetof(BranchArgs, dst), zs), mB, mBN);
+                const atc_state_t ch = child_rows(kernarg_reread<atc_state_t>(dst_off, zs), mB, mBN);
                 if (ATC_RARE((fin & nev) != 0ull)) {   // not evaluated: every output word of this (candidate, env) is zero ...
                     const bool zero = ((nev >> d.lane) & 1ull) != 0ull;
 #pragma unroll
@@ -216,8 +196,7 @@ k_branch(const float* __restrict__ blob, int off_grid, int B, int N, int K_steps
     }
 }
 
-static_assert(last_kernarg_offset(&k_branch<1, false>) == offsetof(BranchArgs, dst),
-              "BranchArgs must mirror k_branch's whole parameter list: the kernel re-reads dst by its offset in the struct");
+static_assert(kernargs_like_step<decltype(k_branch<1, false>)>(), ATC_KERNARGS_REFUSAL);
 
 // ---------------------------------------------------------------------------------------------------------------
 // k_select (atc_state_select): dst env e takes src env index[e]'s rows — a gather of whole records, no arithmetic.  Flat mapping: one

@@ -14,20 +14,9 @@
 //   unwritten side record holds until then; nothing of that is stored.
 //   FULL: flags, ac_reward, min_sep or obs is requested (each a run-time null test); the fast form compiles all four out, and with
 //   them the group minimum and the observation's normalisation (dead once nothing reads StepVals::o).
-struct LookArgs {
-    const float* blob;
-    int off_grid, B, N, K, M;
-    atc_state_t st;
-    const float* actions;
-    atc_out_t out;      // obs, reward, ac_reward, done, flags, min_sep of atc_lookahead_out_t; the other fields null
-    atc_params_t p;
-    StepDerived q;
-    uint8_t* n_steps;
-    int cpg, groups, tiles;
-};
-static_assert(offsetof(LookArgs, st) == offsetof(StepArgs, st) && offsetof(LookArgs, out) == offsetof(StepArgs, out) &&
-              offsetof(LookArgs, q) == offsetof(StepArgs, q),
-              "k_lookahead's kernel arguments must lie where k_step's do: the step re-reads them by StepArgs offsets");
+//   ARGUMENTS: `out` carries obs, reward, ac_reward, done, flags, min_sep of atc_lookahead_out_t, the other fields null.  The step halves
+//   re-read st, out and q from the kernarg segment by StepArgs offsets: the static_assert behind the kernel holds its own parameter list
+//   (KernArgs, atc_kernarg.h) to them.
 
 // Workgroup id -> (tile, candidate group).  Workgroups are dealt round-robin to the 8 XCDs, so ids are laid out in chunks of
 // 8 tiles x `groups`: id = (chunk * groups + g) * 8 + j serves tile 8 chunk + j — every group of a tile has the same id mod 8 (one
@@ -161,3 +150,4 @@ k_lookahead(const float* __restrict__ blob, int off_grid, int B, int N, int K_st
         }
     }
 }
+static_assert(kernargs_like_step<decltype(k_lookahead<1, false>)>(), ATC_KERNARGS_REFUSAL);

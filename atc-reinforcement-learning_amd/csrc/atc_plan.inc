@@ -14,21 +14,9 @@
 //   never spans two episodes.  It stores its verdicts then, and zeros into the seg_reward words of the segments it did not run — for
 //   a not-evaluated env also over those it did run (same lane, same address, later store).
 //   FULL: as in k_lookahead.  seg_reward is a run-time null test in both forms.
-struct PlanArgs {
-    const float* blob;
-    int off_grid, B, N, K, H, M;
-    atc_state_t st;
-    const float* actions;
-    atc_out_t out;      // obs, reward, ac_reward, done, flags, min_sep of atc_plan_out_t; the other fields null
-    atc_params_t p;
-    StepDerived q;
-    uint16_t* n_steps;
-    float* seg_reward;
-    int cpg, groups, tiles;
-};
-static_assert(offsetof(PlanArgs, st) == offsetof(StepArgs, st) && offsetof(PlanArgs, out) == offsetof(StepArgs, out) &&
-              offsetof(PlanArgs, q) == offsetof(StepArgs, q),
-              "k_plan's kernel arguments must lie where k_step's do: the step re-reads them by StepArgs offsets");
+//   ARGUMENTS: `out` carries obs, reward, ac_reward, done, flags, min_sep of atc_plan_out_t, the other fields null.  The step halves re-read
+//   st, out and q from the kernarg segment by StepArgs offsets: the static_assert behind the kernel holds its own parameter list
+//   (KernArgs, atc_kernarg.h) to them.
 
 template <int W, bool FULL>
 __global__ void __launch_bounds__(kBlock, ATC_SKIP_WAVES)
@@ -193,3 +181,4 @@ k_plan(const float* __restrict__ blob, int off_grid, int B, int N, int K_steps, 
         }
     }
 }
+static_assert(kernargs_like_step<decltype(k_plan<1, false>)>(), ATC_KERNARGS_REFUSAL);

@@ -33,23 +33,9 @@ __device__ __forceinline__ Float3 plan_draw(uint64_t cand_key, bool mean_only, u
     return Float3{plan_draw_clamp(mu.a + sd.a * za), plan_draw_clamp(mu.b + sd.b * zb), plan_draw_clamp(mu.c + sd.c * zc)};
 }
 
-struct PlanSampledArgs {
-    const float* blob;
-    int off_grid, B, N, K, H, M;
-    atc_state_t st;
-    const float* mean;
-    atc_out_t out;      // obs, reward, ac_reward, done, flags, min_sep of atc_plan_out_t; the other fields null
-    atc_params_t p;
-    StepDerived q;
-    uint16_t* n_steps;
-    float* seg_reward;
-    int cpg, groups, tiles;
-    const float* std;
-    atc_plan_draw_t dr;
-};
-static_assert(offsetof(PlanSampledArgs, st) == offsetof(StepArgs, st) && offsetof(PlanSampledArgs, out) == offsetof(StepArgs, out) &&
-              offsetof(PlanSampledArgs, q) == offsetof(StepArgs, q),
-              "k_plan_sampled's kernel arguments must lie where k_step's do: the step re-reads them by StepArgs offsets");
+// ARGUMENTS: k_plan's, with the mean rows where k_plan has the action blocks and std and the draw's terms behind them.  The step halves
+// re-read st, out and q from the kernarg segment by StepArgs offsets: the static_assert behind the kernel holds its own parameter list
+// (KernArgs, atc_kernarg.h) to them.
 
 template <int W, bool FULL>
 __global__ void __launch_bounds__(kBlock, ATC_SKIP_WAVES)
@@ -228,6 +214,7 @@ k_plan_sampled(const float* __restrict__ blob, int off_grid, int B, int N, int K
         }
     }
 }
+static_assert(kernargs_like_step<decltype(k_plan_sampled<1, false>)>(), ATC_KERNARGS_REFUSAL);
 
 // ---------------------------------------------------------------------------------------------------------------
 // k_plan_draw (atc_plan_draw): the drawn plans as a tensor — rows r < R of actions [R][H][B N 3].  Flat mapping: one lane per aircraft

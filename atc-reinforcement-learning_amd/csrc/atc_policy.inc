@@ -125,50 +125,16 @@ __device__ __forceinline__ PolicyDecision policy_decide(const float* w_arg, int 
     return dec;
 }
 
-struct PolicyArgs {
-    const float* blob;
-    int off_grid, B, N, T, hold;
-    atc_state_t st;
-    const float* obs0;
-    atc_out_t out;      // obs, reward, done, flags of atc_policy_out_t; the other fields null
-    atc_params_t p;
-    StepDerived q;
-    const float* w;
-    uint64_t seed;
-    uint32_t decision0, pflags;
-    float* action;
-    float* logp;
-};
-static_assert(offsetof(PolicyArgs, hold) == offsetof(StepArgs, hold) && offsetof(PolicyArgs, st) == offsetof(StepArgs, st) &&
-              offsetof(PolicyArgs, out) == offsetof(StepArgs, out) && offsetof(PolicyArgs, q) == offsetof(StepArgs, q),
-              "k_rollout_policy's kernel arguments must lie where k_step's do: the step re-reads them by StepArgs offsets");
-
-// k_rollout_policy_traffic's arguments: k_rollout_policy's, then what the traffic stage reads — by kernarg re-read at the decision, so that
-// nothing of it is carried across the step loop
+// ARGUMENTS of both kernels: k_step's up to `q` (obs0 where it has the actions; `out` carries obs, reward, done, flags of atc_policy_out_t,
+// the other fields null), then the policy's.  The loop re-reads hold, st, out and q from the kernarg segment by StepArgs offsets: the
+// static_assert behind each kernel holds its own parameter list (KernArgs, atc_kernarg.h) to them.
+// k_rollout_policy_traffic's list is k_rollout_policy's, then what the traffic stage reads — by kernarg re-read at the decision, at the offset
+// that list gives its last parameter, so that nothing of it is carried across the step loop.  (The kernarg segment packs the parameters flat:
+// a struct that nested the first list would be padded to its own alignment of 64 and name a later offset.)
 struct PolicyTrafficTail {
     TrafficArgs tq;     // the host's traffic_common: the uniform terms of atc_observe_traffic
     float* traffic;     // atc_policy_traffic_out_t.traffic, nullable
 };
-struct PolicyTrafficArgs {   // FLAT, like the kernel's argument list: a nested PolicyArgs would be padded to its own alignment (64), the kernarg segment is not
-    const float* blob;
-    int off_grid, B, N, T, hold;
-    atc_state_t st;
-    const float* obs0;
-    atc_out_t out;
-    atc_params_t p;
-    StepDerived q;
-    const float* w;
-    uint64_t seed;
-    uint32_t decision0, pflags;
-    float* action;
-    float* logp;
-    PolicyTrafficTail tt;
-};
-static_assert(offsetof(PolicyTrafficArgs, hold) == offsetof(StepArgs, hold) && offsetof(PolicyTrafficArgs, st) == offsetof(StepArgs, st) &&
-              offsetof(PolicyTrafficArgs, out) == offsetof(StepArgs, out) && offsetof(PolicyTrafficArgs, q) == offsetof(StepArgs, q) &&
-              offsetof(PolicyTrafficArgs, logp) == offsetof(PolicyArgs, logp) && alignof(PolicyTrafficTail) == 8 &&
-              offsetof(PolicyTrafficArgs, tt) == offsetof(PolicyArgs, logp) + sizeof(float*),
-              "k_rollout_policy_traffic's arguments are k_rollout_policy's with the traffic terms directly behind logp");
 
 // wavefronts per SIMD k_rollout_policy is register-budgeted for (<= 168 VGPRs): the 64 hidden activations are live next to what the
 // step carries across its loop, which the step's own 5 - 6 do not hold.  -DATC_POLICY_WAVES=n: A/B builds.
@@ -180,7 +146,8 @@ static_assert(offsetof(PolicyTrafficArgs, hold) == offsetof(StepArgs, hold) && o
 // traffic_record of atc_traffic.inc: k_traffic's arithmetic, so the same bits), stored, and its words 0..6 per record widen the input row.
 // An env never leaves its wavefront: W = 32 / 64 stage (x, y, tag) in the wavefront's own quarter of the pair-scan staging area (idle
 // between steps), ordered by wave-level waits — no workgroup barrier anywhere in the decision.
-template <int W, int KT>
+// TT_OFF: where k_rollout_policy_traffic's PolicyTrafficTail lies in ITS kernarg segment (the body serves two parameter lists)
+template <int W, int KT, size_t TT_OFF = 0>
 __device__ __forceinline__ void rollout_policy_body(const float* __restrict__ blob, int off_grid, int B, int N, int T, atc_state_t st, const float* __restrict__ obs0,
                                                     atc_params_t p, StepDerived q, const float* __restrict__ pw, uint64_t seed, uint32_t decision0, uint32_t pflags,
                                                     float* __restrict__ action, float* __restrict__ logp) {
@@ -240,7 +207,7 @@ __device__ __forceinline__ void rollout_policy_body(const float* __restrict__ bl
                 dec = policy_decide<ATC_POLICY_IN>(pw, zk, x, seed, decision0 + blk, dl.i, (pflags & ATC_POLICY_DETERMINISTIC) != 0u);
             } else {
                 // ---- the traffic query on the state the env is in now: what step b hold - 1 left, or the fresh spawn after an auto-reset ----
-                const PolicyTrafficTail tt = kernarg_reread<PolicyTrafficTail>(offsetof(PolicyTrafficArgs, tt), zk);
+                const PolicyTrafficTail tt = kernarg_reread<PolicyTrafficTail>(TT_OFF, zk);
                 int phi = ls.a.phi;
                 if (ATC_RARE(is_wide(phi))) phi = phi_wrap(*at<double>(wide_base<false>(st.phi_wide, zk), dl.i * 32u));   // the exact counts, as the step reads them
                 const TrafficSelf me = traffic_self(ls.a.x, ls.a.y, ls.a.h, phi, ls.a.v, tt.tq);
@@ -331,6 +298,7 @@ k_rollout_policy(const float* __restrict__ blob, int off_grid, int B, int N, int
                  float* __restrict__ action, float* __restrict__ logp) {
     rollout_policy_body<W, 0>(blob, off_grid, B, N, T, st, obs0, p, q, pw, seed, decision0, pflags, action, logp);   // (hold, out: kernarg re-reads)
 }
+static_assert(kernargs_hold_like_step<decltype(k_rollout_policy<1>)>(), ATC_KERNARGS_REFUSAL);
 
 // KT: the compiled list length = atc_policy_traffic_t.traffic_k (1, 2, 4)
 template <int W, int KT>
@@ -338,5 +306,8 @@ __global__ void __launch_bounds__(kBlock, ATC_POLICY_WAVES)
 k_rollout_policy_traffic(const float* __restrict__ blob, int off_grid, int B, int N, int T, int hold, atc_state_t st, const float* __restrict__ obs0,
                          atc_out_t out, atc_params_t p, StepDerived q, const float* __restrict__ pw, uint64_t seed, uint32_t decision0, uint32_t pflags,
                          float* __restrict__ action, float* __restrict__ logp, PolicyTrafficTail tt) {
-    rollout_policy_body<W, KT>(blob, off_grid, B, N, T, st, obs0, p, q, pw, seed, decision0, pflags, action, logp);   // (tt: a kernarg re-read at the decision)
+    // (tt: a kernarg re-read at the decision, at the offset this list gives its last parameter)
+    rollout_policy_body<W, KT, KernArgs<decltype(k_rollout_policy_traffic<W, KT>)>::last()>(blob, off_grid, B, N, T, st, obs0, p, q, pw, seed, decision0, pflags,
+                                                                                          action, logp);
 }
+static_assert(kernargs_hold_like_step<decltype(k_rollout_policy_traffic<1, 1>)>(), ATC_KERNARGS_REFUSAL);

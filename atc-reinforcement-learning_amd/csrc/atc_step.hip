@@ -19,6 +19,7 @@
 #include <atomic>
 #include <chrono>
 #include <sched.h>
+#include <stdarg.h>
 #include <emmintrin.h>   // host side of atc_step_packet: 16-byte loads of the mapped result packet
 #include <stdint.h>
 #include <stdio.h>
@@ -27,6 +28,7 @@
 #include <type_traits>
 
 #include "atc_device.h"
+#include "atc_kernarg.h"
 
 using namespace atc;
 
@@ -54,6 +56,15 @@ static thread_local char g_err[512] = "";
 static int fail_arg(const char* msg) {
     snprintf(g_err, sizeof g_err, "bad argument: %s", msg);
     return ATC_ERR_ARG;
+}
+// a refusal with the call's own words in it: formatted here, so only ever on the refusing path
+__attribute__((format(printf, 1, 2))) static int fail_argf(const char* fmt, ...) {
+    char msg[160];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(msg, sizeof msg, fmt, ap);
+    va_end(ap);
+    return fail_arg(msg);
 }
 static int fail_hip(hipError_t e, const char* what) {
     snprintf(g_err, sizeof g_err, "HIP error in %s: %s", what, hipGetErrorString(e));
@@ -406,12 +417,15 @@ static StepDerived derive_uncached(const atc_params_t& p, const atc_scenario* s,
     return q;
 }
 
-// The kernel's argument list as a struct: the kernarg segment is laid out by the same rules, so offsetof() names where an
+// k_step's argument list as a struct: the kernarg segment is laid out by the same rules, so offsetof() names where an
 // argument lives.  Multi-step launches RE-READ their by-value arguments (output pointers, parameters, derived constants, the state
 // pointers needed again after the loop) from the kernarg segment inside the step instead of keeping ~60 SGPRs of them alive
 // across the loop: the allocator spills those to VGPR lanes and every use becomes a v_readlane — VALU work in a launch that is
 // bound by VALU issue — whereas a kernarg re-read is a scalar load.  The offset goes through an opaque zero, or the (invariant)
 // loads would be hoisted out of the loop again.
+//   The step halves are shared by every multi-step kernel, so each of those kernels must put what they re-read where StepArgs says.
+//   The only description of a kernel's layout is its parameter list (KernArgs, atc_kernarg.h): StepArgs is held to k_step's list behind
+//   k_step, and every other kernel's list to StepArgs by kernargs_like_step in a static_assert directly behind the kernel.
 struct StepArgs {
     const float* blob;
     int off_grid, B, N, T, hold;
@@ -424,6 +438,21 @@ struct StepArgs {
     LdsTab lt;
     int pf_stride;   // fill-phase prefetch (k_step): behind everything k_skip's argument list shares with this one
 };
+// F's first atc_state_t, its atc_out_t and its StepDerived lie where k_step's do
+template <typename F>
+constexpr bool kernargs_like_step() {
+    typedef KernArgs<F> A;
+    return A::template of<atc_state_t>() == offsetof(StepArgs, st) && A::template of<atc_out_t>() == offsetof(StepArgs, out) &&
+           A::template of<StepDerived>() == offsetof(StepArgs, q);
+}
+// ... and F's parameter 5 is `hold`: it lies where k_step's does, directly in front of the state (parameters have no names in a type: an
+// int put anywhere in front of `st` moves the state off index 6, or off its offset)
+template <typename F>
+constexpr bool kernargs_hold_like_step() {
+    typedef KernArgs<F> A;
+    return kernargs_like_step<F>() && A::template at<5>() == offsetof(StepArgs, hold) && A::template at<6>() == A::template of<atc_state_t>();
+}
+#define ATC_KERNARGS_REFUSAL "the kernel's arguments must lie where k_step's do: the step re-reads them by StepArgs offsets"
 template <typename T>
 __device__ __forceinline__ T kernarg_reread(size_t byte_off, int opaque_zero) {
 #if __HIP_DEVICE_COMPILE__   // (the host pass only parses this body; the builtin exists for the device target)
@@ -1514,6 +1543,12 @@ k_step(const float* __restrict__ blob, int off_grid, int B, int N, int T, int ho
     if (lane == 0 && trace) trace[((size_t)(blockIdx.x * (kBlock / 64) + (tid >> 6)) * n_steps + (n_steps - 1)) * 8 + 7] = __builtin_amdgcn_s_memtime();
 #endif
 }
+// StepArgs is k_step's list: every member that an offsetof(StepArgs, ...) names, and the last one — a parameter added to one of the two
+// alone does not compile.  (The layout does not depend on the template arguments: one instance stands for all.)
+typedef KernArgs<decltype(k_step<1, false, true, true>)> StepKernArgs;
+static_assert(kernargs_hold_like_step<decltype(k_step<1, false, true, true>)>() && StepKernArgs::of<LdsTab>() == offsetof(StepArgs, lt) &&
+                  StepKernArgs::last() == offsetof(StepArgs, pf_stride),
+              "StepArgs must list k_step's parameters in order: the step re-reads them by StepArgs offsets");
 
 // ---------------------------------------------------------------------------------------------------------------
 // Frame skip (include/atc_step.h: atc_step_skip): up to K steps with ONE held action block in one launch, ONE set of outputs.
@@ -1535,23 +1570,11 @@ k_step(const float* __restrict__ blob, int off_grid, int B, int N, int T, int ho
 //   The loop ends when no env of the wavefront is live.  Steps after the first repeat the block's actions on envs that were not
 //   reset in between (a reset env is stopped): `repeated`, the structural form of ATC_M_ACTIONS_HELD.
 //   The argument list is k_step's up to `q` (StepArgs): step_part_a / step_part_b re-read state pointers and derived constants from
-//   the kernarg segment by those offsets.  The separation-scan horizon is left off (full scan in every step).
+//   the kernarg segment by those offsets (the static_assert behind the kernel holds its list to them).  The separation-scan horizon is left off (full scan in every step).
 //   FULL: an optional output (raw_obs, ac_reward, min_sep, term_obs) is requested — as in k_step the fast form compiles them out
 //   (no raw observation in registers, the conflict-only scan); which of them is present is a run-time null test in the full form.
 //   Registers, launch bound: DESIGN.md, frame skip.
 // ---------------------------------------------------------------------------------------------------------------
-struct SkipArgs {
-    const float* blob;
-    int off_grid, B, N, K, pad;
-    atc_state_t st;
-    const float* actions;
-    atc_out_t out;
-    atc_params_t p;
-    StepDerived q;
-    uint8_t* n_steps;
-};
-static_assert(offsetof(SkipArgs, st) == offsetof(StepArgs, st) && offsetof(SkipArgs, q) == offsetof(StepArgs, q),
-              "k_skip's kernel arguments must lie where k_step's do: the step re-reads them by StepArgs offsets");
 // wavefronts per SIMD k_skip is register-budgeted for (<= 96 VGPRs).  Measured against 4 (no spills, slower) and against 6 for the
 // fast form of 16-aircraft envs (k_step's rule for its loop forms: no faster here): DESIGN.md, frame skip.  -DATC_SKIP_WAVES=n: A/B builds.
 #ifndef ATC_SKIP_WAVES
@@ -1652,6 +1675,7 @@ k_skip(const float* __restrict__ blob, int off_grid, int B, int N, int K_steps, 
         }
     }
 }
+static_assert(kernargs_like_step<decltype(k_skip<1, false>)>(), ATC_KERNARGS_REFUSAL);
 
 // ---------------------------------------------------------------------------------------------------------------
 // Persistent step server of ONE env x ONE aircraft (the drop-in AtcGym, atc_gym.py:128-192; include/atc_step.h: atc_serve_*).
@@ -2069,20 +2093,18 @@ template <typename O>
 static int check_candidates(const atc_scenario_t* s, int B, int N, int K, const int* H, int M, const atc_state_t* st, const float* actions,
                             const O* out, const atc_params_t* p, const char* k_is, const char* out_type, const char* fresh_per,
                             std::initializer_list<Required> drawn = {}) {
-    char msg[160];
-    auto fail = [&](const char* fmt, const char* word) { snprintf(msg, sizeof msg, fmt, word); return fail_arg(msg); };
     const bool is_drawn = drawn.size() != 0;
-    if (K < 1 || K > ATC_SKIP_MAX) return fail("K (the %s length) must be 1 .. 255", k_is);
+    if (K < 1 || K > ATC_SKIP_MAX) return fail_argf("K (the %s length) must be 1 .. 255", k_is);
     if (H) if (const int rc = check_plan_h(*H)) return rc;
     if (is_drawn) {
         if (const int rc = check_drawn_m(M)) return rc;
         if (const int rc = check_required(drawn)) return rc;
     } else if (M < 1 || M > ATC_LOOKAHEAD_MAX_M) return fail_arg("M (the number of candidates) must be 1 .. 64");
-    if (!out || !out->reward || !out->done) return fail("null pointer: %s.reward and .done are required", out_type);
+    if (!out || !out->reward || !out->done) return fail_argf("null pointer: %s.reward and .done are required", out_type);
     if (!is_drawn && !actions) return fail_arg("null pointer");
     if (const int rc = check_env_args(s, B, N, st, p)) return rc;
     if (const int rc = check_dt(s, p)) return rc;
-    if (p->mode & ATC_M_ACTIONS_HELD) return fail("ATC_M_ACTIONS_HELD is for atc_step only: every %s's first step carries a fresh decision", fresh_per);
+    if (p->mode & ATC_M_ACTIONS_HELD) return fail_argf("ATC_M_ACTIONS_HELD is for atc_step only: every %s's first step carries a fresh decision", fresh_per);
     return is_drawn ? check_continuous(p) : ATC_OK;
 }
 
@@ -2102,9 +2124,7 @@ static int check_disjoint(const ByteRange* r, int n, std::initializer_list<std::
             bool in_place = false;
             for (const auto& pair : may_equal) in_place |= pair.first == a && pair.second == b && r[a].ptr == r[b].ptr;
             if (in_place) continue;
-            char msg[160];
-            snprintf(msg, sizeof msg, "%s overlaps %s (%s)", r[a].name, r[b].name, tail);
-            return fail_arg(msg);
+            return fail_argf("%s overlaps %s (%s)", r[a].name, r[b].name, tail);
         }
     return ATC_OK;
 }
@@ -2136,37 +2156,36 @@ static atc_out_t policy_out(const O* o) {
     out.flags = o->flags;
     return out;
 }
-template <int W>
-static int launch_policy(const atc_scenario* s, int B, int N, int T, int hold, const atc_state_t* st, const float* obs0, const atc_policy_t* pol,
-                         const atc_policy_out_t* o, const atc_params_t* p, hipStream_t stream) {
+// W lanes per env.  KT = 0: k_rollout_policy (P, O = atc_policy_t, atc_policy_out_t); KT = 1, 2, 4: k_rollout_policy_traffic<W, KT>, whose
+// selection borrows the pair-scan staging area between steps at W >= 32 (P, O = atc_policy_traffic_t, atc_policy_traffic_out_t)
+template <int W, int KT, typename P, typename O>
+static int launch_policy(const atc_scenario* s, int B, int N, int T, int hold, const atc_state_t* st, const float* obs0, const P* pol, const O* o,
+                         const atc_params_t* p, hipStream_t stream) {
     const size_t lds = lds_bytes(s, W >= 32, true);
     const int grid = step_grid(B, W);
     const StepDerived& q = derive(*p, s, 0);
-    hipLaunchKernelGGL((k_rollout_policy<W>), dim3(grid), dim3(kBlock), lds, stream, s->d_blob, s->off_grid, B, N, T, hold, *st, obs0, policy_out(o), *p, q, pol->w, pol->seed,
-                       pol->decision0, pol->flags, o->action, o->logp);
+    auto launch = [&](auto kernel, auto... tail) {
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), lds, stream, s->d_blob, s->off_grid, B, N, T, hold, *st, obs0, policy_out(o), *p, q, pol->w, pol->seed,
+                           pol->decision0, pol->flags, o->action, o->logp, tail...);
+    };
+    uint64_t* rec;
+    if constexpr (KT == 0) {
+        launch(k_rollout_policy<W>);
+        rec = &record(REC_POLICY)[__builtin_ctz(W)];
+    } else {
+        launch(k_rollout_policy_traffic<W, KT>, PolicyTrafficTail{traffic_common(s, p, KT), o->traffic});
+        rec = &record(REC_POLICY_TRAFFIC)[3 * __builtin_ctz(W) + __builtin_ctz(KT)];
+    }
     HIP_TRY(hipGetLastError());
-    ++record(REC_POLICY)[__builtin_ctz(W)];
+    ++*rec;
     return ATC_OK;
 }
-template <int W, int KT>
-static int launch_policy_traffic2(const atc_scenario* s, int B, int N, int T, int hold, const atc_state_t* st, const float* obs0, const atc_policy_traffic_t* pol,
-                                  const atc_policy_traffic_out_t* o, const atc_params_t* p, hipStream_t stream) {
-    const size_t lds = lds_bytes(s, W >= 32, true);   // (W >= 32: the selection borrows the pair-scan staging area between steps)
-    const int grid = step_grid(B, W);
-    const StepDerived& q = derive(*p, s, 0);
-    const PolicyTrafficTail tt = {traffic_common(s, p, KT), o->traffic};
-    hipLaunchKernelGGL((k_rollout_policy_traffic<W, KT>), dim3(grid), dim3(kBlock), lds, stream, s->d_blob, s->off_grid, B, N, T, hold, *st, obs0, policy_out(o), *p, q, pol->w,
-                       pol->seed, pol->decision0, pol->flags, o->action, o->logp, tt);
-    HIP_TRY(hipGetLastError());
-    ++record(REC_POLICY_TRAFFIC)[3 * __builtin_ctz(W) + __builtin_ctz(KT)];
-    return ATC_OK;
-}
-template <int W>
-static int launch_policy_traffic(const atc_scenario* s, int B, int N, int T, int hold, const atc_state_t* st, const float* obs0, const atc_policy_traffic_t* pol,
-                                 const atc_policy_traffic_out_t* o, const atc_params_t* p, hipStream_t stream) {
-    if (pol->traffic_k == 1) return launch_policy_traffic2<W, 1>(s, B, N, T, hold, st, obs0, pol, o, p, stream);
-    if (pol->traffic_k == 2) return launch_policy_traffic2<W, 2>(s, B, N, T, hold, st, obs0, pol, o, p, stream);
-    return launch_policy_traffic2<W, 4>(s, B, N, T, hold, st, obs0, pol, o, p, stream);
+// f(std::integral_constant<int, KT>) for a checked atc_policy_traffic_t.traffic_k: the compiled list lengths 1, 2, 4
+template <typename F>
+static int with_traffic_k(int k, F f) {
+    if (k == 1) return f(std::integral_constant<int, 1>());
+    if (k == 2) return f(std::integral_constant<int, 2>());
+    return f(std::integral_constant<int, 4>());
 }
 
 // The argument checks of both policy rollouts, in the header's order.  `out_type` names the output struct in the refusals; traffic_k is
@@ -2174,27 +2193,14 @@ static int launch_policy_traffic(const atc_scenario* s, int B, int N, int T, int
 template <typename P, typename O>
 static int check_policy_call(const atc_scenario_t* s, int B, int N, int T, int hold, const atc_state_t* st, const float* obs0, const P* pol, const O* out,
                              const atc_params_t* p, const char* pol_type, const char* out_type, const int32_t* traffic_k, const float* traffic) {
-    char msg[160];
     // T and hold first, before any pointer is looked at
     if (T < 1 || hold < 1) return fail_arg("need T >= 1 and hold >= 1");
     if (T % hold != 0) return fail_arg("T must be a multiple of hold (the launch takes T / hold decisions)");
-    if (!pol) {
-        snprintf(msg, sizeof msg, "null pointer: pol (%s) is required", pol_type);
-        return fail_arg(msg);
-    }
+    if (!pol) return fail_argf("null pointer: pol (%s) is required", pol_type);
     if (const int rc = check_required({{pol->w, "null pointer: pol->w (the policy's weights) is required"}, {obs0, "null pointer: obs0 is required"}})) return rc;
-    if (!out) {
-        snprintf(msg, sizeof msg, "null pointer: out (%s) is required", out_type);
-        return fail_arg(msg);
-    }
-    if (!out->obs || !out->reward || !out->done || !out->flags) {
-        snprintf(msg, sizeof msg, "null pointer: %s.obs, .reward, .done and .flags are required", out_type);
-        return fail_arg(msg);
-    }
-    if (!out->action) {
-        snprintf(msg, sizeof msg, "null pointer: %s.action is required", out_type);
-        return fail_arg(msg);
-    }
+    if (!out) return fail_argf("null pointer: out (%s) is required", out_type);
+    if (!out->obs || !out->reward || !out->done || !out->flags) return fail_argf("null pointer: %s.obs, .reward, .done and .flags are required", out_type);
+    if (!out->action) return fail_argf("null pointer: %s.action is required", out_type);
     if (pol->n_hidden != ATC_POLICY_HIDDEN) return fail_arg("pol->n_hidden must be 64 (ATC_POLICY_HIDDEN)");
     if (traffic_k && *traffic_k != 1 && *traffic_k != 2 && *traffic_k != 4) return fail_arg("pol->traffic_k must be 1, 2 or 4 (the compiled list lengths)");
     if (pol->flags & ~ATC_POLICY_DETERMINISTIC) return fail_arg("pol->flags has unknown bits (ATC_POLICY_DETERMINISTIC or 0)");

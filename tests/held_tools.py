@@ -8,6 +8,7 @@ tests/test_lookahead_plan.py).  TEST INFRASTRUCTURE ONLY; importing it needs no 
   assert_equal, scripted   bit-for-bit comparison; the scripted call sequence queries must leave untouched"""
 import ctypes as C
 import os
+import re
 
 import numpy as np
 
@@ -20,6 +21,13 @@ HEADER = os.path.join(ROOT, "include", "atc_step.h")
 LIB = os.path.join(ROOT, "atc-reinforcement-learning_amd", "atc_hip", "libatcstep.so")
 GUARD = 2          # sentinel rows in front of and behind every output
 TIME_LIMIT = 60    # look_env's default
+
+
+def struct_fields(text, name):
+    """[[type, member], ...] of `typedef struct name {...} name_t;` in the header's text, comments taken out"""
+    body = re.search(r"typedef struct %s \{(.*?)\} %s_t;" % (name, name), text, flags=re.S).group(1)
+    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+    return [" ".join(d.split()).replace("* ", " *").rsplit(" ", 1) for d in body.split(";") if d.strip()]
 
 
 # ---------------------------------------------------------------------------------------------------------------- frame-skip cases

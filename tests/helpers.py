@@ -436,3 +436,74 @@ def extension_known_answers():
     k.append(("refused targets cost 1 each and change nothing", {}, 0, [(FAR_A, (1.5, -1.2, 0.0)), (FAR_B, hold_action(FAR_B)), (near0, hold_action(near0))],
               dict(flags=[F_INVALID_V | F_INVALID_H, 0, 0], ac_reward=[-2.05, -0.05, -0.05], done=False, mask_after=0b111)))
     return k
+
+
+# ------------------------------------------------------------------------------------------ the policy rollouts' tests
+def fake_state():
+    """an atc_state_t of made-up pointers: a call that is refused never follows them"""
+    from atc_hip import lib
+    return lib.AtcState(*[0x200000 + k * 0x100000 for k in range(6)])
+
+
+def bits(a):
+    """a float array as the unsigned integers of its bit patterns (anything else as it is): equality that tells -0 from +0 and NaNs apart"""
+    a = np.ascontiguousarray(a)
+    return a.view(np.uint32) if a.dtype == np.float32 else a.view(np.uint64) if a.dtype == np.float64 else a
+
+
+def same_bytes(a, b):
+    """two dicts of tensors hold the same bytes under every name of the first"""
+    import torch
+    return all(torch.equal(a[k].contiguous().view(torch.uint8), b[k].contiguous().view(torch.uint8)) for k in a)
+
+
+def results_and_state(env, out):
+    """copies of a call's result tensors, and the env's state behind it"""
+    return {k: v.clone() for k, v in out.items()}, snapshot(env)
+
+
+POLICY_CONFIGS = {
+    "norm-shaped-reset4": dict(normalize=True, shaping=True, auto_reset=True, timestep_limit=4, spawn="lattice"),
+    "raw-unshaped-noreset": dict(normalize=False, shaping=False, auto_reset=False, timestep_limit=6000, spawn="lattice"),
+    "random-entry": dict(normalize=True, shaping=False, auto_reset=True, timestep_limit=4, spawn="random"),
+    "noise-area": dict(normalize=False, shaping=True, auto_reset=True, timestep_limit=4, spawn="lattice", noise=True),
+    "wide-heading": dict(normalize=True, shaping=True, auto_reset=True, timestep_limit=4, spawn="lattice", wide=True),
+}
+
+
+def policy_env(cfg, B, N, traffic=0):
+    """the env of one of POLICY_CONFIGS (the dict itself), synchronised"""
+    from atc_hip import layout as L
+    from atc_hip.vec_env import AtcVecEnv
+    from envs.atc import model, scenarios
+    if cfg.get("noise"):
+        import noise_sectors
+        scn = noise_sectors.noise_sector(5, 1, "LOWW")
+    else:
+        scn = scenarios.LOWWDense()
+    env = AtcVecEnv(B, N, sim_parameters=model.SimParameters(1, reward_shaping=cfg["shaping"], normalize_state=cfg["normalize"]), scenario=scn,
+                    auto_reset=cfg["auto_reset"], spawn=cfg["spawn"], seed=11, grid_cell=0.5, timestep_limit=cfg["timestep_limit"],
+                    sep_nm=5.0 if N <= 8 else 13.0 if N <= 16 else 3.0, traffic=traffic)
+    if cfg.get("wide"):      # a heading beyond the 32-bit field's (-76, 436) deg, placed in the first and the last aircraft
+        env.set_phi(0, 1000.0)
+        env.set_phi(B * N - 1, -700.0)
+        env.observe()
+        assert int(env.phi_fix[0]) == L.I32_MAX and int(env.phi_fix[B * N - 1]) == L.I32_MIN
+    env.synchronize()
+    return env
+
+
+def policy_one_env(B=40, N=16, cfg="norm-shaped-reset4", traffic=0):
+    return policy_env(POLICY_CONFIGS[cfg], B, N, traffic)
+
+
+def decision_inputs(r, T, hold, BN):
+    """x [T / hold, B N, 10]: what decision b saw — obs0, then the kernel's own stored observation of step b hold - 1"""
+    rows = [r["obs0"]] + [r["A"]["obs"][b * hold - 1].reshape(BN, 10) for b in range(1, T // hold)]
+    return np.stack(rows)
+
+
+def draw_indices(decision0, T, hold, BN):
+    """(decision, aircraft slot, component) of every draw of T / hold decisions, broadcastable to [T / hold, B N, 3]"""
+    dec = (decision0 + np.arange(T // hold, dtype=np.int64))[:, None, None]
+    return dec, np.arange(BN)[None, :, None], np.arange(3)[None, None, :]

@@ -3,6 +3,8 @@ layout mirror agrees with the header's constants.  (No compute call is made here
 import ctypes
 import os
 import re
+import shutil
+import subprocess
 
 import pytest
 
@@ -80,6 +82,46 @@ def test_struct_mirrors_have_header_field_order():
     assert fields("atc_out") == list(binding.OUT_FIELDS)
     assert fields("atc_params") == [f[0] for f in binding.AtcParams._fields_]
     assert ctypes.sizeof(binding.AtcParams) == 48
+
+
+# A toy kernel whose list has what the real ones have: an 8-byte pointer, an odd number of ints (so the struct behind them is padded to its
+# 8), a struct of pointers, a struct with alignas(64), a pointer and a trailing 8-aligned struct.  The kernarg segment packs the list flat:
+# `tt` lies at 200, directly behind `logp` — a struct that nested the parameters in front of it would be padded to its alignment of 64 and
+# name 256 (k_rollout_policy_traffic's 744 against 768).
+KERNARG_PROBE = r"""
+#include "atc_kernarg.h"
+struct Ptrs { float* a; double* b; int* c; };
+struct alignas(64) Wide { float v[20]; };
+struct Tail { double d; float* p; };
+__global__ void k_toy(const float* __restrict__ blob, int a, int b, int c, Ptrs st, Wide q, float* __restrict__ logp, Tail tt) {}
+struct Head { const float* blob; int a, b, c; Ptrs st; Wide q; float* logp; };
+struct Nested { Head h; Tail tt; };
+struct Flat { const float* blob; int a, b, c; Ptrs st; Wide q; float* logp; Tail tt; };
+typedef KernArgs<decltype(k_toy)> A;
+static_assert(A::count == 8 && A::at<0>() == 0 && A::at<1>() == 8 && A::at<2>() == 12 && A::at<3>() == 16, "pointer, then three ints");
+static_assert(A::at<4>() == 24 && A::of<Ptrs>() == 24, "a struct of pointers behind an odd number of ints is padded to its 8");
+static_assert(A::at<5>() == 64 && A::of<Wide>() == 64 && sizeof(Wide) == 128, "alignas(64)");
+static_assert(A::at<6>() == 192 && A::of<float*>() == 192 && A::of<int>() == 8, "the FIRST parameter of a type; const float* is another type");
+static_assert(A::last() == 200 && A::at<7>() == 200 && A::of<Tail>() == 200, "the last parameter lies directly behind logp ...");
+static_assert(offsetof(Nested, tt) == 256 && offsetof(Flat, tt) == 200, "... where a flat struct has it, not where a nested one would");
+#ifdef ASK_FOR_A_MISSING_TYPE
+static_assert(A::of<double>() == 0, "never evaluated: the list has no double");
+#endif
+"""
+
+
+def test_kernarg_offsets_follow_the_parameter_list(tmp_path):
+    """csrc/atc_kernarg.h alone, on a toy kernel: the offsets the kernarg rules give, and asking for a type the list lacks does not compile"""
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    if not (os.path.exists(hipcc) or shutil.which(hipcc)):
+        pytest.skip("no hipcc here")
+    src = tmp_path / "kernarg_probe.hip"
+    src.write_text(KERNARG_PROBE)
+    cmd = [hipcc, "--offload-arch=gfx950", "-std=c++17", "-fsyntax-only", "-I", os.path.join(ROOT, "atc-reinforcement-learning_amd", "csrc"), str(src)]
+    ok = subprocess.run(cmd, capture_output=True, text=True)
+    assert ok.returncode == 0, ok.stderr
+    bad = subprocess.run(cmd + ["-DASK_FOR_A_MISSING_TYPE"], capture_output=True, text=True)
+    assert bad.returncode != 0 and "the kernel has no parameter of that type" in bad.stderr, bad.stderr
 
 
 def test_product_refuses_to_run_without_gpu():

@@ -23,7 +23,7 @@ import pytest
 import helpers as H
 import policy_ref as P
 from atc_hip import layout as L
-from held_tools import HEADER, LIB
+from held_tools import HEADER, LIB, struct_fields
 
 NAMES = ("atc_rollout_policy", "atc_rollout_policy_launch_counts")
 FAKE = C.c_void_p(0x100000)     # a made-up pointer: a call that is refused never follows it
@@ -47,12 +47,6 @@ def test_exports_and_one_kernel_per_width():
         assert b"_Z16k_rollout_policyILi%dEEv" % w in blob, w
 
 
-def _struct_fields(text, name):
-    body = re.search(r"typedef struct %s \{(.*?)\} %s_t;" % (name, name), text, flags=re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    return [" ".join(d.split()).replace("* ", " *").rsplit(" ", 1) for d in body.split(";") if d.strip()]
-
-
 def test_header_constants_structs_and_argtypes():
     from atc_hip import lib, policy
     text = open(HEADER).read()
@@ -64,11 +58,11 @@ def test_header_constants_structs_and_argtypes():
     assert L.ABI_VERSION == 22 and define("ATC_ABI_VERSION") == 22          # a new entry point: the ABI number stays
     ctype = {"const float": C.c_void_p, "float": C.c_void_p, "uint8_t": C.c_void_p, "uint16_t": C.c_void_p}
     scalar = {"int32_t": C.c_int32, "uint32_t": C.c_uint32, "uint64_t": C.c_uint64}
-    pol = _struct_fields(text, "atc_policy")
+    pol = struct_fields(text, "atc_policy")
     assert [f[1].lstrip("*") for f in pol] == list(lib.POLICY_FIELDS) == [f[0] for f in lib.AtcPolicy._fields_]
     assert [ctype[f[0]] if f[1].startswith("*") else scalar[f[0]] for f in pol] == [f[1] for f in lib.AtcPolicy._fields_]
     assert C.sizeof(lib.AtcPolicy) == 32 and lib.AtcPolicy.seed.offset == 16 and lib.AtcPolicy.decision0.offset == 24
-    out = _struct_fields(text, "atc_policy_out")
+    out = struct_fields(text, "atc_policy_out")
     assert all(f[1].startswith("*") for f in out)
     assert [f[1].lstrip("*") for f in out] == list(lib.POLICY_OUT_FIELDS) == [f[0] for f in lib.AtcPolicyOut._fields_]
     assert C.sizeof(lib.AtcPolicyOut) == 48
@@ -91,11 +85,6 @@ def _call(h, T=1, hold=1, B=1, N=1, s=None, st=None, obs0=None, pol=None, out=No
     return h.atc_rollout_policy(s, B, N, T, hold, st, obs0, pol, out, p, None)
 
 
-def _fake_state():
-    from atc_hip import lib
-    return lib.AtcState(*[0x200000 + k * 0x100000 for k in range(6)])
-
-
 def test_refusal_order_without_a_gpu():
     from atc_hip import lib
     h = lib.load()
@@ -104,7 +93,7 @@ def test_refusal_order_without_a_gpu():
     at = lambda k: 0x1000000 * (k + 1)      # noqa: E731
     pol = lib.AtcPolicy(at(1), 64, 0, 0, 0, 0)
     out = lib.AtcPolicyOut(at(2), at(3), at(4), at(5), at(6), None)
-    st, p = _fake_state(), lib.make_params()
+    st, p = H.fake_state(), lib.make_params()
     ok = dict(s=FAKE, st=C.byref(st), obs0=C.c_void_p(at(7)), pol=C.byref(pol), out=C.byref(out), p=C.byref(p))
     # 1. T and hold, before any pointer is looked at
     for T, hold in ((0, 1), (-1, 1), (1, 0), (4, -2), (0, 0)):
@@ -140,7 +129,7 @@ def test_refusal_order_without_a_gpu():
         assert _call(h, B=0, **dict(ok, **kw)) == -1 and err().endswith(b": null pointer")
     for B, N in ((0, 1), (-1, 1), (1, 0), (1, 65)):
         assert _call(h, B=B, N=N, **dict(ok, p=C.byref(dis))) == -1 and b"B >= 1" in err()       # (before ATC_M_DISCRETE)
-    hole = _fake_state()
+    hole = H.fake_state()
     hole.stats = None
     assert _call(h, **dict(ok, st=C.byref(hole), p=C.byref(dis))) == -1 and b"null field" in err()
     assert _call(h, B=1 << 21, N=64, **dict(ok, p=C.byref(dis))) == -1 and b"too large" in err()
@@ -253,13 +242,7 @@ def test_z_is_a_gaussian_over_a_million_draws():
 
 # ---------------------------------------------------------------------------------------------------------------- GPU: the runs
 SHAPES = ((3, 1), (7, 5), (40, 16), (4, 64))      # idle lanes at N = 5; three workgroups with a partial last one at 640 slots
-CONFIGS = {
-    "norm-shaped-reset4": dict(normalize=True, shaping=True, auto_reset=True, timestep_limit=4, spawn="lattice"),
-    "raw-unshaped-noreset": dict(normalize=False, shaping=False, auto_reset=False, timestep_limit=6000, spawn="lattice"),
-    "random-entry": dict(normalize=True, shaping=False, auto_reset=True, timestep_limit=4, spawn="random"),
-    "noise-area": dict(normalize=False, shaping=True, auto_reset=True, timestep_limit=4, spawn="lattice", noise=True),
-    "wide-heading": dict(normalize=True, shaping=True, auto_reset=True, timestep_limit=4, spawn="lattice", wide=True),
-}
+CONFIGS = H.POLICY_CONFIGS
 RUNS = ((6, 1), (6, 3), (1, 1))                   # (T, hold)
 # variant -> (weights' gain, zero head, log_std, deterministic).  "z": mu is exactly 0 and sigma exactly 1, so the stored u IS z
 VARIANTS = {"z": (1.0, True, (0.0, 0.0, 0.0), False), "det1": (1.0, False, (-0.5, -1.0, 0.0), True), "det8": (8.0, False, (-0.5, -1.0, 0.0), True),
@@ -274,33 +257,13 @@ def _weights(variant):
     return P.random_weights(np.random.default_rng([17, int(gain)]), gain, log_std, zero_head)
 
 
-def _make_env(cfg, B, N):
-    from atc_hip.vec_env import AtcVecEnv
-    from envs.atc import model, scenarios
-    if cfg.get("noise"):
-        import noise_sectors
-        scn = noise_sectors.noise_sector(5, 1, "LOWW")
-    else:
-        scn = scenarios.LOWWDense()
-    env = AtcVecEnv(B, N, sim_parameters=model.SimParameters(1, reward_shaping=cfg["shaping"], normalize_state=cfg["normalize"]), scenario=scn,
-                    auto_reset=cfg["auto_reset"], spawn=cfg["spawn"], seed=11, grid_cell=0.5, timestep_limit=cfg["timestep_limit"],
-                    sep_nm=5.0 if N <= 8 else 13.0 if N <= 16 else 3.0)
-    if cfg.get("wide"):      # a heading beyond the 32-bit field's (-76, 436) deg, placed in the first and the last aircraft
-        env.set_phi(0, 1000.0)
-        env.set_phi(B * N - 1, -700.0)
-        env.observe()
-        assert int(env.phi_fix[0]) == L.I32_MAX and int(env.phi_fix[B * N - 1]) == L.I32_MIN
-    env.synchronize()
-    return env
-
-
 @functools.lru_cache(maxsize=None)
 def _runs(cfg_name, B, N):
     """Every run of one (mode, shape): {(T, hold, variant): dict(w, obs0, A outputs, B outputs, both states, the records' gain)}, numpy."""
     import torch
     from atc_hip import lib
     cfg = CONFIGS[cfg_name]
-    A, Bv = _make_env(cfg, B, N), _make_env(cfg, B, N)
+    A, Bv = H.policy_env(cfg, B, N), H.policy_env(cfg, B, N)
     for k in H.STATE + ("obs",):
         assert torch.equal(getattr(A, k), getattr(Bv, k)), k
     snap, obs0 = H.snapshot(A), A.obs.clone()
@@ -333,11 +296,6 @@ GRID = [(c, B, N) for c in CONFIGS for B, N in SHAPES]
 _grid = pytest.mark.parametrize("cfg,B,N", GRID, ids=["%s-%dx%d" % g for g in GRID])
 
 
-def _bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint32) if a.dtype == np.float32 else a.view(np.uint64) if a.dtype == np.float64 else a
-
-
 @pytest.mark.gpu
 @_grid
 def test_dynamics_equal_rollout_on_the_clamped_actions(cfg, B, N):
@@ -345,9 +303,9 @@ def test_dynamics_equal_rollout_on_the_clamped_actions(cfg, B, N):
     for (T, hold, variant), r in _runs(cfg, B, N).items():
         tag = (cfg, B, N, T, hold, variant)
         for k in OUT_KEYS:
-            assert np.array_equal(_bits(r["A"][k]), _bits(r["B"][k])), (tag, k, int((_bits(r["A"][k]) != _bits(r["B"][k])).sum()))
+            assert np.array_equal(H.bits(r["A"][k]), H.bits(r["B"][k])), (tag, k, int((H.bits(r["A"][k]) != H.bits(r["B"][k])).sum()))
         for k in STATE5:
-            assert np.array_equal(_bits(r["stA"][k]), _bits(r["stB"][k])), (tag, k)
+            assert np.array_equal(H.bits(r["stA"][k]), H.bits(r["stB"][k])), (tag, k)
         if CONFIGS[cfg].get("wide"):        # the side record of an aircraft whose heading field is still saturated: its exact counts
             for i in np.nonzero(np.isin(r["stA"]["ac"][:, L.AC_PHI], (L.I32_MIN, L.I32_MAX)))[0]:
                 assert r["stA"]["phi_wide"][i, 0] == r["stB"]["phi_wide"][i, 0], (tag, i)
@@ -362,17 +320,6 @@ def test_dynamics_equal_rollout_on_the_clamped_actions(cfg, B, N):
         assert {"done", "reset inside a held block"} <= events, (cfg, B, N, events)      # (T = 6 > the time limit of 4: every env ends once)
 
 
-def _decision_inputs(r, T, hold, BN):
-    """x [T / hold, B N, 10]: what decision b saw — obs0, then the kernel's own stored observation of step b hold - 1"""
-    rows = [r["obs0"]] + [r["A"]["obs"][b * hold - 1].reshape(BN, 10) for b in range(1, T // hold)]
-    return np.stack(rows)
-
-
-def _draw_indices(T, hold, BN):
-    dec = (DECISION0 + np.arange(T // hold, dtype=np.int64))[:, None, None]
-    return dec, np.arange(BN)[None, :, None], np.arange(3)[None, None, :]
-
-
 @pytest.mark.gpu
 @_grid
 def test_z_and_logp_within_their_bars(cfg, B, N):
@@ -381,7 +328,7 @@ def test_z_and_logp_within_their_bars(cfg, B, N):
         if VARIANTS[variant][3]:
             continue
         BN = B * N
-        z_ref = P.z64(SEED, *_draw_indices(T, hold, BN))
+        z_ref = P.z64(SEED, *H.draw_indices(DECISION0, T, hold, BN))
         log_std = P.split(r["w"])["log_std"]
         lp = r["A"]["logp"].reshape(T // hold, BN).astype(np.float64)
         worst_lp = max(worst_lp, float(np.abs(lp - P.logp64(z_ref, log_std)).max()))
@@ -401,7 +348,7 @@ def test_mu_and_sampled_u_within_the_bar(cfg, B, N):
         if variant == "z":
             continue
         BN = B * N
-        x = _decision_inputs(r, T, hold, BN)
+        x = H.decision_inputs(r, T, hold, BN)
         bar, dev32 = P.mu_bar(r["w"], x)
         mu = P.mlp(r["w"], x)
         u = r["A"]["action"].reshape(T // hold, BN, 3).astype(np.float64)
@@ -410,7 +357,7 @@ def test_mu_and_sampled_u_within_the_bar(cfg, B, N):
             assert not r["A"]["logp"].any(), "deterministic: logp = 0"
         else:
             sigma = np.exp(P.split(r["w"])["log_std"].astype(np.float64))
-            err = np.abs(u - (mu + sigma * P.z64(SEED, *_draw_indices(T, hold, BN))))
+            err = np.abs(u - (mu + sigma * P.z64(SEED, *H.draw_indices(DECISION0, T, hold, BN))))
             allowed = bar + sigma * P.Z_BAR
         print("%s %dx%d T=%d hold=%d %s: float32-numpy deviation %.3g, bar %.3g, kernel deviation %.3g, max |x| %.3g"
               % (cfg, B, N, T, hold, variant, dev32, bar, float(err.max()), float(np.abs(x).max())))
@@ -420,34 +367,23 @@ def test_mu_and_sampled_u_within_the_bar(cfg, B, N):
 
 
 # ---------------------------------------------------------------------------------------------------------------- GPU: the other properties
-def _one_env(B=40, N=16, cfg="norm-shaped-reset4"):
-    return _make_env(CONFIGS[cfg], B, N)
-
-
-def _all(env, out):
-    return {k: v.clone() for k, v in out.items()}, H.snapshot(env)
-
-
-def _same(a, b):
-    import torch
-    return all(torch.equal(a[k].contiguous().view(torch.uint8), b[k].contiguous().view(torch.uint8)) for k in a)
 
 
 @pytest.mark.gpu
 def test_repeatable_seeded_and_splittable():
     import torch
-    env = _one_env()
+    env = H.policy_one_env()
     w = torch.as_tensor(_weights("sampled"), device=env.device)
     snap, obs0 = H.snapshot(env), env.obs.clone()
 
     def run(T, hold=2, **kw):
-        return _all(env, env.rollout_policy(w, T, hold=hold, **kw))
+        return H.results_and_state(env, env.rollout_policy(w, T, hold=hold, **kw))
 
     one, st_one = run(8, seed=5, decision0=10)
     H.restore(env, snap)
     env.obs.copy_(obs0)
     two, st_two = run(8, seed=5, decision0=10)
-    assert _same(one, two) and _same(st_one, st_two), "two runs from the same state differ"
+    assert H.same_bytes(one, two) and H.same_bytes(st_one, st_two), "two runs from the same state differ"
     for kw in (dict(seed=6, decision0=10), dict(seed=5, decision0=11)):
         H.restore(env, snap)
         other, _ = run(8, obs0=obs0, **kw)
@@ -458,25 +394,25 @@ def test_repeatable_seeded_and_splittable():
     h2, st_h = run(4, seed=5, decision0=12, obs0=h1["obs"][-1])
     for k in one:
         assert torch.equal(torch.cat([h1[k], h2[k]]).view(torch.uint8), one[k].view(torch.uint8)), k
-    assert _same(st_h, st_one)
+    assert H.same_bytes(st_h, st_one)
     # deterministic: logp = 0, no noise: another seed gives the same words
     H.restore(env, snap)
     d1, _ = run(4, seed=1, deterministic=True, obs0=obs0)
     H.restore(env, snap)
     d2, _ = run(4, seed=2, deterministic=True, obs0=obs0)
-    assert _same(d1, d2) and not d1["logp"].any()
+    assert H.same_bytes(d1, d2) and not d1["logp"].any()
     # obs0 defaults to the env's bound observation tensor
     H.restore(env, snap)
     env.obs.copy_(obs0)
     d3, _ = run(4, seed=1, deterministic=True)
-    assert _same(d1, d3)
+    assert H.same_bytes(d1, d3)
     env.close()
 
 
 @pytest.mark.gpu
 def test_nan_weights_fly_minus_one_and_keep_the_state_finite():
     import torch
-    A, Bv = _one_env(7, 5), _one_env(7, 5)
+    A, Bv = H.policy_one_env(7, 5), H.policy_one_env(7, 5)
     w = torch.full((L.POLICY_WORDS,), float("nan"), device=A.device)
     out = A.rollout_policy(w, 6, hold=3, seed=3)
     assert bool(torch.isnan(out["action"]).all())
@@ -496,7 +432,7 @@ def test_refusals_on_the_device():
     the overlap rule — each with every later one wrong as well; nothing is launched and no record moves"""
     import torch
     from atc_hip import lib
-    env = _one_env(7, 5)
+    env = H.policy_one_env(7, 5)
     h, err = lib.load(), lib.load().atc_last_error
     B, N, T = env.B, env.N, 4
     w = torch.zeros(L.POLICY_WORDS, device=env.device)

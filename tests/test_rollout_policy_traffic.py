@@ -25,7 +25,7 @@ import policy_ref as P
 import policy_traffic_ref as PT
 import traffic_ref as R
 from atc_hip import layout as L
-from held_tools import HEADER, LIB
+from held_tools import HEADER, LIB, struct_fields
 
 NAMES = ("atc_rollout_policy_traffic", "atc_rollout_policy_traffic_launch_counts")
 FAKE = C.c_void_p(0x100000)     # a made-up pointer: a call that is refused never follows it
@@ -53,12 +53,6 @@ def test_exports_and_one_kernel_per_width_and_k():
     assert {int(w) for w in re.findall(r"\bk_rollout_policy<(\d+)>\(", text)} == set(WIDTHS)
 
 
-def _struct_fields(text, name):
-    body = re.search(r"typedef struct %s \{(.*?)\} %s_t;" % (name, name), text, flags=re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    return [" ".join(d.split()).replace("* ", " *").rsplit(" ", 1) for d in body.split(";") if d.strip()]
-
-
 def test_header_constants_structs_and_argtypes():
     from atc_hip import lib, policy
     text = open(HEADER).read()
@@ -81,15 +75,15 @@ def test_header_constants_structs_and_argtypes():
         assert off["W1"][1] == (64, L.policy_in(k)) and off["b1"][0] == 64 * L.policy_in(k)
     ctype = {"const float": C.c_void_p, "float": C.c_void_p, "uint8_t": C.c_void_p, "uint16_t": C.c_void_p}
     scalar = {"int32_t": C.c_int32, "uint32_t": C.c_uint32, "uint64_t": C.c_uint64}
-    pol = _struct_fields(text, "atc_policy_traffic")
+    pol = struct_fields(text, "atc_policy_traffic")
     assert [f[1].lstrip("*") for f in pol] == list(lib.POLICY_TRAFFIC_FIELDS) == [f[0] for f in lib.AtcPolicyTraffic._fields_]
-    assert [f[1].lstrip("*") for f in pol] == [f[1].lstrip("*") for f in _struct_fields(text, "atc_policy")] + ["traffic_k"]
+    assert [f[1].lstrip("*") for f in pol] == [f[1].lstrip("*") for f in struct_fields(text, "atc_policy")] + ["traffic_k"]
     assert [ctype[f[0]] if f[1].startswith("*") else scalar[f[0]] for f in pol] == [f[1] for f in lib.AtcPolicyTraffic._fields_]
     assert C.sizeof(lib.AtcPolicyTraffic) == 40 and lib.AtcPolicyTraffic.seed.offset == 16 and lib.AtcPolicyTraffic.traffic_k.offset == 32
-    out = _struct_fields(text, "atc_policy_traffic_out")
+    out = struct_fields(text, "atc_policy_traffic_out")
     assert all(f[1].startswith("*") for f in out)
     assert [f[1].lstrip("*") for f in out] == list(lib.POLICY_TRAFFIC_OUT_FIELDS) == [f[0] for f in lib.AtcPolicyTrafficOut._fields_]
-    assert [f[1].lstrip("*") for f in out] == [f[1].lstrip("*") for f in _struct_fields(text, "atc_policy_out")] + ["traffic"]
+    assert [f[1].lstrip("*") for f in out] == [f[1].lstrip("*") for f in struct_fields(text, "atc_policy_out")] + ["traffic"]
     assert C.sizeof(lib.AtcPolicyTrafficOut) == 56
     decl = re.search(r"^int atc_rollout_policy_traffic\((.*?)\);", text, flags=re.S | re.M).group(1)
     decl = re.sub(r"/\*.*?\*/", "", decl, flags=re.S)
@@ -110,11 +104,6 @@ def _call(h, T=1, hold=1, B=1, N=1, s=None, st=None, obs0=None, pol=None, out=No
     return h.atc_rollout_policy_traffic(s, B, N, T, hold, st, obs0, pol, out, p, None)
 
 
-def _fake_state():
-    from atc_hip import lib
-    return lib.AtcState(*[0x200000 + k * 0x100000 for k in range(6)])
-
-
 def test_refusal_order_without_a_gpu():
     from atc_hip import lib
     h = lib.load()
@@ -123,7 +112,7 @@ def test_refusal_order_without_a_gpu():
     at = lambda k: 0x1000000 * (k + 1)      # noqa: E731
     pol = lib.AtcPolicyTraffic(at(1), 64, 0, 0, 0, 0, 4)
     out = lib.AtcPolicyTrafficOut(at(2), at(3), at(4), at(5), at(6), None, None)
-    st, p = _fake_state(), lib.make_params()
+    st, p = H.fake_state(), lib.make_params()
     ok = dict(s=FAKE, st=C.byref(st), obs0=C.c_void_p(at(7)), pol=C.byref(pol), out=C.byref(out), p=C.byref(p))
     # 1. T and hold, before any pointer is looked at
     for T, hold in ((0, 1), (-1, 1), (1, 0), (4, -2), (0, 0)):
@@ -163,7 +152,7 @@ def test_refusal_order_without_a_gpu():
         assert _call(h, B=0, **dict(ok, **kw)) == -1 and err().endswith(b": null pointer")
     for B, N in ((0, 1), (-1, 1), (1, 0), (1, 65)):
         assert _call(h, B=B, N=N, **dict(ok, p=C.byref(dis))) == -1 and b"B >= 1" in err()       # (before ATC_M_DISCRETE)
-    hole = _fake_state()
+    hole = H.fake_state()
     hole.stats = None
     assert _call(h, **dict(ok, st=C.byref(hole), p=C.byref(dis))) == -1 and b"null field" in err()
     assert _call(h, B=1 << 21, N=64, **dict(ok, p=C.byref(dis))) == -1 and b"too large" in err()
@@ -296,13 +285,7 @@ def test_widen_keeps_the_ten_input_policy():
 
 # ---------------------------------------------------------------------------------------------------------------- GPU: the runs
 SHAPES = ((3, 1), (5, 2), (7, 3), (9, 8), (40, 16), (5, 32), (3, 33), (4, 64))      # ragged B; (40, 16): three workgroups, the last one partial
-CONFIGS = {
-    "norm-shaped-reset4": dict(normalize=True, shaping=True, auto_reset=True, timestep_limit=4, spawn="lattice"),
-    "raw-unshaped-noreset": dict(normalize=False, shaping=False, auto_reset=False, timestep_limit=6000, spawn="lattice"),
-    "random-entry": dict(normalize=True, shaping=False, auto_reset=True, timestep_limit=4, spawn="random"),
-    "noise-area": dict(normalize=False, shaping=True, auto_reset=True, timestep_limit=4, spawn="lattice", noise=True),
-    "wide-heading": dict(normalize=True, shaping=True, auto_reset=True, timestep_limit=4, spawn="lattice", wide=True),
-}
+CONFIGS = H.POLICY_CONFIGS
 FULL = {(40, 16): 4, (4, 64): 2}                  # the five-way product runs at these (shape, K) only
 RUNS = ((6, 1), (6, 3), (1, 1))                   # (T, hold)
 # variant -> (weights' gain, zero head, log_std, deterministic).  "z": mu is exactly 0 and sigma exactly 1, so the stored u IS z
@@ -335,31 +318,6 @@ def _weights(variant, K):
     return PT.random_weights(np.random.default_rng([17, int(gain), K]), K, gain, log_std, zero_head)
 
 
-def _make_env(cfg, B, N, traffic=0):
-    from atc_hip.vec_env import AtcVecEnv
-    from envs.atc import model, scenarios
-    if cfg.get("noise"):
-        import noise_sectors
-        scn = noise_sectors.noise_sector(5, 1, "LOWW")
-    else:
-        scn = scenarios.LOWWDense()
-    env = AtcVecEnv(B, N, sim_parameters=model.SimParameters(1, reward_shaping=cfg["shaping"], normalize_state=cfg["normalize"]), scenario=scn,
-                    auto_reset=cfg["auto_reset"], spawn=cfg["spawn"], seed=11, grid_cell=0.5, timestep_limit=cfg["timestep_limit"],
-                    sep_nm=5.0 if N <= 8 else 13.0 if N <= 16 else 3.0, traffic=traffic)
-    if cfg.get("wide"):      # a heading beyond the 32-bit field's (-76, 436) deg, placed in the first and the last aircraft
-        env.set_phi(0, 1000.0)
-        env.set_phi(B * N - 1, -700.0)
-        env.observe()
-        assert int(env.phi_fix[0]) == L.I32_MAX and int(env.phi_fix[B * N - 1]) == L.I32_MIN
-    env.synchronize()
-    return env
-
-
-def _bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint32) if a.dtype == np.float32 else a.view(np.uint64) if a.dtype == np.float64 else a
-
-
 def _put_lattice(envs, B, N):
     """traffic_ref's clustered family — an 8 x 8 integer-nm lattice, exact d^2 ties, coincident aircraft, some WIDE headings, masks with
     0 .. N bits — written into the live state of every env of `envs` alike"""
@@ -387,7 +345,7 @@ def _runs(cfg_name, B, N, K, lattice=False):
     import torch
     from atc_hip import lib
     cfg = CONFIGS[cfg_name]
-    A, Bv = _make_env(cfg, B, N), _make_env(cfg, B, N, traffic=K)
+    A, Bv = H.policy_env(cfg, B, N), H.policy_env(cfg, B, N, traffic=K)
     if lattice:
         _put_lattice((A, Bv), B, N)
     for k in H.STATE + ("obs",):
@@ -418,8 +376,8 @@ def _runs(cfg_name, B, N, K, lattice=False):
                 Bv.synchronize()
                 for k in OUT_KEYS:
                     got = out[k][b * hold:(b + 1) * hold]
-                    if not np.array_equal(_bits(got.cpu().numpy()), _bits(ref[k].cpu().numpy())):
-                        mismatch.append((k, b, int((_bits(got.cpu().numpy()) != _bits(ref[k].cpu().numpy())).sum())))
+                    if not np.array_equal(H.bits(got.cpu().numpy()), H.bits(ref[k].cpu().numpy())):
+                        mismatch.append((k, b, int((H.bits(got.cpu().numpy()) != H.bits(ref[k].cpu().numpy())).sum())))
             res[(T, hold, variant)] = dict(
                 w=w, obs0=obs0.cpu().numpy().reshape(B * N, 10), A={k: v.cpu().numpy() for k, v in out.items()}, mismatch=mismatch,
                 stA={k: getattr(A, k).cpu().numpy() for k in H.STATE}, stB={k: getattr(Bv, k).cpu().numpy() for k in H.STATE},
@@ -435,7 +393,7 @@ def _check_traffic_and_dynamics(runs, tag0, B, N, K, from_reset):
         tag = tag0 + (T, hold, variant)
         assert not r["mismatch"], (tag, r["mismatch"])
         for k in STATE5:
-            assert np.array_equal(_bits(r["stA"][k]), _bits(r["stB"][k])), (tag, k)
+            assert np.array_equal(H.bits(r["stA"][k]), H.bits(r["stB"][k])), (tag, k)
         for i in np.nonzero(np.isin(r["stA"]["ac"][:, L.AC_PHI], (L.I32_MIN, L.I32_MAX)))[0]:      # the exact counts of a heading still saturated
             assert r["stA"]["phi_wide"][i, 0] == r["stB"]["phi_wide"][i, 0], (tag, i)
         # only the new record moved, in slot (W, K)
@@ -471,13 +429,8 @@ def test_from_a_lattice_state_with_ties_and_coincident_aircraft(B, N, K):
 
 def _decision_inputs(r, T, hold, B, N):
     """x [T / hold, B N, 10 + 7 K]: what decision b saw — obs0 or the kernel's own stored observation of step b hold - 1, and its stored records"""
-    own = np.stack([r["obs0"]] + [r["A"]["obs"][b * hold - 1].reshape(B * N, 10) for b in range(1, T // hold)])
+    own = H.decision_inputs(r, T, hold, B * N)
     return PT.input_rows(own.reshape(T // hold, B, N, 10), r["A"]["traffic"]).reshape(T // hold, B * N, -1)
-
-
-def _draw_indices(T, hold, BN):
-    dec = (DECISION0 + np.arange(T // hold, dtype=np.int64))[:, None, None]
-    return dec, np.arange(BN)[None, :, None], np.arange(3)[None, None, :]
 
 
 @pytest.mark.gpu
@@ -488,7 +441,7 @@ def test_z_and_logp_within_their_bars(cfg, B, N, K):
         if VARIANTS[variant][3]:
             continue
         BN = B * N
-        z_ref = PT.z64(SEED, *_draw_indices(T, hold, BN))
+        z_ref = PT.z64(SEED, *H.draw_indices(DECISION0, T, hold, BN))
         log_std = PT.split(r["w"], K)["log_std"]
         lp = r["A"]["logp"].reshape(T // hold, BN).astype(np.float64)
         worst_lp = max(worst_lp, float(np.abs(lp - PT.logp64(z_ref, log_std)).max()))
@@ -517,7 +470,7 @@ def test_mu_and_sampled_u_within_the_bar(cfg, B, N, K):
             assert not r["A"]["logp"].any(), "deterministic: logp = 0"
         else:
             sigma = np.exp(PT.split(r["w"], K)["log_std"].astype(np.float64))
-            err = np.abs(u - (mu + sigma * PT.z64(SEED, *_draw_indices(T, hold, BN))))
+            err = np.abs(u - (mu + sigma * PT.z64(SEED, *H.draw_indices(DECISION0, T, hold, BN))))
             allowed = bar + sigma * PT.Z_BAR
         print("%s %dx%d K=%d T=%d hold=%d %s: float32-numpy deviation %.3g, bar %.3g, kernel deviation %.3g, max |x| %.3g"
               % (cfg, B, N, K, T, hold, variant, dev32, bar, float(err.max()), float(np.abs(x).max())))
@@ -529,60 +482,49 @@ def test_mu_and_sampled_u_within_the_bar(cfg, B, N, K):
 
 
 # ---------------------------------------------------------------------------------------------------------------- GPU: the other properties
-def _one_env(B=40, N=16, cfg="norm-shaped-reset4", traffic=0):
-    return _make_env(CONFIGS[cfg], B, N, traffic)
-
-
-def _all(env, out):
-    return {k: v.clone() for k, v in out.items()}, H.snapshot(env)
-
-
-def _same(a, b):
-    import torch
-    return all(torch.equal(a[k].contiguous().view(torch.uint8), b[k].contiguous().view(torch.uint8)) for k in a)
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("B,N,K", ((40, 16, 4), (4, 64, 2)))
 def test_two_launches_of_half_equal_one(B, N, K):
     import torch
-    env = _one_env(B, N)
+    env = H.policy_one_env(B, N)
     w = torch.as_tensor(_weights("sampled", K), device=env.device)
     snap, obs0 = H.snapshot(env), env.obs.clone()
 
     def run(T, hold=2, **kw):
-        return _all(env, env.rollout_policy_traffic(w, T, K, hold=hold, **kw))
+        return H.results_and_state(env, env.rollout_policy_traffic(w, T, K, hold=hold, **kw))
 
     one, st_one = run(8, seed=5, decision0=10)
     assert set(one) == {"obs", "reward", "done", "flags", "action", "logp", "traffic"}
     H.restore(env, snap)
     env.obs.copy_(obs0)
     two, st_two = run(8, seed=5, decision0=10)
-    assert _same(one, two) and _same(st_one, st_two), "two runs from the same state differ"
+    assert H.same_bytes(one, two) and H.same_bytes(st_one, st_two), "two runs from the same state differ"
     H.restore(env, snap)
     h1, _ = run(4, seed=5, decision0=10, obs0=obs0)
     h2, st_h = run(4, seed=5, decision0=12, obs0=h1["obs"][-1])
     for k in one:
         assert torch.equal(torch.cat([h1[k], h2[k]]).view(torch.uint8), one[k].view(torch.uint8)), k
-    assert _same(st_h, st_one)
+    assert H.same_bytes(st_h, st_one)
     assert bool(one["done"].any()), "no env auto-reset inside the launch"
     # out= may carry the buffers; "traffic" None stores no records and changes nothing else
     H.restore(env, snap)
     bufs = {k: torch.full_like(v, 7) for k, v in one.items()}
     got = env.rollout_policy_traffic(w, 8, K, hold=2, seed=5, decision0=10, obs0=obs0, out=bufs)
-    assert got is bufs and _same(bufs, one)
+    assert got is bufs and H.same_bytes(bufs, one)
     H.restore(env, snap)
     bufs = {k: torch.full_like(v, 7) for k, v in one.items()}
     guard = bufs.pop("traffic")
     env.rollout_policy_traffic(w, 8, K, hold=2, seed=5, decision0=10, obs0=obs0, out=dict(bufs, traffic=None))
-    assert _same(bufs, {k: one[k] for k in bufs}) and _same(H.snapshot(env), st_one) and bool((guard == 7).all())
+    assert H.same_bytes(bufs, {k: one[k] for k in bufs}) and H.same_bytes(H.snapshot(env), st_one) and bool((guard == 7).all())
     # traffic=0 is rollout_policy
     w10 = torch.as_tensor(P.random_weights(np.random.default_rng(4)), device=env.device)
     H.restore(env, snap)
-    a, _ = _all(env, env.rollout_policy_traffic(w10, 4, 0, hold=2, seed=5, obs0=obs0))
+    a, _ = H.results_and_state(env, env.rollout_policy_traffic(w10, 4, 0, hold=2, seed=5, obs0=obs0))
     H.restore(env, snap)
-    b, _ = _all(env, env.rollout_policy(w10, 4, hold=2, seed=5, obs0=obs0))
-    assert set(a) == set(b) and _same(a, b)
+    b, _ = H.results_and_state(env, env.rollout_policy(w10, 4, hold=2, seed=5, obs0=obs0))
+    assert set(a) == set(b) and H.same_bytes(a, b)
     env.close()
 
 
@@ -592,14 +534,14 @@ def test_the_traffic_columns_are_what_the_traffic_changes(B, N, K, cfg):
     """W1's 7 K traffic columns zero and the rest a 10-input policy's: rollout_policy with that policy, within the mu bar (the summation may
     differ); only the traffic columns changed: another action for N >= 2, the same words for N = 1 (no record is ever present)"""
     import torch
-    env = _one_env(B, N, cfg)
+    env = H.policy_one_env(B, N, cfg)
     snap, obs0 = H.snapshot(env), env.obs.clone()
     w10 = P.random_weights(np.random.default_rng([31, K]))
     dev = lambda w: torch.as_tensor(w, device=env.device)      # noqa: E731
     T, hold = 4, 2
-    base = _all(env, env.rollout_policy(dev(w10), T, hold=hold, seed=9, obs0=obs0))[0]
+    base = H.results_and_state(env, env.rollout_policy(dev(w10), T, hold=hold, seed=9, obs0=obs0))[0]
     H.restore(env, snap)
-    zero = _all(env, env.rollout_policy_traffic(dev(PT.widen(w10, K)), T, K, hold=hold, seed=9, obs0=obs0))[0]
+    zero = H.results_and_state(env, env.rollout_policy_traffic(dev(PT.widen(w10, K)), T, K, hold=hold, seed=9, obs0=obs0))[0]
     # decision 0 saw the same ten words in both; later ones may follow a trajectory that differs by the bar: compared on decision 0, and
     # on every decision whose input rows are equal
     own = [obs0.reshape(B * N, 10).cpu().numpy()] + [base["obs"][b * hold - 1].reshape(B * N, 10).cpu().numpy() for b in range(1, T // hold)]
@@ -617,9 +559,9 @@ def test_the_traffic_columns_are_what_the_traffic_changes(B, N, K, cfg):
     print("%dx%d K=%d %s: zero traffic columns against rollout_policy: max |du| = %.3g" % (B, N, K, cfg, worst))
     cols = np.random.default_rng(6).normal(0.0, 1.0, (64, 7 * K)).astype(np.float32)
     H.restore(env, snap)
-    full = _all(env, env.rollout_policy_traffic(dev(PT.widen(w10, K, cols)), T, K, hold=hold, seed=9, obs0=obs0))[0]
+    full = H.results_and_state(env, env.rollout_policy_traffic(dev(PT.widen(w10, K, cols)), T, K, hold=hold, seed=9, obs0=obs0))[0]
     if N == 1:
-        assert _same(full, zero)
+        assert H.same_bytes(full, zero)
         assert not bool(full["traffic"][..., 0].any())
     else:
         assert not torch.equal(full["action"][0], zero["action"][0])
@@ -630,7 +572,7 @@ def test_the_traffic_columns_are_what_the_traffic_changes(B, N, K, cfg):
 @pytest.mark.gpu
 def test_nan_weights_fly_minus_one_and_keep_the_state_finite():
     import torch
-    A, Bv = _one_env(7, 5), _one_env(7, 5)
+    A, Bv = H.policy_one_env(7, 5), H.policy_one_env(7, 5)
     w = torch.full((L.policy_words(2),), float("nan"), device=A.device)
     out = A.rollout_policy_traffic(w, 6, 2, hold=3, seed=3)
     assert bool(torch.isnan(out["action"]).all())
@@ -651,7 +593,7 @@ def test_refusals_on_the_device():
     out->obs, then out->traffic against obs0, out->obs and the state arrays; nothing is launched and no record moves"""
     import torch
     from atc_hip import lib
-    env = _one_env(7, 5)
+    env = H.policy_one_env(7, 5)
     h, err = lib.load(), lib.load().atc_last_error
     B, N, T, K = env.B, env.N, 4, 2
     w = torch.zeros(L.policy_words(K), device=env.device)
