@@ -118,6 +118,12 @@ ROLLOUT_POLICY_TRAFFIC_LAUNCH_SLOTS = 21
 GAE_PER_DECISION, GAE_REWARD_PER_COLUMN = 1, 2
 GAE_MAX_NV = 64
 GAE_LAUNCH_SLOTS = 1
+# policy rollout with episode ends (include/atc_step.h: atc_rollout_policy_ends): TERM_ENDED is the bit of term_flags that says the block has
+# an ending step (the flag bits of the env's aircraft at that step are OR-ed below it); its record counts by width and K in (0, 1, 2, 4).
+# atc_gae_boot has one slot.
+TERM_ENDED = 0x8000
+ROLLOUT_POLICY_ENDS_LAUNCH_SLOTS = 28
+GAE_BOOT_LAUNCH_SLOTS = 1
 
 
 def policy_in(traffic=0):

@@ -107,6 +107,14 @@ class AtcPolicyTrafficOut(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in POLICY_TRAFFIC_OUT_FIELDS]
 
 
+POLICY_ENDS_OUT_FIELDS = POLICY_TRAFFIC_OUT_FIELDS + ("term_obs", "term_flags", "control")
+
+
+class AtcPolicyEndsOut(C.Structure):
+    """atc_policy_ends_out_t"""
+    _fields_ = [(n, C.c_void_p) for n in POLICY_ENDS_OUT_FIELDS]
+
+
 GAE_FIELDS = ("gamma", "lam", "flags", "_pad")
 
 
@@ -139,7 +147,8 @@ EXPORTS = ("atc_abi_version", "atc_last_error", "atc_launch_counts", "atc_host_m
            "atc_plan_draw", "atc_lookahead_plan_sampled", "atc_plan_sampled_launch_counts", "atc_plan_draw_launch_counts",
            "atc_plan_refit", "atc_plan_refit_launch_counts", "atc_plan_score", "atc_plan_score_launch_counts",
            "atc_rollout_policy", "atc_rollout_policy_launch_counts", "atc_rollout_policy_traffic", "atc_rollout_policy_traffic_launch_counts",
-           "atc_gae", "atc_gae_launch_counts")
+           "atc_gae", "atc_gae_launch_counts", "atc_rollout_policy_ends", "atc_rollout_policy_ends_launch_counts", "atc_gae_boot",
+           "atc_gae_boot_launch_counts")
 
 def load():
     """Loads libatcstep.so; raises (never falls back) when it has not been built."""
@@ -194,6 +203,9 @@ def load():
     lib.atc_rollout_policy_traffic.argtypes = [vp, ci, ci, ci, ci, C.POINTER(AtcState), vp, C.POINTER(AtcPolicyTraffic), C.POINTER(AtcPolicyTrafficOut),
                                                C.POINTER(AtcParams), vp]
     lib.atc_gae.argtypes = [vp, ci, ci, ci, ci, vp, vp, vp, vp, C.POINTER(AtcGae), C.POINTER(AtcGaeOut), vp]
+    lib.atc_rollout_policy_ends.argtypes = [vp, ci, ci, ci, ci, C.POINTER(AtcState), vp, C.POINTER(AtcPolicyTraffic), C.POINTER(AtcPolicyEndsOut),
+                                            C.POINTER(AtcParams), vp]
+    lib.atc_gae_boot.argtypes = [vp, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, C.POINTER(AtcGae), C.POINTER(AtcGaeOut), vp]
     for getter in LAUNCH_RECORDS:
         getattr(lib, getter).argtypes = [C.POINTER(C.c_uint64), ci]
     for name in EXPORTS:
@@ -226,6 +238,11 @@ def _width_k(slot):
     return (1 << (slot // 3), 1 << (slot % 3))
 
 
+def _width_k0(slot):
+    """(W, K) of a slot of the record of the policy rollout with episode ends: slot = 4 log2(W) + {0, 1, 2, 3 for K = 0, 1, 2, 4}"""
+    return (1 << (slot // 4), (0, 1, 2, 4)[slot % 4])
+
+
 # The library's launch records (include/atc_step.h): getter -> (slots, name of a slot: a function of the slot number, or the one
 # slot's name).  load() gives every getter its argtypes from this table; each has a wrapper below, and launch_records() reads all.
 LAUNCH_RECORDS = {
@@ -243,6 +260,8 @@ LAUNCH_RECORDS = {
     "atc_rollout_policy_launch_counts": (L.ROLLOUT_POLICY_LAUNCH_SLOTS, _width),
     "atc_rollout_policy_traffic_launch_counts": (L.ROLLOUT_POLICY_TRAFFIC_LAUNCH_SLOTS, _width_k),
     "atc_gae_launch_counts": (L.GAE_LAUNCH_SLOTS, "gae"),
+    "atc_rollout_policy_ends_launch_counts": (L.ROLLOUT_POLICY_ENDS_LAUNCH_SLOTS, _width_k0),
+    "atc_gae_boot_launch_counts": (L.GAE_BOOT_LAUNCH_SLOTS, "gae_boot"),
 }
 
 
@@ -337,6 +356,17 @@ def rollout_policy_traffic_launch_counts():
 def gae_launch_counts():
     """Launches of the advantages and returns of a collection (atc_gae) made by the calling thread so far: {"gae": n}, or {} before the first."""
     return _counts("atc_gae_launch_counts")
+
+
+def rollout_policy_ends_launch_counts():
+    """Launches of the policy rollout with episode ends (atc_rollout_policy_ends) made by the calling thread so far, by lane-group width and
+    records per aircraft (0: the ten-word policy): {(16, 0): n, ...}, zero counts left out.  Separate from the other launch records."""
+    return _counts("atc_rollout_policy_ends_launch_counts")
+
+
+def gae_boot_launch_counts():
+    """Launches of the advantages with bootstrapped truncations (atc_gae_boot) made by the calling thread so far: {"gae_boot": n}, or {}."""
+    return _counts("atc_gae_boot_launch_counts")
 
 
 def lookahead_set_mapping(candidates_per_workgroup=0):

@@ -1,8 +1,10 @@
 """A PPO collection in three calls on fixed shapes: AtcVecEnv.rollout_policy (or rollout_policy_traffic) -> one value forward ->
 AtcVecEnv.gae.  The collection loop and the advantage recurrence each run inside one launch (include/atc_step.h: atc_rollout_policy,
 atc_gae); the value network is the trainer's own and runs as one batched forward over the rows the decisions saw.
-Not covered, the trainer's: bootstrapping a time-limit done (rollout_policy does not store the terminal observation), masking aircraft
-that are not under control, advantage normalisation."""
+collect_bootstrap() also bootstraps time-limit ends (atc_rollout_policy_ends, atc_gae_boot: the terminal observations join the one
+value forward) and returns the mask of the aircraft each decision controlled.
+Not covered, the trainer's: advantage normalisation — with `control` in hand three reductions over [D, B, N] — and bootstrapping a
+traffic policy's collection: the traffic records of a terminal state are not produced."""
 from . import layout as L
 from . import policy as _policy
 
@@ -24,6 +26,15 @@ def value_rows(env, rollout, obs0, hold=1, traffic=0):
     return _policy.input_rows(own, records)
 
 
+def truncated(term_flags):
+    """[D, B] uint8 from rollout_policy_ends()'s term_flags: 1 where the block's ending step is a time-limit end — ATC_F_TIMEOUT set
+    with ATC_F_BELOW_MVA, ATC_F_OUTSIDE and ATC_F_CONFLICT clear among the env's aircraft — which gae_boot() bootstraps."""
+    import torch
+    f = term_flags.to(torch.int32)
+    hit = ((f & L.F_TIMEOUT) != 0) & ((f & (L.F_BELOW_MVA | L.F_OUTSIDE | L.F_CONFLICT)) == 0)
+    return hit.to(torch.uint8).contiguous()
+
+
 def collect(env, weights, value_fn, T, hold=1, traffic=0, gamma=0.99, lam=0.95, seed=0, decision0=0, obs0=None, per_decision=False):
     """One on-policy collection of T steps, D = T // hold decisions, in three calls, in this order:
       1. env.rollout_policy(weights, T, hold, seed, decision0, obs0=obs0) — env.rollout_policy_traffic with traffic=K;
@@ -34,7 +45,26 @@ def collect(env, weights, value_fn, T, hold=1, traffic=0, gamma=0.99, lam=0.95, 
     the own words of the last stored observation, and its traffic records are obtained with observe_traffic() on the state the rollout
     left, so the env must have been made with AtcVecEnv(traffic=K); which of the columns the critic reads is value_fn's choice.
     obs0 defaults to the env's bound observation tensor, as in rollout_policy; a copy is taken before the launch overwrites it.
-    Returns the rollout's dict plus "values", "adv", "ret", "block_reward", "block_done" and "block_steps" (AtcVecEnv.gae)."""
+    Returns the rollout's dict plus "values", "adv", "ret", "block_reward", "block_done" and "block_steps" (AtcVecEnv.gae).
+    Every done is a terminal state here; collect_bootstrap() bootstraps the time-limit ends."""
+    return _collect(env, weights, value_fn, T, hold, traffic, gamma, lam, seed, decision0, obs0, per_decision, False)
+
+
+def collect_bootstrap(env, weights, value_fn, T, hold=1, traffic=0, gamma=0.99, lam=0.95, seed=0, decision0=0, obs0=None, per_decision=False):
+    """collect() that treats time-limit ends as truncations, in the same three calls:
+      1. env.rollout_policy_ends(weights, T, 0, hold, seed, decision0, obs0=obs0);
+      2. ONE forward over [2 D + 1, B, N, 10]: collect()'s D + 1 rows, then rows D + 1 .. 2 D = term_obs (zeros where a block did not
+         end its episode); the result is split into values [D + 1, ...] and boot [D, ...];
+      3. env.gae_boot(reward, done, values, boot, truncated(term_flags), hold, gamma, lam, per_decision=per_decision).
+    Returns collect()'s dict plus "term_obs", "term_flags", "control" (the rollout's), "boot" and "trunc".
+    traffic=K raises ValueError: the traffic records of a terminal state are not produced, so a critic that reads them cannot be
+    evaluated there — next to advantage normalisation the one thing left to the trainer."""
+    if int(traffic):
+        raise ValueError("collect_bootstrap() is for traffic=0: the traffic records of a terminal state are not produced")
+    return _collect(env, weights, value_fn, T, hold, 0, gamma, lam, seed, decision0, obs0, per_decision, True)
+
+
+def _collect(env, weights, value_fn, T, hold, traffic, gamma, lam, seed, decision0, obs0, per_decision, bootstrap):
     torch = env.torch
     K = int(traffic)
     if K and env.traffic_k != K:
@@ -42,11 +72,23 @@ def collect(env, weights, value_fn, T, hold=1, traffic=0, gamma=0.99, lam=0.95, 
     x0 = (env.obs if obs0 is None else obs0).clone()
     if K:
         out = env.rollout_policy_traffic(weights, T, K, hold=hold, seed=seed, decision0=decision0, obs0=x0)
+    elif bootstrap:
+        out = env.rollout_policy_ends(weights, T, 0, hold=hold, seed=seed, decision0=decision0, obs0=x0)
     else:
         out = env.rollout_policy(weights, T, hold=hold, seed=seed, decision0=decision0, obs0=x0)
+    rows = value_rows(env, out, x0, hold=hold, traffic=K)
+    if bootstrap:
+        rows = torch.cat([rows, out["term_obs"].reshape((-1,) + tuple(rows.shape[1:]))], dim=0)
     with torch.no_grad():
-        values = value_fn(value_rows(env, out, x0, hold=hold, traffic=K))
+        values = value_fn(rows)
     values = values.to(dtype=torch.float32).contiguous()
-    res = dict(out, values=values)
-    res.update(env.gae(out["reward"], out["done"], values, hold=hold, gamma=gamma, lam=lam, per_decision=per_decision))
+    if not bootstrap:
+        res = dict(out, values=values)
+        res.update(env.gae(out["reward"], out["done"], values, hold=hold, gamma=gamma, lam=lam, per_decision=per_decision))
+        return res
+    D = int(rows.shape[0]) // 2
+    values, boot = values[:D + 1].contiguous(), values[D + 1:].contiguous()
+    trunc = truncated(out["term_flags"])
+    res = dict(out, values=values, boot=boot, trunc=trunc)
+    res.update(env.gae_boot(out["reward"], out["done"], values, boot, trunc, hold=hold, gamma=gamma, lam=lam, per_decision=per_decision))
     return res

@@ -854,7 +854,7 @@ class AtcVecEnv:
         Returns a dict of device tensors: obs / reward / done / flags [T, ...] as rollout() returns them, action [T // hold, B, N, 3] —
         the UNCLAMPED sample, what logp is about; its clamp to [-1, 1] is what was flown — and logp [T // hold, B, N].  Values are not
         computed: run the value network once over the stored obs.  Like rollout(), it produces no traffic observation: a policy that sees
-        traffic is rolled out by rollout_policy_traffic()."""
+        traffic is rolled out by rollout_policy_traffic(); rollout_policy_ends() also stores the terminal observations and the control mask."""
         return AtcVecEnv._rollout_policy(self, 0, weights, T, hold, seed, decision0, deterministic, obs0, out)
 
     def rollout_policy_traffic(self, weights, T, traffic, hold=1, seed=0, decision0=0, deterministic=False, obs0=None, out=None):
@@ -873,9 +873,26 @@ class AtcVecEnv:
             raise ValueError("traffic must be 0 or one of %s records per aircraft" % (L.POLICY_TRAFFIC_K,))
         return AtcVecEnv._rollout_policy(self, K, weights, T, hold, seed, decision0, deterministic, obs0, out)   # (through the class: see gae)
 
-    def _rollout_policy(self, K, weights, T, hold, seed, decision0, deterministic, obs0, out):
+    def rollout_policy_ends(self, weights, T, traffic=0, hold=1, seed=0, decision0=0, deterministic=False, obs0=None, out=None):
+        """rollout_policy (traffic=0) or rollout_policy_traffic (traffic=K) through atc_rollout_policy_ends (include/atc_step.h), which adds
+        what a trainer needs to treat episode ends and handed-over aircraft correctly and cannot rebuild from the [T, ...] tensors.  Per
+        decision d = 0 .. T // hold - 1, whose ending step is the first step of its block with done set:
+          term_obs [D, B, N, 10]: where block d has an ending step, the observation of the state that step ended in — what rollout()
+            returns as term_obs there (the env has been reset inside that step, so obs holds the spawn observation).  Other rows are
+            NOT written: a fresh tensor is zeros there, one given in `out` keeps its content;
+          term_flags [D, B] int16: 0 where block d has no ending step, else L.TERM_ENDED | the OR of the env's flag words at that step
+            (atc_hip.ppo.truncated() picks the time-limit ends);
+          control [D, B, N] uint8: 1 where the aircraft was under control when decision d was taken.
+        With out=, each of the three is stored only where `out` names it.  Every other output and the state afterwards are bit for bit
+        those of the other two methods, which go through their own entry points as before."""
+        K = int(traffic)
+        if K and K not in L.POLICY_TRAFFIC_K:
+            raise ValueError("traffic must be 0 or one of %s records per aircraft" % (L.POLICY_TRAFFIC_K,))
+        return AtcVecEnv._rollout_policy(self, K, weights, T, hold, seed, decision0, deterministic, obs0, out, True)
+
+    def _rollout_policy(self, K, weights, T, hold, seed, decision0, deterministic, obs0, out, ends=False):
         """rollout_policy (K = 0) and rollout_policy_traffic (K = 1, 2, 4): the checks of weights and obs0, the result tensors, the two
-        structs, the launch"""
+        structs, the launch.  ends: through atc_rollout_policy_ends, with its three further outputs"""
         torch = self.torch
         T, hold = int(T), int(hold)
         B, N, dev = self.B, self.N, self.device
@@ -886,7 +903,7 @@ class AtcVecEnv:
         x0 = self.obs if obs0 is None else obs0
         if not (torch.is_tensor(x0) and x0.dtype == torch.float32 and x0.is_contiguous() and x0.numel() == B * N * L.OBS_DIM):
             raise ValueError("obs0 must be a contiguous float32 tensor of B*N*%d words" % L.OBS_DIM)
-        if out is None or K:
+        if out is None or K or ends:
             n_dec = T // hold if hold >= 1 else 0     # (a T or hold the library refuses is refused by it, below)
         if out is None:
             out = self._step_rows(T)
@@ -894,6 +911,16 @@ class AtcVecEnv:
             out["logp"] = torch.empty((n_dec, B, N), dtype=torch.float32, device=dev)
             if K:
                 out["traffic"] = torch.empty((n_dec, B, N, K, L.TRAFFIC_DIM), dtype=torch.float32, device=dev)
+            if ends:   # (term_obs: zeros, since the rows of a block without an ending step are not written)
+                out["term_obs"] = torch.zeros((n_dec, B, N, L.OBS_DIM), dtype=torch.float32, device=dev)
+                out["term_flags"] = torch.empty((n_dec, B), dtype=torch.int16, device=dev)
+                out["control"] = torch.empty((n_dec, B, N), dtype=torch.uint8, device=dev)
+        if ends:
+            for name, dtype, shape in (("term_obs", torch.float32, (n_dec, B, N, L.OBS_DIM)), ("term_flags", torch.int16, (n_dec, B)),
+                                       ("control", torch.uint8, (n_dec, B, N))):
+                t = out.get(name)
+                if t is not None and not (torch.is_tensor(t) and t.dtype == dtype and t.device == dev and t.is_contiguous() and t.numel() == int(np.prod(shape))):
+                    raise ValueError("out[%r] must be a contiguous %s tensor of %r on %s" % (name, dtype, shape, dev))
         if K:
             tr = out.get("traffic")
             if tr is not None and not (torch.is_tensor(tr) and tr.dtype == torch.float32 and tr.is_contiguous() and tr.numel() == n_dec * B * N * K * L.TRAFFIC_DIM):
@@ -901,7 +928,9 @@ class AtcVecEnv:
             call, pol_type, out_type, fields = self._lib.atc_rollout_policy_traffic, _lib.AtcPolicyTraffic, _lib.AtcPolicyTrafficOut, _lib.POLICY_TRAFFIC_OUT_FIELDS
         else:
             call, pol_type, out_type, fields = self._lib.atc_rollout_policy, _lib.AtcPolicy, _lib.AtcPolicyOut, _lib.POLICY_OUT_FIELDS
-        o = out_type(*[self._ptr(out.get(k)) for k in fields])
+        if ends:
+            call, pol_type, out_type, fields = self._lib.atc_rollout_policy_ends, _lib.AtcPolicyTraffic, _lib.AtcPolicyEndsOut, _lib.POLICY_ENDS_OUT_FIELDS
+        o = out_type(*[self._ptr(out.get(k)) if (K or k != "traffic") else None for k in fields])
         pol = pol_type(self._ptr(w), L.POLICY_HIDDEN, L.POLICY_DETERMINISTIC if deterministic else 0, int(seed) & (2 ** 64 - 1),
                        int(decision0) & 0xffffffff, 0)     # (traffic_k, where the struct has it, is zero so far)
         if K:
@@ -931,8 +960,25 @@ class AtcVecEnv:
         those names, shapes and dtypes to write into — "adv" and "ret" required, the three block outputs stored only where it names
         them; with it the method allocates nothing.  No two of the tensors may share memory (refused by the library).  Two calls split
         at D / 2, the later half first and its adv[0] as the earlier half's adv_next, equal one call bit for bit.
-        Not covered, the trainer's: bootstrapping a time-limit done (the terminal observation is not stored by rollout_policy), masking
-        aircraft that are not under control, advantage normalisation.  The method reads no action and no state."""
+        Every done is a true terminal state here: gae_boot() bootstraps a time-limit done from the terminal observation that
+        rollout_policy_ends() stores, next to the mask of the aircraft that were not under control.  Not covered, the trainer's: advantage
+        normalisation (with that mask, three reductions over [D, B, N]) and the traffic records of a terminal state.  The method reads no
+        action and no state."""
+        return AtcVecEnv._gae(self, reward, done, values, hold, gamma, lam, per_decision, adv_next, out, None, None)
+
+    def gae_boot(self, reward, done, values, boot, trunc, hold=1, gamma=0.99, lam=0.95, *, per_decision=False, adv_next=None, out=None):
+        """gae() with bootstrapped truncations (atc_gae_boot, include/atc_step.h).  boot: [D, B, NV] float32 ([D, B] where values is) and
+        trunc: [D, B] uint8, contiguous on this env's device, both or neither (None, None is gae() through atc_gae_boot; one without the
+        other: ValueError).  A block that ended its episode with trunc[d, e] != 0 — a time-limit end: atc_hip.ppo.truncated() of
+        rollout_policy_ends()'s term_flags — bootstraps from boot[d], the critic's value of term_obs[d]:
+        A = (R + Gn boot[d]) - V[d] with Gn = gamma^(steps the block counted) (gamma with per_decision); A_next does not enter, the episode
+        still ends there.  A boot word anywhere else is not read into anything (a NaN may stand there).  Everything else is gae()'s."""
+        if (boot is None) != (trunc is None):
+            raise ValueError("boot and trunc go together: both or neither")
+        return AtcVecEnv._gae(self, reward, done, values, hold, gamma, lam, per_decision, adv_next, out, boot, trunc, True)
+
+    def _gae(self, reward, done, values, hold, gamma, lam, per_decision, adv_next, out, boot, trunc, through_boot=False):
+        """gae() and gae_boot(): the checks, the result tensors, the two structs, the launch"""
         torch = self.torch
         dev, f32 = self.device, (self.torch.float32,)
         # (the helpers through the class: these refusals are also tested on a stand-in env that has none of the class's methods)
@@ -960,18 +1006,22 @@ class AtcVecEnv:
                     raise ValueError("%s must be finite (in float32)" % name)
         if adv_next is not None:
             need(adv_next, f32, cols, "adv_next")
+        if boot is not None:
+            need(boot, f32, (D,) + cols, "boot")
+            need(trunc, (torch.uint8,), (D, self.B), "trunc")
         want = {"adv": (f32, (D,) + cols), "ret": (f32, (D,) + cols), "block_reward": (f32, (D,) + (cols if per_column else (self.B,))),
                 "block_done": ((torch.uint8,), (D, self.B)), "block_steps": ((torch.uint8,), (D, self.B))}
         res = AtcVecEnv._results(self, out, want, {"adv", "ret"}, "out must be a dict with adv and ret, and any of block_reward, block_done, block_steps")
         g = _lib.AtcGae(float(gamma), float(lam), (L.GAE_PER_DECISION if per_decision else 0) | (L.GAE_REWARD_PER_COLUMN if per_column else 0), 0)
         o = _lib.AtcGaeOut(*[res[n].data_ptr() if n in res else None for n in _lib.GAE_OUT_FIELDS])
-        fn = self._lib.atc_gae
+        fn = self._lib.atc_gae_boot if through_boot else self._lib.atc_gae
         with torch.cuda.device(dev):
+            extra = (None if boot is None else boot.data_ptr(), None if trunc is None else trunc.data_ptr()) if through_boot else ()
             rc = fn(self.sector.handle, self.B, NV, D, hold, reward.data_ptr(), done.data_ptr(), values.data_ptr(),
-                    None if adv_next is None else adv_next.data_ptr(), C.byref(g), C.byref(o), self._stream())
+                    None if adv_next is None else adv_next.data_ptr(), *extra, C.byref(g), C.byref(o), self._stream())
             if rc:
                 _lib.check(rc)
-        self._keep_gae = (reward, done, values, adv_next)   # the inputs outlive the launch (like _keep_score)
+        self._keep_gae = (reward, done, values, adv_next, boot, trunc)   # the inputs outlive the launch (like _keep_score)
         return res
 
     def get_attr(self, name, indices=None):

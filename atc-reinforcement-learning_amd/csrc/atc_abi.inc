@@ -26,6 +26,8 @@ int atc_select_launch_counts(uint64_t* out, int n) { return copy_counts(REC_SELE
 int atc_rollout_policy_launch_counts(uint64_t* out, int n) { return copy_counts(REC_POLICY, out, n); }
 int atc_rollout_policy_traffic_launch_counts(uint64_t* out, int n) { return copy_counts(REC_POLICY_TRAFFIC, out, n); }
 int atc_gae_launch_counts(uint64_t* out, int n) { return copy_counts(REC_GAE, out, n); }
+int atc_rollout_policy_ends_launch_counts(uint64_t* out, int n) { return copy_counts(REC_POLICY_ENDS, out, n); }
+int atc_gae_boot_launch_counts(uint64_t* out, int n) { return copy_counts(REC_GAE_BOOT, out, n); }
 int atc_lookahead_set_mapping(int candidates_per_workgroup) {
     if (candidates_per_workgroup < 0 || candidates_per_workgroup > ATC_LOOKAHEAD_MAX_M) return fail_arg("candidates per workgroup must be 0 (the library's choice) .. 64");
     t_look_cpg = candidates_per_workgroup;
@@ -578,8 +580,9 @@ int atc_rollout_policy_traffic(const atc_scenario_t* s, int B, int N, int T, int
     });
 }
 
-int atc_gae(const atc_scenario_t* s, int B, int NV, int D, int hold, const float* reward, const uint8_t* done, const float* values,
-            const float* adv_next, const atc_gae_t* g, const atc_gae_out_t* out, void* stream) {
+// atc_gae and atc_gae_boot: the checks in the header's order, then k_gae, or k_gae_boot where boot and trunc are given
+static int gae_call(Record rec, const atc_scenario_t* s, int B, int NV, int D, int hold, const float* reward, const uint8_t* done, const float* values,
+                    const float* adv_next, const float* boot, const uint8_t* trunc, const atc_gae_t* g, const atc_gae_out_t* out, void* stream) {
     // D, hold, NV, B, before any pointer is looked at
     if (D < 1) return fail_arg("D (the number of decisions) must be >= 1");
     if (hold < 1 || hold > ATC_SKIP_MAX) return fail_arg("hold (the steps of a decision) must be 1 .. 255");
@@ -590,24 +593,53 @@ int atc_gae(const atc_scenario_t* s, int B, int NV, int D, int hold, const float
                                        {out, "null pointer: out (atc_gae_out_t) is required"}}))
         return rc;
     if (const int rc = check_required({{out->adv, "null pointer: out->adv is required"}, {out->ret, "null pointer: out->ret is required"}})) return rc;
+    if (boot && !trunc) return fail_arg("null pointer: trunc is required where boot is given (both, or neither)");
+    if (trunc && !boot) return fail_arg("null pointer: boot is required where trunc is given (both, or neither)");
     if (g->flags & ~(ATC_GAE_PER_DECISION | ATC_GAE_REWARD_PER_COLUMN)) return fail_arg("g->flags has unknown bits");
     if (!(fabsf(g->gamma) <= __FLT_MAX__)) return fail_arg("g->gamma must be finite");
     if (!(fabsf(g->lam) <= __FLT_MAX__)) return fail_arg("g->lam must be finite");
-    // any overlap is refused (adv_next and the three block outputs may be absent)
+    // any overlap is refused (adv_next, boot and trunc and the three block outputs may be absent)
     const bool per_column = (g->flags & ATC_GAE_REWARD_PER_COLUMN) != 0u;
     const uintptr_t b = (uintptr_t)B, cols = b * (uintptr_t)NV, d = (uintptr_t)D, t = d * (uintptr_t)hold;
     const uintptr_t r_cols = per_column ? cols : b;
-    const ByteRange ranges[9] = {{reward, t * r_cols * 4u, "reward"}, {done, t * b, "done"}, {values, (d + 1u) * cols * 4u, "values"},
-                                 {adv_next, cols * 4u, "adv_next"}, {out->adv, d * cols * 4u, "adv"}, {out->ret, d * cols * 4u, "ret"},
-                                 {out->block_reward, d * r_cols * 4u, "block_reward"}, {out->block_done, d * b, "block_done"},
-                                 {out->block_steps, d * b, "block_steps"}};
-    if (const int rc = check_disjoint(ranges, 9, {}, "no two arrays of atc_gae may share memory")) return rc;
+    const ByteRange ranges[11] = {{reward, t * r_cols * 4u, "reward"}, {done, t * b, "done"}, {values, (d + 1u) * cols * 4u, "values"},
+                                  {adv_next, cols * 4u, "adv_next"}, {out->adv, d * cols * 4u, "adv"}, {out->ret, d * cols * 4u, "ret"},
+                                  {out->block_reward, d * r_cols * 4u, "block_reward"}, {out->block_done, d * b, "block_done"},
+                                  {out->block_steps, d * b, "block_steps"}, {boot, d * cols * 4u, "boot"}, {trunc, d * b, "trunc"}};
+    if (const int rc = check_disjoint(ranges, 11, {}, rec == REC_GAE ? "no two arrays of atc_gae may share memory" : "no two arrays of atc_gae_boot may share memory"))
+        return rc;
     const unsigned long long tiles = ((unsigned long long)cols + kGaeBlock - 1) / kGaeBlock;
     if (tiles > 0x7fffffffull) return fail_arg("B * NV is more than one launch covers: split the batch");
-    hipLaunchKernelGGL(k_gae, dim3((unsigned)tiles), dim3(kGaeBlock), 0, (hipStream_t)stream, B, NV, D, hold, reward, done, values, adv_next, *g, *out);
+    if (boot)
+        hipLaunchKernelGGL(k_gae_boot, dim3((unsigned)tiles), dim3(kGaeBlock), 0, (hipStream_t)stream, B, NV, D, hold, reward, done, values, adv_next, boot, trunc, *g, *out);
+    else
+        hipLaunchKernelGGL(k_gae, dim3((unsigned)tiles), dim3(kGaeBlock), 0, (hipStream_t)stream, B, NV, D, hold, reward, done, values, adv_next, *g, *out);
     HIP_TRY(hipGetLastError());
-    ++record(REC_GAE)[0];
+    ++record(rec)[0];
     return ATC_OK;
+}
+
+int atc_rollout_policy_ends(const atc_scenario_t* s, int B, int N, int T, int hold, const atc_state_t* st, const float* obs0,
+                            const atc_policy_traffic_t* pol, const atc_policy_ends_out_t* out, const atc_params_t* p, void* stream) {
+    const PolicyEnds ends = {out ? out->term_obs : nullptr, out ? out->term_flags : nullptr, out ? out->control : nullptr};
+    if (const int rc = check_policy_call(s, B, N, T, hold, st, obs0, pol, out, p, "atc_policy_traffic_t", "atc_policy_ends_out_t", pol ? &pol->traffic_k : nullptr,
+                                         out ? out->traffic : nullptr, &ends))
+        return rc;
+    return with_width(N, [&](auto w) {
+        return with_traffic_k0(pol->traffic_k, [&](auto kt) {
+            return launch_policy<decltype(w)::value, decltype(kt)::value, true>(s, B, N, T, hold, st, obs0, pol, out, p, (hipStream_t)stream);
+        });
+    });
+}
+
+int atc_gae(const atc_scenario_t* s, int B, int NV, int D, int hold, const float* reward, const uint8_t* done, const float* values,
+            const float* adv_next, const atc_gae_t* g, const atc_gae_out_t* out, void* stream) {
+    return gae_call(REC_GAE, s, B, NV, D, hold, reward, done, values, adv_next, nullptr, nullptr, g, out, stream);
+}
+
+int atc_gae_boot(const atc_scenario_t* s, int B, int NV, int D, int hold, const float* reward, const uint8_t* done, const float* values,
+                 const float* adv_next, const float* boot, const uint8_t* trunc, const atc_gae_t* g, const atc_gae_out_t* out, void* stream) {
+    return gae_call(REC_GAE_BOOT, s, B, NV, D, hold, reward, done, values, adv_next, boot, trunc, g, out, stream);
 }
 
 }  // extern "C"

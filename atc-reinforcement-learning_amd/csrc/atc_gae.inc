@@ -1,4 +1,4 @@
-// atc_gae.inc — k_gae (atc_gae, include/atc_step.h): the per-step rewards and dones of a rollout and the values of one batched forward
+// atc_gae.inc — k_gae (atc_gae, include/atc_step.h) and k_gae_boot (atc_gae_boot): the per-step rewards and dones of a rollout and the values of one batched forward
 // turned into advantages and returns, one transition per decision, in one launch.  Included by atc_step.hip behind atc_policy.inc.
 //   Mapping: ONE LANE PER COLUMN i = e * NV + k, workgroups of one wavefront (kGaeBlock = 64).  [D][C] has C contiguous, so row d of
 //   values, adv and ret is a coalesced access across the wavefront; the NV lanes of an env read the same reward and done words (one
@@ -34,9 +34,14 @@ struct GaeCursor {      // the (d, j) of the next step of the flat sequence; d <
 
 __device__ __forceinline__ float gae_word(float x) { return x != x ? __uint_as_float(0x7FC00000u) : x; }   // one NaN (atc_plan_score's rule)
 
-__global__ void __launch_bounds__(kGaeBlock)
-k_gae(int B, int NV, int D, int hold, const float* __restrict__ reward, const uint8_t* __restrict__ done, const float* __restrict__ values,
-      const float* __restrict__ adv_next, atc_gae_t gp, atc_gae_out_t out) {
+// BOOT (k_gae_boot, atc_gae_boot): a block whose episode ended at a step the caller marks as truncated (trunc[d][e] != 0) bootstraps from
+// boot[d][i], the value of the state it ended in, discounted by Gn = g * gamma with g the running product at the block's last counted
+// step: delta = (R + (Gn * boot)) - V[d], A = delta.  The two words are loaded with V[d], into the prefetched register set; a boot word that
+// is not selected only reaches the dead arm of a select.
+template <bool BOOT>
+__device__ __forceinline__ void gae_body(int B, int NV, int D, int hold, const float* __restrict__ reward, const uint8_t* __restrict__ done,
+                                         const float* __restrict__ values, const float* __restrict__ adv_next, const float* __restrict__ boot,
+                                         const uint8_t* __restrict__ trunc, const atc_gae_t& gp, const atc_gae_out_t& out) {
     const size_t Bs = (size_t)(uint32_t)B, C = Bs * (uint32_t)NV;
     const size_t i0 = (size_t)blockIdx.x * (uint32_t)kGaeBlock, i = i0 + threadIdx.x;
     if (i >= C) return;                                                // idle lanes neither load nor store (nothing below synchronises)
@@ -69,17 +74,25 @@ k_gae(int B, int NV, int D, int hold, const float* __restrict__ reward, const ui
 
     // one chunk of the flat sequence into a register set: no address depends on the recurrence
     GaeCursor ld{D - 1, 0};
-    auto load = [&](float (&r)[kGaeDepth], uint32_t (&dn)[kGaeDepth], float (&v)[kGaeDepth]) {
+    auto load = [&](float (&r)[kGaeDepth], uint32_t (&dn)[kGaeDepth], float (&v)[kGaeDepth], float (&bt)[kGaeDepth], uint32_t (&tr)[kGaeDepth]) {
 #pragma unroll
         for (int u = 0; u < kGaeDepth; ++u) {
             r[u] = 0.0f;
             dn[u] = 0u;
             v[u] = 0.0f;
+            bt[u] = 0.0f;
+            tr[u] = 0u;
             if (ld.live()) {
                 const size_t t = (size_t)(uint32_t)ld.d * (uint32_t)hold + (uint32_t)ld.j;
                 r[u] = word(reward + (t * r_row + r_first), r_off);
                 dn[u] = (done + (t * Bs + e0))[env_lane];
-                if (ld.j == hold - 1) v[u] = word(values + ((size_t)(uint32_t)ld.d * C + i0), col_off);
+                if (ld.j == hold - 1) {
+                    v[u] = word(values + ((size_t)(uint32_t)ld.d * C + i0), col_off);
+                    if (BOOT) {
+                        bt[u] = word(boot + ((size_t)(uint32_t)ld.d * C + i0), col_off);
+                        tr[u] = (trunc + ((size_t)(uint32_t)ld.d * Bs + e0))[env_lane];
+                    }
+                }
                 ld.advance(hold);
             }
         }
@@ -89,7 +102,8 @@ k_gae(int B, int NV, int D, int hold, const float* __restrict__ reward, const ui
     float g = 1.0f, R = 0.0f;
     uint32_t n = 0u;
     bool term = false;
-    auto compute = [&](const float (&r)[kGaeDepth], const uint32_t (&dn)[kGaeDepth], const float (&v)[kGaeDepth]) {
+    auto compute = [&](const float (&r)[kGaeDepth], const uint32_t (&dn)[kGaeDepth], const float (&v)[kGaeDepth], const float (&bt)[kGaeDepth],
+                       const uint32_t (&tr)[kGaeDepth]) {
 #pragma unroll
         for (int u = 0; u < kGaeDepth; ++u) {
             if (!at.live()) break;
@@ -112,6 +126,11 @@ k_gae(int B, int NV, int D, int hold, const float* __restrict__ reward, const ui
                 float A;
                 if (term) {
                     A = R - vd;
+                    if (BOOT) {
+                        const float Gn = g * gp.gamma;
+                        const float delta = (R + (Gn * bt[u])) - vd;
+                        A = tr[u] != 0u ? delta : A;
+                    }
                 } else {
                     const float delta = (R + (G * v_next)) - vd;
                     A = delta + (c * a_next);
@@ -131,13 +150,25 @@ k_gae(int B, int NV, int D, int hold, const float* __restrict__ reward, const ui
         }
     };
 
-    float r0[kGaeDepth], v0[kGaeDepth], r1[kGaeDepth], v1[kGaeDepth];
-    uint32_t d0[kGaeDepth], d1[kGaeDepth];
-    load(r0, d0, v0);
+    float r0[kGaeDepth], v0[kGaeDepth], b0[kGaeDepth], r1[kGaeDepth], v1[kGaeDepth], b1[kGaeDepth];
+    uint32_t d0[kGaeDepth], t0[kGaeDepth], d1[kGaeDepth], t1[kGaeDepth];
+    load(r0, d0, v0, b0, t0);
     while (at.live()) {
-        load(r1, d1, v1);
-        compute(r0, d0, v0);
-        load(r0, d0, v0);
-        compute(r1, d1, v1);
+        load(r1, d1, v1, b1, t1);
+        compute(r0, d0, v0, b0, t0);
+        load(r0, d0, v0, b0, t0);
+        compute(r1, d1, v1, b1, t1);
     }
+}
+
+__global__ void __launch_bounds__(kGaeBlock)
+k_gae(int B, int NV, int D, int hold, const float* __restrict__ reward, const uint8_t* __restrict__ done, const float* __restrict__ values,
+      const float* __restrict__ adv_next, atc_gae_t gp, atc_gae_out_t out) {
+    gae_body<false>(B, NV, D, hold, reward, done, values, adv_next, nullptr, nullptr, gp, out);
+}
+
+__global__ void __launch_bounds__(kGaeBlock)
+k_gae_boot(int B, int NV, int D, int hold, const float* __restrict__ reward, const uint8_t* __restrict__ done, const float* __restrict__ values,
+           const float* __restrict__ adv_next, const float* __restrict__ boot, const uint8_t* __restrict__ trunc, atc_gae_t gp, atc_gae_out_t out) {
+    gae_body<true>(B, NV, D, hold, reward, done, values, adv_next, boot, trunc, gp, out);
 }

@@ -136,6 +136,15 @@ struct PolicyTrafficTail {
     float* traffic;     // atc_policy_traffic_out_t.traffic, nullable
 };
 
+// ENDS (atc_rollout_policy_ends, k_rollout_policy_ends<W, KT>): the three nullable per-decision outputs, read by kernarg re-read where
+// they are stored — control at the decision, term_obs and term_flags at the step that ends an episode, term_flags' zero at a block's
+// last step.  What the loop carries for them is one predicate per env: the block has ended an episode already.
+struct PolicyEnds {
+    float* term_obs;        // atc_policy_ends_out_t.term_obs
+    uint16_t* term_flags;   // .term_flags
+    uint8_t* control;       // .control
+};
+
 // wavefronts per SIMD k_rollout_policy is register-budgeted for (<= 168 VGPRs): the 64 hidden activations are live next to what the
 // step carries across its loop, which the step's own 5 - 6 do not hold.  -DATC_POLICY_WAVES=n: A/B builds.
 #ifndef ATC_POLICY_WAVES
@@ -146,12 +155,14 @@ struct PolicyTrafficTail {
 // traffic_record of atc_traffic.inc: k_traffic's arithmetic, so the same bits), stored, and its words 0..6 per record widen the input row.
 // An env never leaves its wavefront: W = 32 / 64 stage (x, y, tag) in the wavefront's own quarter of the pair-scan staging area (idle
 // between steps), ordered by wave-level waits — no workgroup barrier anywhere in the decision.
-// TT_OFF: where k_rollout_policy_traffic's PolicyTrafficTail lies in ITS kernarg segment (the body serves two parameter lists)
-template <int W, int KT, size_t TT_OFF = 0>
+// TT_OFF: where the kernel's PolicyTrafficTail lies in ITS kernarg segment (the body serves three parameter lists); ET_OFF: where its
+// PolicyEnds lies, 0 for the two kernels that have none (ENDS below).
+template <int W, int KT, size_t TT_OFF = 0, size_t ET_OFF = 0>
 __device__ __forceinline__ void rollout_policy_body(const float* __restrict__ blob, int off_grid, int B, int N, int T, atc_state_t st, const float* __restrict__ obs0,
                                                     atc_params_t p, StepDerived q, const float* __restrict__ pw, uint64_t seed, uint32_t decision0, uint32_t pflags,
                                                     float* __restrict__ action, float* __restrict__ logp) {
     constexpr bool ONE = false, LAT = false, FULL = false;   // (QGET: the multi-step form — kernarg re-reads inside the step)
+    constexpr bool ENDS = ET_OFF != 0;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float4* pos = reinterpret_cast<float4*>(smem);                    // [2 kBlock] pair-scan staging (W >= 32)
     float* obs_stage = smem + (W >= 32 ? 2 * kBlock * 4 : 0);  // [4 waves][64 x 10] obs transpose
@@ -186,6 +197,7 @@ __device__ __forceinline__ void rollout_policy_body(const float* __restrict__ bl
     bool all_active = false, mask_dirty = true;
     int left = 0;                 // steps the current block is still flown for
     uint32_t blk = 0u;            // the number of the coming decision
+    bool ended = false;           // ENDS: an earlier step of the current block ended an episode of this lane's env
     QRates qr_next = kernarg_reread<QRates>(offsetof(StepArgs, q) + offsetof(StepDerived, r), opaque_zero());
     settle_state(ls, es);
 #pragma unroll
@@ -252,6 +264,12 @@ __device__ __forceinline__ void rollout_policy_body(const float* __restrict__ bl
                 *at<Float3>(action + (size_t)blk * BN * 3u, times12(dl.i)) = dec.u;
                 if (logp) *at<float>(logp + (size_t)blk * BN, dl.i * 4u) = dec.logp;
             }
+            if constexpr (ENDS) {   // which aircraft this decision controls: the active mask of the state it is taken in
+                uint8_t* const control = kernarg_reread<uint8_t*>(ET_OFF + offsetof(PolicyEnds, control), zk);
+                const bool under = ((dl.k < 32 ? ((uint32_t)es.amask >> dl.k) : ((uint32_t)(es.amask >> 32) >> (dl.k - 32))) & 1u) != 0u;
+                if (control && dl.lane_valid) *at<uint8_t>(control + (size_t)blk * BN, dl.i) = under ? 1 : 0;
+                ended = false;
+            }
             act = dec.a;
             tg = decode_targets(qr, act);
             refused_known = false;
@@ -271,9 +289,30 @@ __device__ __forceinline__ void rollout_policy_body(const float* __restrict__ bl
         Float3 nxt = act;
         int scan_skip = 0;
         uint32_t scan_mask = 0u;
-        const bool quiet = step_part_b<W, FULL, false, false, false, true>(K, grid, pl, q, qs, zk, N, dl, m, ls, es, so, st.stats, st.phi_wide, pos, obs_stage,
-                                                                            nullptr, nxt, qr_next, scan_skip, scan_mask, nullptr, nullptr, &sv);
+        // (ENDS: the step that ends an episode stores the terminal observation itself, ahead of the spawn that overwrites it)
+        constexpr size_t TERM_OFF = ENDS ? ET_OFF + offsetof(PolicyEnds, term_obs) : 0;
+        const size_t ends_row = (size_t)(blk - 1u) * BN;   // the current block's row of the [D] outputs, in aircraft
+        const bool quiet = step_part_b<W, FULL, false, false, false, true, false, false, TERM_OFF>(K, grid, pl, q, qs, zk, N, dl, m, ls, es, so, st.stats, st.phi_wide,
+                                                                                                   pos, obs_stage, nullptr, nxt, qr_next, scan_skip, scan_mask, nullptr,
+                                                                                                   nullptr, &sv, ends_row * ATC_OBS_DIM, !ended);
         if (ATC_RARE(!quiet)) mask_dirty = true;
+        if constexpr (ENDS) {
+            const bool ends_now = sv.done && !ended;   // the block's ending step for this env (uniform over the env's lanes)
+            if (ATC_RARE(__builtin_amdgcn_ballot_w64(ends_now) != 0ull)) {
+                const PolicyEnds en = kernarg_reread<PolicyEnds>(ET_OFF, zk);
+                const int seen = group_or_i<W>(dl.lane_valid ? (int)(sv.fl & 0xffffu) : 0);   // the env's flag words as flags[t] stores them
+                if (ends_now) {
+                    if (en.term_flags && dl.k == 0) *at<uint16_t>(en.term_flags + (size_t)(blk - 1u) * (uint32_t)B, (uint32_t)dl.e * 2u) = (uint16_t)(ATC_TERM_ENDED | (uint32_t)seen);
+                    // without an auto-reset the stored observation is the terminal one
+                    if (!(pl.mode & ATC_M_AUTO_RESET) && en.term_obs && dl.lane_valid) store_obs(at<float>(en.term_obs + ends_row * ATC_OBS_DIM, times40(dl.i)), sv.o);
+                    ended = true;
+                }
+            }
+            if (left == 0) {   // the block's last step: no ending step in it stores the zero
+                uint16_t* const term_flags = kernarg_reread<uint16_t*>(ET_OFF + offsetof(PolicyEnds, term_flags), zk);
+                if (term_flags && !ended && dl.env_valid && dl.k == 0) *at<uint16_t>(term_flags + (size_t)(blk - 1u) * (uint32_t)B, (uint32_t)dl.e * 2u) = 0;
+            }
+        }
         // ---- this step's row of the [T][...] outputs: the tail of step_part_b (observation first, the three small stores last) ----
         const atc_out_t o_t = kernarg_reread<atc_out_t>(offsetof(StepArgs, out), zk);
         store_obs_rows(o_t.obs + sBN * ATC_OBS_DIM, dl, sv.o, obs_stage);
@@ -311,3 +350,17 @@ k_rollout_policy_traffic(const float* __restrict__ blob, int off_grid, int B, in
                                                                                           action, logp);
 }
 static_assert(kernargs_hold_like_step<decltype(k_rollout_policy_traffic<1, 1>)>(), ATC_KERNARGS_REFUSAL);
+
+// KT = 0, 1, 2, 4: atc_policy_traffic_t.traffic_k as atc_rollout_policy_ends takes it.  One parameter list for all four (tt is not read
+// where KT = 0): k_rollout_policy_traffic's, then the three pointers.
+template <int W, int KT>
+__global__ void __launch_bounds__(kBlock, ATC_POLICY_WAVES)
+k_rollout_policy_ends(const float* __restrict__ blob, int off_grid, int B, int N, int T, int hold, atc_state_t st, const float* __restrict__ obs0,
+                      atc_out_t out, atc_params_t p, StepDerived q, const float* __restrict__ pw, uint64_t seed, uint32_t decision0, uint32_t pflags,
+                      float* __restrict__ action, float* __restrict__ logp, PolicyTrafficTail tt, PolicyEnds en) {
+    // (tt, en: kernarg re-reads where they are used, at the offsets this list gives them)
+    typedef KernArgs<decltype(k_rollout_policy_ends<W, KT>)> A;
+    rollout_policy_body<W, KT, A::template of<PolicyTrafficTail>(), A::last()>(blob, off_grid, B, N, T, st, obs0, p, q, pw, seed, decision0, pflags, action, logp);
+}
+static_assert(kernargs_hold_like_step<decltype(k_rollout_policy_ends<1, 0>)>() && KernArgs<decltype(k_rollout_policy_ends<1, 0>)>::last() != 0, ATC_KERNARGS_REFUSAL);
+static_assert(ATC_POLICY_TRAFFIC_WORDS(0) == ATC_POLICY_WORDS && ATC_POLICY_TRAFFIC_IN(0) == ATC_POLICY_IN, "traffic_k == 0 is the ten-word policy");

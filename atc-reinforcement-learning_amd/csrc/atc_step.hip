@@ -857,13 +857,16 @@ struct StepVals {
 // RO: see step_part_a — here the auto-reset path reads the episode number and writes nothing: no per-episode record update, no fences
 // around it, no terminal observation.
 // NB: see step_part_a — the per-episode record and the side record are addressed from the bases handed in (stp, wide_named).
-template <int W, bool FULL, bool ONE, bool LAT, bool LDSG = false, bool SKIP = false, bool RO = false, bool NB = ONE>
+// TERM_OFF != 0 (k_rollout_policy_ends): the terminal observation is stored without FULL — by the lanes with term_ok set, to row
+// `term_row` (in floats) of the array whose pointer lies at byte TERM_OFF of the kernarg segment, read there and then; a NULL stores nothing.
+template <int W, bool FULL, bool ONE, bool LAT, bool LDSG = false, bool SKIP = false, bool RO = false, bool NB = ONE, size_t TERM_OFF = 0>
 __device__ __forceinline__ bool step_part_b(const float* __restrict__ K, const float* __restrict__ grid,
                                             const atc_params_t& p, const StepDerived& q, const QScan& qs, int zk, int N,
                                             const LaneIds& d, const Mid& m, LaneState& ls,
                                             EnvState& es, const StepOut& so, int32_t* stp, double* wide_named, float4* pos, float* obs_stage,
                                             const float* act_next, Float3& a_next, QRates& qr_next, int& scan_skip, uint32_t& scan_mask,
-                                            const char* ltab = nullptr, const LdsTab* lt = nullptr, StepVals* sv = nullptr) {
+                                            const char* ltab = nullptr, const LdsTab* lt = nullptr, StepVals* sv = nullptr, size_t term_row = 0,
+                                            bool term_ok = false) {
     Aircraft& a = ls.a;
     const bool active = m.active;
     const float x32 = m.x32, y32 = m.y32;
@@ -1237,6 +1240,10 @@ __device__ __forceinline__ bool step_part_b(const float* __restrict__ K, const f
         if (!RO) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         if (d.lane_valid) {
             if (!RO && FULL && so.term_obs) store_obs(at<float>(so.term_obs, times40(i)), o);
+            if constexpr (TERM_OFF != 0) {
+                float* const term_obs = kernarg_reread<float*>(TERM_OFF, zk);
+                if (term_obs && term_ok) store_obs(at<float>(term_obs + term_row, times40(i)), o);
+            }
             // (slot through this step's opaque zero: the spawn-record address is then formed here, on the rare path, instead of
             // being carried — and spilled — across the step loop as a 64-bit per-lane pointer)
             a = spawn(K, qs.off_spawn, p, e, k + zk, episode, o);   // state + raw reset observation from the blob's spawn records
@@ -1758,8 +1765,8 @@ k_serve(const float* __restrict__ blob, int off_grid, atc_state_t st, atc_out_t 
 #include "atc_plan_refit.inc"    // k_plan_refit (atc_plan_refit)
 #include "atc_plan_score.inc"    // k_plan_score (atc_plan_score)
 #include "atc_branch.inc"        // k_branch (atc_branch), k_select (atc_state_select)
-#include "atc_policy.inc"        // k_rollout_policy (atc_rollout_policy), k_rollout_policy_traffic (atc_rollout_policy_traffic)
-#include "atc_gae.inc"           // k_gae (atc_gae)
+#include "atc_policy.inc"        // k_rollout_policy (atc_rollout_policy), k_rollout_policy_traffic (atc_rollout_policy_traffic), k_rollout_policy_ends (atc_rollout_policy_ends)
+#include "atc_gae.inc"           // k_gae (atc_gae), k_gae_boot (atc_gae_boot)
 
 // ---------------------------------------------------------------------------------------------------------------
 // host side of the C-ABI
@@ -1787,13 +1794,14 @@ static size_t lds_bytes(const atc_scenario*, bool pair_scan, bool step_kernel = 
 // the launch records (include/atc_step.h: the atc_*_launch_counts getters): launches made by the calling thread, every record's
 // counters in one table — plain thread-local counters that nothing in the library reads back.  REC_STEP has a slot for each k_step
 // instantiation and one for k_serve starts; a record of 7 slots counts by lane-group width (slot = log2(W)); a record of one slot
-// counts its entry point's launches; REC_POLICY_TRAFFIC counts by width and list length (slot = 3 log2(W) + log2(K)).  A call moves its
-// own record only.
-enum Record { REC_STEP, REC_SKIP, REC_TRAFFIC, REC_LOOKAHEAD, REC_PLAN, REC_PLAN_SAMPLED, REC_PLAN_DRAW, REC_PLAN_REFIT, REC_PLAN_SCORE, REC_BRANCH, REC_SELECT, REC_POLICY, REC_POLICY_TRAFFIC, REC_GAE, REC_COUNT };
+// counts its entry point's launches; REC_POLICY_TRAFFIC counts by width and list length (slot = 3 log2(W) + log2(K)), REC_POLICY_ENDS
+// likewise with K = 0 in front (slot = 4 log2(W) + {0, 1, 2, 3}).  A call moves its own record only.
+enum Record { REC_STEP, REC_SKIP, REC_TRAFFIC, REC_LOOKAHEAD, REC_PLAN, REC_PLAN_SAMPLED, REC_PLAN_DRAW, REC_PLAN_REFIT, REC_PLAN_SCORE, REC_BRANCH, REC_SELECT, REC_POLICY, REC_POLICY_TRAFFIC, REC_GAE, REC_POLICY_ENDS, REC_GAE_BOOT, REC_COUNT };
 constexpr int kRecordSlots[REC_COUNT] = {ATC_LAUNCH_SLOTS, ATC_SKIP_LAUNCH_SLOTS, ATC_TRAFFIC_LAUNCH_SLOTS, ATC_LOOKAHEAD_LAUNCH_SLOTS, ATC_PLAN_LAUNCH_SLOTS,
                                          ATC_PLAN_SAMPLED_LAUNCH_SLOTS, ATC_PLAN_DRAW_LAUNCH_SLOTS, ATC_PLAN_REFIT_LAUNCH_SLOTS, ATC_PLAN_SCORE_LAUNCH_SLOTS,
                                          ATC_BRANCH_LAUNCH_SLOTS, ATC_SELECT_LAUNCH_SLOTS, ATC_ROLLOUT_POLICY_LAUNCH_SLOTS,
-                                         ATC_ROLLOUT_POLICY_TRAFFIC_LAUNCH_SLOTS, ATC_GAE_LAUNCH_SLOTS};
+                                         ATC_ROLLOUT_POLICY_TRAFFIC_LAUNCH_SLOTS, ATC_GAE_LAUNCH_SLOTS, ATC_ROLLOUT_POLICY_ENDS_LAUNCH_SLOTS,
+                                         ATC_GAE_BOOT_LAUNCH_SLOTS};
 constexpr int record_offset(int id) {
     int o = 0;
     for (int i = 0; i < id; ++i) o += kRecordSlots[i];
@@ -2157,8 +2165,9 @@ static atc_out_t policy_out(const O* o) {
     return out;
 }
 // W lanes per env.  KT = 0: k_rollout_policy (P, O = atc_policy_t, atc_policy_out_t); KT = 1, 2, 4: k_rollout_policy_traffic<W, KT>, whose
-// selection borrows the pair-scan staging area between steps at W >= 32 (P, O = atc_policy_traffic_t, atc_policy_traffic_out_t)
-template <int W, int KT, typename P, typename O>
+// selection borrows the pair-scan staging area between steps at W >= 32 (P, O = atc_policy_traffic_t, atc_policy_traffic_out_t).
+// ENDS: k_rollout_policy_ends<W, KT> for KT = 0, 1, 2, 4 (P, O = atc_policy_traffic_t, atc_policy_ends_out_t)
+template <int W, int KT, bool ENDS = false, typename P, typename O>
 static int launch_policy(const atc_scenario* s, int B, int N, int T, int hold, const atc_state_t* st, const float* obs0, const P* pol, const O* o,
                          const atc_params_t* p, hipStream_t stream) {
     const size_t lds = lds_bytes(s, W >= 32, true);
@@ -2169,7 +2178,10 @@ static int launch_policy(const atc_scenario* s, int B, int N, int T, int hold, c
                            pol->decision0, pol->flags, o->action, o->logp, tail...);
     };
     uint64_t* rec;
-    if constexpr (KT == 0) {
+    if constexpr (ENDS) {
+        launch(k_rollout_policy_ends<W, KT>, PolicyTrafficTail{KT ? traffic_common(s, p, KT) : TrafficArgs{}, o->traffic}, PolicyEnds{o->term_obs, o->term_flags, o->control});
+        rec = &record(REC_POLICY_ENDS)[4 * __builtin_ctz(W) + (KT ? 1 + __builtin_ctz(KT) : 0)];
+    } else if constexpr (KT == 0) {
         launch(k_rollout_policy<W>);
         rec = &record(REC_POLICY)[__builtin_ctz(W)];
     } else {
@@ -2187,12 +2199,19 @@ static int with_traffic_k(int k, F f) {
     if (k == 2) return f(std::integral_constant<int, 2>());
     return f(std::integral_constant<int, 4>());
 }
+// ... and for atc_rollout_policy_ends, whose traffic_k may also be 0 (the ten-word policy)
+template <typename F>
+static int with_traffic_k0(int k, F f) {
+    return k == 0 ? f(std::integral_constant<int, 0>()) : with_traffic_k(k, f);
+}
 
-// The argument checks of both policy rollouts, in the header's order.  `out_type` names the output struct in the refusals; traffic_k is
-// null for atc_rollout_policy, and `traffic` is atc_policy_traffic_out_t.traffic (its range joins the overlap rule).
+// The argument checks of the policy rollouts, in the header's order.  `out_type` names the output struct in the refusals; traffic_k is
+// null for atc_rollout_policy, and `traffic` is atc_policy_traffic_out_t.traffic (its range joins the overlap rule).  `ends`: the call is
+// atc_rollout_policy_ends — traffic_k may be 0 (then `traffic` must be NULL), and its three arrays join the overlap rule.
 template <typename P, typename O>
 static int check_policy_call(const atc_scenario_t* s, int B, int N, int T, int hold, const atc_state_t* st, const float* obs0, const P* pol, const O* out,
-                             const atc_params_t* p, const char* pol_type, const char* out_type, const int32_t* traffic_k, const float* traffic) {
+                             const atc_params_t* p, const char* pol_type, const char* out_type, const int32_t* traffic_k, const float* traffic,
+                             const PolicyEnds* ends = nullptr) {
     // T and hold first, before any pointer is looked at
     if (T < 1 || hold < 1) return fail_arg("need T >= 1 and hold >= 1");
     if (T % hold != 0) return fail_arg("T must be a multiple of hold (the launch takes T / hold decisions)");
@@ -2202,23 +2221,34 @@ static int check_policy_call(const atc_scenario_t* s, int B, int N, int T, int h
     if (!out->obs || !out->reward || !out->done || !out->flags) return fail_argf("null pointer: %s.obs, .reward, .done and .flags are required", out_type);
     if (!out->action) return fail_argf("null pointer: %s.action is required", out_type);
     if (pol->n_hidden != ATC_POLICY_HIDDEN) return fail_arg("pol->n_hidden must be 64 (ATC_POLICY_HIDDEN)");
-    if (traffic_k && *traffic_k != 1 && *traffic_k != 2 && *traffic_k != 4) return fail_arg("pol->traffic_k must be 1, 2 or 4 (the compiled list lengths)");
+    if (traffic_k && !(ends && *traffic_k == 0) && *traffic_k != 1 && *traffic_k != 2 && *traffic_k != 4)
+        return fail_arg(ends ? "pol->traffic_k must be 0, 1, 2 or 4 (the ten-word policy, or a compiled list length)" : "pol->traffic_k must be 1, 2 or 4 (the compiled list lengths)");
     if (pol->flags & ~ATC_POLICY_DETERMINISTIC) return fail_arg("pol->flags has unknown bits (ATC_POLICY_DETERMINISTIC or 0)");
+    if (ends && *traffic_k == 0 && traffic) return fail_argf("%s.traffic must be NULL where pol->traffic_k is 0 (no traffic query is evaluated)", out_type);
     if (const int rc = check_env_args(s, B, N, st, p)) return rc;
     if (const int rc = check_dt(s, p)) return rc;
     if (p->mode & ATC_M_DISCRETE) return fail_arg("ATC_M_DISCRETE: a Gaussian policy draws the continuous action space only");
     if (p->mode & ATC_M_ACTIONS_HELD) return fail_arg("ATC_M_ACTIONS_HELD is for atc_step only: every block's first step carries a fresh decision");
-    const uintptr_t bn = (uintptr_t)B * (uintptr_t)N, row = bn * (ATC_OBS_DIM * 4u);
+    const uintptr_t bn = (uintptr_t)B * (uintptr_t)N, row = bn * (ATC_OBS_DIM * 4u), n_dec = (uintptr_t)(T / hold);
     const ByteRange ranges[2] = {{obs0, row, "obs0"}, {out->obs, row * (uintptr_t)T, "out->obs"}};
     if (const int rc = check_disjoint(ranges, 2, {}, "decision 0 reads obs0 while the steps write out->obs")) return rc;
-    if (traffic) {   // ... and the records written at every decision: against what the launch reads or writes next to them
-        const ByteRange tr = {traffic, (uintptr_t)(T / hold) * bn * (uintptr_t)*traffic_k * (ATC_TRAFFIC_DIM * 4u), "out->traffic"};
-        const ByteRange others[8] = {ranges[0], ranges[1], {st->ac, bn * 16u, "st->ac"}, {st->alt, bn * 8u, "st->alt"}, {st->last_act, bn * 16u, "st->last_act"},
-                                     {st->env, (uintptr_t)B * (ATC_ENV_WORDS * 4u), "st->env"}, {st->stats, (uintptr_t)B * (ATC_STAT_WORDS * 4u), "st->stats"},
-                                     {st->phi_wide, bn * 32u, "st->phi_wide"}};
-        for (const ByteRange& o : others) {
-            const ByteRange pair[2] = {tr, o};
-            if (const int rc = check_disjoint(pair, 2, {}, "the records are written while the launch reads and writes the other")) return rc;
+    // ... and what is written per decision (NULL: left out): against what the launch reads or writes next to it, and against one another
+    const ByteRange per_decision[4] = {{traffic, traffic ? n_dec * bn * (uintptr_t)*traffic_k * (ATC_TRAFFIC_DIM * 4u) : 0u, "out->traffic"},
+                                       {ends ? ends->term_obs : nullptr, n_dec * row, "out->term_obs"},
+                                       {ends ? ends->term_flags : nullptr, n_dec * (uintptr_t)B * 2u, "out->term_flags"},
+                                       {ends ? ends->control : nullptr, n_dec * bn, "out->control"}};
+    for (int w = 0; w < 4; ++w) {
+        if (!per_decision[w].ptr) continue;
+        ByteRange others[11] = {ranges[0], ranges[1], {st->ac, bn * 16u, "st->ac"}, {st->alt, bn * 8u, "st->alt"}, {st->last_act, bn * 16u, "st->last_act"},
+                                {st->env, (uintptr_t)B * (ATC_ENV_WORDS * 4u), "st->env"}, {st->stats, (uintptr_t)B * (ATC_STAT_WORDS * 4u), "st->stats"},
+                                {st->phi_wide, bn * 32u, "st->phi_wide"}};
+        int n = 8;
+        for (int v = 0; v < w; ++v) others[n++] = per_decision[v];
+        for (int i = 0; i < n; ++i) {
+            const ByteRange pair[2] = {per_decision[w], others[i]};
+            if (const int rc = check_disjoint(pair, 2, {}, w == 0 ? "the records are written while the launch reads and writes the other"
+                                                                  : "it is written while the launch reads and writes the other"))
+                return rc;
         }
     }
     return ATC_OK;

@@ -49,6 +49,16 @@ __device__ __forceinline__ int group_sum_i(int v) {
     return v;
 }
 template <int W>
+__device__ __forceinline__ int group_or_i(int v) {
+    if (W > 1) v |= xchg<1>(v);
+    if (W > 2) v |= xchg<2>(v);
+    if (W > 4) v |= xchg<4>(v);
+    if (W > 8) v |= xchg<8>(v);
+    if (W > 16) v |= xchg<16>(v);
+    if (W > 32) v |= xchg<32>(v);
+    return v;
+}
+template <int W>
 __device__ __forceinline__ float group_min(float v) {
     if (W > 1) v = fminf(v, xchg<1>(v));
     if (W > 2) v = fminf(v, xchg<2>(v));

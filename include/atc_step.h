@@ -1093,7 +1093,7 @@ typedef struct atc_policy_traffic {
     uint64_t seed;
     uint32_t decision0;  /* number of the launch's first decision */
     uint32_t reserved;
-    int32_t traffic_k;   /* K: 1, 2 or 4 records per aircraft */
+    int32_t traffic_k;   /* K: 1, 2 or 4 records per aircraft (atc_rollout_policy_ends: also 0, the ten-word policy) */
 } atc_policy_traffic_t;
 typedef struct atc_policy_traffic_out {
     float* obs;          /* [T][B*N*10]     required: atc_rollout's per-step outputs */
@@ -1109,6 +1109,50 @@ int atc_rollout_policy_traffic(const atc_scenario_t* s, int B, int N, int T, int
                                const atc_params_t* p, void* stream);
 enum { ATC_ROLLOUT_POLICY_TRAFFIC_LAUNCH_SLOTS = 21 };
 int atc_rollout_policy_traffic_launch_counts(uint64_t* out, int n);
+
+/* POLICY ROLLOUT WITH EPISODE ENDS (extension): atc_rollout_policy and atc_rollout_policy_traffic behind one entry point, with the three
+ * per-decision outputs a trainer cannot rebuild from the [T] arrays: the env is reset INSIDE the step that ends its episode, so the
+ * observation of the state the episode ended in, and which aircraft a decision controlled, never leave the other two launches.
+ * pol->traffic_k is 0, 1, 2 or 4.  0 is the ten-word policy of atc_rollout_policy (ATC_POLICY_TRAFFIC_WORDS(0) == ATC_POLICY_WORDS; no
+ * traffic query is evaluated, and out->traffic must be NULL: refused otherwise, naming the field); 1, 2, 4 is atc_rollout_policy_traffic.
+ * ENDING STEP.  With D = T / hold, decision d owns steps d*hold .. d*hold + hold - 1; its ending step t* is the first of them with
+ * done != 0 for that env — atc_gae's BLOCK rule and atc_step_skip's: a transition never spans two episodes.
+ *   - term_obs[d], the env's N rows: written only where block d has an ending step — the observation of the state step t* ENDED in, bit
+ *     for bit what atc_rollout_hold writes to out->term_obs of step t* under ATC_M_AUTO_RESET (normalised or not like obs, zeros for an
+ *     aircraft not under control); without ATC_M_AUTO_RESET it is obs of step t*.  The rows of an env whose block has no ending step are
+ *     NOT written and keep what they hold; a second episode end inside the same block writes nothing.
+ *   - term_flags[d][e], written for every env and decision: 0 where block d has no ending step, otherwise ATC_TERM_ENDED OR-ed with the
+ *     flag words of the env's N aircraft at step t*, exactly as flags[t*] stores them (the defined flag bits end at bit 9).  A time-limit
+ *     end reads as ATC_F_TIMEOUT set with ATC_F_BELOW_MVA | ATC_F_OUTSIDE | ATC_F_CONFLICT clear: the one end a trainer bootstraps
+ *     (atc_gae_boot).
+ *   - control[d][i] = 1 iff aircraft i's bit of its env's active mask (ATC_ENV_MASK_LO / ATC_STAT_MASK_HI) is set in the state decision d
+ *     is taken in: the state at launch for d = 0, otherwise what step d*hold - 1 left — all ones after an auto-reset.  The predicate the
+ *     traffic query ranks by.
+ * EVERYTHING ELSE is the contract of the two calls, word for word: every other output, the key, the draw, logp, traffic, the dynamics and
+ * the state afterwards are bit-identical to theirs for the same arguments, and two launches of T / 2 equal one of T bit for bit, the
+ * three outputs included.
+ * ATC_ERR_ARG: the refusals of atc_rollout_policy_traffic in its order (traffic_k outside {0, 1, 2, 4}; behind the flag bits, a non-NULL
+ * out->traffic with traffic_k == 0); the overlap rule also refuses term_obs (T/hold * B*N*40 bytes), term_flags (T/hold * B*2) or control
+ * (T/hold * B*N) sharing memory with obs0, out->obs, a state array, out->traffic or one another.
+ * Counted by atc_rollout_policy_ends_launch_counts only: slot = 4 log2(W) + {0, 1, 2, 3 for K = 0, 1, 2, 4}. */
+#define ATC_TERM_ENDED 0x8000u       /* term_flags: block d has an ending step */
+typedef struct atc_policy_ends_out {
+    float* obs;          /* [T][B*N*10]     required: atc_rollout's per-step outputs */
+    float* reward;       /* [T][B]          required */
+    uint8_t* done;       /* [T][B]          required */
+    uint16_t* flags;     /* [T][B*N]        required */
+    float* action;       /* [T/hold][B*N*3] required: the UNCLAMPED sample u */
+    float* logp;         /* [T/hold][B*N]   nullable */
+    float* traffic;      /* [T/hold][B*N*K*8] nullable; must be NULL with traffic_k == 0 */
+    float* term_obs;     /* [T/hold][B*N*10] nullable: rows of envs whose block ended, the others are left as they are */
+    uint16_t* term_flags;/* [T/hold][B]     nullable: 0, or ATC_TERM_ENDED | the OR of the env's flag words at the ending step */
+    uint8_t* control;    /* [T/hold][B*N]   nullable: 1 = under control when the decision was taken */
+} atc_policy_ends_out_t;
+int atc_rollout_policy_ends(const atc_scenario_t* s, int B, int N, int T, int hold, const atc_state_t* st,
+                            const float* obs0 /* [B*N*10] */, const atc_policy_traffic_t* pol, const atc_policy_ends_out_t* out,
+                            const atc_params_t* p, void* stream);
+enum { ATC_ROLLOUT_POLICY_ENDS_LAUNCH_SLOTS = 28 };
+int atc_rollout_policy_ends_launch_counts(uint64_t* out, int n);
 
 /* GAE (extension): what lies between the collection launch and the update of an on-policy trainer, in one launch — the per-step
  * rewards and dones of a rollout (atc_rollout_policy's reward [T][B] and done [T][B]) and the values of one batched forward turned into
@@ -1145,8 +1189,10 @@ int atc_rollout_policy_traffic_launch_counts(uint64_t* out, int n);
  * word (tests/gae_ref.py does, in numpy).
  * SPLITTING.  A call on decisions D/2 .. D-1 (values + (D/2) * C, the later half of reward and done), then a call on decisions
  * 0 .. D/2 - 1 with adv_next = the first call's adv row 0, equal one call of D bit for bit.
- * NOT COVERED (the trainer's): bootstrapping a time-limit done needs the terminal observation, which atc_rollout_policy does not
- * store; masking aircraft that are not under control; advantage normalisation.
+ * TIME-LIMIT ENDS AND THE CONTROL MASK.  atc_gae treats every done as a true terminal state.  atc_gae_boot (below) bootstraps the ends
+ * the caller marks as truncated from the value of the terminal observation, which atc_rollout_policy_ends stores together with the mask
+ * of the aircraft each decision controlled.  NOT COVERED (the trainer's): advantage normalisation — with that mask in hand three
+ * reductions over [D][B][N] — and the traffic records of a terminal state, which no launch produces.
  * ATC_ERR_ARG, in this order, the first four before any pointer is looked at, atc_last_error() naming the argument: D < 1; hold
  * outside 1 .. ATC_SKIP_MAX; NV outside 1 .. 64; B < 1; a NULL among s, reward, done, values, g, out, out->adv, out->ret; unknown flag
  * bits; gamma or lam not finite; any overlap among the byte ranges of reward (T*B*4 bytes, T*C*4 per column), done (T*B), values
@@ -1175,6 +1221,28 @@ int atc_gae(const atc_scenario_t* s, int B, int NV, int D, int hold,
             const atc_gae_t* g, const atc_gae_out_t* out, void* stream);
 enum { ATC_GAE_LAUNCH_SLOTS = 1 };
 int atc_gae_launch_counts(uint64_t* out, int n);
+
+/* GAE WITH BOOTSTRAPPED TRUNCATIONS (extension): atc_gae plus two inputs — boot [D][C], the value of the state block d ENDED in (the
+ * critic on atc_rollout_policy_ends' term_obs[d]), and trunc [D][B], non-zero where that end is a truncation (a time limit) and not a
+ * terminal state.  With g the running product at the block's last counted step (1.0f throughout under ATC_GAE_PER_DECISION):
+ *
+ *     term and trunc[d][e] != 0:  Gn = g * gamma;  delta = (R + (Gn * boot[d][i])) - V[d][i];  A = delta
+ *     term and trunc[d][e] == 0:  as atc_gae
+ *     not term:                   as atc_gae (trunc is not looked at)
+ *
+ * fp32, every operation rounded once, like atc_gae.  Gn is G where the block ran all `hold` steps, and gamma under ATC_GAE_PER_DECISION.
+ * The episode still ends there: A_next does not enter.  A boot word is read into an output only where term and trunc both hold: anywhere
+ * else it may be a NaN without changing an output word.  With boot == NULL and trunc == NULL the call equals atc_gae bit for bit; one
+ * NULL without the other is ATC_ERR_ARG, refused behind the other NULL checks.  boot (D*C*4 bytes) and trunc (D*B) join atc_gae's
+ * overlap rule, SPLITTING holds unchanged (boot and trunc split like reward's rows: by decision), and every other refusal is atc_gae's in
+ * its order.  Counted by atc_gae_boot_launch_counts only (one slot). */
+int atc_gae_boot(const atc_scenario_t* s, int B, int NV, int D, int hold,
+                 const float* reward /* [T][B], or [T][C] per column */, const uint8_t* done /* [T][B] */,
+                 const float* values /* [D+1][C] */, const float* adv_next /* nullable [C] */,
+                 const float* boot /* nullable [D][C] */, const uint8_t* trunc /* nullable [D][B], with boot */,
+                 const atc_gae_t* g, const atc_gae_out_t* out, void* stream);
+enum { ATC_GAE_BOOT_LAUNCH_SLOTS = 1 };
+int atc_gae_boot_launch_counts(uint64_t* out, int n);
 
 #ifdef __cplusplus
 }
