@@ -124,6 +124,14 @@ GAE_LAUNCH_SLOTS = 1
 TERM_ENDED = 0x8000
 ROLLOUT_POLICY_ENDS_LAUNCH_SLOTS = 28
 GAE_BOOT_LAUNCH_SLOTS = 1
+# the PPO policy loss and gradient (include/atc_step.h: atc_ppo_policy_grad): at most PPO_GRAD_MAX_WG workgroups = partial rows of `scratch`,
+# PPO_GRAD_DEFAULT_WG where the caller leaves the choice to the library; the words of `stats`; its record counts calls by K in (0, 1, 2, 4)
+PPO_GRAD_MAX_WG = 1024
+PPO_GRAD_DEFAULT_WG = 512
+PPO_GRAD_TILE = 64
+PPO_GRAD_STATS = 8
+PPO_STAT_N, PPO_STAT_LOSS, PPO_STAT_KL, PPO_STAT_CUT, PPO_STAT_RATIO, PPO_STAT_DLOGP_MAX = range(6)
+PPO_GRAD_LAUNCH_SLOTS = 4
 
 
 def policy_in(traffic=0):
@@ -134,3 +142,8 @@ def policy_in(traffic=0):
 def policy_words(traffic=0):
     """floats in the packed weight array (ATC_POLICY_WORDS; ATC_POLICY_TRAFFIC_WORDS(K))"""
     return POLICY_WORDS + POLICY_HIDDEN * POLICY_TRAFFIC_WORDS_PER_RECORD * int(traffic)
+
+
+def ppo_grad_workgroups(R, workgroups=0):
+    """G of an atc_ppo_policy_grad call on R rows: `workgroups`, or with 0 min(tiles of 64 rows, PPO_GRAD_DEFAULT_WG); `scratch` has G rows"""
+    return int(workgroups) if workgroups else min((int(R) + PPO_GRAD_TILE - 1) // PPO_GRAD_TILE, PPO_GRAD_DEFAULT_WG)

@@ -131,6 +131,23 @@ class AtcGaeOut(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in GAE_OUT_FIELDS]
 
 
+PPO_GRAD_FIELDS = ("traffic_k", "clip", "adv_shift", "adv_scale", "workgroups", "_pad")
+
+
+class AtcPpoGrad(C.Structure):
+    """atc_ppo_grad_t"""
+    _fields_ = [("traffic_k", C.c_int32), ("clip", C.c_float), ("adv_shift", C.c_float), ("adv_scale", C.c_float), ("workgroups", C.c_int32),
+                ("_pad", C.c_uint32)]
+
+
+PPO_GRAD_OUT_FIELDS = ("grad", "stats", "logp_new", "scratch")
+
+
+class AtcPpoGradOut(C.Structure):
+    """atc_ppo_grad_out_t"""
+    _fields_ = [(n, C.c_void_p) for n in PPO_GRAD_OUT_FIELDS]
+
+
 class AtcStepCall(C.Structure):
     """atc_step_call_t"""
     _fields_ = [("s", C.c_void_p), ("B", C.c_int32), ("N", C.c_int32), ("st", C.POINTER(AtcState)), ("actions", C.c_void_p),
@@ -148,7 +165,7 @@ EXPORTS = ("atc_abi_version", "atc_last_error", "atc_launch_counts", "atc_host_m
            "atc_plan_refit", "atc_plan_refit_launch_counts", "atc_plan_score", "atc_plan_score_launch_counts",
            "atc_rollout_policy", "atc_rollout_policy_launch_counts", "atc_rollout_policy_traffic", "atc_rollout_policy_traffic_launch_counts",
            "atc_gae", "atc_gae_launch_counts", "atc_rollout_policy_ends", "atc_rollout_policy_ends_launch_counts", "atc_gae_boot",
-           "atc_gae_boot_launch_counts")
+           "atc_gae_boot_launch_counts", "atc_ppo_policy_grad", "atc_ppo_policy_grad_launch_counts")
 
 def load():
     """Loads libatcstep.so; raises (never falls back) when it has not been built."""
@@ -206,6 +223,7 @@ def load():
     lib.atc_rollout_policy_ends.argtypes = [vp, ci, ci, ci, ci, C.POINTER(AtcState), vp, C.POINTER(AtcPolicyTraffic), C.POINTER(AtcPolicyEndsOut),
                                             C.POINTER(AtcParams), vp]
     lib.atc_gae_boot.argtypes = [vp, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, C.POINTER(AtcGae), C.POINTER(AtcGaeOut), vp]
+    lib.atc_ppo_policy_grad.argtypes = [vp, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(AtcPpoGrad), C.POINTER(AtcPpoGradOut), vp]
     for getter in LAUNCH_RECORDS:
         getattr(lib, getter).argtypes = [C.POINTER(C.c_uint64), ci]
     for name in EXPORTS:
@@ -243,6 +261,11 @@ def _width_k0(slot):
     return (1 << (slot // 4), (0, 1, 2, 4)[slot % 4])
 
 
+def _traffic_k0(slot):
+    """K of a slot of the PPO policy gradient's record: slot = {0, 1, 2, 3 for K = 0, 1, 2, 4}"""
+    return (0, 1, 2, 4)[slot]
+
+
 # The library's launch records (include/atc_step.h): getter -> (slots, name of a slot: a function of the slot number, or the one
 # slot's name).  load() gives every getter its argtypes from this table; each has a wrapper below, and launch_records() reads all.
 LAUNCH_RECORDS = {
@@ -262,6 +285,7 @@ LAUNCH_RECORDS = {
     "atc_gae_launch_counts": (L.GAE_LAUNCH_SLOTS, "gae"),
     "atc_rollout_policy_ends_launch_counts": (L.ROLLOUT_POLICY_ENDS_LAUNCH_SLOTS, _width_k0),
     "atc_gae_boot_launch_counts": (L.GAE_BOOT_LAUNCH_SLOTS, "gae_boot"),
+    "atc_ppo_policy_grad_launch_counts": (L.PPO_GRAD_LAUNCH_SLOTS, _traffic_k0),
 }
 
 
@@ -367,6 +391,12 @@ def rollout_policy_ends_launch_counts():
 def gae_boot_launch_counts():
     """Launches of the advantages with bootstrapped truncations (atc_gae_boot) made by the calling thread so far: {"gae_boot": n}, or {}."""
     return _counts("atc_gae_boot_launch_counts")
+
+
+def ppo_policy_grad_launch_counts():
+    """Calls of the PPO policy loss and gradient (atc_ppo_policy_grad; two launches each) made by the calling thread so far, by records per
+    aircraft (0: the ten-word policy): {0: n, 4: n, ...}, zero counts left out.  Separate from the other launch records."""
+    return _counts("atc_ppo_policy_grad_launch_counts")
 
 
 def lookahead_set_mapping(candidates_per_workgroup=0):

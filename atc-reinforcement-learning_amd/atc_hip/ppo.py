@@ -3,8 +3,11 @@ AtcVecEnv.gae.  The collection loop and the advantage recurrence each run inside
 atc_gae); the value network is the trainer's own and runs as one batched forward over the rows the decisions saw.
 collect_bootstrap() also bootstraps time-limit ends (atc_rollout_policy_ends, atc_gae_boot: the terminal observations join the one
 value forward) and returns the mask of the aircraft each decision controlled.
-Not covered, the trainer's: advantage normalisation — with `control` in hand three reductions over [D, B, N] — and bootstrapping a
-traffic policy's collection: the traffic records of a terminal state are not produced."""
+policy_grad() is the policy half of the update on such a collection: the clipped surrogate loss and its gradient with respect to the
+packed weights in one call (atc_ppo_policy_grad), for the trainer's own optimiser.
+Not covered, the trainer's: advantage normalisation — with `control` in hand three reductions over [D, B, N], which policy_grad() makes
+in torch and passes on as two scalars — and bootstrapping a traffic policy's collection: the traffic records of a terminal state are not
+produced."""
 from . import layout as L
 from . import policy as _policy
 
@@ -45,7 +48,8 @@ def collect(env, weights, value_fn, T, hold=1, traffic=0, gamma=0.99, lam=0.95, 
     the own words of the last stored observation, and its traffic records are obtained with observe_traffic() on the state the rollout
     left, so the env must have been made with AtcVecEnv(traffic=K); which of the columns the critic reads is value_fn's choice.
     obs0 defaults to the env's bound observation tensor, as in rollout_policy; a copy is taken before the launch overwrites it.
-    Returns the rollout's dict plus "values", "adv", "ret", "block_reward", "block_done" and "block_steps" (AtcVecEnv.gae).
+    Returns the rollout's dict plus "values", "adv", "ret", "block_reward", "block_done" and "block_steps" (AtcVecEnv.gae).  The copy of
+    obs0 that decision 0 saw is kept on the env for policy_grad(), next to the collection's obs tensor it belongs to.
     Every done is a terminal state here; collect_bootstrap() bootstraps the time-limit ends."""
     return _collect(env, weights, value_fn, T, hold, traffic, gamma, lam, seed, decision0, obs0, per_decision, False)
 
@@ -76,6 +80,7 @@ def _collect(env, weights, value_fn, T, hold, traffic, gamma, lam, seed, decisio
         out = env.rollout_policy_ends(weights, T, 0, hold=hold, seed=seed, decision0=decision0, obs0=x0)
     else:
         out = env.rollout_policy(weights, T, hold=hold, seed=seed, decision0=decision0, obs0=x0)
+    env._collected_obs0 = (out["obs"], x0)      # what decision 0 saw, for policy_grad() on this collection
     rows = value_rows(env, out, x0, hold=hold, traffic=K)
     if bootstrap:
         rows = torch.cat([rows, out["term_obs"].reshape((-1,) + tuple(rows.shape[1:]))], dim=0)
@@ -92,3 +97,40 @@ def _collect(env, weights, value_fn, T, hold, traffic, gamma, lam, seed, decisio
     res = dict(out, values=values, boot=boot, trunc=trunc)
     res.update(env.gae_boot(out["reward"], out["done"], values, boot, trunc, hold=hold, gamma=gamma, lam=lam, per_decision=per_decision))
     return res
+
+
+
+def policy_grad(env, collected, weights, index=None, clip=0.2, normalise=True, workgroups=0, out=None):
+    """The PPO policy loss and gradient on a collection (AtcVecEnv.ppo_policy_grad), from the dict collect() / collect_bootstrap() return —
+    the row decision 0 saw is the copy that call kept on `env`, so it must be `env`'s latest collection — or from one put together by hand:
+    "obs0", "obs", "action", "logp", "adv" (and "traffic", "control" where the rollout stored them).
+    The D * B * N source rows are flat views, nothing is copied: the rows the decisions saw are value_rows(...)[:-1] (obs0, then the
+    observation each block's last step stored), "traffic" the records next to them (the policy sees K = traffic.shape[-2] of them),
+    "action" and "logp" as stored; adv is [D, B, N], or a per-env [D, B] / [D, B, 1] expanded over the env's aircraft.
+    mask = "control" where the dict has it: an aircraft that was not under control takes no part.  index: int32 [R] or None, the
+    minibatch (torch.randperm(D * B * N, dtype=torch.int32, device=...)[a:b]).  normalise=True: shift and scale are the mean and
+    1 / (std + 1e-8) of adv over the controlled rows of the whole collection, three torch reductions; False passes 0 and 1.
+    Returns ppo_policy_grad's dict: "grad" (to be assigned to weights.grad), "stats", "logp"."""
+    torch = env.torch
+    action = collected["action"]
+    D, B, N = int(action.shape[0]), env.B, env.N
+    hold = int(collected["obs"].shape[0]) // D
+    obs0 = collected.get("obs0")
+    if obs0 is None:
+        kept = getattr(env, "_collected_obs0", None)
+        if kept is None or kept[0] is not collected["obs"]:
+            raise ValueError("collected is not this env's latest collect() / collect_bootstrap(): give the row decision 0 saw as collected['obs0']")
+        obs0 = kept[1]
+    own = value_rows(env, collected, obs0, hold=hold)[:-1]
+    adv = collected["adv"]
+    if adv.dim() == 2 or int(adv.shape[-1]) != N:
+        if adv.dim() == 3 and int(adv.shape[-1]) != 1:
+            raise ValueError("adv must be [D, B, N], or per env [D, B] / [D, B, 1]")
+        adv = adv.reshape(D, B, 1).expand(D, B, N).contiguous()
+    control = collected.get("control")
+    shift, scale = 0.0, 1.0
+    if normalise:
+        a = adv if control is None else adv[control.bool()]
+        shift, scale = float(a.mean()), float(1.0 / (a.std() + 1e-8))
+    return env.ppo_policy_grad(weights, own, action, collected["logp"], adv, traffic=collected.get("traffic"), mask=control, index=index, clip=clip,
+                               adv_shift=shift, adv_scale=scale, workgroups=workgroups, out=out)

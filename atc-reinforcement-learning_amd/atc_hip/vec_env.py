@@ -1024,6 +1024,91 @@ class AtcVecEnv:
         self._keep_gae = (reward, done, values, adv_next, boot, trunc)   # the inputs outlive the launch (like _keep_score)
         return res
 
+    def ppo_policy_grad(self, weights, obs_rows, action, logp_old, adv, *, traffic=None, mask=None, index=None, clip=0.2, adv_shift=0.0,
+                        adv_scale=1.0, workgroups=0, out=None):
+        """The PPO policy loss and its gradient with respect to the packed weights in one call on this env's current stream
+        (atc_ppo_policy_grad, include/atc_step.h): the policy half of an update is `w.grad = env.ppo_policy_grad(...)["grad"]` and the
+        trainer's own optimiser on the packed tensor; no activation is written to memory.  Over R_src stored decisions:
+        weights: the L.policy_words(K)-word tensor of atc_hip.policy.pack_mlp; obs_rows [..., 10]: what each decision saw; traffic
+        [..., K, 8] (K = 1, 2, 4) the records it saw — words 0..6 widen the row as atc_hip.policy.input_rows does — or None for the
+        ten-word policy; action [..., 3]: the UNCLAMPED sample; logp_old, adv: [...] float32; mask: uint8 of R_src elements or None
+        (rollout_policy_ends' control); index: int32 [R] or None — the minibatch: row i evaluates source row index[i], an index outside
+        0 .. R_src - 1 is skipped.  All contiguous tensors on this env's device; nothing is converted (ValueError otherwise).
+        Per row that takes part: ratio = exp(logp - logp_old), A = (adv - adv_shift) * adv_scale (normalisation stays the trainer's: it
+        passes the two scalars), L = -min(ratio A, clamp(ratio, 1 - clip, 1 + clip) A), and the gradient torch.autograd gives for it.
+        Returns {"grad": [policy_words(K)] — the mean over the n rows that take part, zeros if there is none —, "stats": [8] (the
+        L.PPO_STAT_* words: n, mean L, mean (logp_old - logp), the fraction of rows whose gradient was cut, mean ratio,
+        max |logp - logp_old|, two zeros), "logp": [R], written where a row takes part (NaN elsewhere in a fresh tensor; a tensor given in
+        `out` keeps what it holds there)}.  out: a dict with any of "grad", "stats", "logp" and "scratch" ([G, policy_words(K) + 8] float32
+        with G = L.ppo_grad_workgroups(R, workgroups)); with all four the method allocates nothing.  workgroups: 0, or the number G of
+        workgroups, 1 .. L.PPO_GRAD_MAX_WG — the same inputs and the same G give the same bits on every run.  No output may share memory
+        with another tensor of the call (refused by the library).
+        Not covered, the trainer's: the entropy bonus (sum(log_std) + a constant), the value loss, the optimiser."""
+        torch = self.torch
+        dev, f32 = self.device, (self.torch.float32,)
+        need = AtcVecEnv._on_device.__get__(self)
+        K = 0
+        if traffic is not None:
+            if not (torch.is_tensor(traffic) and traffic.dim() >= 3 and int(traffic.shape[-1]) == L.TRAFFIC_DIM and int(traffic.shape[-2]) in L.POLICY_TRAFFIC_K):
+                raise ValueError("traffic must be [..., K, %d] with K one of %s records per aircraft, or None" % (L.TRAFFIC_DIM, L.POLICY_TRAFFIC_K))
+            K = int(traffic.shape[-2])
+        words = L.policy_words(K)
+        need(weights, f32, (words,), text="weights must be the contiguous float32 tensor of %r words (atc_hip.policy.pack_mlp) on %s", elements=True)
+        if not (torch.is_tensor(obs_rows) and obs_rows.dim() >= 1 and int(obs_rows.shape[-1]) == L.OBS_DIM and obs_rows.numel() >= L.OBS_DIM):
+            raise ValueError("obs_rows must be [..., %d] with at least one row" % L.OBS_DIM)
+        R_src = obs_rows.numel() // L.OBS_DIM
+        if R_src > 2 ** 31 - 1:
+            raise ValueError("obs_rows holds more rows than one call covers (2^31 - 1)")
+        need(obs_rows, f32, (R_src, L.OBS_DIM), "obs_rows", elements=True)
+        if traffic is not None:
+            need(traffic, f32, (R_src, K, L.TRAFFIC_DIM), "traffic", elements=True)
+        if not (torch.is_tensor(action) and action.dim() >= 1 and int(action.shape[-1]) == L.ACT_DIM):
+            raise ValueError("action must be [..., %d]" % L.ACT_DIM)
+        need(action, f32, (R_src, L.ACT_DIM), "action", elements=True)
+        need(logp_old, f32, (R_src,), "logp_old", elements=True)
+        need(adv, f32, (R_src,), "adv", elements=True)
+        if mask is not None:
+            need(mask, (torch.uint8,), (R_src,), "mask", elements=True)
+        R = R_src
+        if index is not None:
+            if not (torch.is_tensor(index) and index.dim() == 1 and 1 <= index.numel() <= 2 ** 31 - 1):
+                raise ValueError("index must be an int32 tensor [R] with R >= 1")
+            R = int(index.numel())
+            need(index, (torch.int32,), (R,), "index")
+        with np.errstate(over="ignore"):
+            if not (np.isfinite(np.float32(clip)) and np.float32(clip) > 0):
+                raise ValueError("clip must be finite (in float32) and > 0")
+        workgroups = int(workgroups)
+        if not 0 <= workgroups <= L.PPO_GRAD_MAX_WG:
+            raise ValueError("0 <= workgroups <= %d" % L.PPO_GRAD_MAX_WG)
+        G = L.ppo_grad_workgroups(R, workgroups)
+        want = {"grad": (f32, (words,)), "stats": (f32, (L.PPO_GRAD_STATS,)), "logp": (f32, (R,)), "scratch": (f32, (G, words + L.PPO_GRAD_STATS))}
+        if out is None:
+            res = {"grad": torch.empty(words, dtype=torch.float32, device=dev), "stats": torch.empty(L.PPO_GRAD_STATS, dtype=torch.float32, device=dev),
+                   "logp": torch.full((R,), float("nan"), dtype=torch.float32, device=dev)}
+        else:
+            res = AtcVecEnv._results(self, out, want, set(), "out must be a dict with any of grad, stats, logp, scratch")
+            for n in ("grad", "stats"):
+                if n not in res:
+                    res[n] = torch.empty(want[n][1], dtype=torch.float32, device=dev)
+            if "logp" not in res:
+                res["logp"] = torch.full((R,), float("nan"), dtype=torch.float32, device=dev)
+        scratch = res.pop("scratch", None)
+        if scratch is None:
+            scratch = torch.empty((G, words + L.PPO_GRAD_STATS), dtype=torch.float32, device=dev)
+        g = _lib.AtcPpoGrad(K, float(clip), float(adv_shift), float(adv_scale), workgroups, 0)
+        o = _lib.AtcPpoGradOut(res["grad"].data_ptr(), res["stats"].data_ptr(), res["logp"].data_ptr(), scratch.data_ptr())
+        fn = self._lib.atc_ppo_policy_grad
+        with torch.cuda.device(dev):
+            rc = fn(self.sector.handle, R_src, R, weights.data_ptr(), obs_rows.data_ptr(),
+                                               None if traffic is None else traffic.data_ptr(), action.data_ptr(), logp_old.data_ptr(), adv.data_ptr(),
+                                               None if mask is None else mask.data_ptr(), None if index is None else index.data_ptr(),
+                                               C.byref(g), C.byref(o), self._stream())
+            if rc:
+                _lib.check(rc)
+        self._keep_ppo_grad = (weights, obs_rows, traffic, action, logp_old, adv, mask, index, scratch)   # they outlive the two launches
+        return res
+
     def get_attr(self, name, indices=None):
         """VecEnv.get_attr for the attributes the reference's trainer reads (learning/atc-gym-stable-baselines.py:34,36)
         and the episode counters."""

@@ -28,6 +28,7 @@ int atc_rollout_policy_traffic_launch_counts(uint64_t* out, int n) { return copy
 int atc_gae_launch_counts(uint64_t* out, int n) { return copy_counts(REC_GAE, out, n); }
 int atc_rollout_policy_ends_launch_counts(uint64_t* out, int n) { return copy_counts(REC_POLICY_ENDS, out, n); }
 int atc_gae_boot_launch_counts(uint64_t* out, int n) { return copy_counts(REC_GAE_BOOT, out, n); }
+int atc_ppo_policy_grad_launch_counts(uint64_t* out, int n) { return copy_counts(REC_PPO_GRAD, out, n); }
 int atc_lookahead_set_mapping(int candidates_per_workgroup) {
     if (candidates_per_workgroup < 0 || candidates_per_workgroup > ATC_LOOKAHEAD_MAX_M) return fail_arg("candidates per workgroup must be 0 (the library's choice) .. 64");
     t_look_cpg = candidates_per_workgroup;
@@ -640,6 +641,58 @@ int atc_gae(const atc_scenario_t* s, int B, int NV, int D, int hold, const float
 int atc_gae_boot(const atc_scenario_t* s, int B, int NV, int D, int hold, const float* reward, const uint8_t* done, const float* values,
                  const float* adv_next, const float* boot, const uint8_t* trunc, const atc_gae_t* g, const atc_gae_out_t* out, void* stream) {
     return gae_call(REC_GAE_BOOT, s, B, NV, D, hold, reward, done, values, adv_next, boot, trunc, g, out, stream);
+}
+
+// atc_ppo_policy_grad: the checks in the header's order, then k_ppo_grad<K> on G workgroups and k_ppo_grad_reduce, both on `stream`
+int atc_ppo_policy_grad(const atc_scenario_t* s, int R_src, int R, const float* w, const float* obs_rows, const float* traffic, const float* action,
+                        const float* logp_old, const float* adv, const uint8_t* mask, const int32_t* index, const atc_ppo_grad_t* g,
+                        const atc_ppo_grad_out_t* out, void* stream) {
+    if (const int rc = check_required({{s, "null pointer: s"}, {w, "null pointer: w (the policy's weights) is required"}, {obs_rows, "null pointer: obs_rows is required"},
+                                       {action, "null pointer: action is required"}, {logp_old, "null pointer: logp_old is required"},
+                                       {adv, "null pointer: adv is required"}, {g, "null pointer: g (atc_ppo_grad_t) is required"},
+                                       {out, "null pointer: out (atc_ppo_grad_out_t) is required"}}))
+        return rc;
+    if (const int rc = check_required({{out->grad, "null pointer: out->grad is required"}, {out->stats, "null pointer: out->stats is required"},
+                                       {out->scratch, "null pointer: out->scratch is required"}}))
+        return rc;
+    const int K = g->traffic_k;
+    if (K != 0 && K != 1 && K != 2 && K != 4) return fail_arg("g->traffic_k must be 0, 1, 2 or 4 (the ten-word policy, or a compiled list length)");
+    if (R_src < 1) return fail_arg("R_src (the number of source rows) must be >= 1");
+    if (R < 1) return fail_arg("R (the number of rows to evaluate) must be >= 1");
+    if (!index && R != R_src) return fail_arg("R must equal R_src where index is NULL (the identity)");
+    if (!(g->clip > 0.0f && g->clip <= __FLT_MAX__)) return fail_arg("g->clip must be finite and > 0");
+    if (g->workgroups < 0 || g->workgroups > ATC_PPO_GRAD_MAX_WG) return fail_arg("g->workgroups must be 0 (the library's choice) .. 1024 (ATC_PPO_GRAD_MAX_WG)");
+    if (K > 0 && !traffic) return fail_arg("null pointer: traffic is required where g->traffic_k > 0");
+    if (K == 0 && traffic) return fail_arg("traffic must be NULL where g->traffic_k is 0 (the ten-word policy reads no records)");
+    const long long tiles = ((long long)R + (kPpoBlock - 1)) / kPpoBlock;
+    const int G = g->workgroups ? g->workgroups : (int)(tiles < ATC_PPO_GRAD_DEFAULT_WG ? tiles : ATC_PPO_GRAD_DEFAULT_WG);
+    const int words = ATC_POLICY_TRAFFIC_WORDS(K);
+    // no output may share memory with any array of the call (the inputs may share among themselves)
+    const uintptr_t rs = (uintptr_t)R_src, r = (uintptr_t)R;
+    const ByteRange outputs[4] = {{out->grad, (uintptr_t)words * 4u, "grad"}, {out->stats, ATC_PPO_GRAD_STATS * 4u, "stats"}, {out->logp_new, r * 4u, "logp_new"},
+                                  {out->scratch, (uintptr_t)G * (uintptr_t)(words + ATC_PPO_GRAD_STATS) * 4u, "scratch"}};
+    const ByteRange inputs[8] = {{w, (uintptr_t)words * 4u, "w"}, {obs_rows, rs * (ATC_OBS_DIM * 4u), "obs_rows"},
+                                 {traffic, rs * (uintptr_t)K * (ATC_TRAFFIC_DIM * 4u), "traffic"}, {action, rs * 12u, "action"}, {logp_old, rs * 4u, "logp_old"},
+                                 {adv, rs * 4u, "adv"}, {mask, rs, "mask"}, {index, r * 4u, "index"}};
+    for (int a = 0; a < 4; ++a) {
+        if (!outputs[a].ptr) continue;
+        for (int b = 0; b < 8 + a; ++b) {
+            const ByteRange pair[2] = {b < 8 ? inputs[b] : outputs[b - 8], outputs[a]};
+            if (const int rc = check_disjoint(pair, 2, {}, "no output of atc_ppo_policy_grad may share memory with another array")) return rc;
+        }
+    }
+    const atc_ppo_grad_t gp = *g;
+    with_traffic_k0(K, [&](auto kt) {
+        hipLaunchKernelGGL(k_ppo_grad<decltype(kt)::value>, dim3((unsigned)G), dim3(kPpoBlock), 0, (hipStream_t)stream, R_src, R, w, obs_rows, traffic, action, logp_old,
+                           adv, mask, index, gp, out->logp_new, out->scratch);
+        return ATC_OK;
+    });
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_ppo_grad_reduce, dim3((unsigned)((words + ATC_PPO_GRAD_STATS + kPpoReduceBlock - 1) / kPpoReduceBlock)), dim3(kPpoReduceBlock), 0,
+                       (hipStream_t)stream, words, G, out->scratch, out->grad, out->stats);
+    HIP_TRY(hipGetLastError());
+    ++record(REC_PPO_GRAD)[K ? 1 + __builtin_ctz(K) : 0];
+    return ATC_OK;
 }
 
 }  // extern "C"

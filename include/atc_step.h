@@ -1244,6 +1244,78 @@ int atc_gae_boot(const atc_scenario_t* s, int B, int NV, int D, int hold,
 enum { ATC_GAE_BOOT_LAUNCH_SLOTS = 1 };
 int atc_gae_boot_launch_counts(uint64_t* out, int n);
 
+/* PPO POLICY GRADIENT (extension): the policy half of a PPO update in one call — the clipped surrogate loss of the 10 + 7 K -> 64 -> 64 -> 3
+ * policy of atc_rollout_policy_ends on stored decisions, and its gradient with respect to every word of the packed weight array, summed over
+ * the rows of a minibatch.  No activation is written to global memory: the forward and the backward of a row stay in one workgroup.  A pure
+ * function of its arrays, like atc_gae: `s` names the device only.  All array pointers are device pointers.
+ * ROWS.  R_src source rows, R rows to evaluate.  Row i evaluates source row index[i]; an index outside [0, R_src) is skipped: it is not
+ * counted and nothing of it is read.  index == NULL means R == R_src and the identity.  A row PARTICIPATES if its source row is in range and
+ * mask is NULL or mask[source row] != 0 (atc_rollout_policy_ends' control, flattened).  A row that does not participate is taken out by
+ * selects, never by a product with zero: any word may stand in it, a NaN included, without changing an output bit.
+ * INPUT ROW.  x = obs_rows[row][0..9], then words 0..6 of each of the K = traffic_k records traffic[row][r][0..7] (word 7 is not read):
+ * atc_rollout_policy_traffic's INPUT ROW.  w is the packed policy, ATC_POLICY_TRAFFIC_WORDS(K) floats.
+ * PER PARTICIPATING ROW, in fp32, with u = action[row] (the UNCLAMPED sample) and A = (adv[row] - adv_shift) * adv_scale:
+ *
+ *     mu = MLP(x)                                       atc_rollout_policy's arithmetic, the float64 first layer included (a wavefront of 64
+ *                                                       consecutive rows i that holds a participating input above 4 in magnitude takes it)
+ *     sigma_c = expf(log_std_c);  d_c = (u_c - mu_c) / sigma_c
+ *     logp  = sum_c (-0.5 d_c^2 - log_std_c) - 1.5 log(2 pi)
+ *     ratio = expf(logp - logp_old[row])
+ *     L     = -min(ratio * A, clamp(ratio, 1 - clip, 1 + clip) * A)
+ *     the gradient flows through the unclipped term iff (A >= 0 and ratio <= 1 + clip) or (A < 0 and ratio >= 1 - clip), and is zero
+ *     otherwise (the row is CUT): what autograd yields for minimum(ratio A, clamp(ratio, 1 - clip, 1 + clip) A), boundaries inclusive
+ *     dL/dlogp = -A ratio where it flows;  dlogp/dmu_c = d_c / sigma_c;  dlogp/dlog_std_c = d_c^2 - 1;  backpropagation through the two
+ *     tanh layers
+ *
+ * OUTPUTS, with n the number of participating rows:
+ *   grad   [ATC_POLICY_TRAFFIC_WORDS(K)], laid out like w: the sum of dL/dw over the participating rows, divided by n; all zeros if n == 0.
+ *   stats  [ATC_PPO_GRAD_STATS] (the ATC_PPO_STAT_* words): n; mean L; mean (logp_old - logp), the approximate KL; the fraction of
+ *          participating rows that were cut; mean ratio; max |logp - logp_old|; two reserved zeros.  All zeros if n == 0.
+ *   logp_new [R], nullable: logp of row i, written for participating rows only; the others keep what they hold.
+ *   scratch [G][ATC_POLICY_TRAFFIC_WORDS(K) + ATC_PPO_GRAD_STATS] floats, required: the G partial sums, overwritten by every call.
+ * WORKGROUPS AND DETERMINISM.  G workgroups of one wavefront each take the tiles of 64 consecutive rows i in turn (workgroup g: tiles g,
+ * g + G, ...).  workgroups == 0: G = min(number of tiles, ATC_PPO_GRAD_DEFAULT_WG); otherwise G = workgroups, 1 .. ATC_PPO_GRAD_MAX_WG.  No
+ * floating-point atomics: a workgroup adds its rows in row order, the G partial sums are added in the order of g in float64 and rounded
+ * once, and the division by n comes last.  The same inputs and the same G give the same bits on every run; another G gives another
+ * rounding of the same sums.  One call is two launches on `stream`.
+ * NOT IN THE CALL (the trainer's): the entropy bonus — with a log_std that does not depend on the state it is sum_c log_std_c + a constant,
+ * three words —, the value loss and the critic, advantage normalisation (the trainer passes its two scalars), and the optimiser.
+ * ATC_ERR_ARG, in this order, atc_last_error() naming the argument: a NULL among s, w, obs_rows, action, logp_old, adv, g, out, out->grad,
+ * out->stats, out->scratch; traffic_k outside {0, 1, 2, 4}; R_src < 1, R < 1, or index == NULL with R != R_src; clip not finite or <= 0;
+ * workgroups outside 0 .. ATC_PPO_GRAD_MAX_WG; traffic NULL with traffic_k > 0, or given with traffic_k == 0; an output (grad, stats,
+ * logp_new, scratch) sharing a byte with any other array of the call — pointer values only, ranges that only touch are accepted.
+ * Counted by atc_ppo_policy_grad_launch_counts only: one count per CALL, slot = {0, 1, 2, 3 for traffic_k = 0, 1, 2, 4}. */
+#define ATC_PPO_GRAD_MAX_WG 1024
+#define ATC_PPO_GRAD_DEFAULT_WG 512
+#define ATC_PPO_GRAD_STATS 8
+#define ATC_PPO_STAT_N 0          /* participating rows */
+#define ATC_PPO_STAT_LOSS 1       /* mean L */
+#define ATC_PPO_STAT_KL 2         /* mean (logp_old - logp) */
+#define ATC_PPO_STAT_CUT 3        /* fraction of participating rows whose gradient was cut */
+#define ATC_PPO_STAT_RATIO 4      /* mean ratio */
+#define ATC_PPO_STAT_DLOGP_MAX 5  /* max |logp - logp_old| */
+typedef struct atc_ppo_grad {
+    int32_t  traffic_k;   /* K: 0, 1, 2 or 4 */
+    float    clip;        /* > 0, finite */
+    float    adv_shift;   /* A = (adv - adv_shift) * adv_scale */
+    float    adv_scale;
+    int32_t  workgroups;  /* 0: the library's choice; else G = 1 .. ATC_PPO_GRAD_MAX_WG */
+    uint32_t _pad;
+} atc_ppo_grad_t;
+typedef struct atc_ppo_grad_out {
+    float* grad;      /* [ATC_POLICY_TRAFFIC_WORDS(K)] required */
+    float* stats;     /* [ATC_PPO_GRAD_STATS] required */
+    float* logp_new;  /* [R] nullable */
+    float* scratch;   /* [G][ATC_POLICY_TRAFFIC_WORDS(K) + ATC_PPO_GRAD_STATS] required */
+} atc_ppo_grad_out_t;
+int atc_ppo_policy_grad(const atc_scenario_t* s, int R_src, int R, const float* w /* [ATC_POLICY_TRAFFIC_WORDS(K)] */,
+                        const float* obs_rows /* [R_src][10] */, const float* traffic /* [R_src][K][8], with K > 0 */,
+                        const float* action /* [R_src][3] */, const float* logp_old /* [R_src] */, const float* adv /* [R_src] */,
+                        const uint8_t* mask /* nullable [R_src] */, const int32_t* index /* nullable [R] */,
+                        const atc_ppo_grad_t* g, const atc_ppo_grad_out_t* out, void* stream);
+enum { ATC_PPO_GRAD_LAUNCH_SLOTS = 4 };
+int atc_ppo_policy_grad_launch_counts(uint64_t* out, int n);
+
 #ifdef __cplusplus
 }
 #endif
