@@ -132,6 +132,14 @@ PPO_GRAD_TILE = 64
 PPO_GRAD_STATS = 8
 PPO_STAT_N, PPO_STAT_LOSS, PPO_STAT_KL, PPO_STAT_CUT, PPO_STAT_RATIO, PPO_STAT_DLOGP_MAX = range(6)
 PPO_GRAD_LAUNCH_SLOTS = 4
+# the critic (include/atc_step.h: atc_value_forward, atc_ppo_value_grad): the policy's trunk with one output, value_words(K) floats in one array
+# (W1, b1, W2, b2, W3[1][64], b3[1]); the words of atc_ppo_value_grad's `stats`; both records count calls by K in (0, 1, 2, 4).  Workgroups and
+# scratch rows are the policy gradient's (PPO_GRAD_MAX_WG, PPO_GRAD_DEFAULT_WG, ppo_grad_workgroups).
+VALUE_WORDS = 4929
+PPO_VALUE_STATS = 8
+(PPO_VSTAT_N, PPO_VSTAT_LOSS, PPO_VSTAT_CUT, PPO_VSTAT_V, PPO_VSTAT_RET, PPO_VSTAT_RET2, PPO_VSTAT_ERR2, PPO_VSTAT_DV_MAX) = range(8)
+VALUE_FORWARD_LAUNCH_SLOTS = 4
+PPO_VALUE_GRAD_LAUNCH_SLOTS = 4
 
 
 def policy_in(traffic=0):
@@ -144,6 +152,11 @@ def policy_words(traffic=0):
     return POLICY_WORDS + POLICY_HIDDEN * POLICY_TRAFFIC_WORDS_PER_RECORD * int(traffic)
 
 
+def value_words(traffic=0):
+    """floats in the packed critic (ATC_VALUE_WORDS(K))"""
+    return VALUE_WORDS + POLICY_HIDDEN * POLICY_TRAFFIC_WORDS_PER_RECORD * int(traffic)
+
+
 def ppo_grad_workgroups(R, workgroups=0):
-    """G of an atc_ppo_policy_grad call on R rows: `workgroups`, or with 0 min(tiles of 64 rows, PPO_GRAD_DEFAULT_WG); `scratch` has G rows"""
+    """G of an atc_ppo_policy_grad or atc_ppo_value_grad call on R rows: `workgroups`, or with 0 min(tiles of 64 rows, PPO_GRAD_DEFAULT_WG); `scratch` has G rows"""
     return int(workgroups) if workgroups else min((int(R) + PPO_GRAD_TILE - 1) // PPO_GRAD_TILE, PPO_GRAD_DEFAULT_WG)

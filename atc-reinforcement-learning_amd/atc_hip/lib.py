@@ -148,6 +148,22 @@ class AtcPpoGradOut(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in PPO_GRAD_OUT_FIELDS]
 
 
+PPO_VALUE_GRAD_FIELDS = ("clip", "workgroups")
+
+
+class AtcPpoValueGrad(C.Structure):
+    """atc_ppo_value_grad_t"""
+    _fields_ = [("clip", C.c_float), ("workgroups", C.c_int32)]
+
+
+PPO_VALUE_GRAD_OUT_FIELDS = ("grad", "stats", "value", "scratch")
+
+
+class AtcPpoValueGradOut(C.Structure):
+    """atc_ppo_value_grad_out_t"""
+    _fields_ = [(n, C.c_void_p) for n in PPO_VALUE_GRAD_OUT_FIELDS]
+
+
 class AtcStepCall(C.Structure):
     """atc_step_call_t"""
     _fields_ = [("s", C.c_void_p), ("B", C.c_int32), ("N", C.c_int32), ("st", C.POINTER(AtcState)), ("actions", C.c_void_p),
@@ -165,7 +181,8 @@ EXPORTS = ("atc_abi_version", "atc_last_error", "atc_launch_counts", "atc_host_m
            "atc_plan_refit", "atc_plan_refit_launch_counts", "atc_plan_score", "atc_plan_score_launch_counts",
            "atc_rollout_policy", "atc_rollout_policy_launch_counts", "atc_rollout_policy_traffic", "atc_rollout_policy_traffic_launch_counts",
            "atc_gae", "atc_gae_launch_counts", "atc_rollout_policy_ends", "atc_rollout_policy_ends_launch_counts", "atc_gae_boot",
-           "atc_gae_boot_launch_counts", "atc_ppo_policy_grad", "atc_ppo_policy_grad_launch_counts")
+           "atc_gae_boot_launch_counts", "atc_ppo_policy_grad", "atc_ppo_policy_grad_launch_counts",
+           "atc_value_forward", "atc_value_forward_launch_counts", "atc_ppo_value_grad", "atc_ppo_value_grad_launch_counts")
 
 def load():
     """Loads libatcstep.so; raises (never falls back) when it has not been built."""
@@ -224,6 +241,8 @@ def load():
                                             C.POINTER(AtcParams), vp]
     lib.atc_gae_boot.argtypes = [vp, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, C.POINTER(AtcGae), C.POINTER(AtcGaeOut), vp]
     lib.atc_ppo_policy_grad.argtypes = [vp, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(AtcPpoGrad), C.POINTER(AtcPpoGradOut), vp]
+    lib.atc_value_forward.argtypes = [vp, ci, ci, vp, vp, vp, vp]
+    lib.atc_ppo_value_grad.argtypes = [vp, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, C.POINTER(AtcPpoValueGrad), C.POINTER(AtcPpoValueGradOut), vp]
     for getter in LAUNCH_RECORDS:
         getattr(lib, getter).argtypes = [C.POINTER(C.c_uint64), ci]
     for name in EXPORTS:
@@ -262,7 +281,7 @@ def _width_k0(slot):
 
 
 def _traffic_k0(slot):
-    """K of a slot of the PPO policy gradient's record: slot = {0, 1, 2, 3 for K = 0, 1, 2, 4}"""
+    """K of a slot of the PPO policy gradient's record, and of the critic's two: slot = {0, 1, 2, 3 for K = 0, 1, 2, 4}"""
     return (0, 1, 2, 4)[slot]
 
 
@@ -286,6 +305,8 @@ LAUNCH_RECORDS = {
     "atc_rollout_policy_ends_launch_counts": (L.ROLLOUT_POLICY_ENDS_LAUNCH_SLOTS, _width_k0),
     "atc_gae_boot_launch_counts": (L.GAE_BOOT_LAUNCH_SLOTS, "gae_boot"),
     "atc_ppo_policy_grad_launch_counts": (L.PPO_GRAD_LAUNCH_SLOTS, _traffic_k0),
+    "atc_value_forward_launch_counts": (L.VALUE_FORWARD_LAUNCH_SLOTS, _traffic_k0),
+    "atc_ppo_value_grad_launch_counts": (L.PPO_VALUE_GRAD_LAUNCH_SLOTS, _traffic_k0),
 }
 
 
@@ -397,6 +418,18 @@ def ppo_policy_grad_launch_counts():
     """Calls of the PPO policy loss and gradient (atc_ppo_policy_grad; two launches each) made by the calling thread so far, by records per
     aircraft (0: the ten-word policy): {0: n, 4: n, ...}, zero counts left out.  Separate from the other launch records."""
     return _counts("atc_ppo_policy_grad_launch_counts")
+
+
+def value_forward_launch_counts():
+    """Calls of the critic's forward (atc_value_forward; one launch each) made by the calling thread so far, by records per aircraft (0: the
+    ten-word row): {0: n, 4: n, ...}, zero counts left out.  Separate from the other launch records."""
+    return _counts("atc_value_forward_launch_counts")
+
+
+def ppo_value_grad_launch_counts():
+    """Calls of the PPO value loss and gradient (atc_ppo_value_grad; two launches each) made by the calling thread so far, by records per
+    aircraft, like ppo_policy_grad_launch_counts().  Separate from the other launch records."""
+    return _counts("atc_ppo_value_grad_launch_counts")
 
 
 def lookahead_set_mapping(candidates_per_workgroup=0):

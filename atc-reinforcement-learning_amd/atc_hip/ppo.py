@@ -1,10 +1,13 @@
 """A PPO collection in three calls on fixed shapes: AtcVecEnv.rollout_policy (or rollout_policy_traffic) -> one value forward ->
 AtcVecEnv.gae.  The collection loop and the advantage recurrence each run inside one launch (include/atc_step.h: atc_rollout_policy,
-atc_gae); the value network is the trainer's own and runs as one batched forward over the rows the decisions saw.
+atc_gae); the value network runs as one batched forward over the rows the decisions saw — any callable of the trainer's, or critic(env,
+weights): the library's own forward of a critic packed by atc_hip.value (atc_value_forward).
 collect_bootstrap() also bootstraps time-limit ends (atc_rollout_policy_ends, atc_gae_boot: the terminal observations join the one
 value forward) and returns the mask of the aircraft each decision controlled.
 policy_grad() is the policy half of the update on such a collection: the clipped surrogate loss and its gradient with respect to the
-packed weights in one call (atc_ppo_policy_grad), for the trainer's own optimiser.
+packed weights in one call (atc_ppo_policy_grad), and value_grad() the value half: the clipped value loss of the packed critic and its
+gradient (atc_ppo_value_grad).  One iteration then touches autograd nowhere: what is left to the trainer is the optimiser, stepped on the
+two packed tensors, and the entropy bonus (log_std.sum() plus a constant).
 Not covered, the trainer's: advantage normalisation — with `control` in hand three reductions over [D, B, N], which policy_grad() makes
 in torch and passes on as two scalars — and bootstrapping a traffic policy's collection: the traffic records of a terminal state are not
 produced."""
@@ -134,3 +137,40 @@ def policy_grad(env, collected, weights, index=None, clip=0.2, normalise=True, w
         shift, scale = float(a.mean()), float(1.0 / (a.std() + 1e-8))
     return env.ppo_policy_grad(weights, own, action, collected["logp"], adv, traffic=collected.get("traffic"), mask=control, index=index, clip=clip,
                                adv_shift=shift, adv_scale=scale, workgroups=workgroups, out=out)
+
+
+def critic(env, weights):
+    """A value_fn for collect() / collect_bootstrap() that runs the library's critic: env.value_forward(weights, rows) on the rows it is
+    given, [D + 1, B, N, IN] or [2 D + 1, B, N, IN] -> one value per aircraft.  weights: the tensor of atc_hip.value.pack_mlp(traffic=K) for
+    the K of the collection (collect(traffic=K) hands it rows of 10 + 7 K words)."""
+    def value_fn(rows):
+        return env.value_forward(weights, rows.contiguous())
+    return value_fn
+
+
+def value_grad(env, collected, weights, index=None, clip=0.2, workgroups=0, out=None):
+    """The PPO value loss and gradient on a collection (AtcVecEnv.ppo_value_grad), from the dict collect() / collect_bootstrap() return, or
+    from one put together by hand, as policy_grad() takes it: "obs0" (or the copy the collection kept on `env`), "obs", "action", "values",
+    "ret" (and "traffic", "control" where the rollout stored them).
+    v_old = values[:-1] and ret, both [D, B, N] — a per-env [D, B] or [D, B, 1] is expanded over the env's aircraft —; the rows are
+    value_rows(...)[:-1], "traffic" the records next to them, mask = "control", index the int32 minibatch; nothing else is copied.
+    Returns ppo_value_grad's dict: "grad" (to be assigned to weights.grad), "stats", "value"."""
+    action = collected["action"]
+    D, B, N = int(action.shape[0]), env.B, env.N
+    hold = int(collected["obs"].shape[0]) // D
+    obs0 = collected.get("obs0")
+    if obs0 is None:
+        kept = getattr(env, "_collected_obs0", None)
+        if kept is None or kept[0] is not collected["obs"]:
+            raise ValueError("collected is not this env's latest collect() / collect_bootstrap(): give the row decision 0 saw as collected['obs0']")
+        obs0 = kept[1]
+    own = value_rows(env, collected, obs0, hold=hold)[:-1]
+
+    def per_aircraft(v, name):
+        if v.dim() == 3 and int(v.shape[-1]) == N:
+            return v.contiguous()
+        if v.dim() == 3 and int(v.shape[-1]) != 1:
+            raise ValueError("%s must be [D, B, N], or per env [D, B] / [D, B, 1]" % name)
+        return v.reshape(D, B, 1).expand(D, B, N).contiguous()
+    return env.ppo_value_grad(weights, own, per_aircraft(collected["values"][:-1], "values[:-1]"), per_aircraft(collected["ret"], "ret"),
+                              traffic=collected.get("traffic"), mask=collected.get("control"), index=index, clip=clip, workgroups=workgroups, out=out)

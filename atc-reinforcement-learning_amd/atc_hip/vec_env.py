@@ -1043,7 +1043,8 @@ class AtcVecEnv:
         with G = L.ppo_grad_workgroups(R, workgroups)); with all four the method allocates nothing.  workgroups: 0, or the number G of
         workgroups, 1 .. L.PPO_GRAD_MAX_WG — the same inputs and the same G give the same bits on every run.  No output may share memory
         with another tensor of the call (refused by the library).
-        Not covered, the trainer's: the entropy bonus (sum(log_std) + a constant), the value loss, the optimiser."""
+        Not in this call: the value loss (ppo_value_grad, on a critic packed by atc_hip.value); the trainer's: the entropy bonus
+        (sum(log_std) + a constant) and the optimiser, stepped on the two packed tensors."""
         torch = self.torch
         dev, f32 = self.device, (self.torch.float32,)
         need = AtcVecEnv._on_device.__get__(self)
@@ -1107,6 +1108,114 @@ class AtcVecEnv:
             if rc:
                 _lib.check(rc)
         self._keep_ppo_grad = (weights, obs_rows, traffic, action, logp_old, adv, mask, index, scratch)   # they outlive the two launches
+        return res
+
+    def value_forward(self, weights, rows, *, out=None):
+        """V of every row in one launch on this env's current stream (atc_value_forward, include/atc_step.h): the critic of atc_hip.value —
+        (10 + 7 K) -> 64 -> 64 -> 1, tanh — evaluated one lane per row, no activation written to memory.
+        weights: the L.value_words(K)-word tensor of atc_hip.value.pack_mlp; rows [..., IN] float32, contiguous, on this env's device, with
+        IN = 10 + 7 K for K = 0, 1, 2 or 4: the rows as atc_hip.ppo.value_rows() makes them (atc_hip.policy.input_rows widens them).  Nothing
+        is converted (ValueError otherwise).  Returns a float32 tensor of shape rows.shape[:-1]; out: that tensor, and nothing is allocated."""
+        torch = self.torch
+        f32 = (torch.float32,)
+        need = AtcVecEnv._on_device.__get__(self)
+        ins = {L.policy_in(k): k for k in (0,) + L.POLICY_TRAFFIC_K}
+        if not (torch.is_tensor(rows) and rows.dim() >= 1 and int(rows.shape[-1]) in ins and rows.numel() >= int(rows.shape[-1])):
+            raise ValueError("rows must be [..., IN] with IN one of %s (10 + 7 K) and at least one row" % (sorted(ins),))
+        IN = int(rows.shape[-1])
+        K = ins[IN]
+        R = rows.numel() // IN
+        if R > 2 ** 31 - 1:
+            raise ValueError("rows holds more rows than one call covers (2^31 - 1)")
+        need(rows, f32, (R, IN), "rows", elements=True)
+        need(weights, f32, (L.value_words(K),), text="weights must be the contiguous float32 tensor of %r words (atc_hip.value.pack_mlp) on %s", elements=True)
+        shape = tuple(rows.shape[:-1])
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float32, device=self.device)
+        else:
+            need(out, f32, shape, "out")
+        fn = self._lib.atc_value_forward
+        with torch.cuda.device(self.device):
+            rc = fn(self.sector.handle, R, K, weights.data_ptr(), rows.data_ptr(), out.data_ptr(), self._stream())
+            if rc:
+                _lib.check(rc)
+        self._keep_value = (weights, rows, out)      # they outlive the launch
+        return out
+
+    def ppo_value_grad(self, weights, obs_rows, v_old, ret, *, traffic=None, mask=None, index=None, clip=0.2, workgroups=0, out=None):
+        """The clipped PPO value loss and its gradient with respect to the packed critic in one call on this env's current stream
+        (atc_ppo_value_grad, include/atc_step.h): the value half of an update is `vw.grad = env.ppo_value_grad(...)["grad"]` and the
+        trainer's own optimiser on the packed tensor; no activation is written to memory.  Over R_src stored decisions:
+        weights: the L.value_words(K)-word tensor of atc_hip.value.pack_mlp; obs_rows [..., 10], traffic [..., K, 8] or None, mask, index:
+        as in ppo_policy_grad (read in place, a minibatch is gathered by `index` without a copy); v_old, ret: [...] float32 of R_src
+        elements — the values the collection stored and its returns.  All contiguous tensors on this env's device.
+        Per row that takes part, with v = V(row): e = v - ret, d = v - v_old, vc = v_old + clamp(d, -clip, clip); L = 0.5 e^2 and
+        dL/dv = e where |d| <= clip or e^2 >= (vc - ret)^2, else the row is cut: L = 0.5 (vc - ret)^2, dL/dv = 0 — PPO2's
+        0.5 max((v - ret)^2, (vc - ret)^2).  clip=float("inf") is the plain squared error.
+        Returns {"grad": [value_words(K)] — the mean over the n rows that take part, zeros if there is none —, "stats": [8] (the
+        L.PPO_VSTAT_* words: n, mean L, the fraction cut, mean v, mean ret, mean ret^2, mean (ret - v)^2, max |v - v_old|; words 4 .. 6 give
+        the explained variance), "value": [R], written where a row takes part (NaN elsewhere in a fresh tensor; a tensor given in `out`
+        keeps what it holds there) — bit for bit value_forward's output where the tiles of 64 rows hold the same rows}.  out: a dict with
+        any of "grad", "stats", "value" and "scratch" ([G, value_words(K) + 8] float32 with G = L.ppo_grad_workgroups(R, workgroups)); with
+        all four the method allocates nothing.  workgroups: as in ppo_policy_grad.  No output may share memory with another tensor of the
+        call (refused by the library)."""
+        torch = self.torch
+        dev, f32 = self.device, (self.torch.float32,)
+        need = AtcVecEnv._on_device.__get__(self)
+        K = 0
+        if traffic is not None:
+            if not (torch.is_tensor(traffic) and traffic.dim() >= 3 and int(traffic.shape[-1]) == L.TRAFFIC_DIM and int(traffic.shape[-2]) in L.POLICY_TRAFFIC_K):
+                raise ValueError("traffic must be [..., K, %d] with K one of %s records per aircraft, or None" % (L.TRAFFIC_DIM, L.POLICY_TRAFFIC_K))
+            K = int(traffic.shape[-2])
+        words = L.value_words(K)
+        need(weights, f32, (words,), text="weights must be the contiguous float32 tensor of %r words (atc_hip.value.pack_mlp) on %s", elements=True)
+        if not (torch.is_tensor(obs_rows) and obs_rows.dim() >= 1 and int(obs_rows.shape[-1]) == L.OBS_DIM and obs_rows.numel() >= L.OBS_DIM):
+            raise ValueError("obs_rows must be [..., %d] with at least one row" % L.OBS_DIM)
+        R_src = obs_rows.numel() // L.OBS_DIM
+        if R_src > 2 ** 31 - 1:
+            raise ValueError("obs_rows holds more rows than one call covers (2^31 - 1)")
+        need(obs_rows, f32, (R_src, L.OBS_DIM), "obs_rows", elements=True)
+        if traffic is not None:
+            need(traffic, f32, (R_src, K, L.TRAFFIC_DIM), "traffic", elements=True)
+        need(v_old, f32, (R_src,), "v_old", elements=True)
+        need(ret, f32, (R_src,), "ret", elements=True)
+        if mask is not None:
+            need(mask, (torch.uint8,), (R_src,), "mask", elements=True)
+        R = R_src
+        if index is not None:
+            if not (torch.is_tensor(index) and index.dim() == 1 and 1 <= index.numel() <= 2 ** 31 - 1):
+                raise ValueError("index must be an int32 tensor [R] with R >= 1")
+            R = int(index.numel())
+            need(index, (torch.int32,), (R,), "index")
+        with np.errstate(over="ignore"):
+            if not np.float32(clip) > 0:
+                raise ValueError("clip must be > 0 in float32 (float('inf'): no clipping) and not a NaN")
+        workgroups = int(workgroups)
+        if not 0 <= workgroups <= L.PPO_GRAD_MAX_WG:
+            raise ValueError("0 <= workgroups <= %d" % L.PPO_GRAD_MAX_WG)
+        G = L.ppo_grad_workgroups(R, workgroups)
+        want = {"grad": (f32, (words,)), "stats": (f32, (L.PPO_VALUE_STATS,)), "value": (f32, (R,)), "scratch": (f32, (G, words + L.PPO_VALUE_STATS))}
+        if out is None:
+            res = {}
+        else:
+            res = AtcVecEnv._results(self, out, want, set(), "out must be a dict with any of grad, stats, value, scratch")
+        for n in ("grad", "stats"):
+            if n not in res:
+                res[n] = torch.empty(want[n][1], dtype=torch.float32, device=dev)
+        if "value" not in res:
+            res["value"] = torch.full((R,), float("nan"), dtype=torch.float32, device=dev)
+        scratch = res.pop("scratch", None)
+        if scratch is None:
+            scratch = torch.empty((G, words + L.PPO_VALUE_STATS), dtype=torch.float32, device=dev)
+        g = _lib.AtcPpoValueGrad(float(clip), workgroups)
+        o = _lib.AtcPpoValueGradOut(res["grad"].data_ptr(), res["stats"].data_ptr(), res["value"].data_ptr(), scratch.data_ptr())
+        fn = self._lib.atc_ppo_value_grad
+        with torch.cuda.device(dev):
+            rc = fn(self.sector.handle, R_src, R, K, weights.data_ptr(), obs_rows.data_ptr(), None if traffic is None else traffic.data_ptr(), v_old.data_ptr(),
+                    ret.data_ptr(), None if mask is None else mask.data_ptr(), None if index is None else index.data_ptr(), C.byref(g), C.byref(o), self._stream())
+            if rc:
+                _lib.check(rc)
+        self._keep_ppo_value_grad = (weights, obs_rows, traffic, v_old, ret, mask, index, scratch)   # they outlive the two launches
         return res
 
     def get_attr(self, name, indices=None):

@@ -29,6 +29,8 @@ int atc_gae_launch_counts(uint64_t* out, int n) { return copy_counts(REC_GAE, ou
 int atc_rollout_policy_ends_launch_counts(uint64_t* out, int n) { return copy_counts(REC_POLICY_ENDS, out, n); }
 int atc_gae_boot_launch_counts(uint64_t* out, int n) { return copy_counts(REC_GAE_BOOT, out, n); }
 int atc_ppo_policy_grad_launch_counts(uint64_t* out, int n) { return copy_counts(REC_PPO_GRAD, out, n); }
+int atc_value_forward_launch_counts(uint64_t* out, int n) { return copy_counts(REC_VALUE_FORWARD, out, n); }
+int atc_ppo_value_grad_launch_counts(uint64_t* out, int n) { return copy_counts(REC_PPO_VALUE_GRAD, out, n); }
 int atc_lookahead_set_mapping(int candidates_per_workgroup) {
     if (candidates_per_workgroup < 0 || candidates_per_workgroup > ATC_LOOKAHEAD_MAX_M) return fail_arg("candidates per workgroup must be 0 (the library's choice) .. 64");
     t_look_cpg = candidates_per_workgroup;
@@ -692,6 +694,82 @@ int atc_ppo_policy_grad(const atc_scenario_t* s, int R_src, int R, const float* 
                        (hipStream_t)stream, words, G, out->scratch, out->grad, out->stats);
     HIP_TRY(hipGetLastError());
     ++record(REC_PPO_GRAD)[K ? 1 + __builtin_ctz(K) : 0];
+    return ATC_OK;
+}
+
+// atc_value_forward: the checks in the header's order, then k_value_forward<K> on `stream`, one lane per row
+int atc_value_forward(const atc_scenario_t* s, int R, int traffic_k, const float* w, const float* x, float* values, void* stream) {
+    if (const int rc = check_required({{s, "null pointer: s"}, {w, "null pointer: w (the critic's weights) is required"}, {x, "null pointer: x (the input rows) is required"},
+                                       {values, "null pointer: values is required"}}))
+        return rc;
+    if (R < 1) return fail_arg("R (the number of rows) must be >= 1");
+    const int K = traffic_k;
+    if (K != 0 && K != 1 && K != 2 && K != 4) return fail_arg("traffic_k must be 0, 1, 2 or 4 (the ten-word row, or a compiled list length)");
+    const uintptr_t r = (uintptr_t)R;
+    const ByteRange out = {values, r * 4u, "values"};
+    const ByteRange inputs[2] = {{x, r * (uintptr_t)ATC_POLICY_TRAFFIC_IN(K) * 4u, "x"}, {w, (uintptr_t)ATC_VALUE_WORDS(K) * 4u, "w"}};
+    for (int b = 0; b < 2; ++b) {
+        const ByteRange pair[2] = {inputs[b], out};
+        if (const int rc = check_disjoint(pair, 2, {}, "values of atc_value_forward may not share memory with its inputs")) return rc;
+    }
+    const unsigned blocks = (unsigned)(((long long)R + (kValueBlock - 1)) / kValueBlock);
+    with_traffic_k0(K, [&](auto kt) {
+        hipLaunchKernelGGL(k_value_forward<decltype(kt)::value>, dim3(blocks), dim3(kValueBlock), 0, (hipStream_t)stream, R, w, x, values);
+        return ATC_OK;
+    });
+    HIP_TRY(hipGetLastError());
+    ++record(REC_VALUE_FORWARD)[K ? 1 + __builtin_ctz(K) : 0];
+    return ATC_OK;
+}
+
+// atc_ppo_value_grad: the checks in the header's order, then k_ppo_value_grad<K> on G workgroups and k_ppo_value_grad_reduce, both on `stream`
+int atc_ppo_value_grad(const atc_scenario_t* s, int R_src, int R, int traffic_k, const float* w, const float* obs_rows, const float* traffic, const float* v_old,
+                       const float* ret, const uint8_t* mask, const int32_t* index, const atc_ppo_value_grad_t* g, const atc_ppo_value_grad_out_t* out,
+                       void* stream) {
+    if (const int rc = check_required({{s, "null pointer: s"}, {w, "null pointer: w (the critic's weights) is required"}, {obs_rows, "null pointer: obs_rows is required"},
+                                       {v_old, "null pointer: v_old is required"}, {ret, "null pointer: ret is required"},
+                                       {g, "null pointer: g (atc_ppo_value_grad_t) is required"}, {out, "null pointer: out (atc_ppo_value_grad_out_t) is required"}}))
+        return rc;
+    if (const int rc = check_required({{out->grad, "null pointer: out->grad is required"}, {out->stats, "null pointer: out->stats is required"},
+                                       {out->scratch, "null pointer: out->scratch is required"}}))
+        return rc;
+    const int K = traffic_k;
+    if (K != 0 && K != 1 && K != 2 && K != 4) return fail_arg("traffic_k must be 0, 1, 2 or 4 (the ten-word row, or a compiled list length)");
+    if (R_src < 1) return fail_arg("R_src (the number of source rows) must be >= 1");
+    if (R < 1) return fail_arg("R (the number of rows to evaluate) must be >= 1");
+    if (!index && R != R_src) return fail_arg("R must equal R_src where index is NULL (the identity)");
+    if (!(g->clip > 0.0f)) return fail_arg("g->clip must be > 0 (+inf: no clipping) and not a NaN");
+    if (g->workgroups < 0 || g->workgroups > ATC_PPO_GRAD_MAX_WG) return fail_arg("g->workgroups must be 0 (the library's choice) .. 1024 (ATC_PPO_GRAD_MAX_WG)");
+    if (K > 0 && !traffic) return fail_arg("null pointer: traffic is required where traffic_k > 0");
+    if (K == 0 && traffic) return fail_arg("traffic must be NULL where traffic_k is 0 (the ten-word row has no records)");
+    const long long tiles = ((long long)R + (kPpoBlock - 1)) / kPpoBlock;
+    const int G = g->workgroups ? g->workgroups : (int)(tiles < ATC_PPO_GRAD_DEFAULT_WG ? tiles : ATC_PPO_GRAD_DEFAULT_WG);
+    const int words = ATC_VALUE_WORDS(K);
+    // no output may share memory with any array of the call (the inputs may share among themselves)
+    const uintptr_t rs = (uintptr_t)R_src, r = (uintptr_t)R;
+    const ByteRange outputs[4] = {{out->grad, (uintptr_t)words * 4u, "grad"}, {out->stats, ATC_PPO_VALUE_STATS * 4u, "stats"}, {out->value, r * 4u, "value"},
+                                  {out->scratch, (uintptr_t)G * (uintptr_t)(words + ATC_PPO_VALUE_STATS) * 4u, "scratch"}};
+    const ByteRange inputs[7] = {{w, (uintptr_t)words * 4u, "w"}, {obs_rows, rs * (ATC_OBS_DIM * 4u), "obs_rows"},
+                                 {traffic, rs * (uintptr_t)K * (ATC_TRAFFIC_DIM * 4u), "traffic"}, {v_old, rs * 4u, "v_old"}, {ret, rs * 4u, "ret"},
+                                 {mask, rs, "mask"}, {index, r * 4u, "index"}};
+    for (int a = 0; a < 4; ++a) {
+        if (!outputs[a].ptr) continue;
+        for (int b = 0; b < 7 + a; ++b) {
+            const ByteRange pair[2] = {b < 7 ? inputs[b] : outputs[b - 7], outputs[a]};
+            if (const int rc = check_disjoint(pair, 2, {}, "no output of atc_ppo_value_grad may share memory with another array")) return rc;
+        }
+    }
+    const float clip = g->clip;
+    with_traffic_k0(K, [&](auto kt) {
+        hipLaunchKernelGGL(k_ppo_value_grad<decltype(kt)::value>, dim3((unsigned)G), dim3(kPpoBlock), 0, (hipStream_t)stream, R_src, R, w, obs_rows, traffic, v_old, ret,
+                           mask, index, clip, out->value, out->scratch);
+        return ATC_OK;
+    });
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_ppo_value_grad_reduce, dim3((unsigned)((words + ATC_PPO_VALUE_STATS + kPpoReduceBlock - 1) / kPpoReduceBlock)), dim3(kPpoReduceBlock), 0,
+                       (hipStream_t)stream, words, G, out->scratch, out->grad, out->stats);
+    HIP_TRY(hipGetLastError());
+    ++record(REC_PPO_VALUE_GRAD)[K ? 1 + __builtin_ctz(K) : 0];
     return ATC_OK;
 }
 

@@ -1278,8 +1278,9 @@ int atc_gae_boot_launch_counts(uint64_t* out, int n);
  * floating-point atomics: a workgroup adds its rows in row order, the G partial sums are added in the order of g in float64 and rounded
  * once, and the division by n comes last.  The same inputs and the same G give the same bits on every run; another G gives another
  * rounding of the same sums.  One call is two launches on `stream`.
- * NOT IN THE CALL (the trainer's): the entropy bonus — with a log_std that does not depend on the state it is sum_c log_std_c + a constant,
- * three words —, the value loss and the critic, advantage normalisation (the trainer passes its two scalars), and the optimiser.
+ * NOT IN THE CALL: the value loss and the critic — atc_ppo_value_grad and atc_value_forward below —; the trainer's: the entropy bonus —
+ * with a log_std that does not depend on the state it is sum_c log_std_c + a constant, three words —, advantage normalisation (the trainer
+ * passes its two scalars), and the optimiser.
  * ATC_ERR_ARG, in this order, atc_last_error() naming the argument: a NULL among s, w, obs_rows, action, logp_old, adv, g, out, out->grad,
  * out->stats, out->scratch; traffic_k outside {0, 1, 2, 4}; R_src < 1, R < 1, or index == NULL with R != R_src; clip not finite or <= 0;
  * workgroups outside 0 .. ATC_PPO_GRAD_MAX_WG; traffic NULL with traffic_k > 0, or given with traffic_k == 0; an output (grad, stats,
@@ -1315,6 +1316,84 @@ int atc_ppo_policy_grad(const atc_scenario_t* s, int R_src, int R, const float* 
                         const atc_ppo_grad_t* g, const atc_ppo_grad_out_t* out, void* stream);
 enum { ATC_PPO_GRAD_LAUNCH_SLOTS = 4 };
 int atc_ppo_policy_grad_launch_counts(uint64_t* out, int n);
+
+/* THE CRITIC (extension): a value network with the policy's trunk and packing, evaluated and differentiated inside the library.
+ * THE PACKED CRITIC.  One float32 array of ATC_VALUE_WORDS(K) words, IN = ATC_POLICY_TRAFFIC_IN(K) = 10 + 7 K:
+ *     W1[64][IN], b1[64], W2[64][64], b2[64], W3[1][64], b3[1]          every matrix row-major [out][in]
+ * — atc_policy_traffic_t.w without the two further rows of its head and without log_std.  V(x) = b3 + W3 tanh(b2 + W2 tanh(b1 + W1 x)).
+ * It reads the input row of the policy: the own observation row, then words 0..6 of K traffic records.
+ *
+ * atc_value_forward: V of R rows in one launch.  x [R][IN] holds the rows already widened and contiguous (with K = 0: plain observation
+ * rows); values [R] receives one word per row; no activation is written to memory.  All pointers are device pointers; `s` names the device
+ * only.  ARITHMETIC, in fp32: atc_rollout_policy's for the hidden layers, in its operation order — layer 1 an fmaf chain over the inputs
+ * starting from the bias, summed in float64 where a wavefront (64 consecutive rows, row 0 first) holds an input above 4 in magnitude, or a
+ * NaN; layer 2 in four partial sums —, then v = b3; v = fmaf(W3[j], h2_j, v) for j = 0 .. 63.
+ * ATC_ERR_ARG, in this order: a NULL among s, w, x, values; R < 1; traffic_k outside {0, 1, 2, 4}; values sharing a byte with x or w.
+ * Counted by atc_value_forward_launch_counts only: slot = {0, 1, 2, 3 for traffic_k = 0, 1, 2, 4}. */
+#define ATC_VALUE_WORDS(K) (4289 + 64 * ATC_POLICY_TRAFFIC_IN(K))   /* 4929, 5377, 5825, 6721 for K = 0, 1, 2, 4 */
+int atc_value_forward(const atc_scenario_t* s, int R, int traffic_k, const float* w /* [ATC_VALUE_WORDS(K)] */,
+                      const float* x /* [R][10 + 7 K] */, float* values /* [R] */, void* stream);
+enum { ATC_VALUE_FORWARD_LAUNCH_SLOTS = 4 };
+int atc_value_forward_launch_counts(uint64_t* out, int n);
+
+/* PPO VALUE GRADIENT (extension): the value half of a PPO update in one call — the clipped value loss of the packed critic on stored
+ * decisions and its gradient with respect to every word of w, summed over the rows of a minibatch.  With atc_ppo_policy_grad an update
+ * touches no autograd: what is left to the trainer is the optimiser step on the two packed arrays (and the entropy bonus and advantage
+ * normalisation named there).  No activation is written to global memory.
+ * ROWS, INPUT ROW: atc_ppo_policy_grad's, word for word — R_src source rows read in place (obs_rows [R_src][10], traffic [R_src][K][8]),
+ * R rows to evaluate through the nullable index, mask = atc_rollout_policy_ends' control; a row that does not participate loads nothing
+ * but its index and mask byte and is taken out by selects: a NaN standing in it changes no output bit.
+ * PER PARTICIPATING ROW, in fp32, with v = V(x) in atc_value_forward's arithmetic (a wavefront = the 64 consecutive rows i of a tile, the
+ * rows that do not participate counting as zeros):
+ *
+ *     e = v - ret;  d = v - v_old;  vc = v_old + clamp(d, -clip, +clip);  ec = vc - ret
+ *     |d| <= clip (always so with clip = +inf):  L = 0.5 e^2,   dL/dv = e
+ *     otherwise, e^2 >= ec^2:                    L = 0.5 e^2,   dL/dv = e
+ *     otherwise the row is CUT:                  L = 0.5 ec^2,  dL/dv = 0
+ *
+ * — PPO2's 0.5 max((v - ret)^2, (vc - ret)^2), with the one gradient autograd's maximum has away from a tie.  A NaN v is not cut: it stays
+ * a NaN in L, in the gradient and in value.  Backpropagation through the two tanh layers as in atc_ppo_policy_grad.
+ * OUTPUTS, with n the number of participating rows:
+ *   grad   [ATC_VALUE_WORDS(K)], laid out like w: the sum of dL/dw over the participating rows, divided by n; all zeros if n == 0.
+ *   stats  [ATC_PPO_VALUE_STATS] (the ATC_PPO_VSTAT_* words): n; mean L; the fraction of participating rows that were cut; mean v; mean
+ *          ret; mean ret^2; mean (ret - v)^2; max |v - v_old|.  Words 4 .. 6 give the explained variance 1 - mean (ret - v)^2 /
+ *          (mean ret^2 - (mean ret)^2) without another pass.  All zeros if n == 0.
+ *   value  [R], nullable: v of row i, written for participating rows only; the others keep what they hold.  Where the tiles of 64 rows
+ *          hold the same rows (those that do not participate as zeros), it equals atc_value_forward's output bit for bit.
+ *   scratch [G][ATC_VALUE_WORDS(K) + ATC_PPO_VALUE_STATS] floats, required: the G partial sums, overwritten by every call.
+ * WORKGROUPS AND DETERMINISM: atc_ppo_policy_grad's (the same default, the same maximum, no atomics, float64 in the order of g, the
+ * division by n last).  One call is two launches on `stream`.
+ * ATC_ERR_ARG, in this order: a NULL among s, w, obs_rows, v_old, ret, g, out, out->grad, out->stats, out->scratch; traffic_k outside
+ * {0, 1, 2, 4}; R_src < 1, R < 1, or index == NULL with R != R_src; clip NaN or <= 0 (+inf is the plain squared error); workgroups outside
+ * 0 .. ATC_PPO_GRAD_MAX_WG; traffic NULL with traffic_k > 0, or given with traffic_k == 0; an output (grad, stats, value, scratch) sharing
+ * a byte with any other array of the call.
+ * Counted by atc_ppo_value_grad_launch_counts only: one count per CALL, slot = {0, 1, 2, 3 for traffic_k = 0, 1, 2, 4}. */
+#define ATC_PPO_VALUE_STATS 8
+#define ATC_PPO_VSTAT_N 0        /* participating rows */
+#define ATC_PPO_VSTAT_LOSS 1     /* mean L */
+#define ATC_PPO_VSTAT_CUT 2      /* fraction of participating rows whose gradient was cut */
+#define ATC_PPO_VSTAT_V 3        /* mean v */
+#define ATC_PPO_VSTAT_RET 4      /* mean ret */
+#define ATC_PPO_VSTAT_RET2 5     /* mean ret^2 */
+#define ATC_PPO_VSTAT_ERR2 6     /* mean (ret - v)^2 */
+#define ATC_PPO_VSTAT_DV_MAX 7   /* max |v - v_old| */
+typedef struct atc_ppo_value_grad {
+    float    clip;        /* > 0; +inf: no clipping */
+    int32_t  workgroups;  /* 0: the library's choice; else G = 1 .. ATC_PPO_GRAD_MAX_WG */
+} atc_ppo_value_grad_t;
+typedef struct atc_ppo_value_grad_out {
+    float* grad;      /* [ATC_VALUE_WORDS(K)] required */
+    float* stats;     /* [ATC_PPO_VALUE_STATS] required */
+    float* value;     /* [R] nullable */
+    float* scratch;   /* [G][ATC_VALUE_WORDS(K) + ATC_PPO_VALUE_STATS] required */
+} atc_ppo_value_grad_out_t;
+int atc_ppo_value_grad(const atc_scenario_t* s, int R_src, int R, int traffic_k, const float* w /* [ATC_VALUE_WORDS(K)] */,
+                       const float* obs_rows /* [R_src][10] */, const float* traffic /* [R_src][K][8], with K > 0 */,
+                       const float* v_old /* [R_src] */, const float* ret /* [R_src] */,
+                       const uint8_t* mask /* nullable [R_src] */, const int32_t* index /* nullable [R] */,
+                       const atc_ppo_value_grad_t* g, const atc_ppo_value_grad_out_t* out, void* stream);
+enum { ATC_PPO_VALUE_GRAD_LAUNCH_SLOTS = 4 };
+int atc_ppo_value_grad_launch_counts(uint64_t* out, int n);
 
 #ifdef __cplusplus
 }
