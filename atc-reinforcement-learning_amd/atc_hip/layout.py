@@ -140,6 +140,14 @@ PPO_VALUE_STATS = 8
 (PPO_VSTAT_N, PPO_VSTAT_LOSS, PPO_VSTAT_CUT, PPO_VSTAT_V, PPO_VSTAT_RET, PPO_VSTAT_RET2, PPO_VSTAT_ERR2, PPO_VSTAT_DV_MAX) = range(8)
 VALUE_FORWARD_LAUNCH_SLOTS = 4
 PPO_VALUE_GRAD_LAUNCH_SLOTS = 4
+# policy evaluation (include/atc_step.h: atc_policy_eval): the words of the per-env record (int32 [B, EVAL_WORDS]; words 7 .. 10 are float32
+# bit patterns, words 13 .. 15 reserved), EVAL_CLEAR the flag of atc_policy_eval_out_t that starts the record afresh; its record counts by
+# width and K in (0, 1, 2, 4) like the rollout with episode ends
+(EVAL_EPISODES, EVAL_WINS, EVAL_END_BELOW_MVA, EVAL_END_OUTSIDE, EVAL_END_CONFLICT, EVAL_END_TIMEOUT, EVAL_STEPS, EVAL_RETURN_SUM, EVAL_RETURN_SQ,
+ EVAL_RETURN_MIN, EVAL_RETURN_MAX, EVAL_FLAGS_OR, EVAL_LAUNCH_STEPS) = range(13)
+EVAL_WORDS = 16
+EVAL_CLEAR = 1
+POLICY_EVAL_LAUNCH_SLOTS = 28
 
 
 def policy_in(traffic=0):

@@ -115,6 +115,14 @@ class AtcPolicyEndsOut(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in POLICY_ENDS_OUT_FIELDS]
 
 
+POLICY_EVAL_OUT_FIELDS = ("record", "obs_last", "flags")
+
+
+class AtcPolicyEvalOut(C.Structure):
+    """atc_policy_eval_out_t"""
+    _fields_ = [("record", C.c_void_p), ("obs_last", C.c_void_p), ("flags", C.c_uint32)]
+
+
 GAE_FIELDS = ("gamma", "lam", "flags", "_pad")
 
 
@@ -182,7 +190,8 @@ EXPORTS = ("atc_abi_version", "atc_last_error", "atc_launch_counts", "atc_host_m
            "atc_rollout_policy", "atc_rollout_policy_launch_counts", "atc_rollout_policy_traffic", "atc_rollout_policy_traffic_launch_counts",
            "atc_gae", "atc_gae_launch_counts", "atc_rollout_policy_ends", "atc_rollout_policy_ends_launch_counts", "atc_gae_boot",
            "atc_gae_boot_launch_counts", "atc_ppo_policy_grad", "atc_ppo_policy_grad_launch_counts",
-           "atc_value_forward", "atc_value_forward_launch_counts", "atc_ppo_value_grad", "atc_ppo_value_grad_launch_counts")
+           "atc_value_forward", "atc_value_forward_launch_counts", "atc_ppo_value_grad", "atc_ppo_value_grad_launch_counts",
+           "atc_policy_eval", "atc_policy_eval_launch_counts")
 
 def load():
     """Loads libatcstep.so; raises (never falls back) when it has not been built."""
@@ -239,6 +248,8 @@ def load():
     lib.atc_gae.argtypes = [vp, ci, ci, ci, ci, vp, vp, vp, vp, C.POINTER(AtcGae), C.POINTER(AtcGaeOut), vp]
     lib.atc_rollout_policy_ends.argtypes = [vp, ci, ci, ci, ci, C.POINTER(AtcState), vp, C.POINTER(AtcPolicyTraffic), C.POINTER(AtcPolicyEndsOut),
                                             C.POINTER(AtcParams), vp]
+    lib.atc_policy_eval.argtypes = [vp, ci, ci, ci, ci, C.POINTER(AtcState), vp, C.POINTER(AtcPolicyTraffic), C.POINTER(AtcPolicyEvalOut),
+                                    C.POINTER(AtcParams), vp]
     lib.atc_gae_boot.argtypes = [vp, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, C.POINTER(AtcGae), C.POINTER(AtcGaeOut), vp]
     lib.atc_ppo_policy_grad.argtypes = [vp, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(AtcPpoGrad), C.POINTER(AtcPpoGradOut), vp]
     lib.atc_value_forward.argtypes = [vp, ci, ci, vp, vp, vp, vp]
@@ -307,6 +318,7 @@ LAUNCH_RECORDS = {
     "atc_ppo_policy_grad_launch_counts": (L.PPO_GRAD_LAUNCH_SLOTS, _traffic_k0),
     "atc_value_forward_launch_counts": (L.VALUE_FORWARD_LAUNCH_SLOTS, _traffic_k0),
     "atc_ppo_value_grad_launch_counts": (L.PPO_VALUE_GRAD_LAUNCH_SLOTS, _traffic_k0),
+    "atc_policy_eval_launch_counts": (L.POLICY_EVAL_LAUNCH_SLOTS, _width_k0),
 }
 
 
@@ -407,6 +419,12 @@ def rollout_policy_ends_launch_counts():
     """Launches of the policy rollout with episode ends (atc_rollout_policy_ends) made by the calling thread so far, by lane-group width and
     records per aircraft (0: the ten-word policy): {(16, 0): n, ...}, zero counts left out.  Separate from the other launch records."""
     return _counts("atc_rollout_policy_ends_launch_counts")
+
+
+def policy_eval_launch_counts():
+    """Launches of the policy evaluation (atc_policy_eval) made by the calling thread so far, by lane-group width and records per aircraft
+    (0: the ten-word policy): {(16, 0): n, ...}, zero counts left out.  Separate from the other launch records."""
+    return _counts("atc_policy_eval_launch_counts")
 
 
 def gae_boot_launch_counts():

@@ -890,6 +890,48 @@ class AtcVecEnv:
             raise ValueError("traffic must be 0 or one of %s records per aircraft" % (L.POLICY_TRAFFIC_K,))
         return AtcVecEnv._rollout_policy(self, K, weights, T, hold, seed, decision0, deterministic, obs0, out, True)
 
+    def evaluate_policy(self, weights, T, traffic=0, hold=1, seed=0, decision0=0, deterministic=True, obs0=None, record=None, clear=True):
+        """Flies the packed policy for T steps exactly as rollout_policy_ends() would — same decisions, same draws, same state afterwards —
+        and stores none of its [T, ...] or [T // hold, ...] tensors (include/atc_step.h: atc_policy_eval).  What comes back is the per-env
+        record, int32 [B, L.EVAL_WORDS]: episodes finished, wins, ends by cause, the finished episodes' summed length, return sum / sum of
+        squares / min / max (float32 bit patterns: record[:, L.EVAL_RETURN_SUM].view(torch.float32)), the OR of every flag word seen, and
+        the steps flown; atc_hip.evaluate.summary() folds it.  The record ACCUMULATES: clear=False adds this launch to what `record` holds,
+        so chunks of a long evaluation chain — pass decision0 += T // hold and obs0 = the previous call's obs_last — and equal one launch
+        bit for bit.  An episode that began before the call counts in full where it ends; one still running at the end is left in the env.
+        The env must auto-reset.  obs0: default the env's bound observation tensor; a copy is taken.  Returns {"record", "obs_last"}."""
+        torch = self.torch
+        K, T, hold = int(traffic), int(T), int(hold)
+        B, N, dev = self.B, self.N, self.device
+        if K and K not in L.POLICY_TRAFFIC_K:
+            raise ValueError("traffic must be 0 or one of %s records per aircraft" % (L.POLICY_TRAFFIC_K,))
+        w, words = weights, L.policy_words(K) if K else L.POLICY_WORDS
+        if not (torch.is_tensor(w) and w.dtype == torch.float32 and w.device == dev and w.is_contiguous() and w.numel() == words):
+            raise ValueError("weights must be the contiguous float32 tensor of %d words (atc_hip.policy.pack_mlp%s) on %s" % (
+                words, "(traffic=%d)" % K if K else "", dev))
+        x0 = self.obs if obs0 is None else obs0
+        if not (torch.is_tensor(x0) and x0.dtype == torch.float32 and x0.is_contiguous() and x0.numel() == B * N * L.OBS_DIM):
+            raise ValueError("obs0 must be a contiguous float32 tensor of B*N*%d words" % L.OBS_DIM)
+        x0 = x0.clone()
+        if record is None:
+            if not clear:
+                raise ValueError("clear=False needs the record to add to")
+            record = torch.empty((B, L.EVAL_WORDS), dtype=torch.int32, device=dev)
+        elif not (torch.is_tensor(record) and record.dtype == torch.int32 and record.device == dev and record.is_contiguous() and record.numel() == B * L.EVAL_WORDS):
+            raise ValueError("record must be a contiguous int32 tensor of [B, %d] on %s" % (L.EVAL_WORDS, dev))
+        obs_last = torch.empty((B, N * L.OBS_DIM), dtype=torch.float32, device=dev)
+        o = _lib.AtcPolicyEvalOut(self._ptr(record), self._ptr(obs_last), L.EVAL_CLEAR if clear else 0)
+        pol = _lib.AtcPolicyTraffic(self._ptr(w), L.POLICY_HIDDEN, L.POLICY_DETERMINISTIC if deterministic else 0, int(seed) & (2 ** 64 - 1),
+                                    int(decision0) & 0xffffffff, 0, K)
+        with torch.cuda.device(dev):
+            rc = self._lib.atc_policy_eval(self.sector.handle, B, N, T, hold, C.byref(self._state), self._ptr(x0), C.byref(pol), C.byref(o),
+                                           C.byref(self.params), self._stream())
+            if rc:
+                _lib.check(rc)
+        self._keep = (w, x0)
+        if self.host_mapped:
+            self._finish()
+        return {"record": record, "obs_last": obs_last}
+
     def _rollout_policy(self, K, weights, T, hold, seed, decision0, deterministic, obs0, out, ends=False):
         """rollout_policy (K = 0) and rollout_policy_traffic (K = 1, 2, 4): the checks of weights and obs0, the result tensors, the two
         structs, the launch.  ends: through atc_rollout_policy_ends, with its three further outputs"""

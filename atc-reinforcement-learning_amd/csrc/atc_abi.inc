@@ -31,6 +31,7 @@ int atc_gae_boot_launch_counts(uint64_t* out, int n) { return copy_counts(REC_GA
 int atc_ppo_policy_grad_launch_counts(uint64_t* out, int n) { return copy_counts(REC_PPO_GRAD, out, n); }
 int atc_value_forward_launch_counts(uint64_t* out, int n) { return copy_counts(REC_VALUE_FORWARD, out, n); }
 int atc_ppo_value_grad_launch_counts(uint64_t* out, int n) { return copy_counts(REC_PPO_VALUE_GRAD, out, n); }
+int atc_policy_eval_launch_counts(uint64_t* out, int n) { return copy_counts(REC_POLICY_EVAL, out, n); }
 int atc_lookahead_set_mapping(int candidates_per_workgroup) {
     if (candidates_per_workgroup < 0 || candidates_per_workgroup > ATC_LOOKAHEAD_MAX_M) return fail_arg("candidates per workgroup must be 0 (the library's choice) .. 64");
     t_look_cpg = candidates_per_workgroup;
@@ -631,6 +632,16 @@ int atc_rollout_policy_ends(const atc_scenario_t* s, int B, int N, int T, int ho
     return with_width(N, [&](auto w) {
         return with_traffic_k0(pol->traffic_k, [&](auto kt) {
             return launch_policy<decltype(w)::value, decltype(kt)::value, true>(s, B, N, T, hold, st, obs0, pol, out, p, (hipStream_t)stream);
+        });
+    });
+}
+
+int atc_policy_eval(const atc_scenario_t* s, int B, int N, int T, int hold, const atc_state_t* st, const float* obs0, const atc_policy_traffic_t* pol,
+                    const atc_policy_eval_out_t* out, const atc_params_t* p, void* stream) {
+    if (const int rc = check_policy_eval_call(s, B, N, T, hold, st, obs0, pol, out, p)) return rc;
+    return with_width(N, [&](auto w) {
+        return with_traffic_k0(pol->traffic_k, [&](auto kt) {
+            return launch_policy_eval<decltype(w)::value, decltype(kt)::value>(s, B, N, T, hold, st, obs0, pol, out, p, (hipStream_t)stream);
         });
     });
 }

@@ -145,6 +145,15 @@ struct PolicyEnds {
     uint8_t* control;       // .control
 };
 
+// EVAL (atc_policy_eval, k_policy_eval<W, KT>): the loop with every per-step and per-decision store compiled out.  What leaves the launch is
+// the env's record of ATC_EVAL_WORDS words — read at the start (or cleared), held in registers uniformly over the env's lanes like the env
+// state, updated on the rare path where a step ends an episode, written once by lane k == 0 — and the last step's observation.
+struct PolicyEval {
+    int32_t* record;     // atc_policy_eval_out_t.record
+    float* obs_last;     // .obs_last, nullable
+    uint32_t flags;      // .flags
+};
+
 // wavefronts per SIMD k_rollout_policy is register-budgeted for (<= 168 VGPRs): the 64 hidden activations are live next to what the
 // step carries across its loop, which the step's own 5 - 6 do not hold.  -DATC_POLICY_WAVES=n: A/B builds.
 #ifndef ATC_POLICY_WAVES
@@ -156,13 +165,15 @@ struct PolicyEnds {
 // An env never leaves its wavefront: W = 32 / 64 stage (x, y, tag) in the wavefront's own quarter of the pair-scan staging area (idle
 // between steps), ordered by wave-level waits — no workgroup barrier anywhere in the decision.
 // TT_OFF: where the kernel's PolicyTrafficTail lies in ITS kernarg segment (the body serves three parameter lists); ET_OFF: where its
-// PolicyEnds lies, 0 for the two kernels that have none (ENDS below).
-template <int W, int KT, size_t TT_OFF = 0, size_t ET_OFF = 0>
+// PolicyEnds lies, 0 for the kernels that have none (ENDS below); EV_OFF: where its PolicyEval lies, 0 for all but k_policy_eval (EVAL).
+template <int W, int KT, size_t TT_OFF = 0, size_t ET_OFF = 0, size_t EV_OFF = 0>
 __device__ __forceinline__ void rollout_policy_body(const float* __restrict__ blob, int off_grid, int B, int N, int T, atc_state_t st, const float* __restrict__ obs0,
                                                     atc_params_t p, StepDerived q, const float* __restrict__ pw, uint64_t seed, uint32_t decision0, uint32_t pflags,
                                                     float* __restrict__ action, float* __restrict__ logp) {
     constexpr bool ONE = false, LAT = false, FULL = false;   // (QGET: the multi-step form — kernarg re-reads inside the step)
     constexpr bool ENDS = ET_OFF != 0;
+    constexpr bool EVAL = EV_OFF != 0;
+    static_assert(!(ENDS && EVAL), "k_policy_eval stores none of the per-decision outputs");
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float4* pos = reinterpret_cast<float4*>(smem);                    // [2 kBlock] pair-scan staging (W >= 32)
     float* obs_stage = smem + (W >= 32 ? 2 * kBlock * 4 : 0);  // [4 waves][64 x 10] obs transpose
@@ -198,6 +209,23 @@ __device__ __forceinline__ void rollout_policy_body(const float* __restrict__ bl
     int left = 0;                 // steps the current block is still flown for
     uint32_t blk = 0u;            // the number of the coming decision
     bool ended = false;           // ENDS: an earlier step of the current block ended an episode of this lane's env
+    // EVAL: words 0 .. 11 of the env's record (the initial values under ATC_EVAL_CLEAR), and this lane's OR of its flag words
+    int4 ev_n = make_int4(0, 0, 0, 0);                              // episodes, wins, below-MVA ends, outside ends
+    int ev_conflict = 0, ev_timeout = 0, ev_steps = 0;
+    float ev_sum = 0.0f, ev_sq = 0.0f, ev_min = __builtin_inff(), ev_max = -__builtin_inff();
+    uint32_t ev_or = 0u, ev_or0 = 0u;
+    if constexpr (EVAL) {
+        const PolicyEval ev = kernarg_reread<PolicyEval>(EV_OFF, opaque_zero());
+        if (!(ev.flags & ATC_EVAL_CLEAR)) {   // (d.e is clamped for lanes without an env: in bounds, never stored)
+            const int4* rec = at<int4>(ev.record, (uint32_t)d.e * (ATC_EVAL_WORDS * 4u));
+            const int4 r0 = rec[0], r1 = rec[1], r2 = rec[2];
+            ev_n = r0;
+            ev_conflict = r1.x; ev_timeout = r1.y; ev_steps = r1.z; ev_sum = __int_as_float(r1.w);
+            ev_sq = __int_as_float(r2.x); ev_min = __int_as_float(r2.y); ev_max = __int_as_float(r2.z); ev_or0 = (uint32_t)r2.w;
+            asm volatile("" : "+v"(ev_n.x), "+v"(ev_n.y), "+v"(ev_n.z), "+v"(ev_n.w), "+v"(ev_conflict), "+v"(ev_timeout), "+v"(ev_steps));   // (waited for here: see settle_state)
+            asm volatile("" : "+v"(ev_sum), "+v"(ev_sq), "+v"(ev_min), "+v"(ev_max), "+v"(ev_or0));
+        }
+    }
     QRates qr_next = kernarg_reread<QRates>(offsetof(StepArgs, q) + offsetof(StepDerived, r), opaque_zero());
     settle_state(ls, es);
 #pragma unroll
@@ -250,9 +278,11 @@ __device__ __forceinline__ void rollout_policy_body(const float* __restrict__ bl
                 for (int r = 0; r < KT; ++r) {
                     float4 ra, rb;
                     traffic_record<W>(best[r], under, dl.lane, me, tt.tq, ra, rb);
-                    if (tt.traffic && dl.lane_valid) {
-                        dst[2 * r] = ra;
-                        dst[2 * r + 1] = rb;
+                    if constexpr (!EVAL) {
+                        if (tt.traffic && dl.lane_valid) {
+                            dst[2 * r] = ra;
+                            dst[2 * r + 1] = rb;
+                        }
                     }
                     float* xr = xin + ATC_OBS_DIM + 7 * r;   // words 0..6: word 7 (the slot) is stored, not an input
                     xr[0] = ra.x; xr[1] = ra.y; xr[2] = ra.z; xr[3] = ra.w;
@@ -260,9 +290,11 @@ __device__ __forceinline__ void rollout_policy_body(const float* __restrict__ bl
                 }
                 dec = policy_decide<IN>(pw, zk, xin, seed, decision0 + blk, dl.i, (pflags & ATC_POLICY_DETERMINISTIC) != 0u);
             }
-            if (dl.lane_valid) {
-                *at<Float3>(action + (size_t)blk * BN * 3u, times12(dl.i)) = dec.u;
-                if (logp) *at<float>(logp + (size_t)blk * BN, dl.i * 4u) = dec.logp;
+            if constexpr (!EVAL) {
+                if (dl.lane_valid) {
+                    *at<Float3>(action + (size_t)blk * BN * 3u, times12(dl.i)) = dec.u;
+                    if (logp) *at<float>(logp + (size_t)blk * BN, dl.i * 4u) = dec.logp;
+                }
             }
             if constexpr (ENDS) {   // which aircraft this decision controls: the active mask of the state it is taken in
                 uint8_t* const control = kernarg_reread<uint8_t*>(ET_OFF + offsetof(PolicyEnds, control), zk);
@@ -313,13 +345,40 @@ __device__ __forceinline__ void rollout_policy_body(const float* __restrict__ bl
                 if (term_flags && !ended && dl.env_valid && dl.k == 0) *at<uint16_t>(term_flags + (size_t)(blk - 1u) * (uint32_t)B, (uint32_t)dl.e * 2u) = 0;
             }
         }
-        // ---- this step's row of the [T][...] outputs: the tail of step_part_b (observation first, the three small stores last) ----
-        const atc_out_t o_t = kernarg_reread<atc_out_t>(offsetof(StepArgs, out), zk);
-        store_obs_rows(o_t.obs + sBN * ATC_OBS_DIM, dl, sv.o, obs_stage);
-        if (dl.lane_valid) stream_store(at<uint16_t>(o_t.flags + sBN, dl.i * 2u), (uint16_t)sv.fl);
-        if (dl.env_valid && dl.k == 0) {
-            *at<float>(o_t.reward + sB, (uint32_t)dl.e * 4u) = sv.env_r;
-            *at<uint8_t>(o_t.done + sB, (uint32_t)dl.e) = sv.done ? 1 : 0;
+        if constexpr (EVAL) {
+            ev_or |= dl.lane_valid ? (sv.fl & 0xffffu) : 0u;
+            if (ATC_RARE(__builtin_amdgcn_ballot_w64(sv.done) != 0ull)) {
+                const int seen = group_or_i<W>(dl.lane_valid ? (int)(sv.fl & 0xffffu) : 0);   // the env's flag words as flags[t] would store them
+                // The ended episode's length, return and win bit are the words the step has just written to the per-episode record
+                // (done && ATC_M_AUTO_RESET, which the host requires: lane k == 0 wrote them, every lane of the env reads them back —
+                // one wavefront, whose memory operations are issued in order; the fences are the ones step_part_b pairs with).
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                const int32_t* stats = kernarg_reread<int32_t*>(offsetof(StepArgs, st) + offsetof(atc_state_t, stats), zk);
+                const int4 s1 = *at<int4>(stats, (uint32_t)dl.e * (ATC_STAT_WORDS * 4u));   // episodes, ep_length, ep_return, win_bits
+                if (sv.done) {
+                    const float r = __int_as_float(s1.z);
+                    ev_n.x += 1;
+                    ev_n.y += s1.w & 1;
+                    ev_n.z += (seen & ATC_F_BELOW_MVA) ? 1 : 0;
+                    ev_n.w += (seen & ATC_F_OUTSIDE) ? 1 : 0;
+                    ev_conflict += (seen & ATC_F_CONFLICT) ? 1 : 0;
+                    ev_timeout += (seen & ATC_F_TIMEOUT) ? 1 : 0;
+                    ev_steps += s1.y;
+                    ev_sum = ev_sum + r;
+                    ev_sq = ev_sq + (r * r);   // (the file is built with -ffp-contract=off: a product, then an add)
+                    ev_min = fminf(ev_min, r);
+                    ev_max = fmaxf(ev_max, r);
+                }
+            }
+        } else {
+            // ---- this step's row of the [T][...] outputs: the tail of step_part_b (observation first, the three small stores last) ----
+            const atc_out_t o_t = kernarg_reread<atc_out_t>(offsetof(StepArgs, out), zk);
+            store_obs_rows(o_t.obs + sBN * ATC_OBS_DIM, dl, sv.o, obs_stage);
+            if (dl.lane_valid) stream_store(at<uint16_t>(o_t.flags + sBN, dl.i * 2u), (uint16_t)sv.fl);
+            if (dl.env_valid && dl.k == 0) {
+                *at<float>(o_t.reward + sB, (uint32_t)dl.e * 4u) = sv.env_r;
+                *at<uint8_t>(o_t.done + sB, (uint32_t)dl.e) = sv.done ? 1 : 0;
+            }
         }
         // what the next decision sees, if the next step opens a block: the observation as stored
 #pragma unroll
@@ -328,6 +387,21 @@ __device__ __forceinline__ void rollout_policy_body(const float* __restrict__ bl
     const atc_state_t st_end = kernarg_reread<atc_state_t>(offsetof(StepArgs, st), opaque_zero());
     store_lane_state(st_end, d, ls, true);
     store_env_state<W>(st_end, d, es, hi0);
+    if constexpr (EVAL) {
+        const PolicyEval ev = kernarg_reread<PolicyEval>(EV_OFF, opaque_zero());
+        const uint32_t seen_all = ev_or0 | (uint32_t)group_or_i<W>((int)ev_or);
+        if (ev.obs_last) store_obs_rows(ev.obs_last, d, x, obs_stage);   // (T >= 1: x holds the last step's observation as stored)
+        if (d.env_valid && d.k == 0) {
+            int4* rec = at<int4>(ev.record, (uint32_t)d.e * (ATC_EVAL_WORDS * 4u));
+            int4 r3 = make_int4(0, 0, 0, 0);   // launch steps and the three reserved words: read here, nothing of them is carried
+            if (!(ev.flags & ATC_EVAL_CLEAR)) r3 = rec[3];
+            r3.x += T;
+            rec[0] = ev_n;
+            rec[1] = make_int4(ev_conflict, ev_timeout, ev_steps, __float_as_int(ev_sum));
+            rec[2] = make_int4(__float_as_int(ev_sq), __float_as_int(ev_min), __float_as_int(ev_max), (int)seen_all);
+            rec[3] = r3;
+        }
+    }
 }
 
 template <int W>
@@ -364,3 +438,19 @@ k_rollout_policy_ends(const float* __restrict__ blob, int off_grid, int B, int N
 }
 static_assert(kernargs_hold_like_step<decltype(k_rollout_policy_ends<1, 0>)>() && KernArgs<decltype(k_rollout_policy_ends<1, 0>)>::last() != 0, ATC_KERNARGS_REFUSAL);
 static_assert(ATC_POLICY_TRAFFIC_WORDS(0) == ATC_POLICY_WORDS && ATC_POLICY_TRAFFIC_IN(0) == ATC_POLICY_IN, "traffic_k == 0 is the ten-word policy");
+
+// KT = 0, 1, 2, 4 as k_rollout_policy_ends takes it.  The parameter list is k_rollout_policy_traffic's — out, action and logp are passed
+// as zeros and never read — then the record's three fields.
+// REQUIRES ATC_M_AUTO_RESET in p.mode (the host refuses the call without it, check_policy_eval_call): the ended episode's length, return and
+// win bit are re-loaded from the per-episode record, which step_part_b writes on its auto-reset path only.  Without the reset a done step
+// would count the words of an EARLIER episode, silently; a host that relaxes the refusal has to hand the pair back through StepVals instead.
+template <int W, int KT>
+__global__ void __launch_bounds__(kBlock, ATC_POLICY_WAVES)
+k_policy_eval(const float* __restrict__ blob, int off_grid, int B, int N, int T, int hold, atc_state_t st, const float* __restrict__ obs0,
+              atc_out_t out, atc_params_t p, StepDerived q, const float* __restrict__ pw, uint64_t seed, uint32_t decision0, uint32_t pflags,
+              float* __restrict__ action, float* __restrict__ logp, PolicyTrafficTail tt, PolicyEval ev) {
+    // (tt, ev: kernarg re-reads where they are used, at the offsets this list gives them)
+    typedef KernArgs<decltype(k_policy_eval<W, KT>)> A;
+    rollout_policy_body<W, KT, A::template of<PolicyTrafficTail>(), 0, A::last()>(blob, off_grid, B, N, T, st, obs0, p, q, pw, seed, decision0, pflags, action, logp);
+}
+static_assert(kernargs_hold_like_step<decltype(k_policy_eval<1, 0>)>() && KernArgs<decltype(k_policy_eval<1, 0>)>::last() != 0, ATC_KERNARGS_REFUSAL);

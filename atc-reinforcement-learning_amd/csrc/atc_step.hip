@@ -1797,15 +1797,15 @@ static size_t lds_bytes(const atc_scenario*, bool pair_scan, bool step_kernel = 
 // counters in one table — plain thread-local counters that nothing in the library reads back.  REC_STEP has a slot for each k_step
 // instantiation and one for k_serve starts; a record of 7 slots counts by lane-group width (slot = log2(W)); a record of one slot
 // counts its entry point's launches; REC_POLICY_TRAFFIC counts by width and list length (slot = 3 log2(W) + log2(K)), REC_POLICY_ENDS
-// likewise with K = 0 in front (slot = 4 log2(W) + {0, 1, 2, 3}); REC_PPO_GRAD, REC_VALUE_FORWARD and REC_PPO_VALUE_GRAD count calls by K
+// and REC_POLICY_EVAL likewise with K = 0 in front (slot = 4 log2(W) + {0, 1, 2, 3}); REC_PPO_GRAD, REC_VALUE_FORWARD and REC_PPO_VALUE_GRAD count calls by K
 // (slot = {0, 1, 2, 3}).  A call moves its own record only.
-enum Record { REC_STEP, REC_SKIP, REC_TRAFFIC, REC_LOOKAHEAD, REC_PLAN, REC_PLAN_SAMPLED, REC_PLAN_DRAW, REC_PLAN_REFIT, REC_PLAN_SCORE, REC_BRANCH, REC_SELECT, REC_POLICY, REC_POLICY_TRAFFIC, REC_GAE, REC_POLICY_ENDS, REC_GAE_BOOT, REC_PPO_GRAD, REC_VALUE_FORWARD, REC_PPO_VALUE_GRAD, REC_COUNT };
+enum Record { REC_STEP, REC_SKIP, REC_TRAFFIC, REC_LOOKAHEAD, REC_PLAN, REC_PLAN_SAMPLED, REC_PLAN_DRAW, REC_PLAN_REFIT, REC_PLAN_SCORE, REC_BRANCH, REC_SELECT, REC_POLICY, REC_POLICY_TRAFFIC, REC_GAE, REC_POLICY_ENDS, REC_GAE_BOOT, REC_PPO_GRAD, REC_VALUE_FORWARD, REC_PPO_VALUE_GRAD, REC_POLICY_EVAL, REC_COUNT };
 constexpr int kRecordSlots[REC_COUNT] = {ATC_LAUNCH_SLOTS, ATC_SKIP_LAUNCH_SLOTS, ATC_TRAFFIC_LAUNCH_SLOTS, ATC_LOOKAHEAD_LAUNCH_SLOTS, ATC_PLAN_LAUNCH_SLOTS,
                                          ATC_PLAN_SAMPLED_LAUNCH_SLOTS, ATC_PLAN_DRAW_LAUNCH_SLOTS, ATC_PLAN_REFIT_LAUNCH_SLOTS, ATC_PLAN_SCORE_LAUNCH_SLOTS,
                                          ATC_BRANCH_LAUNCH_SLOTS, ATC_SELECT_LAUNCH_SLOTS, ATC_ROLLOUT_POLICY_LAUNCH_SLOTS,
                                          ATC_ROLLOUT_POLICY_TRAFFIC_LAUNCH_SLOTS, ATC_GAE_LAUNCH_SLOTS, ATC_ROLLOUT_POLICY_ENDS_LAUNCH_SLOTS,
                                          ATC_GAE_BOOT_LAUNCH_SLOTS, ATC_PPO_GRAD_LAUNCH_SLOTS, ATC_VALUE_FORWARD_LAUNCH_SLOTS,
-                                         ATC_PPO_VALUE_GRAD_LAUNCH_SLOTS};
+                                         ATC_PPO_VALUE_GRAD_LAUNCH_SLOTS, ATC_POLICY_EVAL_LAUNCH_SLOTS};
 constexpr int record_offset(int id) {
     int o = 0;
     for (int i = 0; i < id; ++i) o += kRecordSlots[i];
@@ -2203,36 +2203,72 @@ static int with_traffic_k(int k, F f) {
     if (k == 2) return f(std::integral_constant<int, 2>());
     return f(std::integral_constant<int, 4>());
 }
+// atc_policy_eval's launch: k_policy_eval<W, KT> for KT = 0, 1, 2, 4 on launch_policy's grid, its out, action and logp parameters zero
+template <int W, int KT>
+static int launch_policy_eval(const atc_scenario* s, int B, int N, int T, int hold, const atc_state_t* st, const float* obs0, const atc_policy_traffic_t* pol,
+                              const atc_policy_eval_out_t* o, const atc_params_t* p, hipStream_t stream) {
+    atc_out_t none;
+    memset(&none, 0, sizeof(none));
+    hipLaunchKernelGGL((k_policy_eval<W, KT>), dim3(step_grid(B, W)), dim3(kBlock), lds_bytes(s, W >= 32, true), stream, s->d_blob, s->off_grid, B, N, T, hold, *st, obs0,
+                       none, *p, derive(*p, s, 0), pol->w, pol->seed, pol->decision0, pol->flags, (float*)nullptr, (float*)nullptr,
+                       PolicyTrafficTail{KT ? traffic_common(s, p, KT) : TrafficArgs{}, nullptr}, PolicyEval{o->record, o->obs_last, o->flags});
+    HIP_TRY(hipGetLastError());
+    ++record(REC_POLICY_EVAL)[4 * __builtin_ctz(W) + (KT ? 1 + __builtin_ctz(KT) : 0)];
+    return ATC_OK;
+}
 // ... and for atc_rollout_policy_ends, whose traffic_k may also be 0 (the ten-word policy)
 template <typename F>
 static int with_traffic_k0(int k, F f) {
     return k == 0 ? f(std::integral_constant<int, 0>()) : with_traffic_k(k, f);
 }
 
-// The argument checks of the policy rollouts, in the header's order.  `out_type` names the output struct in the refusals; traffic_k is
-// null for atc_rollout_policy, and `traffic` is atc_policy_traffic_out_t.traffic (its range joins the overlap rule).  `ends`: the call is
-// atc_rollout_policy_ends — traffic_k may be 0 (then `traffic` must be NULL), and its three arrays join the overlap rule.
-template <typename P, typename O>
-static int check_policy_call(const atc_scenario_t* s, int B, int N, int T, int hold, const atc_state_t* st, const float* obs0, const P* pol, const O* out,
-                             const atc_params_t* p, const char* pol_type, const char* out_type, const int32_t* traffic_k, const float* traffic,
-                             const PolicyEnds* ends = nullptr) {
+// The argument checks of the policy launches (the three rollouts and atc_policy_eval), in the header's order, in three parts: what is
+// refused up to `out` itself (policy_call_head), the call's own required outputs (at the caller), what is refused from n_hidden to the mode
+// (policy_call_env), then the call's own tail — the overlap rule of the rollouts (check_policy_call) or atc_policy_eval's two refusals
+// and its overlap rule (check_policy_eval_call).  `out_type` names the output struct in the refusals; traffic_k is null for
+// atc_rollout_policy; `k0`: traffic_k may be 0, the ten-word policy (atc_rollout_policy_ends, atc_policy_eval) — then `traffic` must be NULL.
+template <typename P>
+static int policy_call_head(int T, int hold, const float* obs0, const P* pol, const void* out, const char* pol_type, const char* out_type) {
     // T and hold first, before any pointer is looked at
     if (T < 1 || hold < 1) return fail_arg("need T >= 1 and hold >= 1");
     if (T % hold != 0) return fail_arg("T must be a multiple of hold (the launch takes T / hold decisions)");
     if (!pol) return fail_argf("null pointer: pol (%s) is required", pol_type);
     if (const int rc = check_required({{pol->w, "null pointer: pol->w (the policy's weights) is required"}, {obs0, "null pointer: obs0 is required"}})) return rc;
     if (!out) return fail_argf("null pointer: out (%s) is required", out_type);
-    if (!out->obs || !out->reward || !out->done || !out->flags) return fail_argf("null pointer: %s.obs, .reward, .done and .flags are required", out_type);
-    if (!out->action) return fail_argf("null pointer: %s.action is required", out_type);
+    return ATC_OK;
+}
+template <typename P>
+static int policy_call_env(const atc_scenario_t* s, int B, int N, const atc_state_t* st, const P* pol, const atc_params_t* p, const char* out_type,
+                           const int32_t* traffic_k, const float* traffic, bool k0) {
     if (pol->n_hidden != ATC_POLICY_HIDDEN) return fail_arg("pol->n_hidden must be 64 (ATC_POLICY_HIDDEN)");
-    if (traffic_k && !(ends && *traffic_k == 0) && *traffic_k != 1 && *traffic_k != 2 && *traffic_k != 4)
-        return fail_arg(ends ? "pol->traffic_k must be 0, 1, 2 or 4 (the ten-word policy, or a compiled list length)" : "pol->traffic_k must be 1, 2 or 4 (the compiled list lengths)");
+    if (traffic_k && !(k0 && *traffic_k == 0) && *traffic_k != 1 && *traffic_k != 2 && *traffic_k != 4)
+        return fail_arg(k0 ? "pol->traffic_k must be 0, 1, 2 or 4 (the ten-word policy, or a compiled list length)" : "pol->traffic_k must be 1, 2 or 4 (the compiled list lengths)");
     if (pol->flags & ~ATC_POLICY_DETERMINISTIC) return fail_arg("pol->flags has unknown bits (ATC_POLICY_DETERMINISTIC or 0)");
-    if (ends && *traffic_k == 0 && traffic) return fail_argf("%s.traffic must be NULL where pol->traffic_k is 0 (no traffic query is evaluated)", out_type);
+    if (k0 && *traffic_k == 0 && traffic) return fail_argf("%s.traffic must be NULL where pol->traffic_k is 0 (no traffic query is evaluated)", out_type);
     if (const int rc = check_env_args(s, B, N, st, p)) return rc;
     if (const int rc = check_dt(s, p)) return rc;
     if (p->mode & ATC_M_DISCRETE) return fail_arg("ATC_M_DISCRETE: a Gaussian policy draws the continuous action space only");
     if (p->mode & ATC_M_ACTIONS_HELD) return fail_arg("ATC_M_ACTIONS_HELD is for atc_step only: every block's first step carries a fresh decision");
+    return ATC_OK;
+}
+// `w` against each of others[0 .. n-1] (NULL entries left out), refused with `tail`
+static int check_apart(const ByteRange& w, const ByteRange* others, int n, const char* tail) {
+    for (int i = 0; i < n; ++i) {
+        const ByteRange pair[2] = {w, others[i]};
+        if (const int rc = check_disjoint(pair, 2, {}, tail)) return rc;
+    }
+    return ATC_OK;
+}
+// the three rollouts.  `traffic` is atc_policy_traffic_out_t.traffic (its range joins the overlap rule); `ends`: the call is
+// atc_rollout_policy_ends, whose three arrays join the overlap rule.
+template <typename P, typename O>
+static int check_policy_call(const atc_scenario_t* s, int B, int N, int T, int hold, const atc_state_t* st, const float* obs0, const P* pol, const O* out,
+                             const atc_params_t* p, const char* pol_type, const char* out_type, const int32_t* traffic_k, const float* traffic,
+                             const PolicyEnds* ends = nullptr) {
+    if (const int rc = policy_call_head(T, hold, obs0, pol, out, pol_type, out_type)) return rc;
+    if (!out->obs || !out->reward || !out->done || !out->flags) return fail_argf("null pointer: %s.obs, .reward, .done and .flags are required", out_type);
+    if (!out->action) return fail_argf("null pointer: %s.action is required", out_type);
+    if (const int rc = policy_call_env(s, B, N, st, pol, p, out_type, traffic_k, traffic, ends != nullptr)) return rc;
     const uintptr_t bn = (uintptr_t)B * (uintptr_t)N, row = bn * (ATC_OBS_DIM * 4u), n_dec = (uintptr_t)(T / hold);
     const ByteRange ranges[2] = {{obs0, row, "obs0"}, {out->obs, row * (uintptr_t)T, "out->obs"}};
     if (const int rc = check_disjoint(ranges, 2, {}, "decision 0 reads obs0 while the steps write out->obs")) return rc;
@@ -2248,14 +2284,31 @@ static int check_policy_call(const atc_scenario_t* s, int B, int N, int T, int h
                                 {st->phi_wide, bn * 32u, "st->phi_wide"}};
         int n = 8;
         for (int v = 0; v < w; ++v) others[n++] = per_decision[v];
-        for (int i = 0; i < n; ++i) {
-            const ByteRange pair[2] = {per_decision[w], others[i]};
-            if (const int rc = check_disjoint(pair, 2, {}, w == 0 ? "the records are written while the launch reads and writes the other"
-                                                                  : "it is written while the launch reads and writes the other"))
-                return rc;
-        }
+        if (const int rc = check_apart(per_decision[w], others, n, w == 0 ? "the records are written while the launch reads and writes the other"
+                                                                          : "it is written while the launch reads and writes the other"))
+            return rc;
     }
     return ATC_OK;
+}
+// atc_policy_eval: out->record stands where the rollouts' required outputs do; behind the mode's refusals its own two; record and obs_last
+// against obs0, the six state arrays and each other.
+static int check_policy_eval_call(const atc_scenario_t* s, int B, int N, int T, int hold, const atc_state_t* st, const float* obs0, const atc_policy_traffic_t* pol,
+                                  const atc_policy_eval_out_t* out, const atc_params_t* p) {
+    const char* const out_type = "atc_policy_eval_out_t";
+    if (const int rc = policy_call_head(T, hold, obs0, pol, out, "atc_policy_traffic_t", out_type)) return rc;
+    if (!out->record) return fail_argf("null pointer: %s.record is required", out_type);
+    if (const int rc = policy_call_env(s, B, N, st, pol, p, out_type, &pol->traffic_k, nullptr, true)) return rc;
+    // (the step forms the per-episode words k_policy_eval reads back only on its auto-reset path)
+    if (!(p->mode & ATC_M_AUTO_RESET)) return fail_arg("ATC_M_AUTO_RESET is required: an evaluation counts episodes, which end and restart inside the step");
+    if (out->flags & ~ATC_EVAL_CLEAR) return fail_argf("%s.flags has unknown bits (ATC_EVAL_CLEAR or 0)", out_type);
+    const uintptr_t bn = (uintptr_t)B * (uintptr_t)N, row = bn * (ATC_OBS_DIM * 4u);
+    const ByteRange record = {out->record, (uintptr_t)B * (ATC_EVAL_WORDS * 4u), "out->record"};
+    const ByteRange others[8] = {{out->obs_last, row, "out->obs_last"}, {obs0, row, "obs0"}, {st->ac, bn * 16u, "st->ac"}, {st->alt, bn * 8u, "st->alt"},
+                                 {st->last_act, bn * 16u, "st->last_act"}, {st->env, (uintptr_t)B * (ATC_ENV_WORDS * 4u), "st->env"},
+                                 {st->stats, (uintptr_t)B * (ATC_STAT_WORDS * 4u), "st->stats"}, {st->phi_wide, bn * 32u, "st->phi_wide"}};
+    const char* const tail = "it is written while the launch reads and writes the other";
+    if (const int rc = check_apart(record, others, 8, tail)) return rc;
+    return check_apart(others[0], others + 1, 7, tail);
 }
 
 #include "atc_abi.inc"   // the extern "C" entry points (host side)

@@ -1154,6 +1154,54 @@ int atc_rollout_policy_ends(const atc_scenario_t* s, int B, int N, int T, int ho
 enum { ATC_ROLLOUT_POLICY_ENDS_LAUNCH_SLOTS = 28 };
 int atc_rollout_policy_ends_launch_counts(uint64_t* out, int n);
 
+/* POLICY EVALUATION (extension): how good is this policy?  The reference's trainer logs winning_ratio, the mean episode length and
+ * Monitor's r / l after every update (learning/atc-gym-stable-baselines.py).  atc_policy_eval flies a packed policy for T steps exactly as
+ * atc_rollout_policy_ends does — the decisions, the key, the draw, the clamp, ATC_POLICY_DETERMINISTIC, the traffic query for traffic_k > 0,
+ * held blocks stepping through auto-resets, and the state afterwards (the per-episode record included) are that call's, bit for bit — and
+ * stores NONE of its per-step or per-decision streams.  What leaves the launch is one record of ATC_EVAL_WORDS 32-bit words per env
+ * (float words by bit pattern), and optionally the last step's observation.
+ * THE RECORD ACCUMULATES.  The launch reads out->record at its start — or, under ATC_EVAL_CLEAR, takes the initial values below without
+ * reading — and writes it once at its end.  An ENDING STEP is any step of the launch with done set for the env; every one counts, also a
+ * second one inside a held block (evaluation counts episodes, not transitions).  `seen` is the OR of the env's valid aircraft's flag words
+ * at that step, as atc_rollout's flags[t] stores them; r and the length are the words that step writes to ATC_STAT_EP_RETURN and
+ * ATC_STAT_EP_LENGTH, the win bit the one it shifts into ATC_STAT_WIN_BITS.  They are the whole episode's: an episode that began before
+ * the launch (ATC_ENV_TIMESTEPS / ATC_ENV_TOTAL_REWARD carried in the state) is counted in full, one still running at the end of the
+ * launch is not counted and stays in the state.  Hence two launches of T / 2 on the same record — the second with decision0 + T / (2 hold),
+ * obs0 = the first's obs_last and no ATC_EVAL_CLEAR — equal one launch of T bit for bit: record, obs_last and state.
+ * Every float operation is fp32, rounded once, never fused: sum = sum + r; sq = sq + (r * r); fminf / fmaxf.
+ * ATC_ERR_ARG: the refusals of atc_rollout_policy_ends in its order, with out->record in the place of its required outputs; behind the
+ * ATC_M_DISCRETE / ATC_M_ACTIONS_HELD refusals, ATC_M_AUTO_RESET missing from p->mode (without the reset inside the step the per-episode
+ * words are never formed) and unknown bits in out->flags; then record (B * 64 bytes) or obs_last (B*N*40 bytes) sharing memory with obs0,
+ * each other or one of the six state arrays.
+ * Counted by atc_policy_eval_launch_counts only: slot = 4 log2(W) + {0, 1, 2, 3 for K = 0, 1, 2, 4}; a refused call moves no record. */
+enum {
+    ATC_EVAL_EPISODES = 0,        /* i32  + 1 at every ending step */
+    ATC_EVAL_WINS = 1,            /* i32  + the bit that step shifts into ATC_STAT_WIN_BITS */
+    ATC_EVAL_END_BELOW_MVA = 2,   /* i32  + 1 if `seen` has ATC_F_BELOW_MVA (an end can count in several of the four) */
+    ATC_EVAL_END_OUTSIDE = 3,     /* i32  ... ATC_F_OUTSIDE */
+    ATC_EVAL_END_CONFLICT = 4,    /* i32  ... ATC_F_CONFLICT */
+    ATC_EVAL_END_TIMEOUT = 5,     /* i32  ... ATC_F_TIMEOUT */
+    ATC_EVAL_STEPS = 6,           /* i32  + the ended episode's length */
+    ATC_EVAL_RETURN_SUM = 7,      /* f32  sum = sum + r */
+    ATC_EVAL_RETURN_SQ = 8,       /* f32  sq = sq + (r * r) */
+    ATC_EVAL_RETURN_MIN = 9,      /* f32  fminf(min, r); initially +inf */
+    ATC_EVAL_RETURN_MAX = 10,     /* f32  fmaxf(max, r); initially -inf */
+    ATC_EVAL_FLAGS_OR = 11,       /* u32  the OR of the env's valid aircraft's flag words at EVERY step of the launch */
+    ATC_EVAL_LAUNCH_STEPS = 12,   /* i32  + T, once per launch */
+    ATC_EVAL_WORDS = 16           /* words 13 .. 15 are reserved: written as read, 0 under ATC_EVAL_CLEAR */
+};
+#define ATC_EVAL_CLEAR 1u
+typedef struct atc_policy_eval_out {
+    int32_t* record;     /* [B][ATC_EVAL_WORDS] required */
+    float* obs_last;     /* [B*N*10]            nullable: the observation the last step stored, the next launch's obs0 */
+    uint32_t flags;      /* ATC_EVAL_CLEAR or 0 */
+} atc_policy_eval_out_t;
+int atc_policy_eval(const atc_scenario_t* s, int B, int N, int T, int hold, const atc_state_t* st,
+                    const float* obs0 /* [B*N*10] */, const atc_policy_traffic_t* pol, const atc_policy_eval_out_t* out,
+                    const atc_params_t* p, void* stream);
+enum { ATC_POLICY_EVAL_LAUNCH_SLOTS = 28 };
+int atc_policy_eval_launch_counts(uint64_t* out, int n);
+
 /* GAE (extension): what lies between the collection launch and the update of an on-policy trainer, in one launch — the per-step
  * rewards and dones of a rollout (atc_rollout_policy's reward [T][B] and done [T][B]) and the values of one batched forward turned into
  * generalised advantage estimates and returns, one transition per DECISION.  A pure function of its arrays: `s` names the device only,
