@@ -148,6 +148,21 @@ PPO_VALUE_GRAD_LAUNCH_SLOTS = 4
 EVAL_WORDS = 16
 EVAL_CLEAR = 1
 POLICY_EVAL_LAUNCH_SLOTS = 28
+# advantage normalisation (include/atc_step.h: atc_adv_normalise): tiles of ADV_TILE rows, at most ADV_MAX_WG workgroups = triples of `scratch`
+# (float64 [G, 3]), ADV_DEFAULT_WG where the caller leaves the choice to the library; the words of `stats`; one slot, one count per call
+ADV_TILE = 256
+ADV_MAX_WG = 1024
+ADV_DEFAULT_WG = 256
+ADV_STATS = 4
+ADV_STAT_N, ADV_STAT_MEAN, ADV_STAT_SCALE, ADV_STAT_STD = range(4)
+ADV_NORMALISE_LAUNCH_SLOTS = 1
+# the optimiser step (include/atc_step.h: atc_adam_step): one workgroup of ADAM_BLOCK lanes over at most ADAM_MAX_WORDS words per tensor; the
+# words of `stats`; its record counts calls by the number of tensors (slot = n_tensors - 1)
+ADAM_BLOCK = 1024
+ADAM_MAX_WORDS = 65536
+ADAM_STATS = 4
+ADAM_STAT_NORM, ADAM_STAT_COEF, ADAM_STAT_SKIPPED, ADAM_STAT_STEP = range(4)
+ADAM_STEP_LAUNCH_SLOTS = 2
 
 
 def policy_in(traffic=0):
@@ -168,3 +183,8 @@ def value_words(traffic=0):
 def ppo_grad_workgroups(R, workgroups=0):
     """G of an atc_ppo_policy_grad or atc_ppo_value_grad call on R rows: `workgroups`, or with 0 min(tiles of 64 rows, PPO_GRAD_DEFAULT_WG); `scratch` has G rows"""
     return int(workgroups) if workgroups else min((int(R) + PPO_GRAD_TILE - 1) // PPO_GRAD_TILE, PPO_GRAD_DEFAULT_WG)
+
+
+def adv_workgroups(R, workgroups=0):
+    """G of an atc_adv_normalise call on R rows: `workgroups`, or with 0 min(tiles of 256 rows, ADV_DEFAULT_WG); `scratch` is float64 [G, 3]"""
+    return int(workgroups) if workgroups else min((int(R) + ADV_TILE - 1) // ADV_TILE, ADV_DEFAULT_WG)

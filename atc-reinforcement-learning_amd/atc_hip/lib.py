@@ -172,6 +172,39 @@ class AtcPpoValueGradOut(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in PPO_VALUE_GRAD_OUT_FIELDS]
 
 
+ADV_NORM_FIELDS = ("eps", "workgroups")
+
+
+class AtcAdvNorm(C.Structure):
+    """atc_adv_norm_t"""
+    _fields_ = [("eps", C.c_float), ("workgroups", C.c_int32)]
+
+
+ADV_NORM_OUT_FIELDS = ("out_adv", "stats", "scratch")
+
+
+class AtcAdvNormOut(C.Structure):
+    """atc_adv_norm_out_t"""
+    _fields_ = [(n, C.c_void_p) for n in ADV_NORM_OUT_FIELDS]
+
+
+ADAM_TENSOR_FIELDS = ("w", "grad", "m", "v", "words", "grad_scale", "add_first", "add_count", "add_value")
+
+
+class AtcAdamTensor(C.Structure):
+    """atc_adam_tensor_t"""
+    _fields_ = [("w", C.c_void_p), ("grad", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("words", C.c_int32), ("grad_scale", C.c_float),
+                ("add_first", C.c_int32), ("add_count", C.c_int32), ("add_value", C.c_float)]
+
+
+ADAM_FIELDS = ("lr", "beta1", "beta2", "eps", "max_norm", "step")
+
+
+class AtcAdam(C.Structure):
+    """atc_adam_t"""
+    _fields_ = [("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double), ("max_norm", C.c_double), ("step", C.c_int32)]
+
+
 class AtcStepCall(C.Structure):
     """atc_step_call_t"""
     _fields_ = [("s", C.c_void_p), ("B", C.c_int32), ("N", C.c_int32), ("st", C.POINTER(AtcState)), ("actions", C.c_void_p),
@@ -191,7 +224,8 @@ EXPORTS = ("atc_abi_version", "atc_last_error", "atc_launch_counts", "atc_host_m
            "atc_gae", "atc_gae_launch_counts", "atc_rollout_policy_ends", "atc_rollout_policy_ends_launch_counts", "atc_gae_boot",
            "atc_gae_boot_launch_counts", "atc_ppo_policy_grad", "atc_ppo_policy_grad_launch_counts",
            "atc_value_forward", "atc_value_forward_launch_counts", "atc_ppo_value_grad", "atc_ppo_value_grad_launch_counts",
-           "atc_policy_eval", "atc_policy_eval_launch_counts")
+           "atc_policy_eval", "atc_policy_eval_launch_counts", "atc_adv_normalise", "atc_adv_normalise_launch_counts",
+           "atc_adam_step", "atc_adam_step_launch_counts")
 
 def load():
     """Loads libatcstep.so; raises (never falls back) when it has not been built."""
@@ -254,6 +288,8 @@ def load():
     lib.atc_ppo_policy_grad.argtypes = [vp, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(AtcPpoGrad), C.POINTER(AtcPpoGradOut), vp]
     lib.atc_value_forward.argtypes = [vp, ci, ci, vp, vp, vp, vp]
     lib.atc_ppo_value_grad.argtypes = [vp, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, C.POINTER(AtcPpoValueGrad), C.POINTER(AtcPpoValueGradOut), vp]
+    lib.atc_adv_normalise.argtypes = [vp, ci, vp, vp, C.POINTER(AtcAdvNorm), C.POINTER(AtcAdvNormOut), vp]
+    lib.atc_adam_step.argtypes = [vp, ci, C.POINTER(AtcAdamTensor), C.POINTER(AtcAdam), vp, vp]
     for getter in LAUNCH_RECORDS:
         getattr(lib, getter).argtypes = [C.POINTER(C.c_uint64), ci]
     for name in EXPORTS:
@@ -296,6 +332,11 @@ def _traffic_k0(slot):
     return (0, 1, 2, 4)[slot]
 
 
+def _tensors(slot):
+    """number of tensors of a slot of the optimiser step's record: slot = n_tensors - 1"""
+    return slot + 1
+
+
 # The library's launch records (include/atc_step.h): getter -> (slots, name of a slot: a function of the slot number, or the one
 # slot's name).  load() gives every getter its argtypes from this table; each has a wrapper below, and launch_records() reads all.
 LAUNCH_RECORDS = {
@@ -319,6 +360,8 @@ LAUNCH_RECORDS = {
     "atc_value_forward_launch_counts": (L.VALUE_FORWARD_LAUNCH_SLOTS, _traffic_k0),
     "atc_ppo_value_grad_launch_counts": (L.PPO_VALUE_GRAD_LAUNCH_SLOTS, _traffic_k0),
     "atc_policy_eval_launch_counts": (L.POLICY_EVAL_LAUNCH_SLOTS, _width_k0),
+    "atc_adv_normalise_launch_counts": (L.ADV_NORMALISE_LAUNCH_SLOTS, "adv_normalise"),
+    "atc_adam_step_launch_counts": (L.ADAM_STEP_LAUNCH_SLOTS, _tensors),
 }
 
 
@@ -448,6 +491,18 @@ def ppo_value_grad_launch_counts():
     """Calls of the PPO value loss and gradient (atc_ppo_value_grad; two launches each) made by the calling thread so far, by records per
     aircraft, like ppo_policy_grad_launch_counts().  Separate from the other launch records."""
     return _counts("atc_ppo_value_grad_launch_counts")
+
+
+def adv_normalise_launch_counts():
+    """Calls of the advantage normalisation (atc_adv_normalise; two launches each) made by the calling thread so far: {"adv_normalise": n},
+    or {} before the first.  Separate from the other launch records."""
+    return _counts("atc_adv_normalise_launch_counts")
+
+
+def adam_step_launch_counts():
+    """Calls of the optimiser step (atc_adam_step; one launch each) made by the calling thread so far, by the number of tensors: {1: n, 2: n},
+    zero counts left out.  Separate from the other launch records."""
+    return _counts("atc_adam_step_launch_counts")
 
 
 def lookahead_set_mapping(candidates_per_workgroup=0):

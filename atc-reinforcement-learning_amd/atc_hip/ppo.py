@@ -6,11 +6,12 @@ collect_bootstrap() also bootstraps time-limit ends (atc_rollout_policy_ends, at
 value forward) and returns the mask of the aircraft each decision controlled.
 policy_grad() is the policy half of the update on such a collection: the clipped surrogate loss and its gradient with respect to the
 packed weights in one call (atc_ppo_policy_grad), and value_grad() the value half: the clipped value loss of the packed critic and its
-gradient (atc_ppo_value_grad).  One iteration then touches autograd nowhere: what is left to the trainer is the optimiser, stepped on the
-two packed tensors, and the entropy bonus (log_std.sum() plus a constant).
-Not covered, the trainer's: advantage normalisation — with `control` in hand three reductions over [D, B, N], which policy_grad() makes
-in torch and passes on as two scalars — and bootstrapping a traffic policy's collection: the traffic records of a terminal state are not
-produced."""
+gradient (atc_ppo_value_grad).  update() closes the iteration: the advantages normalised once per collection (atc_adv_normalise), then per
+minibatch the two gradient calls and ONE optimiser step on both packed tensors (atc_adam_step: the gradient-norm clip over both, the entropy
+term on log_std, Adam), with adam_state() holding the moments and every buffer.  An iteration then touches neither autograd nor torch.optim,
+and update() reads no device value on the host.  (policy_grad(normalise=True) on its own still makes its three reductions in torch.)
+Not covered, the trainer's: bootstrapping a traffic policy's collection — the traffic records of a terminal state are not produced — and
+learning-rate or clip-range schedules, which are update()'s arguments from call to call."""
 from . import layout as L
 from . import policy as _policy
 
@@ -174,3 +175,86 @@ def value_grad(env, collected, weights, index=None, clip=0.2, workgroups=0, out=
         return v.reshape(D, B, 1).expand(D, B, N).contiguous()
     return env.ppo_value_grad(weights, own, per_aircraft(collected["values"][:-1], "values[:-1]"), per_aircraft(collected["ret"], "ret"),
                               traffic=collected.get("traffic"), mask=collected.get("control"), index=index, clip=clip, workgroups=workgroups, out=out)
+
+
+def adam_state(env, w, vw=None):
+    """What update() keeps from call to call for the packed policy `w` and, where given, the packed critic `vw`: zeroed first and second
+    moments per tensor ("m", "v": lists in the order policy, critic), the update count "t" = 0, and every out= buffer of the calls update()
+    makes, allocated once — those whose size depends on the collection are made by the first update() that meets that size and kept."""
+    torch = env.torch
+    tensors = [w] if vw is None else [w, vw]
+    for t in tensors:
+        if not (torch.is_tensor(t) and t.dtype == torch.float32 and t.dim() == 1 and t.is_contiguous()):
+            raise ValueError("w and vw must be contiguous 1-D float32 tensors (atc_hip.policy.pack_mlp, atc_hip.value.pack_mlp)")
+    new = lambda *shape, **kw: torch.empty(shape, dtype=kw.get("dtype", torch.float32), device=w.device)      # noqa: E731
+    return {"t": 0, "m": [torch.zeros_like(t) for t in tensors], "v": [torch.zeros_like(t) for t in tensors],
+            "grad": [new(int(t.numel())) for t in tensors],
+            "scratch": [new(L.PPO_GRAD_DEFAULT_WG, int(t.numel()) + L.PPO_GRAD_STATS) for t in tensors],
+            "rows": {}, "adv": {}}
+
+
+def update(env, collected, w, vw, state, *, epochs=4, minibatches=4, clip=0.2, vclip=0.2, lr=3e-4, ent_coef=0.0, vf_coef=0.5, max_grad_norm=0.5,
+           eps=1e-5, perm=None, seed=0):
+    """The update half of a PPO iteration on a collection, with no torch op between the library's calls and no device value read on the host:
+      once:          env.adv_normalise(adv, mask=collected.get("control")) — a per-env [D, B] adv expanded over the aircraft as in policy_grad();
+      per epoch e:   one int32 permutation of the D * B * N rows: perm[e] if given (an int32 tensor [E, R] or a list of [R] tensors on the
+                     env's device), else torch.randperm on the device from a generator seeded with (seed, e);
+      per minibatch: policy_grad(..., normalise=False) on a shallow copy of `collected` whose "adv" is the normalised tensor, value_grad(),
+                     then ONE env.adam_step over both tensors with step = state["t"] + 1: the critic's gradient scaled by vf_coef, -ent_coef
+                     added to the three log_std words, the norm over both clipped to max_grad_norm.
+    w and vw are updated in place; state is adam_state(env, w, vw)'s and carries the moments and the count.  The minibatches are the
+    `minibatches` consecutive slices of the permutation ([k R // M, (k + 1) R // M)).
+    Returns {"policy_stats" [E, M, 8], "value_stats" [E, M, 8], "adam_stats" [E, M, 4], "adv_stats" [4]} as device tensors."""
+    torch = env.torch
+    action = collected["action"]
+    D, B, N = int(action.shape[0]), env.B, env.N
+    R = D * B * N
+    E, M = int(epochs), int(minibatches)
+    if E < 1 or not 1 <= M <= R:
+        raise ValueError("epochs must be >= 1 and minibatches 1 .. the number of rows")
+    if len(state["m"]) != 2:
+        raise ValueError("state must be adam_state(env, w, vw) of both tensors")
+    K = {L.policy_words(k): k for k in (0,) + L.POLICY_TRAFFIC_K}.get(int(w.numel()))
+    if K is None:
+        raise ValueError("w is not a packed policy (atc_hip.policy.pack_mlp)")
+    if perm is not None and len(perm) < E:
+        raise ValueError("perm must hold one permutation per epoch")
+    adv = collected["adv"]
+    if adv.dim() == 2 or int(adv.shape[-1]) != N:
+        if adv.dim() == 3 and int(adv.shape[-1]) != 1:
+            raise ValueError("adv must be [D, B, N], or per env [D, B] / [D, B, 1]")
+        adv = adv.reshape(D, B, 1).expand(D, B, N).contiguous()
+    dev = adv.device
+    abuf = state["adv"].get((D, B, N))
+    if abuf is None:
+        abuf = state["adv"][(D, B, N)] = {"adv": torch.empty((D, B, N), dtype=torch.float32, device=dev), "stats": torch.empty(L.ADV_STATS, dtype=torch.float32, device=dev),
+                                          "scratch": torch.empty((L.adv_workgroups(R), 3), dtype=torch.float64, device=dev)}
+    normed = env.adv_normalise(adv, collected.get("control"), out=abuf)
+    mb = dict(collected, adv=normed["adv"])
+    res = {"policy_stats": torch.empty((E, M, L.PPO_GRAD_STATS), dtype=torch.float32, device=dev),
+           "value_stats": torch.empty((E, M, L.PPO_VALUE_STATS), dtype=torch.float32, device=dev),
+           "adam_stats": torch.empty((E, M, L.ADAM_STATS), dtype=torch.float32, device=dev), "adv_stats": normed["stats"].clone()}
+    add = (_policy.offsets(K)["log_std"][0], 3, -float(ent_coef))
+    for e in range(E):
+        if perm is not None:
+            order = perm[e]
+        else:
+            gen = torch.Generator(device=dev)
+            gen.manual_seed(((int(seed) & 0xffffffff) << 24) + e)
+            order = torch.randperm(R, generator=gen, dtype=torch.int32, device=dev)
+        for k in range(M):
+            index = order[k * R // M:(k + 1) * R // M]
+            n = int(index.numel())
+            G = L.ppo_grad_workgroups(n)
+            rows = state["rows"].get(n)
+            if rows is None:
+                rows = state["rows"][n] = (torch.empty(n, dtype=torch.float32, device=dev), torch.empty(n, dtype=torch.float32, device=dev))
+            policy_grad(env, mb, w, index=index, clip=clip, normalise=False,
+                        out={"grad": state["grad"][0], "stats": res["policy_stats"][e, k], "logp": rows[0], "scratch": state["scratch"][0][:G]})
+            value_grad(env, collected, vw, index=index, clip=vclip,
+                       out={"grad": state["grad"][1], "stats": res["value_stats"][e, k], "value": rows[1], "scratch": state["scratch"][1][:G]})
+            state["t"] += 1
+            env.adam_step([{"w": w, "grad": state["grad"][0], "m": state["m"][0], "v": state["v"][0], "add": add},
+                           {"w": vw, "grad": state["grad"][1], "m": state["m"][1], "v": state["v"][1], "grad_scale": vf_coef}],
+                          lr=lr, step=state["t"], eps=eps, max_norm=max_grad_norm, out=res["adam_stats"][e, k])
+    return res

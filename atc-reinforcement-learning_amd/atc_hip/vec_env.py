@@ -1260,6 +1260,108 @@ class AtcVecEnv:
         self._keep_ppo_value_grad = (weights, obs_rows, traffic, v_old, ret, mask, index, scratch)   # they outlive the two launches
         return res
 
+    def adv_normalise(self, adv, mask=None, *, eps=1e-8, workgroups=0, out=None):
+        """Mean, standard deviation and the normalised advantages of a collection in one call on this env's current stream (atc_adv_normalise,
+        include/atc_step.h): two launches, nothing is read on the host.  adv: float32, any shape, contiguous, on this env's device; mask: uint8
+        with as many elements (rollout_policy_ends' control) or None — a row whose mask is 0 takes no part and is not read.
+        In float64: mean = S / n, std = sqrt(max(0, S2 - S mean) / (n - 1)) (torch.std's unbiased form; 0 with n == 1); then in float32
+        out = (adv - float32(mean)) * float32(1 / (std + eps)) — ppo_policy_grad's A = (adv - adv_shift) * adv_scale word for word — and 0
+        where a row takes no part.  Returns {"adv": of adv's shape, "stats": [4] (the L.ADV_STAT_* words: n, mean, scale, std)}; all zeros
+        with n == 0.  out: a dict with any of "adv" (which may be the input itself: in place), "stats" and "scratch" (float64 [G, 3] with
+        G = L.adv_workgroups(R, workgroups)); with all three the method allocates nothing.  workgroups: 0, or G = 1 .. L.ADV_MAX_WG — the same
+        inputs and the same G give the same bits on every run."""
+        torch = self.torch
+        dev, f32 = self.device, (self.torch.float32,)
+        need = AtcVecEnv._on_device.__get__(self)
+        if not (torch.is_tensor(adv) and 1 <= adv.numel() <= 2 ** 31 - 1):
+            raise ValueError("adv must be a float32 tensor of 1 .. 2^31 - 1 elements")
+        R, shape = int(adv.numel()), tuple(adv.shape)
+        need(adv, f32, shape, "adv")
+        if mask is not None:
+            need(mask, (torch.uint8,), (R,), "mask", elements=True)
+        with np.errstate(over="ignore"):
+            if not (np.isfinite(np.float32(eps)) and np.float32(eps) >= 0):
+                raise ValueError("eps must be finite (in float32) and >= 0")
+        workgroups = int(workgroups)
+        if not 0 <= workgroups <= L.ADV_MAX_WG:
+            raise ValueError("0 <= workgroups <= %d" % L.ADV_MAX_WG)
+        G = L.adv_workgroups(R, workgroups)
+        want = {"adv": (f32, shape), "stats": (f32, (L.ADV_STATS,)), "scratch": ((torch.float64,), (G, 3))}
+        res = {} if out is None else AtcVecEnv._results(self, out, want, set(), "out must be a dict with any of adv, stats, scratch")
+        if "adv" not in res:
+            res["adv"] = torch.empty(shape, dtype=torch.float32, device=dev)
+        if "stats" not in res:
+            res["stats"] = torch.empty(L.ADV_STATS, dtype=torch.float32, device=dev)
+        scratch = res.pop("scratch", None)
+        if scratch is None:
+            scratch = torch.empty((G, 3), dtype=torch.float64, device=dev)
+        g = _lib.AtcAdvNorm(float(eps), workgroups)
+        o = _lib.AtcAdvNormOut(res["adv"].data_ptr(), res["stats"].data_ptr(), scratch.data_ptr())
+        fn = self._lib.atc_adv_normalise
+        with torch.cuda.device(dev):
+            rc = fn(self.sector.handle, R, adv.data_ptr(), None if mask is None else mask.data_ptr(), C.byref(g), C.byref(o), self._stream())
+            if rc:
+                _lib.check(rc)
+        self._keep_adv_normalise = (adv, mask, scratch)      # they outlive the two launches
+        return res
+
+    def adam_step(self, tensors, *, lr, step, beta1=0.9, beta2=0.999, eps=1e-5, max_norm=0.0, out=None):
+        """PPO2's optimiser step on one or two packed tensors in ONE launch on this env's current stream (atc_adam_step, include/atc_step.h):
+        the gradient-norm clip over all of them, the entropy term, and torch.optim.Adam's update, in float64 with one rounding per stored word.
+        tensors: a list of 1 - 2 dicts {"w", "grad", "m", "v": contiguous float32 tensors of the same 1 .. L.ADAM_MAX_WORDS elements on this
+        env's device, all updated in place but grad; "grad_scale": 1.0 (vf_coef for the critic); "add": (first, count, value) or None — value is
+        added to the effective gradient of words first .. first + count - 1: the entropy bonus is (policy.offsets(K)["log_std"][0], 3, -ent_coef)}.
+        lr; step: the number of this update, from 1 (the bias corrections 1 - beta^step); max_norm: <= 0 or inf: no clip, else the norm over
+        all tensors' effective gradients is clipped to it (clip_grad_norm_'s rule).  A norm that is not finite skips the update: w, m, v keep
+        their bits.  Returns `stats` [4] (the L.ADAM_STAT_* words: norm, the coefficient applied, skipped, step); out: that tensor, and
+        nothing is allocated.  No two tensors of the call may share memory (refused by the library)."""
+        torch = self.torch
+        f32 = (torch.float32,)
+        need = AtcVecEnv._on_device.__get__(self)
+        if not (isinstance(tensors, (list, tuple)) and 1 <= len(tensors) <= 2 and all(isinstance(t, dict) for t in tensors)):
+            raise ValueError("tensors must be a list of 1 or 2 dicts with w, grad, m, v (and grad_scale, add)")
+        arr = (_lib.AtcAdamTensor * len(tensors))()
+        for k, t in enumerate(tensors):
+            if not {"w", "grad", "m", "v"} <= t.keys() <= {"w", "grad", "m", "v", "grad_scale", "add"}:
+                raise ValueError("tensors[%d] must be a dict with w, grad, m, v (and grad_scale, add)" % k)
+            w = t["w"]
+            if not (torch.is_tensor(w) and 1 <= w.numel() <= L.ADAM_MAX_WORDS):
+                raise ValueError("tensors[%d]['w'] must be a float32 tensor of 1 .. %d elements" % (k, L.ADAM_MAX_WORDS))
+            words = int(w.numel())
+            for n in ("w", "grad", "m", "v"):
+                need(t[n], f32, (words,), "tensors[%d][%r]" % (k, n), elements=True)
+            first, count, value = t.get("add") or (0, 0, 0.0)
+            first, count = int(first), int(count)
+            if count < 0 or (count > 0 and not 0 <= first <= words - count):
+                raise ValueError("tensors[%d]['add'] = (first, count, value) must lie inside the tensor" % k)
+            scale = float(t.get("grad_scale", 1.0))
+            with np.errstate(over="ignore"):
+                if not (np.isfinite(np.float32(scale)) and np.isfinite(np.float32(value))):
+                    raise ValueError("tensors[%d]: grad_scale and the added value must be finite in float32" % k)
+            arr[k] = _lib.AtcAdamTensor(w.data_ptr(), t["grad"].data_ptr(), t["m"].data_ptr(), t["v"].data_ptr(), words, scale, first, count, float(value))
+        step = int(step)
+        if not 1 <= step <= 2 ** 31 - 1:
+            raise ValueError("step must be >= 1 (the number of this update)")
+        lr, beta1, beta2, eps, max_norm = float(lr), float(beta1), float(beta2), float(eps), float(max_norm)
+        if not (np.isfinite(lr) and lr >= 0 and np.isfinite(eps) and eps >= 0):
+            raise ValueError("lr and eps must be finite and >= 0")
+        if not (0 <= beta1 < 1 and 0 <= beta2 < 1):
+            raise ValueError("beta1 and beta2 must lie in [0, 1)")
+        if max_norm != max_norm:
+            raise ValueError("max_norm must not be a NaN (<= 0 or inf: no clip)")
+        if out is None:
+            out = torch.empty(L.ADAM_STATS, dtype=torch.float32, device=self.device)
+        else:
+            need(out, f32, (L.ADAM_STATS,), "out")
+        g = _lib.AtcAdam(lr, beta1, beta2, eps, max_norm, step)
+        fn = self._lib.atc_adam_step
+        with torch.cuda.device(self.device):
+            rc = fn(self.sector.handle, len(tensors), arr, C.byref(g), out.data_ptr(), self._stream())
+            if rc:
+                _lib.check(rc)
+        self._keep_adam_step = [tuple(t[n] for n in ("w", "grad", "m", "v")) for t in tensors]      # they outlive the launch
+        return out
+
     def get_attr(self, name, indices=None):
         """VecEnv.get_attr for the attributes the reference's trainer reads (learning/atc-gym-stable-baselines.py:34,36)
         and the episode counters."""

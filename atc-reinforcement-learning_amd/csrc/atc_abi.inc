@@ -32,6 +32,8 @@ int atc_ppo_policy_grad_launch_counts(uint64_t* out, int n) { return copy_counts
 int atc_value_forward_launch_counts(uint64_t* out, int n) { return copy_counts(REC_VALUE_FORWARD, out, n); }
 int atc_ppo_value_grad_launch_counts(uint64_t* out, int n) { return copy_counts(REC_PPO_VALUE_GRAD, out, n); }
 int atc_policy_eval_launch_counts(uint64_t* out, int n) { return copy_counts(REC_POLICY_EVAL, out, n); }
+int atc_adv_normalise_launch_counts(uint64_t* out, int n) { return copy_counts(REC_ADV_NORMALISE, out, n); }
+int atc_adam_step_launch_counts(uint64_t* out, int n) { return copy_counts(REC_ADAM_STEP, out, n); }
 int atc_lookahead_set_mapping(int candidates_per_workgroup) {
     if (candidates_per_workgroup < 0 || candidates_per_workgroup > ATC_LOOKAHEAD_MAX_M) return fail_arg("candidates per workgroup must be 0 (the library's choice) .. 64");
     t_look_cpg = candidates_per_workgroup;
@@ -781,6 +783,85 @@ int atc_ppo_value_grad(const atc_scenario_t* s, int R_src, int R, int traffic_k,
                        (hipStream_t)stream, words, G, out->scratch, out->grad, out->stats);
     HIP_TRY(hipGetLastError());
     ++record(REC_PPO_VALUE_GRAD)[K ? 1 + __builtin_ctz(K) : 0];
+    return ATC_OK;
+}
+
+// atc_adv_normalise: the checks in the header's order, then k_adv_moments on G workgroups and k_adv_apply, both on `stream`
+int atc_adv_normalise(const atc_scenario_t* s, int R, const float* adv, const uint8_t* mask, const atc_adv_norm_t* g, const atc_adv_norm_out_t* out,
+                      void* stream) {
+    if (const int rc = check_required({{s, "null pointer: s"}, {adv, "null pointer: adv is required"}, {g, "null pointer: g (atc_adv_norm_t) is required"},
+                                       {out, "null pointer: out (atc_adv_norm_out_t) is required"}}))
+        return rc;
+    if (const int rc = check_required({{out->stats, "null pointer: out->stats is required"}, {out->scratch, "null pointer: out->scratch is required"}})) return rc;
+    if (R < 1) return fail_arg("R (the number of rows) must be >= 1");
+    if (!(g->eps >= 0.0f && g->eps <= __FLT_MAX__)) return fail_arg("g->eps must be finite and >= 0");
+    if (g->workgroups < 0 || g->workgroups > ATC_ADV_MAX_WG) return fail_arg("g->workgroups must be 0 (the library's choice) .. 1024 (ATC_ADV_MAX_WG)");
+    const long long tiles = ((long long)R + (kAdvBlock - 1)) / kAdvBlock;
+    const int G = g->workgroups ? g->workgroups : (int)(tiles < ATC_ADV_DEFAULT_WG ? tiles : ATC_ADV_DEFAULT_WG);
+    // no output may share memory with any array of the call; out_adv may BE adv (the one in-place pair)
+    const uintptr_t r = (uintptr_t)R;
+    const ByteRange arrays[5] = {{adv, r * 4u, "adv"}, {mask, r, "mask"}, {out->out_adv, r * 4u, "out_adv"}, {out->stats, ATC_ADV_STATS * 4u, "stats"},
+                                 {out->scratch, (uintptr_t)G * 24u, "scratch"}};
+    for (int a = 2; a < 5; ++a)
+        for (int b = 0; b < a; ++b) {
+            if (a == 2 && b == 0 && adv == out->out_adv) continue;
+            const ByteRange pair[2] = {arrays[b], arrays[a]};
+            if (const int rc = check_disjoint(pair, 2, {}, "no output of atc_adv_normalise may share memory with another array; out_adv may be adv itself")) return rc;
+        }
+    hipLaunchKernelGGL(k_adv_moments, dim3((unsigned)G), dim3(kAdvBlock), 0, (hipStream_t)stream, R, adv, mask, out->scratch);
+    HIP_TRY(hipGetLastError());
+    const unsigned grid = (unsigned)(tiles < kAdvApplyMaxGrid ? tiles : kAdvApplyMaxGrid);
+    hipLaunchKernelGGL(k_adv_apply, dim3(out->out_adv ? grid : 1u), dim3(kAdvBlock), 0, (hipStream_t)stream, R, G, g->eps, adv, mask,
+                       (const double*)out->scratch, out->out_adv, out->stats);
+    HIP_TRY(hipGetLastError());
+    ++record(REC_ADV_NORMALISE)[0];
+    return ATC_OK;
+}
+
+// atc_adam_step: the checks in the header's order, then k_adam_step, one workgroup on `stream`
+int atc_adam_step(const atc_scenario_t* s, int n_tensors, const atc_adam_tensor_t* t, const atc_adam_t* g, float* stats, void* stream) {
+    if (const int rc = check_required({{s, "null pointer: s"}, {t, "null pointer: t (atc_adam_tensor_t) is required"}, {g, "null pointer: g (atc_adam_t) is required"},
+                                       {stats, "null pointer: stats is required"}}))
+        return rc;
+    if (n_tensors != 1 && n_tensors != 2) return fail_arg("n_tensors must be 1 or 2");
+    auto finite = [](double x) { return x - x == 0.0; };
+    for (int k = 0; k < n_tensors; ++k) {
+        if (!t[k].w || !t[k].grad || !t[k].m || !t[k].v) return fail_argf("null pointer: w, grad, m and v of tensor %d are required", k);
+        if (t[k].words < 1 || t[k].words > ATC_ADAM_MAX_WORDS) return fail_argf("words of tensor %d must be 1 .. 65536 (ATC_ADAM_MAX_WORDS)", k);
+        if (t[k].add_count < 0 || (t[k].add_count > 0 && (t[k].add_first < 0 || (long long)t[k].add_first + t[k].add_count > t[k].words)))
+            return fail_argf("the add window of tensor %d must lie inside the tensor (add_first >= 0, add_first + add_count <= words), or add_count be 0", k);
+        if (!finite(t[k].grad_scale) || !finite(t[k].add_value)) return fail_argf("grad_scale and add_value of tensor %d must be finite", k);
+    }
+    if (g->step < 1) return fail_arg("g->step must be >= 1 (the number of this update, counted from 1)");
+    if (!finite(g->lr) || g->lr < 0.0) return fail_arg("g->lr must be finite and >= 0");
+    if (!finite(g->eps) || g->eps < 0.0) return fail_arg("g->eps must be finite and >= 0");
+    if (!(g->beta1 >= 0.0 && g->beta1 < 1.0) || !(g->beta2 >= 0.0 && g->beta2 < 1.0)) return fail_arg("g->beta1 and g->beta2 must lie in [0, 1)");
+    if (g->max_norm != g->max_norm) return fail_arg("g->max_norm must not be a NaN (<= 0 or +inf: no clip)");
+    // every array of the call is read and written in place: none may share memory with another
+    ByteRange arrays[9];
+    static const char* const names[2][4] = {{"w of tensor 0", "grad of tensor 0", "m of tensor 0", "v of tensor 0"},
+                                            {"w of tensor 1", "grad of tensor 1", "m of tensor 1", "v of tensor 1"}};
+    int n = 0;
+    for (int k = 0; k < n_tensors; ++k) {
+        const void* ptr[4] = {t[k].w, t[k].grad, t[k].m, t[k].v};
+        for (int a = 0; a < 4; ++a) arrays[n++] = ByteRange{ptr[a], (uintptr_t)t[k].words * 4u, names[k][a]};
+    }
+    arrays[n++] = ByteRange{stats, ATC_ADAM_STATS * 4u, "stats"};
+    if (const int rc = check_disjoint(arrays, n, {}, "atc_adam_step updates in place: no two of its arrays may share memory")) return rc;
+    AdamArgs a = {};
+    for (int k = 0; k < n_tensors; ++k)
+        a.t[k] = AdamTensorArg{t[k].w, t[k].grad, t[k].m, t[k].v, t[k].words, t[k].grad_scale, t[k].add_first, t[k].add_count, t[k].add_value};
+    a.lr = g->lr;
+    a.beta1 = g->beta1;
+    a.beta2 = g->beta2;
+    a.eps = g->eps;
+    a.max_norm = g->max_norm;
+    a.c1 = 1.0 - pow(g->beta1, (double)g->step);
+    a.c2 = 1.0 - pow(g->beta2, (double)g->step);
+    a.step = g->step;
+    hipLaunchKernelGGL(k_adam_step, dim3(1), dim3(kAdamBlock), 0, (hipStream_t)stream, a, stats);
+    HIP_TRY(hipGetLastError());
+    ++record(REC_ADAM_STEP)[n_tensors - 1];
     return ATC_OK;
 }
 

@@ -1443,6 +1443,106 @@ int atc_ppo_value_grad(const atc_scenario_t* s, int R_src, int R, int traffic_k,
 enum { ATC_PPO_VALUE_GRAD_LAUNCH_SLOTS = 4 };
 int atc_ppo_value_grad_launch_counts(uint64_t* out, int n);
 
+/* ADVANTAGE NORMALISATION (extension): mean and standard deviation of the advantages of a collection and the normalised advantages, in two
+ * launches on `stream` with no host read.  `s` names the device only; all array pointers are device pointers.
+ * ROWS.  adv [R] float32.  Row r PARTICIPATES if mask is NULL or mask[r] != 0 (atc_rollout_policy_ends' control, flattened); a row that
+ * does not is not read: a NaN standing there changes no output bit.
+ * LAUNCH 1.  G workgroups of ATC_ADV_TILE = 256 lanes; workgroup g takes the tiles of 256 consecutive rows g, g + G, ...  Lane l adds its row
+ * of each tile, in tile order, into float64 accumulators: n += 1; S += a; S2 += a * a (the product in float64).  Lane 0 adds the 256 lanes'
+ * triples in lane order 0 .. 255 and writes scratch[g] = {n, S, S2}.
+ * LAUNCH 2.  Every workgroup adds the G triples in the order of g in float64, then
+ *     mean = S / n;  var = max(0, S2 - S * mean) / (n - 1), 0 with n == 1 (the unbiased form, torch.std's);  std = sqrt(var)
+ *     shift = (float)mean;  scale = (float)(1.0 / (std + (double)eps))
+ *     out_adv[r] = (adv[r] - shift) * scale in float32 for a participating row — atc_ppo_policy_grad's A = (adv - adv_shift) * adv_scale
+ *     word for word, so that call gives the same bits on (out_adv, 0, 1) as on (adv, stats[MEAN], stats[SCALE]) — and 0.0f, by a select,
+ *     for a row that takes no part.
+ * stats [ATC_ADV_STATS] = {n, shift, scale, (float)std} (the ATC_ADV_STAT_* words).  With n == 0, stats and out_adv are all zeros.
+ * out_adv is nullable, and may be adv itself (in place: equal pointers); no other output may share a byte with another array of the call.
+ * scratch [G][3] doubles, required, overwritten by every call.  workgroups == 0: G = min(tiles, ATC_ADV_DEFAULT_WG); otherwise G =
+ * workgroups, 1 .. ATC_ADV_MAX_WG.  No atomics: the same inputs and the same G give the same bits on every run.
+ * NUMERICAL LIMIT.  S and S2 are plain float64 moments: the variance loses accuracy as |mean| / std approaches 1e7 (the difference
+ * S2 - S * mean cancels about 2 log10(|mean| / std) of float64's 16 digits).  Advantages are nowhere near that.
+ * ATC_ERR_ARG, in this order: a NULL among s, adv, g, out, out->stats, out->scratch; R < 1; eps not finite or < 0; workgroups outside
+ * 0 .. ATC_ADV_MAX_WG; an output sharing a byte with another array (out_adv == adv excepted).
+ * Counted by atc_adv_normalise_launch_counts only: one slot, one count per CALL. */
+#define ATC_ADV_TILE 256
+#define ATC_ADV_MAX_WG 1024
+#define ATC_ADV_DEFAULT_WG 256
+#define ATC_ADV_STATS 4
+#define ATC_ADV_STAT_N 0       /* participating rows */
+#define ATC_ADV_STAT_MEAN 1    /* shift: the mean, rounded to float32 */
+#define ATC_ADV_STAT_SCALE 2   /* scale: 1 / (std + eps), rounded to float32 */
+#define ATC_ADV_STAT_STD 3     /* the standard deviation, rounded to float32 */
+typedef struct atc_adv_norm {
+    float    eps;         /* >= 0, finite */
+    int32_t  workgroups;  /* 0: the library's choice; else G = 1 .. ATC_ADV_MAX_WG */
+} atc_adv_norm_t;
+typedef struct atc_adv_norm_out {
+    float*  out_adv;   /* [R] nullable; may be adv */
+    float*  stats;     /* [ATC_ADV_STATS] required */
+    double* scratch;   /* [G][3] required */
+} atc_adv_norm_out_t;
+int atc_adv_normalise(const atc_scenario_t* s, int R, const float* adv /* [R] */, const uint8_t* mask /* nullable [R] */,
+                      const atc_adv_norm_t* g, const atc_adv_norm_out_t* out, void* stream);
+enum { ATC_ADV_NORMALISE_LAUNCH_SLOTS = 1 };
+int atc_adv_normalise_launch_counts(uint64_t* out, int n);
+
+/* ADAM STEP (extension): PPO2's optimiser step on one or two packed tensors (the policy and the critic) in ONE launch of one workgroup —
+ * the global gradient-norm clip over both, the entropy term on log_std, and Adam.  `s` names the device only.
+ * EFFECTIVE GRADIENT of word i of tensor k, in float64:
+ *     ge = (double)grad_scale * (double)grad[i] + (add_first <= i < add_first + add_count ? (double)add_value : 0)
+ * grad_scale is vf_coef for the critic.  The add window carries the entropy bonus: the entropy of the diagonal Gaussian is sum log_std + a
+ * constant, so -ent_coef * H adds exactly -ent_coef to each of the three log_std words (add_first = their offset, add_count = 3,
+ * add_value = -ent_coef).
+ * THE WORKGROUP.  ATC_ADAM_BLOCK = 1 024 lanes over the concatenated index j (tensor 0's words, then tensor 1's).  Lane l adds ge * ge over
+ * j = l, l + 1024, ... in float64; lane 0 adds the 1 024 sums in lane order; norm = sqrt(total);
+ *     coef = (max_norm > 0 and max_norm < inf) ? min(1, max_norm / (norm + 1e-6)) : 1          (torch.nn.utils.clip_grad_norm_'s rule)
+ * then every word, in float64, each stored word rounded to float32 exactly once, with c1 = 1 - beta1^step and c2 = 1 - beta2^step made on
+ * the host in double:
+ *     gc = ge * coef
+ *     m' = (float)(beta1 * m + (1 - beta1) * gc)
+ *     v' = (float)(beta2 * v + ((1 - beta2) * gc) * gc)
+ *     w' = (float)(w - (lr / c1) * (m' / (sqrt(v') / sqrt(c2) + eps)))          with the ROUNDED m' and v' that are stored
+ * — torch.optim.Adam's step (no weight decay, no amsgrad) in its operation order.  No product is fused with a sum.  Float64 with one
+ * rounding per stored word makes the result independent of how float32 division and square root are lowered.
+ * NON-FINITE GRADIENTS.  If norm is not finite, nothing is written to w, m or v.
+ * stats [ATC_ADAM_STATS] = {(float)norm, (float)coef (0 where skipped), skipped (0 / 1), (float)step}.
+ * ATC_ERR_ARG, in this order: a NULL among s, t, g, stats; n_tensors not 1 or 2; per tensor a NULL among w, grad, m, v; words outside
+ * 1 .. ATC_ADAM_MAX_WORDS; add_count < 0, or add_count > 0 with the window outside the tensor; grad_scale or add_value not finite;
+ * step < 1; lr, eps or a beta not finite, lr < 0, eps < 0, a beta outside [0, 1); max_norm a NaN; any two of w, grad, m, v of both
+ * tensors and stats sharing a byte.
+ * Counted by atc_adam_step_launch_counts only: slot = n_tensors - 1. */
+#define ATC_ADAM_BLOCK 1024
+#define ATC_ADAM_MAX_WORDS 65536
+#define ATC_ADAM_STATS 4
+#define ATC_ADAM_STAT_NORM 0      /* the norm of the effective gradient over all tensors */
+#define ATC_ADAM_STAT_COEF 1      /* the clip coefficient applied (1: not clipped) */
+#define ATC_ADAM_STAT_SKIPPED 2   /* 1 where the norm was not finite and nothing was written */
+#define ATC_ADAM_STAT_STEP 3      /* step, as passed */
+typedef struct atc_adam_tensor {
+    float*       w;            /* [words] updated in place */
+    const float* grad;         /* [words] */
+    float*       m;            /* [words] first moment, updated in place */
+    float*       v;            /* [words] second moment, updated in place */
+    int32_t      words;        /* 1 .. ATC_ADAM_MAX_WORDS */
+    float        grad_scale;
+    int32_t      add_first;
+    int32_t      add_count;    /* 0: no window */
+    float        add_value;
+} atc_adam_tensor_t;
+typedef struct atc_adam {
+    double  lr;
+    double  beta1;
+    double  beta2;
+    double  eps;
+    double  max_norm;   /* <= 0 or +inf: no clip */
+    int32_t step;       /* >= 1 */
+} atc_adam_t;
+int atc_adam_step(const atc_scenario_t* s, int n_tensors /* 1 or 2 */, const atc_adam_tensor_t* t /* [n_tensors] */, const atc_adam_t* g,
+                  float* stats /* [ATC_ADAM_STATS] */, void* stream);
+enum { ATC_ADAM_STEP_LAUNCH_SLOTS = 2 };
+int atc_adam_step_launch_counts(uint64_t* out, int n);
+
 #ifdef __cplusplus
 }
 #endif

@@ -45,6 +45,9 @@ def main():
     bad = [n for n in shared if a[n] != b[n]]
     for n in bad:
         print("DIFFERS %s (%d vs %d instructions)" % (n, len(a[n]), len(b[n])))
+    for tag, x, y in (("ONLY IN A", a, b), ("ONLY IN B", b, a)):   # a kernel one build adds (k_adv_moments, k_adv_apply, k_adam_step over their parent)
+        for n in sorted(n for n in x if n not in y and (pat is None or pat.search(n))):
+            print("%s %s (%d instructions)" % (tag, n, len(x[n])))
     print("%d shared symbols compared (trailing padding / s_nop ignored), %d differ; only in a: %d, only in b: %d"
           % (len(shared), len(bad), len([n for n in a if n not in b]), len([n for n in b if n not in a])))
     return 1 if bad else 0
