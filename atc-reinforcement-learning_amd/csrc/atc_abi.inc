@@ -120,6 +120,7 @@ int atc_scenario_create(const float* blob_host, size_t n_words, int device, atc_
         if (hipDeviceGetAttribute(&optin, hipDeviceAttributeSharedMemPerBlockOptin, device) == hipSuccess && optin > s->max_lds) s->max_lds = optin;
         (void)hipGetLastError();
     }
+    s->cu_lds = (int)std::max<size_t>(prop.maxSharedMemoryPerMultiProcessor, (size_t)s->max_lds);
     e = hipMalloc(&s->d_blob, n_words * sizeof(float));
     if (e != hipSuccess) {
         delete s;

@@ -45,6 +45,7 @@ struct atc_scenario {
     LdsTab lt;                 // ... and the kernel argument that describes it (src == null: none)
     size_t lds_tab_bytes;
     int max_lds;               // the device's LDS bytes per workgroup
+    int cu_lds;                // ... and per CU (what the workgroups resident on a CU share)
 };
 
 static thread_local char g_err[512] = "";
@@ -1826,24 +1827,82 @@ static bool fill_prefetch_enabled() {
     static const bool on = [] { const char* e = getenv("ATC_NO_FILL_PREFETCH"); return !(e && *e && strcmp(e, "0") != 0); }();
     return on;
 }
+// Residency cap of the same launches (profiles/step_resident_ab.txt): the kernel's registers let a CU hold 7
+// workgroups, by estimate more than the memory system needs in flight, at about half a workgroup lifetime lost at either end.  A cap
+// of k workgroups per CU is made with LDS the kernel never touches: the launch asks for so much dynamic LDS — padding BEHIND the obs
+// transpose stage, the only LDS these forms use, so no offset in the kernel moves — that the CU's LDS holds exactly k workgroups
+// (the largest multiple of the allocation granule that is <= cu_lds / k).  The runtime's occupancy for the padded size must confirm k;
+// if it does not, the launch stays unpadded.  Only a grid of more than k workgroups per CU is padded: a smaller one fits either way.
+//   kStepResident<W>: the shipped cap per lane-group width (0 = none), chosen by measurement — and the measurement says none: 6 is
+//   level with the registers' 7, 5 costs 3 % and 4 costs 9 % at 65 536 x 16, the same order at W = 8 and at four times the envs (the
+//   front and the tail of the launch do get shorter, the streaming body loses more).  ATC_STEP_RESIDENT=<k> in the
+//   environment (developer knob, read once per process: the sweep and tests/test_step_resident.py) forces k = 1..8 for every width;
+//   0, or a k at or above what the registers allow, means no padding.
 template <int W>
-static int fill_prefetch_resident(const atc_scenario* s, int* resident) {
-    static thread_local int cached_for = -1, cached = 0;
+constexpr int kStepResident = 0;
+constexpr int kLdsGranule = 1280;   // gfx950 allocates LDS in granules of 320 dwords
+static int step_resident_knob() {   // -1: unset
+    static const int k = [] {
+        const char* e = getenv("ATC_STEP_RESIDENT");
+        if (!e || !*e) return -1;
+        const int v = atoi(e);
+        return v < 0 ? 0 : v > 8 ? 8 : v;
+    }();
+    return k;
+}
+struct StepResidency {
+    int per_cu;   // workgroups a CU holds at once in a launch of more than per_cu * n_cu workgroups
+    size_t pad;   // dynamic LDS bytes such a launch requests beyond lds_bytes() (0: residency is what the registers allow)
+};
+template <int W>
+static int step_residency(const atc_scenario* s, StepResidency* out) {   // (asked once per thread, instantiation and device)
+    static thread_local int cached_for = -1;
+    static thread_local StepResidency cached = {0, 0};
     if (cached_for != s->device) {
-        int per_cu = 0;
-        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(&k_step<W, false, true, true>), kBlock,
-                                                             lds_bytes(s, W >= 32, true)));
-        cached = (per_cu * s->n_cu) & ~7;
+        const void* fn = reinterpret_cast<const void*>(&k_step<W, false, true, true>);
+        const size_t base = lds_bytes(s, W >= 32, true);
+        int free_wgs = 0;
+        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&free_wgs, fn, kBlock, base));
+        StepResidency r = {free_wgs, 0};
+        const int cap = step_resident_knob() >= 0 ? step_resident_knob() : kStepResident<W>;
+        if (cap >= 1 && cap < free_wgs) {
+            const size_t want = (size_t)(s->cu_lds / cap) / kLdsGranule * kLdsGranule;
+            int capped = 0;
+            if (want > base && want <= (size_t)s->max_lds &&   // (a cap of 3 or lower needs more than 48 KB: the launch raises the attribute)
+                (want <= 48 * 1024 || hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, s->max_lds) == hipSuccess) &&
+                hipOccupancyMaxActiveBlocksPerMultiprocessor(&capped, fn, kBlock, want) == hipSuccess && capped == cap)
+                r = StepResidency{cap, want - base};
+            (void)hipGetLastError();
+        }
+        cached = r;
         cached_for = s->device;
     }
-    *resident = cached;
+    *out = cached;
+    return ATC_OK;
+}
+template <int W>
+static int fill_prefetch_resident(const atc_scenario* s, int* resident) {
+    StepResidency r;
+    if (const int rc = step_residency<W>(s, &r)) return rc;
+    *resident = (r.per_cu * s->n_cu) & ~7;
     return ATC_OK;
 }
 
 template <int W, bool FULL, bool ONE, bool ALLV, bool LAT = false, bool LDSG = false>
 static int launch_step2(const atc_scenario* s, int B, int N, int T, int hold, const atc_state_t* st, const float* actions,
                         const atc_out_t* out, const atc_params_t* p, hipStream_t stream) {
-    const size_t lds = lds_bytes(s, W >= 32, true) + (LDSG ? s->lds_tab_bytes : 0);
+    size_t lds = lds_bytes(s, W >= 32, true) + (LDSG ? s->lds_tab_bytes : 0);
+    const int grid = step_grid(B, W);
+    int pf_stride = 0;
+    if constexpr (ATC_FILL_PREFETCH(W, FULL, ONE, ALLV)) {
+        StepResidency r;
+        if (const int rc = step_residency<W>(s, &r)) return rc;
+        if ((long long)grid > (long long)r.per_cu * s->n_cu) lds += r.pad;   // (the residency cap: see step_residency)
+        if (fill_prefetch_enabled()) {
+            pf_stride = (r.per_cu * s->n_cu) & ~7;
+            if (grid <= pf_stride) pf_stride = 0;
+        }
+    }
     if (lds > 48 * 1024) {   // (once per device and instantiation: the attribute sticks)
         static thread_local int raised_for = -1;
         if (raised_for != s->device) {
@@ -1852,16 +1911,8 @@ static int launch_step2(const atc_scenario* s, int B, int N, int T, int hold, co
             raised_for = s->device;
         }
     }
-    const int grid = step_grid(B, W);
     LdsTab lt = s->lt;
     if (!LDSG) lt.src = nullptr;
-    int pf_stride = 0;
-    if constexpr (ATC_FILL_PREFETCH(W, FULL, ONE, ALLV)) {
-        if (fill_prefetch_enabled()) {
-            if (const int rc = fill_prefetch_resident<W>(s, &pf_stride)) return rc;
-            if (grid <= pf_stride) pf_stride = 0;
-        }
-    }
     hipLaunchKernelGGL((k_step<W, FULL, ONE, ALLV, LAT, LDSG>), dim3(grid), dim3(kBlock), lds, stream, s->d_blob, s->off_grid, B, N, T, hold, *st, actions, *out, *p, derive(*p, s, scan_horizon<W, FULL, ONE>()), inline_action(), lt, pf_stride);
     HIP_TRY(hipGetLastError());
     constexpr int form = LDSG ? ATC_LF_LDSG : LAT ? ATC_LF_LAT : FULL ? (ONE ? ATC_LF_FULL_ONE : ATC_LF_FULL_MULTI)

@@ -501,7 +501,9 @@ int atc_skip_launch_counts(uint64_t* out, int n);
  * into the L2 that workgroup will read them from.  Results do not depend on it.  *resident = the device's resident workgroups for
  * that kernel (the runtime's occupancy x CUs, rounded down to a multiple of 8; 0 where the form does not apply), *stride = what an
  * atc_step of B x N passes to the kernel: `resident` when the launch has more workgroups (B * N / 256) than that, else 0 (off) —
- * and 0 always with ATC_NO_FILL_PREFETCH set in the environment (developer knob, read once per process).  Host side only. */
+ * and 0 always with ATC_NO_FILL_PREFETCH set in the environment (developer knob, read once per process).  With a residency cap
+ * (ATC_STEP_RESIDENT=<k> in the environment, developer knob, read once per process; the library ships none) `resident` is the
+ * capped figure, k x CUs rounded down likewise, which is also the stride such a launch uses.  Host side only. */
 int atc_fill_prefetch_info(const atc_scenario_t* s, int B, int N, int* resident, int* stride);
 
 /* Uploads a compiled scenario blob (host pointer, n_words floats) to `device`.
