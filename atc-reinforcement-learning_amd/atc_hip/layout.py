@@ -163,6 +163,10 @@ ADAM_MAX_WORDS = 65536
 ADAM_STATS = 4
 ADAM_STAT_NORM, ADAM_STAT_COEF, ADAM_STAT_SKIPPED, ADAM_STAT_STEP = range(4)
 ADAM_STEP_LAUNCH_SLOTS = 2
+# decisions of the packed policy outside a rollout (include/atc_step.h: atc_policy_forward): at most POLICY_FWD_MAX_SAMPLES draws per row in one
+# call; its record counts calls by K in (0, 1, 2, 4)
+POLICY_FWD_MAX_SAMPLES = 64
+POLICY_FORWARD_LAUNCH_SLOTS = 4
 
 
 def policy_in(traffic=0):

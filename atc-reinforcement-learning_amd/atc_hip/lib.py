@@ -205,6 +205,23 @@ class AtcAdam(C.Structure):
     _fields_ = [("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double), ("max_norm", C.c_double), ("step", C.c_int32)]
 
 
+POLICY_FWD_FIELDS = ("traffic_k", "samples", "rows_per_decision", "flags", "seed", "decision0", "reserved")
+
+
+class AtcPolicyFwd(C.Structure):
+    """atc_policy_fwd_t"""
+    _fields_ = [("traffic_k", C.c_int32), ("samples", C.c_int32), ("rows_per_decision", C.c_int32), ("flags", C.c_uint32), ("seed", C.c_uint64),
+                ("decision0", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+POLICY_FWD_OUT_FIELDS = ("mean", "action", "flown", "logp")
+
+
+class AtcPolicyFwdOut(C.Structure):
+    """atc_policy_fwd_out_t"""
+    _fields_ = [(n, C.c_void_p) for n in POLICY_FWD_OUT_FIELDS]
+
+
 class AtcStepCall(C.Structure):
     """atc_step_call_t"""
     _fields_ = [("s", C.c_void_p), ("B", C.c_int32), ("N", C.c_int32), ("st", C.POINTER(AtcState)), ("actions", C.c_void_p),
@@ -225,7 +242,7 @@ EXPORTS = ("atc_abi_version", "atc_last_error", "atc_launch_counts", "atc_host_m
            "atc_gae_boot_launch_counts", "atc_ppo_policy_grad", "atc_ppo_policy_grad_launch_counts",
            "atc_value_forward", "atc_value_forward_launch_counts", "atc_ppo_value_grad", "atc_ppo_value_grad_launch_counts",
            "atc_policy_eval", "atc_policy_eval_launch_counts", "atc_adv_normalise", "atc_adv_normalise_launch_counts",
-           "atc_adam_step", "atc_adam_step_launch_counts")
+           "atc_adam_step", "atc_adam_step_launch_counts", "atc_policy_forward", "atc_policy_forward_launch_counts")
 
 def load():
     """Loads libatcstep.so; raises (never falls back) when it has not been built."""
@@ -290,6 +307,7 @@ def load():
     lib.atc_ppo_value_grad.argtypes = [vp, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, C.POINTER(AtcPpoValueGrad), C.POINTER(AtcPpoValueGradOut), vp]
     lib.atc_adv_normalise.argtypes = [vp, ci, vp, vp, C.POINTER(AtcAdvNorm), C.POINTER(AtcAdvNormOut), vp]
     lib.atc_adam_step.argtypes = [vp, ci, C.POINTER(AtcAdamTensor), C.POINTER(AtcAdam), vp, vp]
+    lib.atc_policy_forward.argtypes = [vp, ci, vp, vp, vp, C.POINTER(AtcPolicyFwd), C.POINTER(AtcPolicyFwdOut), vp]
     for getter in LAUNCH_RECORDS:
         getattr(lib, getter).argtypes = [C.POINTER(C.c_uint64), ci]
     for name in EXPORTS:
@@ -362,6 +380,7 @@ LAUNCH_RECORDS = {
     "atc_policy_eval_launch_counts": (L.POLICY_EVAL_LAUNCH_SLOTS, _width_k0),
     "atc_adv_normalise_launch_counts": (L.ADV_NORMALISE_LAUNCH_SLOTS, "adv_normalise"),
     "atc_adam_step_launch_counts": (L.ADAM_STEP_LAUNCH_SLOTS, _tensors),
+    "atc_policy_forward_launch_counts": (L.POLICY_FORWARD_LAUNCH_SLOTS, _traffic_k0),
 }
 
 
@@ -503,6 +522,12 @@ def adam_step_launch_counts():
     """Calls of the optimiser step (atc_adam_step; one launch each) made by the calling thread so far, by the number of tensors: {1: n, 2: n},
     zero counts left out.  Separate from the other launch records."""
     return _counts("atc_adam_step_launch_counts")
+
+
+def policy_forward_launch_counts():
+    """Calls of the stand-alone policy forward (atc_policy_forward; one launch each) made by the calling thread so far, by records per
+    aircraft (0: the ten-word policy): {0: n, 4: n, ...}, zero counts left out.  Separate from the other launch records."""
+    return _counts("atc_policy_forward_launch_counts")
 
 
 def lookahead_set_mapping(candidates_per_workgroup=0):

@@ -61,6 +61,48 @@ def from_torch(module, log_std, device=None, traffic=0):
     return pack_mlp(lin[0].weight, lin[0].bias, lin[1].weight, lin[1].bias, lin[2].weight, lin[2].bias, log_std, device=device, traffic=traffic)
 
 
+def traffic_of(words):
+    """K of a packed policy of `words` floats (AtcVecEnv.policy_forward, atc_hip.ppo.update find it so); ValueError for any other size"""
+    for K in (0,) + L.POLICY_TRAFFIC_K:
+        if int(words) == L.policy_words(K):
+            return K
+    raise ValueError("weights must hold %s words (atc_hip.policy.pack_mlp with traffic = 0, 1, 2, 4), got %d" % (
+        ", ".join(str(L.policy_words(K)) for K in (0,) + L.POLICY_TRAFFIC_K), int(words)))
+
+
+def unpack(w, traffic=None):
+    """{name: view} of the seven parts W1 .. log_std of the packed array `w` (a tensor or an array of policy_words(K) elements; K from its
+    size, or `traffic`, which must agree), each in its shape [out, in].  Views: writing to one writes to `w`."""
+    flat = w.reshape(-1)
+    n = int(flat.shape[0])
+    K = traffic_of(n) if traffic is None else int(traffic)
+    if n != L.policy_words(K):
+        raise ValueError("a policy with traffic=%d has %d words, got %d" % (K, L.policy_words(K), n))
+    out = {}
+    for name, (at, shape) in offsets(K).items():
+        size = 1
+        for s in shape:
+            size *= s
+        out[name] = flat[at:at + size].reshape(shape)
+    return out
+
+
+def to_torch(w, traffic=None):
+    """(nn.Sequential(Linear(10 + 7 K, 64), Tanh(), Linear(64, 64), Tanh(), Linear(64, 3)), log_std) holding COPIES of the packed policy `w`,
+    float32, on w's device: the inverse of from_torch — from_torch(*to_torch(w), traffic=K) gives back `w` bit for bit."""
+    import torch
+    from torch import nn
+    p = unpack(torch.as_tensor(w).detach(), traffic)
+    n_in = int(p["W1"].shape[1])
+    net = nn.Sequential(nn.Linear(n_in, L.POLICY_HIDDEN), nn.Tanh(), nn.Linear(L.POLICY_HIDDEN, L.POLICY_HIDDEN), nn.Tanh(),
+                        nn.Linear(L.POLICY_HIDDEN, L.ACT_DIM)).to(device=p["W1"].device, dtype=torch.float32)
+    with torch.no_grad():
+        for lin, (wn, bn) in zip(list(net)[0::2], (("W1", "b1"), ("W2", "b2"), ("W3", "b3"))):
+            lin.weight.copy_(p[wn])
+            lin.bias.copy_(p[bn])
+    return net, p["log_std"].to(torch.float32).clone()
+
+
 def input_rows(obs_rows, traffic_records):
     """The rows a decision of rollout_policy_traffic saw, [..., N, 10 + 7 K]: stored observation rows [..., N, 10] (obs0, or obs of the step
     before the decision; [..., N * 10] is taken as well) next to words 0..6 of the stored records [..., N, K, 8].  Tensors or arrays; a

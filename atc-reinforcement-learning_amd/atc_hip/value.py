@@ -47,6 +47,48 @@ def pack_mlp(W1, b1, W2, b2, W3, b3, device=None, traffic=0):
     return flat
 
 
+def traffic_of(words):
+    """K of a packed critic of `words` floats; ValueError for any other size"""
+    for K in (0,) + L.POLICY_TRAFFIC_K:
+        if int(words) == L.value_words(K):
+            return K
+    raise ValueError("weights must hold %s words (atc_hip.value.pack_mlp with traffic = 0, 1, 2, 4), got %d" % (
+        ", ".join(str(L.value_words(K)) for K in (0,) + L.POLICY_TRAFFIC_K), int(words)))
+
+
+def unpack(w, traffic=None):
+    """{name: view} of the six parts W1 .. b3 of the packed critic `w` (a tensor or an array of value_words(K) elements; K from its size, or
+    `traffic`, which must agree), each in its shape [out, in].  Views: writing to one writes to `w`."""
+    flat = w.reshape(-1)
+    n = int(flat.shape[0])
+    K = traffic_of(n) if traffic is None else int(traffic)
+    if n != L.value_words(K):
+        raise ValueError("a critic with traffic=%d has %d words, got %d" % (K, L.value_words(K), n))
+    out = {}
+    for name, (at, shape) in offsets(K).items():
+        size = 1
+        for s in shape:
+            size *= s
+        out[name] = flat[at:at + size].reshape(shape)
+    return out
+
+
+def to_torch(w, traffic=None):
+    """nn.Sequential(Linear(10 + 7 K, 64), Tanh(), Linear(64, 64), Tanh(), Linear(64, 1)) holding COPIES of the packed critic `w`, float32, on
+    w's device: the inverse of from_torch — from_torch(to_torch(w), traffic=K) gives back `w` bit for bit."""
+    import torch
+    from torch import nn
+    p = unpack(torch.as_tensor(w).detach(), traffic)
+    n_in = int(p["W1"].shape[1])
+    net = nn.Sequential(nn.Linear(n_in, L.POLICY_HIDDEN), nn.Tanh(), nn.Linear(L.POLICY_HIDDEN, L.POLICY_HIDDEN), nn.Tanh(),
+                        nn.Linear(L.POLICY_HIDDEN, 1)).to(device=p["W1"].device, dtype=torch.float32)
+    with torch.no_grad():
+        for lin, (wn, bn) in zip(list(net)[0::2], (("W1", "b1"), ("W2", "b2"), ("W3", "b3"))):
+            lin.weight.copy_(p[wn])
+            lin.bias.copy_(p[bn])
+    return net
+
+
 def from_torch(module, device=None, traffic=0):
     """pack_mlp of an nn.Sequential(Linear(10 + 7 traffic, 64), Tanh(), Linear(64, 64), Tanh(), Linear(64, 1)) — biases required."""
     from torch import nn

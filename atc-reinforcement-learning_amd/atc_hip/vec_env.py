@@ -12,6 +12,7 @@ import numpy as np
 
 from . import layout as L
 from . import lib as _lib
+from . import policy
 
 
 def auto_grid_cell(num_envs, num_aircraft):
@@ -1183,6 +1184,101 @@ class AtcVecEnv:
                 _lib.check(rc)
         self._keep_value = (weights, rows, out)      # they outlive the launch
         return out
+
+    POLICY_FORWARD_OUTPUTS = ("mean", "action", "flown", "logp")
+
+    def policy_forward(self, weights, obs_rows, *, traffic=None, samples=1, rows_per_decision=None, seed=0, decision0=0, deterministic=False,
+                       outputs=("flown", "logp"), out=None):
+        """The decisions of the packed policy on given rows, outside a rollout, in one launch on this env's current stream
+        (atc_policy_forward, include/atc_step.h): the MLP once per row in the rollout's arithmetic, then `samples` draws per row.
+        weights: the L.policy_words(K)-word tensor of atc_hip.policy.pack_mlp — K is found from its size; obs_rows [..., 10]: the own
+        observation rows; traffic [..., K, 8] for K > 0 (words 0..6 of each record widen the row; env.traffic and the rollout's stored
+        records are taken as they are), None for K = 0.  Contiguous float32 tensors on this env's device; nothing is converted.
+        Sample s of row r is drawn with the rollout's key of decision = decision0 + s * ceil(R / P) + r // P and aircraft r % P, with
+        P = rows_per_decision (default: all R rows are one decision): with P = B * N the rows [D, B, N] a rollout's decisions saw get the
+        rollout's draws.  deterministic=True: action = mean, logp = 0, samples must be 1.
+        Returns a dict of the names in `outputs`, any of "mean" [..., 3], "action" [S, ..., 3] (the UNCLAMPED sample), "flown" [S, ..., 3]
+        (its clamp to [-1, 1]: what step / step_skip / lookahead / branch take) and "logp" [S, ...].  out: a dict of those tensors — its
+        keys are the outputs, and nothing is allocated."""
+        torch = self.torch
+        f32 = (torch.float32,)
+        need = AtcVecEnv._on_device.__get__(self)
+        if not (torch.is_tensor(weights) and weights.dim() >= 1):
+            raise ValueError("weights must be the packed float32 tensor of atc_hip.policy.pack_mlp")
+        K = policy.traffic_of(weights.numel())
+        need(weights, f32, (L.policy_words(K),), text="weights must be the contiguous float32 tensor of %r words (atc_hip.policy.pack_mlp) on %s", elements=True)
+        if not (torch.is_tensor(obs_rows) and obs_rows.dim() >= 1 and int(obs_rows.shape[-1]) == L.OBS_DIM and obs_rows.numel() >= L.OBS_DIM):
+            raise ValueError("obs_rows must be [..., %d] with at least one row" % L.OBS_DIM)
+        lead = tuple(obs_rows.shape[:-1])
+        R = obs_rows.numel() // L.OBS_DIM
+        if R > 2 ** 31 - 1:
+            raise ValueError("obs_rows holds more rows than one call covers (2^31 - 1)")
+        need(obs_rows, f32, (R, L.OBS_DIM), "obs_rows", elements=True)
+        if K:
+            if not (torch.is_tensor(traffic) and traffic.dim() >= 2 and tuple(traffic.shape[-2:]) == (K, L.TRAFFIC_DIM)):
+                raise ValueError("traffic must be [..., %d, %d]: these weights are a policy that sees %d records per aircraft" % (K, L.TRAFFIC_DIM, K))
+            need(traffic, f32, (R, K, L.TRAFFIC_DIM), "traffic", elements=True)
+        elif traffic is not None:
+            raise ValueError("traffic must be None: these weights are the ten-word policy")
+        S = int(samples)
+        if not 1 <= S <= L.POLICY_FWD_MAX_SAMPLES:
+            raise ValueError("1 <= samples <= %d" % L.POLICY_FWD_MAX_SAMPLES)
+        if deterministic and S != 1:
+            raise ValueError("deterministic=True draws nothing: samples must be 1")
+        P = R if rows_per_decision is None else int(rows_per_decision)
+        if not 1 <= P <= R:
+            raise ValueError("1 <= rows_per_decision <= the number of rows (%d)" % R)
+        want = {"mean": (f32, lead + (L.ACT_DIM,)), "action": (f32, (S,) + lead + (L.ACT_DIM,)), "flown": (f32, (S,) + lead + (L.ACT_DIM,)),
+                "logp": (f32, (S,) + lead)}
+        if out is None:
+            names = (outputs,) if isinstance(outputs, str) else tuple(outputs)
+            if not names or any(n not in want for n in names):
+                raise ValueError("outputs must name at least one of %s" % ", ".join(want))
+            res = {n: torch.empty(want[n][1], dtype=torch.float32, device=self.device) for n in names}
+        else:
+            if not isinstance(out, dict) or not out:
+                raise ValueError("out must be a dict with any of %s" % ", ".join(want))
+            res = AtcVecEnv._results(self, out, want, set(), "out must be a dict with any of %s" % ", ".join(want))
+        f = _lib.AtcPolicyFwd(K, S, P, L.POLICY_DETERMINISTIC if deterministic else 0, int(seed) & (2 ** 64 - 1), int(decision0) & 0xffffffff, 0)
+        o = _lib.AtcPolicyFwdOut(*[res[n].data_ptr() if n in res else None for n in _lib.POLICY_FWD_OUT_FIELDS])
+        fn = self._lib.atc_policy_forward
+        with torch.cuda.device(self.device):
+            rc = fn(self.sector.handle, R, weights.data_ptr(), obs_rows.data_ptr(), traffic.data_ptr() if K else None, C.byref(f), C.byref(o),
+                    self._stream())
+            if rc:
+                _lib.check(rc)
+        self._keep_policy_forward = (weights, obs_rows, traffic, res)      # they outlive the launch
+        return res
+
+    def act(self, weights, *, samples=None, seed=0, decision=0, deterministic=False, out=None):
+        """The packed policy's decision for the state the env is in NOW (policy_forward on env.obs and, for a policy that sees traffic,
+        env.traffic — the env must have been made with that traffic=K): what rollout_policy(weights, hold, hold=hold, seed=seed,
+        decision0=decision) would fly from here.  Returns flown, [B, N, 3] — or [M, B, N, 3] with samples=M, M candidates per aircraft —:
+        exactly what step / step_skip / lookahead / branch take.  out: that tensor, and nothing is allocated."""
+        torch = self.torch
+        AtcVecEnv._refuse_discrete(self)
+        if not torch.is_tensor(weights):
+            raise ValueError("weights must be the packed float32 tensor of atc_hip.policy.pack_mlp")
+        K = policy.traffic_of(weights.numel())
+        if K != self.traffic_k:
+            raise ValueError("these weights are a policy that sees %d traffic records per aircraft, this env observes %d (AtcVecEnv(traffic=%d))" % (
+                K, self.traffic_k, K))
+        B, N = self.B, self.N
+        S = 1 if samples is None else int(samples)
+        shape = (B, N, L.ACT_DIM) if samples is None else (S, B, N, L.ACT_DIM)
+        if out is not None:
+            AtcVecEnv._on_device(self, out, (torch.float32,), shape, "out")
+        rows = self.obs.view(B, N, L.OBS_DIM)
+        if not rows.is_cuda:      # (a host-mapped env's observation lives in pinned host memory)
+            rows = rows.to(self.device)
+        tr = self.traffic
+        if K and not tr.is_cuda:
+            tr = tr.to(self.device)
+        res = AtcVecEnv.policy_forward(self, weights, rows, traffic=tr if K else None, samples=S, rows_per_decision=B * N, seed=seed,
+                                       decision0=decision, deterministic=deterministic,
+                                       out={"flown": (out if samples is not None else out.view((1,) + shape))} if out is not None else None,
+                                       outputs=("flown",))
+        return out if out is not None else (res["flown"] if samples is not None else res["flown"][0])
 
     def ppo_value_grad(self, weights, obs_rows, v_old, ret, *, traffic=None, mask=None, index=None, clip=0.2, workgroups=0, out=None):
         """The clipped PPO value loss and its gradient with respect to the packed critic in one call on this env's current stream

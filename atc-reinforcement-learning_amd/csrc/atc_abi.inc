@@ -34,6 +34,7 @@ int atc_ppo_value_grad_launch_counts(uint64_t* out, int n) { return copy_counts(
 int atc_policy_eval_launch_counts(uint64_t* out, int n) { return copy_counts(REC_POLICY_EVAL, out, n); }
 int atc_adv_normalise_launch_counts(uint64_t* out, int n) { return copy_counts(REC_ADV_NORMALISE, out, n); }
 int atc_adam_step_launch_counts(uint64_t* out, int n) { return copy_counts(REC_ADAM_STEP, out, n); }
+int atc_policy_forward_launch_counts(uint64_t* out, int n) { return copy_counts(REC_POLICY_FORWARD, out, n); }
 int atc_lookahead_set_mapping(int candidates_per_workgroup) {
     if (candidates_per_workgroup < 0 || candidates_per_workgroup > ATC_LOOKAHEAD_MAX_M) return fail_arg("candidates per workgroup must be 0 (the library's choice) .. 64");
     t_look_cpg = candidates_per_workgroup;
@@ -733,6 +734,48 @@ int atc_value_forward(const atc_scenario_t* s, int R, int traffic_k, const float
     });
     HIP_TRY(hipGetLastError());
     ++record(REC_VALUE_FORWARD)[K ? 1 + __builtin_ctz(K) : 0];
+    return ATC_OK;
+}
+
+// atc_policy_forward: the checks in the header's order, then k_policy_forward<K> on `stream`, one lane per row
+int atc_policy_forward(const atc_scenario_t* s, int R, const float* w, const float* obs_rows, const float* traffic, const atc_policy_fwd_t* f,
+                       const atc_policy_fwd_out_t* out, void* stream) {
+    if (const int rc = check_required({{s, "null pointer: s"}, {w, "null pointer: w (the policy's weights) is required"}, {obs_rows, "null pointer: obs_rows is required"},
+                                       {f, "null pointer: f (atc_policy_fwd_t) is required"}, {out, "null pointer: out (atc_policy_fwd_out_t) is required"}}))
+        return rc;
+    const int K = f->traffic_k;
+    if (K != 0 && K != 1 && K != 2 && K != 4) return fail_arg("f->traffic_k must be 0, 1, 2 or 4 (the ten-word policy, or a compiled list length)");
+    if (R < 1) return fail_arg("R (the number of rows) must be >= 1");
+    const int S = f->samples;
+    if (S < 1 || S > ATC_POLICY_FWD_MAX_SAMPLES) return fail_arg("f->samples must be 1 .. 64 (ATC_POLICY_FWD_MAX_SAMPLES)");
+    if (f->rows_per_decision < 0 || f->rows_per_decision > R) return fail_arg("f->rows_per_decision must be 1 .. R, or 0 for R");
+    if ((f->flags & ATC_POLICY_DETERMINISTIC) && S > 1) return fail_arg("ATC_POLICY_DETERMINISTIC draws nothing: f->samples must be 1");
+    if (f->flags & ~ATC_POLICY_DETERMINISTIC) return fail_arg("f->flags has unknown bits");
+    if (K > 0 && !traffic) return fail_arg("null pointer: traffic is required where f->traffic_k > 0");
+    if (K == 0 && traffic) return fail_arg("traffic must be NULL where f->traffic_k is 0 (the ten-word policy reads no records)");
+    if (!out->mean && !out->action && !out->flown && !out->logp) return fail_arg("null pointer: out names no output (mean, action, flown, logp)");
+    // no output may share memory with any array of the call (the inputs may share among themselves)
+    const uintptr_t r = (uintptr_t)R, sr = (uintptr_t)S * r;
+    const ByteRange outputs[4] = {{out->mean, r * 12u, "mean"}, {out->action, sr * 12u, "action"}, {out->flown, sr * 12u, "flown"}, {out->logp, sr * 4u, "logp"}};
+    const ByteRange inputs[3] = {{w, (uintptr_t)ATC_POLICY_TRAFFIC_WORDS(K) * 4u, "w"}, {obs_rows, r * (ATC_OBS_DIM * 4u), "obs_rows"},
+                                 {traffic, r * (uintptr_t)K * (ATC_TRAFFIC_DIM * 4u), "traffic"}};
+    for (int a = 0; a < 4; ++a) {
+        if (!outputs[a].ptr) continue;
+        for (int b = 0; b < 3 + a; ++b) {
+            const ByteRange pair[2] = {b < 3 ? inputs[b] : outputs[b - 3], outputs[a]};
+            if (const int rc = check_disjoint(pair, 2, {}, "no output of atc_policy_forward may share memory with another array")) return rc;
+        }
+    }
+    const uint32_t P = f->rows_per_decision ? (uint32_t)f->rows_per_decision : (uint32_t)R;
+    const PolicyFwdDraw dr = {f->seed, f->decision0, (uint32_t)(((unsigned long long)R + P - 1u) / P), P, S, f->flags};
+    const unsigned blocks = (unsigned)(((long long)R + (kPolFwdBlock - 1)) / kPolFwdBlock);
+    with_traffic_k0(K, [&](auto kt) {
+        hipLaunchKernelGGL(k_policy_forward<decltype(kt)::value>, dim3(blocks), dim3(kPolFwdBlock), 0, (hipStream_t)stream, R, w, obs_rows, traffic, dr, out->mean,
+                           out->action, out->flown, out->logp);
+        return ATC_OK;
+    });
+    HIP_TRY(hipGetLastError());
+    ++record(REC_POLICY_FORWARD)[K ? 1 + __builtin_ctz(K) : 0];
     return ATC_OK;
 }
 

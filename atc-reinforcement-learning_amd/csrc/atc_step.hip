@@ -1770,6 +1770,7 @@ k_serve(const float* __restrict__ blob, int off_grid, atc_state_t st, atc_out_t 
 #include "atc_gae.inc"           // k_gae (atc_gae), k_gae_boot (atc_gae_boot)
 #include "atc_ppo_grad.inc"      // k_ppo_grad, k_ppo_grad_reduce (atc_ppo_policy_grad)
 #include "atc_value.inc"         // k_value_forward (atc_value_forward), k_ppo_value_grad, k_ppo_value_grad_reduce (atc_ppo_value_grad)
+#include "atc_policy_forward.inc"  // k_policy_forward (atc_policy_forward)
 #include "atc_ppo_update.inc"    // k_adv_moments, k_adv_apply (atc_adv_normalise), k_adam_step (atc_adam_step)
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -1799,17 +1800,17 @@ static size_t lds_bytes(const atc_scenario*, bool pair_scan, bool step_kernel = 
 // counters in one table — plain thread-local counters that nothing in the library reads back.  REC_STEP has a slot for each k_step
 // instantiation and one for k_serve starts; a record of 7 slots counts by lane-group width (slot = log2(W)); a record of one slot
 // counts its entry point's launches; REC_POLICY_TRAFFIC counts by width and list length (slot = 3 log2(W) + log2(K)), REC_POLICY_ENDS
-// and REC_POLICY_EVAL likewise with K = 0 in front (slot = 4 log2(W) + {0, 1, 2, 3}); REC_PPO_GRAD, REC_VALUE_FORWARD and REC_PPO_VALUE_GRAD count calls by K
+// and REC_POLICY_EVAL likewise with K = 0 in front (slot = 4 log2(W) + {0, 1, 2, 3}); REC_PPO_GRAD, REC_VALUE_FORWARD, REC_PPO_VALUE_GRAD and REC_POLICY_FORWARD count calls by K
 // (slot = {0, 1, 2, 3}); REC_ADV_NORMALISE counts calls in one slot and REC_ADAM_STEP by the number of tensors (slot = n_tensors - 1).  A call
 // moves its own record only.
-enum Record { REC_STEP, REC_SKIP, REC_TRAFFIC, REC_LOOKAHEAD, REC_PLAN, REC_PLAN_SAMPLED, REC_PLAN_DRAW, REC_PLAN_REFIT, REC_PLAN_SCORE, REC_BRANCH, REC_SELECT, REC_POLICY, REC_POLICY_TRAFFIC, REC_GAE, REC_POLICY_ENDS, REC_GAE_BOOT, REC_PPO_GRAD, REC_VALUE_FORWARD, REC_PPO_VALUE_GRAD, REC_POLICY_EVAL, REC_ADV_NORMALISE, REC_ADAM_STEP, REC_COUNT };
+enum Record { REC_STEP, REC_SKIP, REC_TRAFFIC, REC_LOOKAHEAD, REC_PLAN, REC_PLAN_SAMPLED, REC_PLAN_DRAW, REC_PLAN_REFIT, REC_PLAN_SCORE, REC_BRANCH, REC_SELECT, REC_POLICY, REC_POLICY_TRAFFIC, REC_GAE, REC_POLICY_ENDS, REC_GAE_BOOT, REC_PPO_GRAD, REC_VALUE_FORWARD, REC_PPO_VALUE_GRAD, REC_POLICY_EVAL, REC_ADV_NORMALISE, REC_ADAM_STEP, REC_POLICY_FORWARD, REC_COUNT };
 constexpr int kRecordSlots[REC_COUNT] = {ATC_LAUNCH_SLOTS, ATC_SKIP_LAUNCH_SLOTS, ATC_TRAFFIC_LAUNCH_SLOTS, ATC_LOOKAHEAD_LAUNCH_SLOTS, ATC_PLAN_LAUNCH_SLOTS,
                                          ATC_PLAN_SAMPLED_LAUNCH_SLOTS, ATC_PLAN_DRAW_LAUNCH_SLOTS, ATC_PLAN_REFIT_LAUNCH_SLOTS, ATC_PLAN_SCORE_LAUNCH_SLOTS,
                                          ATC_BRANCH_LAUNCH_SLOTS, ATC_SELECT_LAUNCH_SLOTS, ATC_ROLLOUT_POLICY_LAUNCH_SLOTS,
                                          ATC_ROLLOUT_POLICY_TRAFFIC_LAUNCH_SLOTS, ATC_GAE_LAUNCH_SLOTS, ATC_ROLLOUT_POLICY_ENDS_LAUNCH_SLOTS,
                                          ATC_GAE_BOOT_LAUNCH_SLOTS, ATC_PPO_GRAD_LAUNCH_SLOTS, ATC_VALUE_FORWARD_LAUNCH_SLOTS,
                                          ATC_PPO_VALUE_GRAD_LAUNCH_SLOTS, ATC_POLICY_EVAL_LAUNCH_SLOTS, ATC_ADV_NORMALISE_LAUNCH_SLOTS,
-                                         ATC_ADAM_STEP_LAUNCH_SLOTS};
+                                         ATC_ADAM_STEP_LAUNCH_SLOTS, ATC_POLICY_FORWARD_LAUNCH_SLOTS};
 constexpr int record_offset(int id) {
     int o = 0;
     for (int i = 0; i < id; ++i) o += kRecordSlots[i];

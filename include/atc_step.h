@@ -1545,6 +1545,56 @@ int atc_adam_step(const atc_scenario_t* s, int n_tensors /* 1 or 2 */, const atc
 enum { ATC_ADAM_STEP_LAUNCH_SLOTS = 2 };
 int atc_adam_step_launch_counts(uint64_t* out, int n);
 
+/* POLICY FORWARD (extension): the decisions of the packed policy on given rows, OUTSIDE a rollout — what deployment (observation ->
+ * decision -> step -> render), a planner that seeds its candidates from the policy, or any other consumer of a trained policy needs without
+ * restating the MLP.  The critic's atc_value_forward with the policy's head and its draw.  A pure function of its arrays: `s` names the
+ * device only; all pointers are device pointers.
+ * INPUT ROW: atc_ppo_policy_grad's — obs_rows[r][0..9], then words 0..6 of each of the K = traffic_k records traffic[r][k][0..7] (word 7 is
+ * not read): what atc_rollout_policy_traffic stores and what atc_observe_traffic writes, read in place.  w is the packed policy,
+ * ATC_POLICY_TRAFFIC_WORDS(K) floats.
+ * ARITHMETIC, in fp32: atc_rollout_policy's, in its operation order — layer 1 an fmaf chain over the inputs starting from the bias, summed in
+ * float64 where a wavefront (64 consecutive rows, row 0 first) holds an input above 4 in magnitude, or a NaN; layer 2 in four partial sums;
+ * mu_c = b3_c, then mu_c = fmaf(W3[c][j], h2_j, mu_c) for j = 0 .. 63.  The MLP is evaluated ONCE per row.  Then, for sample s = 0 .. S - 1
+ * of row r, with P = rows_per_decision (0 means R) and DS = ceil(R / P):
+ *
+ *     decision = decision0 + s * DS + r / P   (modulo 2^32);   i = r % P
+ *     key = mix64( mix64(seed ^ (u64)decision) ^ (u64)i );  z_c, u_c, a_c and logp as in atc_rollout_policy
+ *
+ * With S = 1 and P = B * N, the rows [D][B][N] that a rollout's decisions saw get exactly the rollout's keys; further samples continue the
+ * decision counter behind them, so no two samples of one call share a key.
+ * BIT EQUALITY WITH THE ROLLOUT holds for a row whose wavefront takes the same form of layer 1 here and there: the rollout's wavefront is 64
+ * consecutive lane slots of its launch, this call's is 64 consecutive rows.  Where the two may choose differently (an input above 4 in
+ * one's wavefront and not in the other's), the claim is the bars of tests/policy_ref.py, not bit equality.
+ * OUTPUTS, each nullable, at least one given: mean [R][3] = mu; action [S][R][3] = u, the UNCLAMPED sample (atc_policy_out_t.action);
+ * flown [S][R][3] = a, its clamp to [-1, 1], what a step is to be given (a NaN gives -1); logp [S][R].  ATC_POLICY_DETERMINISTIC: u = mu,
+ * logp = 0, no key is evaluated; S must be 1.
+ * ATC_ERR_ARG, in this order, atc_last_error() naming the argument: a NULL among s, w, obs_rows, f, out; traffic_k outside {0, 1, 2, 4};
+ * R < 1; samples outside 1 .. ATC_POLICY_FWD_MAX_SAMPLES, or rows_per_decision outside 0 .. R; ATC_POLICY_DETERMINISTIC with samples > 1;
+ * unknown flag bits; traffic NULL with traffic_k > 0, or given with traffic_k == 0; every output NULL; an output sharing a byte with any
+ * other array of the call — pointer values only, ranges that only touch are accepted.
+ * Counted by atc_policy_forward_launch_counts only: slot = {0, 1, 2, 3 for traffic_k = 0, 1, 2, 4}; one launch per call. */
+enum { ATC_POLICY_FWD_MAX_SAMPLES = 64 };
+typedef struct atc_policy_fwd {
+    int32_t  traffic_k;          /* K: 0, 1, 2 or 4 */
+    int32_t  samples;            /* S: 1 .. ATC_POLICY_FWD_MAX_SAMPLES */
+    int32_t  rows_per_decision;  /* P: 1 .. R; 0 means R */
+    uint32_t flags;              /* ATC_POLICY_DETERMINISTIC or 0 */
+    uint64_t seed;
+    uint32_t decision0;          /* number of the decision rows 0 .. P - 1 of sample 0 belong to */
+    uint32_t reserved;
+} atc_policy_fwd_t;
+typedef struct atc_policy_fwd_out {
+    float* mean;     /* [R][3]    nullable */
+    float* action;   /* [S][R][3] nullable: the UNCLAMPED sample u */
+    float* flown;    /* [S][R][3] nullable: fminf(fmaxf(u, -1), 1) */
+    float* logp;     /* [S][R]    nullable */
+} atc_policy_fwd_out_t;
+int atc_policy_forward(const atc_scenario_t* s, int R, const float* w /* [ATC_POLICY_TRAFFIC_WORDS(K)] */,
+                       const float* obs_rows /* [R][10] */, const float* traffic /* [R][K][8], with K > 0 */,
+                       const atc_policy_fwd_t* f, const atc_policy_fwd_out_t* out, void* stream);
+enum { ATC_POLICY_FORWARD_LAUNCH_SLOTS = 4 };
+int atc_policy_forward_launch_counts(uint64_t* out, int n);
+
 #ifdef __cplusplus
 }
 #endif
