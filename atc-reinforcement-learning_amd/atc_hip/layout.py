@@ -167,6 +167,9 @@ ADAM_STEP_LAUNCH_SLOTS = 2
 # call; its record counts calls by K in (0, 1, 2, 4)
 POLICY_FWD_MAX_SAMPLES = 64
 POLICY_FORWARD_LAUNCH_SLOTS = 4
+# candidates continued by the policy inside the launch (include/atc_step.h: atc_lookahead_policy): K, H and M are the drawn plans' (SKIP_MAX,
+# PLAN_MAX_H, SAMPLE_MAX_M); its own launch record (slot = log2(W))
+LOOKAHEAD_POLICY_LAUNCH_SLOTS = 7
 
 
 def policy_in(traffic=0):

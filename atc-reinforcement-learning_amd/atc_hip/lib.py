@@ -58,6 +58,14 @@ class AtcPlanOut(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in PLAN_FIELDS]
 
 
+LOOKAHEAD_POLICY_FIELDS = PLAN_FIELDS + ("flown", "logp")
+
+
+class AtcLookaheadPolicyOut(C.Structure):
+    """atc_lookahead_policy_out_t"""
+    _fields_ = [(n, C.c_void_p) for n in LOOKAHEAD_POLICY_FIELDS]
+
+
 PLAN_DRAW_FIELDS = ("seed", "iteration", "flags")
 
 
@@ -242,7 +250,8 @@ EXPORTS = ("atc_abi_version", "atc_last_error", "atc_launch_counts", "atc_host_m
            "atc_gae_boot_launch_counts", "atc_ppo_policy_grad", "atc_ppo_policy_grad_launch_counts",
            "atc_value_forward", "atc_value_forward_launch_counts", "atc_ppo_value_grad", "atc_ppo_value_grad_launch_counts",
            "atc_policy_eval", "atc_policy_eval_launch_counts", "atc_adv_normalise", "atc_adv_normalise_launch_counts",
-           "atc_adam_step", "atc_adam_step_launch_counts", "atc_policy_forward", "atc_policy_forward_launch_counts")
+           "atc_adam_step", "atc_adam_step_launch_counts", "atc_policy_forward", "atc_policy_forward_launch_counts",
+           "atc_lookahead_policy", "atc_lookahead_policy_launch_counts")
 
 def load():
     """Loads libatcstep.so; raises (never falls back) when it has not been built."""
@@ -308,6 +317,8 @@ def load():
     lib.atc_adv_normalise.argtypes = [vp, ci, vp, vp, C.POINTER(AtcAdvNorm), C.POINTER(AtcAdvNormOut), vp]
     lib.atc_adam_step.argtypes = [vp, ci, C.POINTER(AtcAdamTensor), C.POINTER(AtcAdam), vp, vp]
     lib.atc_policy_forward.argtypes = [vp, ci, vp, vp, vp, C.POINTER(AtcPolicyFwd), C.POINTER(AtcPolicyFwdOut), vp]
+    lib.atc_lookahead_policy.argtypes = [vp, ci, ci, ci, ci, ci, C.POINTER(AtcState), vp, vp, C.POINTER(AtcPolicy), C.POINTER(AtcLookaheadPolicyOut),
+                                         C.POINTER(AtcParams), vp]
     for getter in LAUNCH_RECORDS:
         getattr(lib, getter).argtypes = [C.POINTER(C.c_uint64), ci]
     for name in EXPORTS:
@@ -381,6 +392,7 @@ LAUNCH_RECORDS = {
     "atc_adv_normalise_launch_counts": (L.ADV_NORMALISE_LAUNCH_SLOTS, "adv_normalise"),
     "atc_adam_step_launch_counts": (L.ADAM_STEP_LAUNCH_SLOTS, _tensors),
     "atc_policy_forward_launch_counts": (L.POLICY_FORWARD_LAUNCH_SLOTS, _traffic_k0),
+    "atc_lookahead_policy_launch_counts": (L.LOOKAHEAD_POLICY_LAUNCH_SLOTS, _width),
 }
 
 
@@ -528,6 +540,12 @@ def policy_forward_launch_counts():
     """Calls of the stand-alone policy forward (atc_policy_forward; one launch each) made by the calling thread so far, by records per
     aircraft (0: the ten-word policy): {0: n, 4: n, ...}, zero counts left out.  Separate from the other launch records."""
     return _counts("atc_policy_forward_launch_counts")
+
+
+def lookahead_policy_launch_counts():
+    """Launches of the policy look-ahead kernel (atc_lookahead_policy) made by the calling thread so far, by lane-group width: {16: n, ...},
+    widths with a count of zero left out.  Separate from the other launch records, which the call leaves as they are."""
+    return _counts("atc_lookahead_policy_launch_counts")
 
 
 def lookahead_set_mapping(candidates_per_workgroup=0):

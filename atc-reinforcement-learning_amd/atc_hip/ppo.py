@@ -140,6 +140,17 @@ def policy_grad(env, collected, weights, index=None, clip=0.2, normalise=True, w
                                adv_shift=shift, adv_scale=scale, workgroups=workgroups, out=out)
 
 
+def mc_returns(env, w, M, K, H, gamma, *, seed=0, decision0=0, obs0=None, first=None):
+    """Monte-Carlo return of the packed policy `w` from the state the env is in NOW, [B]: the mean over M continuations, flown on copies of
+    the state in one launch (AtcVecEnv.lookahead_policy, which writes no state), of the discounted segment rewards seg[m, 0] + gamma seg[m, 1]
+    + ... (atc_hip.shield.discounted; gamma is per DECISION of K steps) — a target for V(s), a check of the critic, the leaf value of a tree
+    of branch() / select().  first: [M, B, N, 3] fixes the first decision of every continuation, which makes the mean an estimate of Q(s, a)
+    for first[m] = a.  A continuation that was not evaluated (n_steps == 0) enters with its zeros."""
+    from . import shield
+    look = env.lookahead_policy(w, K, H, first=first, M=None if first is not None else M, seed=seed, decision0=decision0, obs0=obs0, outputs=())
+    return shield.discounted(look["seg_reward"], gamma).mean(dim=0)
+
+
 def critic(env, weights):
     """A value_fn for collect() / collect_bootstrap() that runs the library's critic: env.value_forward(weights, rows) on the rows it is
     given, [D + 1, B, N, IN] or [2 D + 1, B, N, IN] -> one value per aircraft.  weights: the tensor of atc_hip.value.pack_mlp(traffic=K) for

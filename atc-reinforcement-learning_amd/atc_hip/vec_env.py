@@ -429,8 +429,9 @@ class AtcVecEnv:
         self._finish()
         return res
 
-    def _candidate_results(self, cache_name, lead, outputs, plan):
-        """The result tensors of a candidate-scoring call and the output struct that points at them, made once per (M[, H], outputs)"""
+    def _candidate_results(self, cache_name, lead, outputs, plan, struct=None):
+        """The result tensors of a candidate-scoring call and the output struct that points at them, made once per (M[, H], outputs).
+        struct: (ctypes type, field names) of a call whose output struct is neither atc_plan_out_t nor atc_lookahead_out_t"""
         torch = self.torch
         cache = self.__dict__.setdefault(cache_name, {})
         key = lead + (outputs,)
@@ -438,9 +439,10 @@ class AtcVecEnv:
             M, B, N, z = lead[0], self.B, self.N, self._new_output
             shapes = {"reward": ((M, B), torch.float32), "done": ((M, B), torch.uint8), "n_steps": ((M, B), torch.int16 if plan else torch.uint8),
                       "seg_reward": (lead + (B,), torch.float32), "flags": ((M, B, N), torch.int16), "min_sep": ((M, B), torch.float32),
-                      "ac_reward": ((M, B, N), torch.float32), "obs": ((M, B, N * L.OBS_DIM), torch.float32)}
+                      "ac_reward": ((M, B, N), torch.float32), "obs": ((M, B, N * L.OBS_DIM), torch.float32),
+                      "flown": (lead + (B, N, L.ACT_DIM), torch.float32), "logp": (lead + (B, N), torch.float32)}
             res = {n: z(*shapes[n]) for n in ("reward", "done", "n_steps") + outputs}
-            out_type, fields = (_lib.AtcPlanOut, _lib.PLAN_FIELDS) if plan else (_lib.AtcLookaheadOut, _lib.LOOKAHEAD_FIELDS)
+            out_type, fields = struct or ((_lib.AtcPlanOut, _lib.PLAN_FIELDS) if plan else (_lib.AtcLookaheadOut, _lib.LOOKAHEAD_FIELDS))
             cache[key] = (res, out_type(*[self._ptr(res.get(n)) for n in fields]))
         return cache[key]
 
@@ -552,6 +554,79 @@ class AtcVecEnv:
                                                             self._ptr(sd), C.byref(dr), C.byref(out), C.byref(self.params), self._stream()))
         self._keep_plan_sampled = (mu, sd)   # mean and std outlive the launch (one pair per call kind, like _keep_plan)
         self._finish()
+        return res
+
+    LOOKAHEAD_POLICY_OUTPUTS = PLAN_OUTPUTS + ("flown", "logp")
+
+    def lookahead_policy(self, weights, K, H, *, first=None, M=None, seed=0, decision0=0, deterministic=False, obs0=None,
+                         outputs=("flags", "min_sep"), out=None):
+        """Plan query whose candidates are CONTINUED BY THE POLICY inside the launch (atc_lookahead_policy, include/atc_step.h): M candidates
+        per env flown on copies of the state the env is in NOW for H segments of K steps, each stopping at its first done — in one launch
+        that writes no state and no per-step stream.  weights: the POLICY_WORDS-word tensor of atc_hip.policy.pack_mlp (a traffic policy is
+        refused).  first: [M, B, N, 3] (or [M, B, N*3]) clamped actions as lookahead() takes them — segment 0 flies first[m] and the policy
+        decides segments 1 .. H-1 from the observation the candidate is then in ("if I take this decision and then go on as I would");
+        without it M is given and the policy decides every segment, segment 0 from obs0 (default: the env's bound observation tensor).
+        The decisions use rollout_policy's key with decision0, decision0 + 1, ... and the aircraft numbering of branch()'s child batch, so
+        the call equals select() / branch() into a child, rollout_policy(hold=K) on it and a fold of its [T, M*B] arrays.  1 <= K <= 255,
+        1 <= H <= 16, 1 <= M <= 1024; continuous action space only.
+        Returns lookahead_plan()'s dict — reward, done [M, B], n_steps [M, B] int16 and seg_reward [M, H, B] always; flags, min_sep,
+        ac_reward, obs as `outputs` names them — plus, where named, flown [M, H, B, N, 3] (the clamped action each segment flew; rows of
+        segments an env did not run are left alone; flown[:, 0] is what step_skip takes to execute a winner) and logp [M, H, B, N]
+        (the segments the policy decided).  Without `out` the tensors are allocated once per (M, H, outputs) and overwritten by the next
+        such call; out: a dict of preallocated tensors of those names (reward and done at least) — its keys are the outputs, and nothing
+        is allocated.  The env state is left as it is."""
+        torch = self.torch
+        K = AtcVecEnv._held_k(K)
+        H = int(H)
+        if not 1 <= H <= L.PLAN_MAX_H:
+            raise ValueError("1 <= H <= %d" % L.PLAN_MAX_H)
+        if not torch.is_tensor(weights):
+            raise ValueError("weights must be the packed float32 tensor of atc_hip.policy.pack_mlp")
+        if policy.traffic_of(weights.numel()) != 0:
+            raise ValueError("lookahead_policy takes the ten-word policy only: these weights are a policy that sees traffic, which is out of its scope")
+        w = AtcVecEnv._on_device(self, weights, (torch.float32,), (L.POLICY_WORDS,),
+                                 text="weights must be the contiguous float32 tensor of %r words (atc_hip.policy.pack_mlp) on %s", elements=True)
+        AtcVecEnv._refuse_discrete(self)
+        B, N = self.B, self.N
+        if first is not None:
+            if not hasattr(first, "shape") or len(first.shape) < 2:
+                raise ValueError("first must be [M, B, N, 3] or [M, B, N*3]")
+            if M is not None and int(M) != int(first.shape[0]):
+                raise ValueError("M is first.shape[0] where first is given")
+            M = AtcVecEnv._drawn_m(int(first.shape[0]), "M (first.shape[0])")
+            a, x0 = AtcVecEnv._as_actions(self, first, lead=(M,)), None
+        else:
+            if M is None:
+                raise ValueError("M is required where first is not given")
+            M = AtcVecEnv._drawn_m(M)
+            a, x0 = None, self.obs if obs0 is None else obs0
+            if not (torch.is_tensor(x0) and x0.dtype == torch.float32 and x0.is_contiguous() and x0.numel() == B * N * L.OBS_DIM):
+                raise ValueError("obs0 must be a contiguous float32 tensor of B*N*%d words" % L.OBS_DIM)
+        if M * B * N >= 2 ** 32:
+            raise ValueError("M * B * N must stay below 2**32")
+        if out is None:
+            if not set(outputs) <= set(AtcVecEnv.LOOKAHEAD_POLICY_OUTPUTS):
+                raise ValueError("outputs must be a subset of %r" % (AtcVecEnv.LOOKAHEAD_POLICY_OUTPUTS,))
+            names = tuple(n for n in AtcVecEnv.LOOKAHEAD_POLICY_OUTPUTS if n in outputs or n == "seg_reward")
+            res, o = AtcVecEnv._candidate_results(self, "_lookahead_policy_cache", (M, H), names, True, (_lib.AtcLookaheadPolicyOut, _lib.LOOKAHEAD_POLICY_FIELDS))
+        else:
+            f32, i16 = (torch.float32,), (torch.int16, getattr(torch, "uint16", torch.int16))
+            want = {"reward": (f32, (M, B)), "done": ((torch.uint8,), (M, B)), "n_steps": (i16, (M, B)), "seg_reward": (f32, (M, H, B)),
+                    "flags": (i16, (M, B, N)), "ac_reward": (f32, (M, B, N)), "min_sep": (f32, (M, B)), "obs": (f32, (M, B, N * L.OBS_DIM)),
+                    "flown": (f32, (M, H, B, N, L.ACT_DIM)), "logp": (f32, (M, H, B, N))}
+            res = AtcVecEnv._results(self, out, want, {"reward", "done"}, "out must be a dict with reward, done and any of %s" % ", ".join(want))
+            o = _lib.AtcLookaheadPolicyOut(*[res[n].data_ptr() if n in res else None for n in _lib.LOOKAHEAD_POLICY_FIELDS])
+        pol = _lib.AtcPolicy(w.data_ptr(), L.POLICY_HIDDEN, L.POLICY_DETERMINISTIC if deterministic else 0, int(seed) & (2 ** 64 - 1),
+                             int(decision0) & 0xffffffff, 0)
+        fn = self._lib.atc_lookahead_policy
+        with torch.cuda.device(self.device):
+            rc = fn(self.sector.handle, B, N, K, H, M, C.byref(self._state), None if x0 is None else self._ptr(x0),
+                                                None if a is None else self._ptr(a), C.byref(pol), C.byref(o), C.byref(self.params), self._stream())
+            if rc:
+                _lib.check(rc)
+        self._keep_lookahead_policy = (w, x0, a)   # the inputs outlive the launch (one set per call kind, like _keep_plan)
+        if self.host_mapped:
+            self._finish()
         return res
 
     def draw_plans(self, mean, std, M, seed=0, iteration=0, mean_first=True, index=None, out=None):

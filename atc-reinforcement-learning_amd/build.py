@@ -20,7 +20,7 @@ DEPS = [SRC, os.path.join(HERE, "csrc", "atc_device.h"), os.path.join(HERE, "csr
         os.path.join(HERE, "csrc", "atc_branch.inc"), os.path.join(HERE, "csrc", "atc_policy.inc"),
         os.path.join(HERE, "csrc", "atc_gae.inc"), os.path.join(HERE, "csrc", "atc_ppo_grad.inc"),
         os.path.join(HERE, "csrc", "atc_value.inc"), os.path.join(HERE, "csrc", "atc_policy_forward.inc"),
-        os.path.join(HERE, "csrc", "atc_ppo_update.inc"),
+        os.path.join(HERE, "csrc", "atc_ppo_update.inc"), os.path.join(HERE, "csrc", "atc_lookahead_policy.inc"),
         os.path.join(os.path.dirname(HERE), "include", "atc_step.h")]
 OUT = os.path.join(HERE, "atc_hip", "libatcstep.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

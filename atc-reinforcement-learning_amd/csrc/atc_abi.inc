@@ -35,6 +35,7 @@ int atc_policy_eval_launch_counts(uint64_t* out, int n) { return copy_counts(REC
 int atc_adv_normalise_launch_counts(uint64_t* out, int n) { return copy_counts(REC_ADV_NORMALISE, out, n); }
 int atc_adam_step_launch_counts(uint64_t* out, int n) { return copy_counts(REC_ADAM_STEP, out, n); }
 int atc_policy_forward_launch_counts(uint64_t* out, int n) { return copy_counts(REC_POLICY_FORWARD, out, n); }
+int atc_lookahead_policy_launch_counts(uint64_t* out, int n) { return copy_counts(REC_LOOKAHEAD_POLICY, out, n); }
 int atc_lookahead_set_mapping(int candidates_per_workgroup) {
     if (candidates_per_workgroup < 0 || candidates_per_workgroup > ATC_LOOKAHEAD_MAX_M) return fail_arg("candidates per workgroup must be 0 (the library's choice) .. 64");
     t_look_cpg = candidates_per_workgroup;
@@ -471,6 +472,51 @@ int atc_lookahead_plan_sampled(const atc_scenario_t* s, int B, int N, int K, int
         return rc;
     return launch_candidates(REC_PLAN_SAMPLED, s, B, N, M, out, cand_any(out), p, [&](auto w, auto full, const CandGrid& g, size_t lds, const atc_out_t& o, const StepDerived& q) {
         hipLaunchKernelGGL((k_plan_sampled<decltype(w)::value, decltype(full)::value>), dim3(g.grid), dim3(kBlock), lds, (hipStream_t)stream, s->d_blob, s->off_grid, B, N, K, H, M, *st, mean, o, *p, q, out->n_steps, out->seg_reward, g.cpg, g.groups, g.tiles, std, *dr);
+    });
+}
+
+// atc_lookahead_policy: the checks in the header's order — the pointers, then K, H, M, the mode, the policy's fields, the batch shape, and the
+// overlap rule on pointer values — then k_lookahead_policy through the candidate kernels' one launch
+int atc_lookahead_policy(const atc_scenario_t* s, int B, int N, int K, int H, int M, const atc_state_t* st, const float* obs0, const float* first,
+                         const atc_policy_t* pol, const atc_lookahead_policy_out_t* out, const atc_params_t* p, void* stream) {
+    if (!pol) return fail_arg("null pointer: pol (atc_policy_t) is required");
+    if (!pol->w) return fail_arg("null pointer: pol->w (the policy's weights) is required");
+    if (!out) return fail_arg("null pointer: out (atc_lookahead_policy_out_t) is required");
+    if (!out->reward || !out->done) return fail_arg("null pointer: atc_lookahead_policy_out_t.reward and .done are required");
+    if (!first && !obs0) return fail_arg("null pointer: obs0 is required where first is NULL (segment 0's decision reads it)");
+    if (!s || !st || !p) return fail_arg("null pointer");
+    if (state_has_null(st)) return fail_arg("atc_state_t has a null field");
+    if (K < 1 || K > ATC_SKIP_MAX) return fail_arg("K (the segment length) must be 1 .. 255");
+    if (const int rc = check_plan_h(H)) return rc;
+    if (M < 1 || M > ATC_SAMPLE_MAX_M) return fail_arg("M (the number of candidates) must be 1 .. 1024");
+    if (p->mode & ATC_M_DISCRETE) return fail_arg("ATC_M_DISCRETE: a Gaussian policy draws the continuous action space only");
+    if (p->mode & ATC_M_ACTIONS_HELD) return fail_arg("ATC_M_ACTIONS_HELD is for atc_step only: every segment's first step carries a fresh decision");
+    if (pol->n_hidden != ATC_POLICY_HIDDEN) return fail_arg("pol->n_hidden must be 64 (ATC_POLICY_HIDDEN)");
+    if (pol->flags & ~ATC_POLICY_DETERMINISTIC) return fail_arg("pol->flags has unknown bits (ATC_POLICY_DETERMINISTIC or 0)");
+    if (const int rc = check_batch_range(B, N)) return rc;
+    if (const int rc = check_batch_size(B, N)) return rc;
+    if ((unsigned long long)M * (unsigned long long)B * (unsigned long long)N >= (1ull << 32))
+        return fail_arg("M*B*N must stay below 2^32 (the aircraft index of a decision's key): split the candidates");
+    const uintptr_t b = (uintptr_t)B, bn = b * (uintptr_t)N, mb = (uintptr_t)M * b, mbn = (uintptr_t)M * bn, h = (uintptr_t)H;
+    const ByteRange weights = {pol->w, ATC_POLICY_WORDS * 4u, "pol->w"};
+    // (obs0 is not read where first is given: then it is no range of the call)
+    const ByteRange arrays[18] = {{first ? nullptr : obs0, bn * (ATC_OBS_DIM * 4u), "obs0"}, {first, mbn * 12u, "first"}, {st->ac, bn * 16u, "st->ac"}, {st->alt, bn * 8u, "st->alt"},
+                                  {st->last_act, bn * 16u, "st->last_act"}, {st->env, b * (ATC_ENV_WORDS * 4u), "st->env"}, {st->stats, b * (ATC_STAT_WORDS * 4u), "st->stats"},
+                                  {st->phi_wide, bn * 32u, "st->phi_wide"},
+                                  // the outputs, from index 8
+                                  {out->reward, mb * 4u, "out->reward"}, {out->done, mb, "out->done"}, {out->n_steps, mb * 2u, "out->n_steps"},
+                                  {out->seg_reward, mb * h * 4u, "out->seg_reward"}, {out->flags, mbn * 2u, "out->flags"}, {out->ac_reward, mbn * 4u, "out->ac_reward"},
+                                  {out->min_sep, mb * 4u, "out->min_sep"}, {out->obs, mbn * (ATC_OBS_DIM * 4u), "out->obs"}, {out->flown, mbn * h * 12u, "out->flown"},
+                                  {out->logp, mbn * h * 4u, "out->logp"}};
+    if (const int rc = check_apart(weights, arrays + 8, 10, "the weights are read while the launch writes the other")) return rc;
+    for (int o = 8; o < 18; ++o) {
+        if (!arrays[o].ptr) continue;
+        if (const int rc = check_apart(arrays[o], arrays, o, "it is written while the launch reads or writes the other")) return rc;
+    }
+    if (const int rc = check_dt(s, p)) return rc;   // (the first check that reads the sector: behind everything that is about pointer values)
+    const LookPolicyTail pt = {obs0, pol->w, pol->seed, pol->decision0, pol->flags, out->flown, out->logp};
+    return launch_candidates(REC_LOOKAHEAD_POLICY, s, B, N, M, out, cand_any(out), p, [&](auto w, auto full, const CandGrid& g, size_t lds, const atc_out_t& o, const StepDerived& q) {
+        hipLaunchKernelGGL((k_lookahead_policy<decltype(w)::value, decltype(full)::value>), dim3(g.grid), dim3(kBlock), lds, (hipStream_t)stream, s->d_blob, s->off_grid, B, N, K, H, M, *st, first, o, *p, q, out->n_steps, out->seg_reward, g.cpg, g.groups, g.tiles, pt);
     });
 }
 

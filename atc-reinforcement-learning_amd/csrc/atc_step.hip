@@ -1767,6 +1767,7 @@ k_serve(const float* __restrict__ blob, int off_grid, atc_state_t st, atc_out_t 
 #include "atc_plan_score.inc"    // k_plan_score (atc_plan_score)
 #include "atc_branch.inc"        // k_branch (atc_branch), k_select (atc_state_select)
 #include "atc_policy.inc"        // k_rollout_policy (atc_rollout_policy), k_rollout_policy_traffic (atc_rollout_policy_traffic), k_rollout_policy_ends (atc_rollout_policy_ends)
+#include "atc_lookahead_policy.inc"   // k_lookahead_policy (atc_lookahead_policy): k_plan_sampled's loop with policy_decide where it draws
 #include "atc_gae.inc"           // k_gae (atc_gae), k_gae_boot (atc_gae_boot)
 #include "atc_ppo_grad.inc"      // k_ppo_grad, k_ppo_grad_reduce (atc_ppo_policy_grad)
 #include "atc_value.inc"         // k_value_forward (atc_value_forward), k_ppo_value_grad, k_ppo_value_grad_reduce (atc_ppo_value_grad)
@@ -1803,14 +1804,14 @@ static size_t lds_bytes(const atc_scenario*, bool pair_scan, bool step_kernel = 
 // and REC_POLICY_EVAL likewise with K = 0 in front (slot = 4 log2(W) + {0, 1, 2, 3}); REC_PPO_GRAD, REC_VALUE_FORWARD, REC_PPO_VALUE_GRAD and REC_POLICY_FORWARD count calls by K
 // (slot = {0, 1, 2, 3}); REC_ADV_NORMALISE counts calls in one slot and REC_ADAM_STEP by the number of tensors (slot = n_tensors - 1).  A call
 // moves its own record only.
-enum Record { REC_STEP, REC_SKIP, REC_TRAFFIC, REC_LOOKAHEAD, REC_PLAN, REC_PLAN_SAMPLED, REC_PLAN_DRAW, REC_PLAN_REFIT, REC_PLAN_SCORE, REC_BRANCH, REC_SELECT, REC_POLICY, REC_POLICY_TRAFFIC, REC_GAE, REC_POLICY_ENDS, REC_GAE_BOOT, REC_PPO_GRAD, REC_VALUE_FORWARD, REC_PPO_VALUE_GRAD, REC_POLICY_EVAL, REC_ADV_NORMALISE, REC_ADAM_STEP, REC_POLICY_FORWARD, REC_COUNT };
+enum Record { REC_STEP, REC_SKIP, REC_TRAFFIC, REC_LOOKAHEAD, REC_PLAN, REC_PLAN_SAMPLED, REC_PLAN_DRAW, REC_PLAN_REFIT, REC_PLAN_SCORE, REC_BRANCH, REC_SELECT, REC_POLICY, REC_POLICY_TRAFFIC, REC_GAE, REC_POLICY_ENDS, REC_GAE_BOOT, REC_PPO_GRAD, REC_VALUE_FORWARD, REC_PPO_VALUE_GRAD, REC_POLICY_EVAL, REC_ADV_NORMALISE, REC_ADAM_STEP, REC_POLICY_FORWARD, REC_LOOKAHEAD_POLICY, REC_COUNT };
 constexpr int kRecordSlots[REC_COUNT] = {ATC_LAUNCH_SLOTS, ATC_SKIP_LAUNCH_SLOTS, ATC_TRAFFIC_LAUNCH_SLOTS, ATC_LOOKAHEAD_LAUNCH_SLOTS, ATC_PLAN_LAUNCH_SLOTS,
                                          ATC_PLAN_SAMPLED_LAUNCH_SLOTS, ATC_PLAN_DRAW_LAUNCH_SLOTS, ATC_PLAN_REFIT_LAUNCH_SLOTS, ATC_PLAN_SCORE_LAUNCH_SLOTS,
                                          ATC_BRANCH_LAUNCH_SLOTS, ATC_SELECT_LAUNCH_SLOTS, ATC_ROLLOUT_POLICY_LAUNCH_SLOTS,
                                          ATC_ROLLOUT_POLICY_TRAFFIC_LAUNCH_SLOTS, ATC_GAE_LAUNCH_SLOTS, ATC_ROLLOUT_POLICY_ENDS_LAUNCH_SLOTS,
                                          ATC_GAE_BOOT_LAUNCH_SLOTS, ATC_PPO_GRAD_LAUNCH_SLOTS, ATC_VALUE_FORWARD_LAUNCH_SLOTS,
                                          ATC_PPO_VALUE_GRAD_LAUNCH_SLOTS, ATC_POLICY_EVAL_LAUNCH_SLOTS, ATC_ADV_NORMALISE_LAUNCH_SLOTS,
-                                         ATC_ADAM_STEP_LAUNCH_SLOTS, ATC_POLICY_FORWARD_LAUNCH_SLOTS};
+                                         ATC_ADAM_STEP_LAUNCH_SLOTS, ATC_POLICY_FORWARD_LAUNCH_SLOTS, ATC_LOOKAHEAD_POLICY_LAUNCH_SLOTS};
 constexpr int record_offset(int id) {
     int o = 0;
     for (int i = 0; i < id; ++i) o += kRecordSlots[i];
@@ -2092,7 +2093,7 @@ template <typename O>
 static bool cand_any(const O* o) {
     return o->flags || o->ac_reward || o->min_sep || o->obs;
 }
-// The one launch of the candidate kernels (k_lookahead, k_plan, k_plan_sampled, k_branch): the grid, the kernels' atc_out_t, the derived
+// The one launch of the candidate kernels (k_lookahead, k_plan, k_plan_sampled, k_branch, k_lookahead_policy): the grid, the kernels' atc_out_t, the derived
 // constants, then `launch(w, full, g, lds, out, q)` — the caller's generic lambda, which names the kernel instantiation
 // <decltype(w)::value, decltype(full)::value> and its argument list — and the count in record `rec`, slot log2(W).  `any` picks the
 // form with the optional outputs compiled in: cand_any(o), or atc_branch's own rule.

@@ -1595,6 +1595,63 @@ int atc_policy_forward(const atc_scenario_t* s, int R, const float* w /* [ATC_PO
 enum { ATC_POLICY_FORWARD_LAUNCH_SLOTS = 4 };
 int atc_policy_forward_launch_counts(uint64_t* out, int n);
 
+/* POLICY LOOK-AHEAD (extension): atc_lookahead_plan whose candidates are CONTINUED BY THE POLICY inside the launch — "if I take this
+ * decision now and then go on as I would, how does it end?" for M candidates per env in ONE launch that writes no state and no per-step
+ * stream: what an action shield, a Monte-Carlo estimate of Q(s, a) / V(s) and the tail value of a planner ask.  1 <= K <= ATC_SKIP_MAX,
+ * 1 <= H <= ATC_PLAN_MAX_H, 1 <= M <= ATC_SAMPLE_MAX_M; pol is the ten-word policy of atc_rollout_policy (a traffic policy is not taken).
+ * Candidate m of env e is a bit-exact private copy of the env's state; segment h = 0 .. H-1 holds ONE decision for K steps.
+ *   first != NULL ([M][B*N*3], clamped actions as atc_lookahead takes them): segment 0 flies first[m], the policy decides segments
+ *                 1 .. H-1, h0 = 1; obs0 is not read and may be NULL.
+ *   first == NULL: the policy decides every segment, h0 = 0; segment 0 sees obs0 ([B*N*10], as in atc_rollout_policy), the same rows for
+ *                 every candidate — the candidates then differ by their draws alone.
+ * The decision of segment h >= h0 is atc_rollout_policy's (h1, h2, mu, key, z, u, a, logp as defined there) on the ten words the previous
+ * step of THAT candidate stored, with
+ *
+ *     decision = pol->decision0 + (h - h0)   (modulo 2^32);     i = (m*B + e)*N + k
+ *
+ * which is the key atc_rollout_policy(seed, decision0) uses on a child batch of M*B envs whose env m*B + e is the candidate — atc_branch's
+ * numbering.  The call therefore EQUALS, in every output, a composition of existing calls on such a child (tests/lookahead_policy_ref.py
+ * folds its [T][M*B] arrays): atc_state_select(index = c % B) then atc_rollout_policy(H*K, hold = K, obs0 tiled M times) where first is NULL;
+ * atc_branch(first, K) then atc_rollout_policy((H-1)*K, hold = K, obs0 = the branch's obs) where it is given — each candidate cut at its
+ * first done.  BIT FOR BIT wherever no wavefront of either side sums layer 1 in float64 (atc_policy_forward: an input above 4 in
+ * magnitude, or a NaN, in the wavefront; here a lane whose env has taken its last step feeds zeros and never switches its wavefront).
+ * Normalised observations lie in [-1, 1]; what exceeds 4 is an unnormalised observation and the raw reset observation that follows an
+ * auto-reset in the CHILD's rollout.  Where the two sides choose differently the policy half is held to the bars of tests/policy_ref.py
+ * at the first affected decision, as for atc_policy_forward, and what follows it is that of the decision taken.
+ * Everything else is atc_lookahead_plan's contract, word for word: an env stops at its first done, so a plan never spans two episodes; the
+ * segments it did not run get seg_reward 0; reward and ac_reward are the two-level sequential fp32 sums; flags the OR, min_sep the minimum,
+ * obs the last executed step's; the WIDE-heading rule (n_steps = 0 and every word of atc_plan_out_t's arrays zero for that (m, e)); no
+ * state written.  Two additions, each nullable:
+ *   flown [M][H][B*N*3]  the clamped action segment h flew (first[m] in segment 0 where given).  Rows of segments an env did not run are
+ *                        left alone.  flown[.][0] is what atc_step_skip takes to execute a winner when first was NULL.
+ *   logp  [M][H][B*N]    written for the segments the policy decided and the env ran (0 under ATC_POLICY_DETERMINISTIC).
+ * (A not-evaluated (m, e) keeps the flown / logp rows written before its WIDE heading was seen; n_steps == 0 tells.)
+ * ATC_ERR_ARG, in this order, atc_last_error() naming the argument: a NULL among pol, pol->w, out, out->reward, out->done, obs0 where first
+ * is NULL, then s, st, p and st's six arrays; K outside 1 .. ATC_SKIP_MAX; H outside 1 .. ATC_PLAN_MAX_H; M outside 1 .. ATC_SAMPLE_MAX_M;
+ * ATC_M_DISCRETE, then ATC_M_ACTIONS_HELD in p->mode; pol->n_hidden != ATC_POLICY_HIDDEN or unknown bits in pol->flags; B or N out of
+ * range, B*N too large for a launch, M*B*N >= 2^32; pol->w overlapping an output; an output overlapping any other array of the call
+ * (obs0, first, st's arrays, another output) — pointer values only, ranges that only touch are accepted; dt out of range (atc_step's rule).
+ * Counted by atc_lookahead_policy_launch_counts only (slot = log2(W); the rules of atc_skip_launch_counts): every other launch record
+ * stays still, and a refused call moves none.  atc_lookahead_set_mapping governs this call's candidates per workgroup as well; results
+ * do not depend on it. */
+typedef struct atc_lookahead_policy_out {
+    float*    reward;     /* [M][B]        required */
+    uint8_t*  done;       /* [M][B]        required */
+    uint16_t* n_steps;    /* [M][B]        nullable; total executed steps (<= H*K = 4080); 0 = not evaluated */
+    float*    seg_reward; /* [M][H][B]     nullable */
+    uint16_t* flags;      /* [M][B*N]      nullable */
+    float*    ac_reward;  /* [M][B*N]      nullable */
+    float*    min_sep;    /* [M][B]        nullable */
+    float*    obs;        /* [M][B*N*10]   nullable */
+    float*    flown;      /* [M][H][B*N*3] nullable */
+    float*    logp;       /* [M][H][B*N]   nullable */
+} atc_lookahead_policy_out_t;
+int atc_lookahead_policy(const atc_scenario_t* s, int B, int N, int K, int H, int M, const atc_state_t* st,
+                         const float* obs0 /* [B*N*10]; nullable where first is given */, const float* first /* nullable [M][B*N*3] */,
+                         const atc_policy_t* pol, const atc_lookahead_policy_out_t* out, const atc_params_t* p, void* stream);
+enum { ATC_LOOKAHEAD_POLICY_LAUNCH_SLOTS = 7 };
+int atc_lookahead_policy_launch_counts(uint64_t* out, int n);
+
 #ifdef __cplusplus
 }
 #endif
