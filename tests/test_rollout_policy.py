@@ -9,7 +9,8 @@ GPU, DYNAMICS: two envs built alike; env A calls rollout_policy, env B the exist
 reward, done, flags and of the state equal, over the mode space, so the env half is pinned to the oracle-tested path however the policy's
 roundings fall; only atc_rollout_policy_launch_counts moves.
 GPU, POLICY: every decision restated by tests/policy_ref.py on the inputs the kernel stored (obs0, or obs[b hold - 1]) — decisions are
-checked independently of each other — against the bars stated there.  Each test prints its largest deviation before it asserts."""
+checked independently of each other — against the bars stated there.  Each test prints its largest deviation before it asserts.
+Per-instantiation coverage — every (W) this call is compiled for, each against its oracle — lives in tests/test_z_policy_matrix.py."""
 import ctypes as C
 import functools
 import inspect

@@ -9,7 +9,8 @@ GPU, TRAFFIC AND DYNAMICS, bit for bit: two envs built alike, B with traffic=K. 
 decisions — observe_traffic() must equal A's stored records on the uint32 view, then rollout(clamp(A.action[b]), hold) must equal A's
 rows of obs / reward / done / flags — and the states are equal at the end.  Only the new launch record moves.
 GPU, POLICY: every decision restated by tests/policy_traffic_ref.py on the inputs the kernel stored, input_rows(obs0 or obs[b hold - 1],
-traffic[b]), against policy_ref's bars.  Each test prints its largest deviation before it asserts."""
+traffic[b]), against policy_ref's bars.  Each test prints its largest deviation before it asserts.
+Per-instantiation coverage — every (W, K) this call is compiled for, each against its oracle — lives in tests/test_z_policy_matrix.py."""
 import ctypes as C
 import functools
 import inspect

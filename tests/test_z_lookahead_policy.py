@@ -15,172 +15,20 @@ layer 1 in float64) — in full for every case without an auto-reset.  WITH an a
 among 16 lattice spawns, the time limit) makes the child's rollout step on through the reset; the raw reset observation switches that child
 wavefront at its next decision, and the header claims bit equality only where no wavefront of either side does.  There the comparison is over the
 candidates whose child wavefront (64 consecutive lane slots) is clean at every decision they took — at least half of the candidates, asserted —
-and the time-limit case asserts that candidates of all three kinds (ended in segment 0, ended before the last segment, ran all H) are among them."""
-import functools
-
+and the time-limit case asserts that candidates of all three kinds (ended in segment 0, ended before the last segment, ran all H) are among them.
+The oracle (one call, both oracles, the comparison) is tests/lookahead_policy_compose.py.  Per-instantiation coverage — every (W, form) this call is compiled for, each against its oracle — lives in tests/test_z_policy_matrix.py."""
 import numpy as np
 import pytest
 
 import helpers as H
 import held_tools as T
+import lookahead_policy_compose as LC
 import lookahead_policy_ref as R
-import policy_ref as P
 from atc_hip import layout as L
+from lookahead_policy_compose import BASE, DECISION0, FULL_OUT, K, SEED      # noqa: F401  (the oracle's constants are this module's)
 
-K = 3
-SEED, DECISION0 = 0x1234567890ABCDEF, 0xFFFFFFFE     # (decision0 + h wraps inside every plan of more than two decisions)
-BASE = dict(normalize=True, shaping=True, spawn="lattice", timestep_limit=6000)
-FULL_OUT = ("seg_reward", "flags", "min_sep", "ac_reward", "obs", "flown", "logp")
-FAST_OUT = ("seg_reward", "flown", "logp")
-PLAN_KEYS = ("reward", "done", "n_steps", "seg_reward", "flags", "min_sep", "ac_reward", "obs")
-
-
-def _weights(sampled=True):
-    return P.random_weights(np.random.default_rng([17, 1]), 1.0, (-0.5, -1.0, 0.25) if sampled else (-0.5, -1.0, 0.0), False)
-
-
-def _root(cfg, B, N, ends):
-    """the root env, stepped at least once behind reset() so that its bound observation is a normalised one.  ends: the envs are taken apart in
-    time — masked resets between the steps — so that under a time limit of 14 a third of them has 2 steps left, a third 8 and a third 13"""
-    import torch
-    env = H.policy_env(cfg, B, N)
-    gen = torch.Generator(device="cpu").manual_seed(5)
-    act = lambda: (torch.rand((B, N, 3), generator=gen) * 0.4 - 0.2).to(env.device)      # noqa: E731
-    if ends:
-        third = torch.arange(B) * 3 // B      # 0: untouched (t = 12), 1: reset behind step 6 (t = 6), 2: reset behind step 11 (t = 1)
-        for t in range(12):
-            if t == 6:
-                env.reset(mask=(third >= 1).to(torch.uint8))
-            if t == 11:
-                env.reset(mask=(third == 2).to(torch.uint8))
-            env.step(act())
-    else:
-        env.step(act())
-    env.synchronize()
-    return env
-
-
-def _np(d):
-    return {k: v.cpu().numpy() for k, v in d.items()}
-
-
-@functools.lru_cache(maxsize=None)
-def _case(B, N, M, Hh, with_first, full, deterministic, auto_reset, ends=False):
-    """one call and its two oracles, numpy: dict(got, want, plan, clean, n, kinds, max_x)"""
-    import torch
-    cfg = dict(BASE, auto_reset=auto_reset, timestep_limit=14 if ends else 6000)
-    root, child = _root(cfg, B, N, ends), H.policy_env(cfg, M * B, N)
-    dev = root.device
-    w = torch.as_tensor(_weights(not deterministic), device=dev)
-    first = None
-    if with_first:
-        first = (torch.rand((M, B, N, 3), generator=torch.Generator(device="cpu").manual_seed(9)) * 2.0 - 1.0).to(dev)
-    snap = H.snapshot(root)
-    bound = {k: getattr(root, k).clone() for k in ("obs", "reward", "done", "flags")}
-    obs0 = root.obs.clone()
-    got = root.lookahead_policy(w, K, Hh, first=first, M=None if with_first else M, seed=SEED, decision0=DECISION0, deterministic=deterministic,
-                                outputs=FULL_OUT if full else FAST_OUT)
-    root.synchronize()
-    got = _np(got)
-    H.bytes_equal(root, snap)      # (asserts: the call wrote no state array)
-    for k, v in bound.items():
-        assert torch.equal(getattr(root, k), v), "the call wrote the bound tensor %s" % k
-    C = M * B
-    # ---- oracle 1: the child batch
-    if with_first:
-        _, r0, d0, info = root.branch(first, K, into=child)
-        child.synchronize()
-        r0, d0, n0 = r0.cpu().numpy().reshape(C), d0.cpu().numpy().reshape(C).astype(bool), info["frame_steps"].cpu().numpy().reshape(C).astype(np.int64)
-        fl0, ob0 = child.flags.cpu().numpy().reshape(C, N).astype(np.uint16), child.obs.cpu().numpy().reshape(C, N * 10)
-        x0, D = child.obs.clone(), Hh - 1
-    else:
-        child.select(root, torch.arange(C, device=dev) % B)
-        x0, D = obs0.repeat(M, 1), Hh
-    seg = np.zeros((Hh, C), np.float32)
-    if D:
-        roll = _np(child.rollout_policy(w, D * K, hold=K, seed=SEED, decision0=DECISION0, deterministic=deterministic, obs0=x0.contiguous()))
-        child.synchronize()
-        f = R.fold(roll["reward"], roll["done"], K, D)
-        xs = np.stack([x0.cpu().numpy().reshape(C, N, 10)] + [roll["obs"][b * K - 1].reshape(C, N, 10) for b in range(1, D)])     # what decision b saw
-    if with_first:
-        cont = ~d0      # candidates the rollout continues
-        seg[0] = r0
-        n, done, total, flags, obs = n0.copy(), d0.copy(), r0.copy(), fl0.copy(), ob0.copy()
-        if D:
-            seg[1:] = np.where(cont, f["seg_reward"], np.float32(0.0))
-            n += np.where(cont, f["n_steps"], 0)
-            done = np.where(cont, f["done"].astype(bool), d0)
-            for h in range(1, Hh):
-                total = np.where(cont & ((h - 1) * K < f["n_steps"]), (total + seg[h]).astype(np.float32), total)
-            flags = np.where(cont[:, None], fl0 | R.or_flags(roll["flags"], f["n_steps"]), fl0)
-            obs = np.where(cont[:, None], R.last_rows(roll["obs"], f["n_steps"]), ob0)
-        decided = np.maximum(-(-n // K) - 1, 0)      # decisions each candidate took
-    else:
-        seg, n, done, total = f["seg_reward"], f["n_steps"], f["done"].astype(bool), f["reward"]
-        flags, obs = R.or_flags(roll["flags"], n), R.last_rows(roll["obs"], n)
-        decided = -(-n // K)
-    want = dict(seg_reward=seg.reshape(Hh, M, B).transpose(1, 0, 2), reward=total.reshape(M, B), done=done.reshape(M, B).astype(np.uint8),
-                n_steps=n.reshape(M, B), flags=flags.reshape(M, B, N), obs=obs.reshape(M, B, N * 10))
-    h0 = 1 if with_first else 0
-    flown = np.zeros((M, Hh, B, N, 3), np.float32)
-    logp = np.zeros((M, Hh, B, N), np.float32)
-    if with_first:
-        flown[:, 0] = first.cpu().numpy()
-    if D:
-        flown[:, h0:] = np.clip(roll["action"], -1.0, 1.0).reshape(D, M, B, N, 3).transpose(1, 0, 2, 3, 4)
-        logp[:, h0:] = roll["logp"].reshape(D, M, B, N).transpose(1, 0, 2, 3)
-    want.update(flown=flown, logp=logp)
-    # ---- which candidates the bit-equality claim covers: the child wavefront of each decision they took saw nothing above 4
-    W = H.lane_width(N)
-    per = 64 // W
-    clean = np.ones(C, bool)
-    max_x = 0.0
-    if D:
-        big = ~(np.abs(xs) <= 4.0)
-        dirty_env = big.reshape(D, C, -1).any(axis=2)
-        pad = (-C) % per
-        dirty_wave = np.pad(dirty_env, ((0, 0), (0, pad))).reshape(D, -1, per).any(axis=2).repeat(per, axis=1)[:, :C]
-        took = np.arange(D)[:, None] < decided[None, :]
-        clean = ~(dirty_wave & took).any(axis=0)
-        max_x = float(np.abs(np.where(took[:, :, None, None], xs, 0.0)).max())
-    # ---- oracle 2: the open-loop plan on the flown actions (M <= 64)
-    plan = None
-    if M <= L.LOOKAHEAD_MAX_M and full:
-        plan = _np(root.lookahead_plan(torch.as_tensor(want["flown"], device=dev), K, outputs=("seg_reward", "flags", "min_sep", "ac_reward", "obs")))
-        root.synchronize()
-    kinds = dict(seg0=(n <= K) & done & (Hh > 1), early=(n <= (Hh - 1) * K) & done, whole=n > (Hh - 1) * K)
-    root.close()
-    child.close()
-    return dict(got=got, want=want, plan=plan, clean=clean.reshape(M, B), n=n.reshape(M, B), kinds={k: v.reshape(M, B) for k, v in kinds.items()}, max_x=max_x,
-                auto_reset=auto_reset)
-
-
-def _compare(r, M, B, N, Hh, with_first):
-    got, want, n = r["got"], r["want"], r["n"]
-    restrict = r["auto_reset"]      # (the child's rollout steps on through an auto-reset: see PRECONDITION above)
-    ok = r["clean"] if restrict else np.ones((M, B), bool)
-    assert 2 * ok.sum() >= M * B, "fewer than half of the candidates are covered by the bit-equality claim"
-    if not restrict:
-        assert r["clean"].all() and r["max_x"] <= 4.0, "precondition: a decision of the oracle saw an observation above 4 (%g)" % r["max_x"]
-    print("max |x| a decision saw: %.3g; candidates compared: %d of %d; steps run: %d .. %d" % (r["max_x"], int(ok.sum()), M * B, n.min(), n.max()))
-    assert n.min() >= 1
-    for k in ("reward", "done", "n_steps"):
-        assert np.array_equal(H.bits(got[k].astype(want[k].dtype))[ok], H.bits(want[k])[ok]), k
-    assert np.array_equal(H.bits(got["seg_reward"]).transpose(0, 2, 1)[ok], H.bits(want["seg_reward"]).transpose(0, 2, 1)[ok]), "seg_reward"
-    ran = (np.arange(Hh)[None, :, None] * K < n[:, None, :]) & ok[:, None, :]           # [M, H, B]: segments run
-    pol = ran & (np.arange(Hh)[None, :, None] >= (1 if with_first else 0))
-    assert np.array_equal(H.bits(got["flown"])[ran], H.bits(want["flown"])[ran]), "flown"
-    assert np.array_equal(H.bits(got["logp"])[pol], H.bits(want["logp"])[pol]), "logp"
-    if "flags" in got:
-        assert np.array_equal(got["flags"].astype(np.uint16)[ok], want["flags"][ok]), "flags"
-        live = ok & ((got["done"] == 0) | (not r["auto_reset"]))       # (behind a look-ahead reset the child env draws another spawn: oracle 2)
-        assert np.array_equal(H.bits(got["obs"])[live], H.bits(want["obs"])[live]), "obs"
-    if r["plan"] is not None:
-        for k in PLAN_KEYS:
-            a, b = H.bits(got[k]), H.bits(r["plan"][k])
-            if k == "seg_reward":
-                a, b = a.transpose(0, 2, 1), b.transpose(0, 2, 1)
-            assert np.array_equal(a[ok], b[ok]), "lookahead_plan on the flown actions: %s" % k
+# the composition oracle lives in tests/lookahead_policy_compose.py, which tests/test_z_policy_matrix.py shares
+_weights, _root, _np, _case, _compare = LC.weights, LC.root, LC.to_numpy, LC.case, LC.compare
 
 
 # B x N x M: W = 1, 16, 64 — idle lanes at N = 40, five envs in a tile of 256 slots at N = 1

@@ -9,7 +9,8 @@ and control equal tests/policy_ends_ref.py; two launches of T / 2 equal one; eac
 unchanged; the state afterwards equals the twin's.  test_the_runs_contain_what_they_are_meant_to_test asserts, on what the runs produced,
 that the events the cases are built for did occur.
 (The module's name sorts it behind the existing test modules on purpose: tests/test_rollout_policy_traffic.py's overlap refusals depend
-on where the allocator places that test's buffers next to the env's state arrays, which every GPU test run before it shifts.)"""
+on where the allocator places that test's buffers next to the env's state arrays, which every GPU test run before it shifts.)
+Per-instantiation coverage — every (W, K) this call is compiled for, each against its oracle — lives in tests/test_z_policy_matrix.py."""
 import ctypes as C
 import functools
 import re

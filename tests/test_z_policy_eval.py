@@ -8,7 +8,8 @@ GPU, bit for bit, on twin envs: the record equals policy_eval_ref folded over ro
 twin's state and obs[-1]; two launches of T / 2 equal one; clear=False adds to the record it is given and clear=True ignores it;
 obs_last = NULL changes nothing else; only the call's own launch record moves; an episode that began before the launch counts in full.
 test_the_runs_contain_what_they_are_meant_to_test asserts, on what the runs produced, that the events the cases are built for did occur.
-(The module's name sorts it behind the existing test modules for the reason given in tests/test_z_policy_ends.py's docstring.)"""
+(The module's name sorts it behind the existing test modules for the reason given in tests/test_z_policy_ends.py's docstring.)
+Per-instantiation coverage — every (W, K) this call is compiled for, each against its oracle — lives in tests/test_z_policy_matrix.py."""
 import ctypes as C
 import functools
 import re
