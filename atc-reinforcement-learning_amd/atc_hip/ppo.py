@@ -166,9 +166,12 @@ def value_grad(env, collected, weights, index=None, clip=0.2, workgroups=0, out=
     "ret" (and "traffic", "control" where the rollout stored them).
     v_old = values[:-1] and ret, both [D, B, N] — a per-env [D, B] or [D, B, 1] is expanded over the env's aircraft —; the rows are
     value_rows(...)[:-1], "traffic" the records next to them, mask = "control", index the int32 minibatch; nothing else is copied.
+    The critic is packed for the collection's K (atc_hip.value.pack_mlp(traffic=K), K = collected["traffic"].shape[-2]) or for K = 0: a
+    critic that reads the own row only, to which the stored records are not passed.  Any other size: ValueError, before any call on `env`.
     Returns ppo_value_grad's dict: "grad" (to be assigned to weights.grad), "stats", "value"."""
     action = collected["action"]
     D, B, N = int(action.shape[0]), env.B, env.N
+    traffic = _critic_traffic(collected, weights)
     hold = int(collected["obs"].shape[0]) // D
     obs0 = collected.get("obs0")
     if obs0 is None:
@@ -185,7 +188,19 @@ def value_grad(env, collected, weights, index=None, clip=0.2, workgroups=0, out=
             raise ValueError("%s must be [D, B, N], or per env [D, B] / [D, B, 1]" % name)
         return v.reshape(D, B, 1).expand(D, B, N).contiguous()
     return env.ppo_value_grad(weights, own, per_aircraft(collected["values"][:-1], "values[:-1]"), per_aircraft(collected["ret"], "ret"),
-                              traffic=collected.get("traffic"), mask=collected.get("control"), index=index, clip=clip, workgroups=workgroups, out=out)
+                              traffic=traffic, mask=collected.get("control"), index=index, clip=clip, workgroups=workgroups, out=out)
+
+
+def _critic_traffic(collected, vw):
+    """The records value_grad() passes next to the rows: the collection's where the critic is packed for its K, None for a K = 0 critic"""
+    traffic = collected.get("traffic")
+    K = 0 if traffic is None else int(traffic.shape[-2])
+    if int(vw.numel()) == L.value_words(K):
+        return traffic
+    if int(vw.numel()) == L.value_words(0):
+        return None
+    raise ValueError("the critic must be packed for the collection's K = %d (atc_hip.value.pack_mlp(traffic=%d): %d words) or for K = 0 (%d words), "
+                     "got %d words" % (K, K, L.value_words(K), L.value_words(0), int(vw.numel())))
 
 
 def adam_state(env, w, vw=None):
@@ -213,7 +228,9 @@ def update(env, collected, w, vw, state, *, epochs=4, minibatches=4, clip=0.2, v
       per minibatch: policy_grad(..., normalise=False) on a shallow copy of `collected` whose "adv" is the normalised tensor, value_grad(),
                      then ONE env.adam_step over both tensors with step = state["t"] + 1: the critic's gradient scaled by vf_coef, -ent_coef
                      added to the three log_std words, the norm over both clipped to max_grad_norm.
-    w and vw are updated in place; state is adam_state(env, w, vw)'s and carries the moments and the count.  The minibatches are the
+    w and vw are updated in place; state is adam_state(env, w, vw)'s and carries the moments and the count.  w is packed for the collection's
+    K (the K of collected["traffic"], 0 without it), vw for that K or for K = 0 — a critic that reads the own row only: value_grad() then
+    passes it no records; any other pair raises ValueError before any call reaches the env.  The minibatches are the
     `minibatches` consecutive slices of the permutation ([k R // M, (k + 1) R // M)).
     Returns {"policy_stats" [E, M, 8], "value_stats" [E, M, 8], "adam_stats" [E, M, 4], "adv_stats" [4]} as device tensors."""
     torch = env.torch
@@ -228,6 +245,11 @@ def update(env, collected, w, vw, state, *, epochs=4, minibatches=4, clip=0.2, v
     K = {L.policy_words(k): k for k in (0,) + L.POLICY_TRAFFIC_K}.get(int(w.numel()))
     if K is None:
         raise ValueError("w is not a packed policy (atc_hip.policy.pack_mlp)")
+    tr = collected.get("traffic")
+    if K != (0 if tr is None else int(tr.shape[-2])):
+        raise ValueError("the policy must be packed for the collection's K = %d (atc_hip.policy.pack_mlp(traffic=%d)), got one for K = %d" % (
+            0 if tr is None else int(tr.shape[-2]), 0 if tr is None else int(tr.shape[-2]), K))
+    _critic_traffic(collected, vw)
     if perm is not None and len(perm) < E:
         raise ValueError("perm must hold one permutation per epoch")
     adv = collected["adv"]
