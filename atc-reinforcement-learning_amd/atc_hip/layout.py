@@ -124,6 +124,9 @@ GAE_LAUNCH_SLOTS = 1
 TERM_ENDED = 0x8000
 ROLLOUT_POLICY_ENDS_LAUNCH_SLOTS = 28
 GAE_BOOT_LAUNCH_SLOTS = 1
+# policy rollout with terminal traffic records (include/atc_step.h: atc_rollout_policy_term): K in POLICY_TRAFFIC_K only; a record of its own,
+# counted by width and K like the traffic rollout's (slot = 3 log2(W) + log2(K))
+ROLLOUT_POLICY_TERM_LAUNCH_SLOTS = 21
 # the PPO policy loss and gradient (include/atc_step.h: atc_ppo_policy_grad): at most PPO_GRAD_MAX_WG workgroups = partial rows of `scratch`,
 # PPO_GRAD_DEFAULT_WG where the caller leaves the choice to the library; the words of `stats`; its record counts calls by K in (0, 1, 2, 4)
 PPO_GRAD_MAX_WG = 1024

@@ -123,6 +123,14 @@ class AtcPolicyEndsOut(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in POLICY_ENDS_OUT_FIELDS]
 
 
+POLICY_TERM_OUT_FIELDS = POLICY_ENDS_OUT_FIELDS + ("term_traffic",)
+
+
+class AtcPolicyTermOut(C.Structure):
+    """atc_policy_term_out_t"""
+    _fields_ = [(n, C.c_void_p) for n in POLICY_TERM_OUT_FIELDS]
+
+
 POLICY_EVAL_OUT_FIELDS = ("record", "obs_last", "flags")
 
 
@@ -251,7 +259,7 @@ EXPORTS = ("atc_abi_version", "atc_last_error", "atc_launch_counts", "atc_host_m
            "atc_value_forward", "atc_value_forward_launch_counts", "atc_ppo_value_grad", "atc_ppo_value_grad_launch_counts",
            "atc_policy_eval", "atc_policy_eval_launch_counts", "atc_adv_normalise", "atc_adv_normalise_launch_counts",
            "atc_adam_step", "atc_adam_step_launch_counts", "atc_policy_forward", "atc_policy_forward_launch_counts",
-           "atc_lookahead_policy", "atc_lookahead_policy_launch_counts")
+           "atc_lookahead_policy", "atc_lookahead_policy_launch_counts", "atc_rollout_policy_term", "atc_rollout_policy_term_launch_counts")
 
 def load():
     """Loads libatcstep.so; raises (never falls back) when it has not been built."""
@@ -307,6 +315,8 @@ def load():
                                                C.POINTER(AtcParams), vp]
     lib.atc_gae.argtypes = [vp, ci, ci, ci, ci, vp, vp, vp, vp, C.POINTER(AtcGae), C.POINTER(AtcGaeOut), vp]
     lib.atc_rollout_policy_ends.argtypes = [vp, ci, ci, ci, ci, C.POINTER(AtcState), vp, C.POINTER(AtcPolicyTraffic), C.POINTER(AtcPolicyEndsOut),
+                                            C.POINTER(AtcParams), vp]
+    lib.atc_rollout_policy_term.argtypes = [vp, ci, ci, ci, ci, C.POINTER(AtcState), vp, C.POINTER(AtcPolicyTraffic), C.POINTER(AtcPolicyTermOut),
                                             C.POINTER(AtcParams), vp]
     lib.atc_policy_eval.argtypes = [vp, ci, ci, ci, ci, C.POINTER(AtcState), vp, C.POINTER(AtcPolicyTraffic), C.POINTER(AtcPolicyEvalOut),
                                     C.POINTER(AtcParams), vp]
@@ -393,6 +403,7 @@ LAUNCH_RECORDS = {
     "atc_adam_step_launch_counts": (L.ADAM_STEP_LAUNCH_SLOTS, _tensors),
     "atc_policy_forward_launch_counts": (L.POLICY_FORWARD_LAUNCH_SLOTS, _traffic_k0),
     "atc_lookahead_policy_launch_counts": (L.LOOKAHEAD_POLICY_LAUNCH_SLOTS, _width),
+    "atc_rollout_policy_term_launch_counts": (L.ROLLOUT_POLICY_TERM_LAUNCH_SLOTS, _width_k),
 }
 
 
@@ -493,6 +504,12 @@ def rollout_policy_ends_launch_counts():
     """Launches of the policy rollout with episode ends (atc_rollout_policy_ends) made by the calling thread so far, by lane-group width and
     records per aircraft (0: the ten-word policy): {(16, 0): n, ...}, zero counts left out.  Separate from the other launch records."""
     return _counts("atc_rollout_policy_ends_launch_counts")
+
+
+def rollout_policy_term_launch_counts():
+    """Launches of the policy rollout with terminal traffic records (atc_rollout_policy_term) made by the calling thread so far, by lane-group
+    width and records per aircraft: {(16, 4): n, ...}, zero counts left out.  Separate from the other launch records, rollout_policy_ends' included."""
+    return _counts("atc_rollout_policy_term_launch_counts")
 
 
 def policy_eval_launch_counts():

@@ -10,8 +10,9 @@ gradient (atc_ppo_value_grad).  update() closes the iteration: the advantages no
 minibatch the two gradient calls and ONE optimiser step on both packed tensors (atc_adam_step: the gradient-norm clip over both, the entropy
 term on log_std, Adam), with adam_state() holding the moments and every buffer.  An iteration then touches neither autograd nor torch.optim,
 and update() reads no device value on the host.  (policy_grad(normalise=True) on its own still makes its three reductions in torch.)
-Not covered, the trainer's: bootstrapping a traffic policy's collection — the traffic records of a terminal state are not produced — and
-learning-rate or clip-range schedules, which are update()'s arguments from call to call."""
+collect_bootstrap_traffic() is collect_bootstrap() for a policy that sees traffic: atc_rollout_policy_term stores the records of the
+terminal states next to their observations, and both join the one value forward.
+Not covered, the trainer's: learning-rate or clip-range schedules, which are update()'s arguments from call to call."""
 from . import layout as L
 from . import policy as _policy
 
@@ -72,13 +73,32 @@ def collect_bootstrap(env, weights, value_fn, T, hold=1, traffic=0, gamma=0.99, 
     return _collect(env, weights, value_fn, T, hold, 0, gamma, lam, seed, decision0, obs0, per_decision, True)
 
 
+def collect_bootstrap_traffic(env, weights, value_fn, T, traffic, hold=1, gamma=0.99, lam=0.95, seed=0, decision0=0, obs0=None, per_decision=False):
+    """collect_bootstrap() for a policy that sees traffic (traffic=K: 1, 2 or 4), in the same three calls:
+      1. env.rollout_policy_term(weights, T, K, hold, seed, decision0, obs0=obs0), which also stores term_traffic, the records of the
+         state each ended block's episode ended in;
+      2. ONE forward over [2 D + 1, B, N, 10 + 7 K]: value_rows(..., traffic=K)'s D + 1 rows, then rows D + 1 .. 2 D =
+         atc_hip.policy.input_rows(term_obs, term_traffic) (zeros where a block did not end its episode); the result is split into
+         values [D + 1, ...] and boot [D, ...];
+      3. env.gae_boot(reward, done, values, boot, truncated(term_flags), hold, gamma, lam, per_decision=per_decision), which reads boot
+         only where trunc is set.
+    The env must have been made with AtcVecEnv(traffic=K), as for collect(traffic=K).  Returns collect_bootstrap()'s dict plus "traffic" and
+    "term_traffic"; policy_grad(), value_grad() and update() take it as they take collect(traffic=K)'s."""
+    K = int(traffic)
+    if K not in L.POLICY_TRAFFIC_K:
+        raise ValueError("collect_bootstrap_traffic() is for traffic in %s; collect_bootstrap() bootstraps the ten-word policy" % (L.POLICY_TRAFFIC_K,))
+    return _collect(env, weights, value_fn, T, hold, K, gamma, lam, seed, decision0, obs0, per_decision, True)
+
+
 def _collect(env, weights, value_fn, T, hold, traffic, gamma, lam, seed, decision0, obs0, per_decision, bootstrap):
     torch = env.torch
     K = int(traffic)
     if K and env.traffic_k != K:
         raise ValueError("collect(traffic=%d) needs an env made with AtcVecEnv(traffic=%d): the last row's records come from observe_traffic()" % (K, K))
     x0 = (env.obs if obs0 is None else obs0).clone()
-    if K:
+    if K and bootstrap:
+        out = env.rollout_policy_term(weights, T, K, hold=hold, seed=seed, decision0=decision0, obs0=x0)
+    elif K:
         out = env.rollout_policy_traffic(weights, T, K, hold=hold, seed=seed, decision0=decision0, obs0=x0)
     elif bootstrap:
         out = env.rollout_policy_ends(weights, T, 0, hold=hold, seed=seed, decision0=decision0, obs0=x0)
@@ -87,7 +107,8 @@ def _collect(env, weights, value_fn, T, hold, traffic, gamma, lam, seed, decisio
     env._collected_obs0 = (out["obs"], x0)      # what decision 0 saw, for policy_grad() on this collection
     rows = value_rows(env, out, x0, hold=hold, traffic=K)
     if bootstrap:
-        rows = torch.cat([rows, out["term_obs"].reshape((-1,) + tuple(rows.shape[1:]))], dim=0)
+        term = _policy.input_rows(out["term_obs"], out["term_traffic"]) if K else out["term_obs"]
+        rows = torch.cat([rows, term.reshape((-1,) + tuple(rows.shape[1:]))], dim=0)
     with torch.no_grad():
         values = value_fn(rows)
     values = values.to(dtype=torch.float32).contiguous()

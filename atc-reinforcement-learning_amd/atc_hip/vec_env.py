@@ -966,6 +966,20 @@ class AtcVecEnv:
             raise ValueError("traffic must be 0 or one of %s records per aircraft" % (L.POLICY_TRAFFIC_K,))
         return AtcVecEnv._rollout_policy(self, K, weights, T, hold, seed, decision0, deterministic, obs0, out, True)
 
+    def rollout_policy_term(self, weights, T, traffic, hold=1, seed=0, decision0=0, deterministic=False, obs0=None, out=None):
+        """rollout_policy_ends(traffic=K) for K = 1, 2 or 4 through atc_rollout_policy_term (include/atc_step.h), which also stores the traffic
+        records of the state an episode ENDED in — the env is reset inside the ending step, so no later observe_traffic() can see it:
+          term_traffic [D, B, N, K, 8]: where block d has an ending step, what observe_traffic() would return on the state term_obs[d]
+            describes (after that step's kinematics and hand-overs, ahead of the spawn), bit for bit.  Like term_obs, other rows are NOT
+            written: a fresh tensor is zeros there, one given in `out` keeps its content.
+        atc_hip.policy.input_rows(term_obs, term_traffic) is then the row a critic over 10 + 7 K inputs bootstraps a time-limit end from
+        (atc_hip.ppo.collect_bootstrap_traffic).  With out=, term_traffic is stored only where `out` names it, and nothing is allocated.
+        Every other output and the state afterwards are rollout_policy_ends' bit for bit; that method goes through its own entry point."""
+        K = int(traffic)
+        if K not in L.POLICY_TRAFFIC_K:
+            raise ValueError("traffic must be one of %s records per aircraft (a ten-word policy sees no records: rollout_policy_ends)" % (L.POLICY_TRAFFIC_K,))
+        return AtcVecEnv._rollout_policy(self, K, weights, T, hold, seed, decision0, deterministic, obs0, out, True, True)
+
     def evaluate_policy(self, weights, T, traffic=0, hold=1, seed=0, decision0=0, deterministic=True, obs0=None, record=None, clear=True):
         """Flies the packed policy for T steps exactly as rollout_policy_ends() would — same decisions, same draws, same state afterwards —
         and stores none of its [T, ...] or [T // hold, ...] tensors (include/atc_step.h: atc_policy_eval).  What comes back is the per-env
@@ -1008,9 +1022,10 @@ class AtcVecEnv:
             self._finish()
         return {"record": record, "obs_last": obs_last}
 
-    def _rollout_policy(self, K, weights, T, hold, seed, decision0, deterministic, obs0, out, ends=False):
+    def _rollout_policy(self, K, weights, T, hold, seed, decision0, deterministic, obs0, out, ends=False, term=False):
         """rollout_policy (K = 0) and rollout_policy_traffic (K = 1, 2, 4): the checks of weights and obs0, the result tensors, the two
-        structs, the launch.  ends: through atc_rollout_policy_ends, with its three further outputs"""
+        structs, the launch.  ends: through atc_rollout_policy_ends, with its three further outputs; term (with ends, K > 0): through
+        atc_rollout_policy_term, with term_traffic behind them"""
         torch = self.torch
         T, hold = int(T), int(hold)
         B, N, dev = self.B, self.N, self.device
@@ -1033,9 +1048,11 @@ class AtcVecEnv:
                 out["term_obs"] = torch.zeros((n_dec, B, N, L.OBS_DIM), dtype=torch.float32, device=dev)
                 out["term_flags"] = torch.empty((n_dec, B), dtype=torch.int16, device=dev)
                 out["control"] = torch.empty((n_dec, B, N), dtype=torch.uint8, device=dev)
+            if term:   # (zeros, like term_obs)
+                out["term_traffic"] = torch.zeros((n_dec, B, N, K, L.TRAFFIC_DIM), dtype=torch.float32, device=dev)
         if ends:
             for name, dtype, shape in (("term_obs", torch.float32, (n_dec, B, N, L.OBS_DIM)), ("term_flags", torch.int16, (n_dec, B)),
-                                       ("control", torch.uint8, (n_dec, B, N))):
+                                       ("control", torch.uint8, (n_dec, B, N))) + ((("term_traffic", torch.float32, (n_dec, B, N, K, L.TRAFFIC_DIM)),) if term else ()):
                 t = out.get(name)
                 if t is not None and not (torch.is_tensor(t) and t.dtype == dtype and t.device == dev and t.is_contiguous() and t.numel() == int(np.prod(shape))):
                     raise ValueError("out[%r] must be a contiguous %s tensor of %r on %s" % (name, dtype, shape, dev))
@@ -1048,7 +1065,9 @@ class AtcVecEnv:
             call, pol_type, out_type, fields = self._lib.atc_rollout_policy, _lib.AtcPolicy, _lib.AtcPolicyOut, _lib.POLICY_OUT_FIELDS
         if ends:
             call, pol_type, out_type, fields = self._lib.atc_rollout_policy_ends, _lib.AtcPolicyTraffic, _lib.AtcPolicyEndsOut, _lib.POLICY_ENDS_OUT_FIELDS
-        o = out_type(*[self._ptr(out.get(k)) if (K or k != "traffic") else None for k in fields])
+        if term:
+            call, out_type, fields = self._lib.atc_rollout_policy_term, _lib.AtcPolicyTermOut, _lib.POLICY_TERM_OUT_FIELDS
+        o =out_type(*[self._ptr(out.get(k)) if (K or k != "traffic") else None for k in fields])
         pol = pol_type(self._ptr(w), L.POLICY_HIDDEN, L.POLICY_DETERMINISTIC if deterministic else 0, int(seed) & (2 ** 64 - 1),
                        int(decision0) & 0xffffffff, 0)     # (traffic_k, where the struct has it, is zero so far)
         if K:

@@ -36,6 +36,7 @@ int atc_adv_normalise_launch_counts(uint64_t* out, int n) { return copy_counts(R
 int atc_adam_step_launch_counts(uint64_t* out, int n) { return copy_counts(REC_ADAM_STEP, out, n); }
 int atc_policy_forward_launch_counts(uint64_t* out, int n) { return copy_counts(REC_POLICY_FORWARD, out, n); }
 int atc_lookahead_policy_launch_counts(uint64_t* out, int n) { return copy_counts(REC_LOOKAHEAD_POLICY, out, n); }
+int atc_rollout_policy_term_launch_counts(uint64_t* out, int n) { return copy_counts(REC_POLICY_TERM, out, n); }
 int atc_lookahead_set_mapping(int candidates_per_workgroup) {
     if (candidates_per_workgroup < 0 || candidates_per_workgroup > ATC_LOOKAHEAD_MAX_M) return fail_arg("candidates per workgroup must be 0 (the library's choice) .. 64");
     t_look_cpg = candidates_per_workgroup;
@@ -681,7 +682,17 @@ int atc_rollout_policy_ends(const atc_scenario_t* s, int B, int N, int T, int ho
         return rc;
     return with_width(N, [&](auto w) {
         return with_traffic_k0(pol->traffic_k, [&](auto kt) {
-            return launch_policy<decltype(w)::value, decltype(kt)::value, true>(s, B, N, T, hold, st, obs0, pol, out, p, (hipStream_t)stream);
+            return launch_policy<decltype(w)::value, decltype(kt)::value, true, false>(s, B, N, T, hold, st, obs0, pol, out, p, (hipStream_t)stream);
+        });
+    });
+}
+
+int atc_rollout_policy_term(const atc_scenario_t* s, int B, int N, int T, int hold, const atc_state_t* st, const float* obs0,
+                            const atc_policy_traffic_t* pol, const atc_policy_term_out_t* out, const atc_params_t* p, void* stream) {
+    if (const int rc = check_policy_term_call(s, B, N, T, hold, st, obs0, pol, out, p)) return rc;
+    return with_width(N, [&](auto w) {
+        return with_traffic_k(pol->traffic_k, [&](auto kt) {
+            return launch_policy<decltype(w)::value, decltype(kt)::value, true, true>(s, B, N, T, hold, st, obs0, pol, out, p, (hipStream_t)stream);
         });
     });
 }

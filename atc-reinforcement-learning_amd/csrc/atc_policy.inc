@@ -145,6 +145,28 @@ struct PolicyEnds {
     uint8_t* control;       // .control
 };
 
+// TERM (atc_rollout_policy_term, k_rollout_policy_term<W, KT>, KT = 1, 2, 4): ENDS plus one more nullable per-decision output, the traffic
+// records of the state term_obs describes — the query of the decision site (traffic_self / traffic_select / traffic_record: the same bits)
+// run once more at the step that ends an episode, on the wave-uniform ballot(ends_now) path.
+//   THE TERMINAL STATE is a snapshot, not a new form of the step: every change a step makes to an aircraft (speed, altitude, heading,
+//   position) is made in step_part_a; step_part_b changes it only by the spawn of its auto-reset path.  So ls.a between the two halves IS the
+//   state the episode ends in, with or without ATC_M_AUTO_RESET, and a copy taken there (x, y, the float64 altitude, heading counts, speed:
+//   six registers) survives the spawn.  The active mask at the end is the mask before the second half less the aircraft this step hands
+//   over: the ballot of ATC_F_WON over the env's lanes that step_part_b itself takes (not under ATC_M_KEEP_ACTIVE), recomputed here from
+//   the flag word it returns; the copy of the mask is two more registers.  step_part_a and step_part_b are untouched, and every addition to
+//   rollout_policy_body stands behind `if constexpr (TERMQ)`: the other kernels' device code is what it was (tools/isa_compare.py).
+//   WIDE headings: the exact counts of a WIDE terminal heading are in the aircraft's row of st.phi_wide, written by step_part_a of this
+//   step or an earlier one.  The spawn writes no side record (a spawned heading is plain), and no later step has run yet: the row is read
+//   here, behind step_part_b, by the lane that wrote it, and holds the terminal heading.
+//   LDS (W >= 32): the selection stages (x, y, tag) in the wavefront's own quarter of the pair-scan staging area, which this step's pair
+//   scan has finished reading (a wavefront's LDS operations are issued and executed in order); the same wave-level fences as at the
+//   decision site order the stage against its readers and against the next stage or pair scan.  No workgroup barrier: the path is taken
+//   by whole wavefronts that hold an ending env, not by the workgroup.
+//   The decision site's text is not factored out into a function shared with this one: that site's machine code is pinned.
+struct PolicyTerm {
+    float* term_traffic;    // atc_policy_term_out_t.term_traffic
+};
+
 // EVAL (atc_policy_eval, k_policy_eval<W, KT>): the loop with every per-step and per-decision store compiled out.  What leaves the launch is
 // the env's record of ATC_EVAL_WORDS words — read at the start (or cleared), held in registers uniformly over the env's lanes like the env
 // state, updated on the rare path where a step ends an episode, written once by lane k == 0 — and the last step's observation.
@@ -165,15 +187,18 @@ struct PolicyEval {
 // An env never leaves its wavefront: W = 32 / 64 stage (x, y, tag) in the wavefront's own quarter of the pair-scan staging area (idle
 // between steps), ordered by wave-level waits — no workgroup barrier anywhere in the decision.
 // TT_OFF: where the kernel's PolicyTrafficTail lies in ITS kernarg segment (the body serves three parameter lists); ET_OFF: where its
-// PolicyEnds lies, 0 for the kernels that have none (ENDS below); EV_OFF: where its PolicyEval lies, 0 for all but k_policy_eval (EVAL).
-template <int W, int KT, size_t TT_OFF = 0, size_t ET_OFF = 0, size_t EV_OFF = 0>
+// PolicyEnds lies, 0 for the kernels that have none (ENDS below); EV_OFF: where its PolicyEval lies, 0 for all but k_policy_eval (EVAL);
+// TQ_OFF: where its PolicyTerm lies, 0 for all but k_rollout_policy_term (TERM above).
+template <int W, int KT, size_t TT_OFF = 0, size_t ET_OFF = 0, size_t EV_OFF = 0, size_t TQ_OFF = 0>
 __device__ __forceinline__ void rollout_policy_body(const float* __restrict__ blob, int off_grid, int B, int N, int T, atc_state_t st, const float* __restrict__ obs0,
                                                     atc_params_t p, StepDerived q, const float* __restrict__ pw, uint64_t seed, uint32_t decision0, uint32_t pflags,
                                                     float* __restrict__ action, float* __restrict__ logp) {
     constexpr bool ONE = false, LAT = false, FULL = false;   // (QGET: the multi-step form — kernarg re-reads inside the step)
     constexpr bool ENDS = ET_OFF != 0;
     constexpr bool EVAL = EV_OFF != 0;
+    constexpr bool TERMQ = TQ_OFF != 0;
     static_assert(!(ENDS && EVAL), "k_policy_eval stores none of the per-decision outputs");
+    static_assert(!TERMQ || (ENDS && KT > 0), "the terminal traffic records belong to the ends of a policy that sees traffic");
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float4* pos = reinterpret_cast<float4*>(smem);                    // [2 kBlock] pair-scan staging (W >= 32)
     float* obs_stage = smem + (W >= 32 ? 2 * kBlock * 4 : 0);  // [4 waves][64 x 10] obs transpose
@@ -324,6 +349,9 @@ __device__ __forceinline__ void rollout_policy_body(const float* __restrict__ bl
         // (ENDS: the step that ends an episode stores the terminal observation itself, ahead of the spawn that overwrites it)
         constexpr size_t TERM_OFF = ENDS ? ET_OFF + offsetof(PolicyEnds, term_obs) : 0;
         const size_t ends_row = (size_t)(blk - 1u) * BN;   // the current block's row of the [D] outputs, in aircraft
+        // (TERMQ: the state this step ends in, should it end an episode — the second half changes an aircraft by its spawn only — and the mask before its hand-overs)
+        [[maybe_unused]] const Aircraft term_a = ls.a;
+        [[maybe_unused]] const uint64_t term_mask = es.amask;
         const bool quiet = step_part_b<W, FULL, false, false, false, true, false, false, TERM_OFF>(K, grid, pl, q, qs, zk, N, dl, m, ls, es, so, st.stats, st.phi_wide,
                                                                                                    pos, obs_stage, nullptr, nxt, qr_next, scan_skip, scan_mask, nullptr,
                                                                                                    nullptr, &sv, ends_row * ATC_OBS_DIM, !ended);
@@ -338,6 +366,46 @@ __device__ __forceinline__ void rollout_policy_body(const float* __restrict__ bl
                     // without an auto-reset the stored observation is the terminal one
                     if (!(pl.mode & ATC_M_AUTO_RESET) && en.term_obs && dl.lane_valid) store_obs(at<float>(en.term_obs + ends_row * ATC_OBS_DIM, times40(dl.i)), sv.o);
                     ended = true;
+                }
+                if constexpr (TERMQ) {
+                    // ---- the traffic query on the state term_obs describes: the decision site's, on the snapshot (wave-uniform: every lane runs it, the ending envs' store) ----
+                    float* const term_traffic = kernarg_reread<float*>(TQ_OFF, zk);
+                    if (term_traffic) {
+                        const PolicyTrafficTail tt = kernarg_reread<PolicyTrafficTail>(TT_OFF, zk);
+                        uint64_t mask = term_mask;   // less this step's hand-overs, as step_part_b takes them
+                        if (!(pl.mode & ATC_M_KEEP_ACTIVE)) mask &= ~group_ballot<W>((sv.fl & ATC_F_WON) != 0, dl.lane);
+                        int phi = term_a.phi;
+                        if (ATC_RARE(is_wide(phi))) phi = phi_wrap(*at<double>(wide_base<false>(st.phi_wide, zk), dl.i * 32u));   // the exact counts: the spawn wrote no side record
+                        const TrafficSelf me = traffic_self(term_a.x, term_a.y, term_a.h, phi, term_a.v, tt.tq);
+                        const bool under = dl.lane_valid && ((dl.k < 32 ? ((uint32_t)mask >> dl.k) : ((uint32_t)(mask >> 32) >> (dl.k - 32))) & 1u);
+                        const int tag = under ? dl.k : -1;
+                        uint64_t best[KT > 0 ? KT : 1];
+                        if constexpr (W >= 32) {
+                            float* sl = reinterpret_cast<float*>(pos) + 8 * (dl.tid & ~63);   // this wavefront's quarter, behind this step's pair scan: [64] x | [64] y | [64] tag
+                            sl[dl.lane] = me.x;
+                            sl[64 + dl.lane] = me.y;
+                            reinterpret_cast<int*>(sl)[128 + dl.lane] = tag;
+                            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                            __builtin_amdgcn_wave_barrier();
+                            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                            const int gb = dl.lane & ~(W - 1);
+                            traffic_select<W, (KT > 0 ? KT : 1)>(best, me.x, me.y, tag, dl.k, N, sl + gb, sl + 64 + gb, reinterpret_cast<const int*>(sl) + 128 + gb);
+                            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");   // (the reads above, before the next decision or pair scan stages over them)
+                            __builtin_amdgcn_wave_barrier();
+                        } else {
+                            traffic_select<W, (KT > 0 ? KT : 1)>(best, me.x, me.y, tag, dl.k, N, nullptr, nullptr, nullptr);
+                        }
+                        float4* dst = reinterpret_cast<float4*>(term_traffic + (ends_row + dl.i) * (size_t)(KT * ATC_TRAFFIC_DIM));   // (64-bit: 32 K bytes per aircraft)
+#pragma unroll
+                        for (int r = 0; r < KT; ++r) {
+                            float4 ra, rb;
+                            traffic_record<W>(best[r], under, dl.lane, me, tt.tq, ra, rb);
+                            if (ends_now && dl.lane_valid) {   // (rows of an env whose block did not end here are left alone: term_obs's rule)
+                                dst[2 * r] = ra;
+                                dst[2 * r + 1] = rb;
+                            }
+                        }
+                    }
                 }
             }
             if (left == 0) {   // the block's last step: no ending step in it stores the zero
@@ -437,6 +505,20 @@ k_rollout_policy_ends(const float* __restrict__ blob, int off_grid, int B, int N
     rollout_policy_body<W, KT, A::template of<PolicyTrafficTail>(), A::last()>(blob, off_grid, B, N, T, st, obs0, p, q, pw, seed, decision0, pflags, action, logp);
 }
 static_assert(kernargs_hold_like_step<decltype(k_rollout_policy_ends<1, 0>)>() && KernArgs<decltype(k_rollout_policy_ends<1, 0>)>::last() != 0, ATC_KERNARGS_REFUSAL);
+// KT = 1, 2, 4.  The parameter list is k_rollout_policy_ends', then the one pointer.
+template <int W, int KT>
+__global__ void __launch_bounds__(kBlock, ATC_POLICY_WAVES)
+k_rollout_policy_term(const float* __restrict__ blob, int off_grid, int B, int N, int T, int hold, atc_state_t st, const float* __restrict__ obs0,
+                      atc_out_t out, atc_params_t p, StepDerived q, const float* __restrict__ pw, uint64_t seed, uint32_t decision0, uint32_t pflags,
+                      float* __restrict__ action, float* __restrict__ logp, PolicyTrafficTail tt, PolicyEnds en, PolicyTerm tr) {
+    // (tt, en, tr: kernarg re-reads where they are used, at the offsets this list gives them)
+    typedef KernArgs<decltype(k_rollout_policy_term<W, KT>)> A;
+    rollout_policy_body<W, KT, A::template of<PolicyTrafficTail>(), A::template of<PolicyEnds>(), 0, A::last()>(blob, off_grid, B, N, T, st, obs0, p, q, pw, seed, decision0,
+                                                                                                                pflags, action, logp);
+}
+static_assert(kernargs_hold_like_step<decltype(k_rollout_policy_term<1, 1>)>() && KernArgs<decltype(k_rollout_policy_term<1, 1>)>::last() != 0, ATC_KERNARGS_REFUSAL);
+static_assert(KernArgs<decltype(k_rollout_policy_term<1, 1>)>::of<PolicyEnds>() == KernArgs<decltype(k_rollout_policy_ends<1, 1>)>::last(),
+              "k_rollout_policy_term's list is k_rollout_policy_ends', then the pointer");
 static_assert(ATC_POLICY_TRAFFIC_WORDS(0) == ATC_POLICY_WORDS && ATC_POLICY_TRAFFIC_IN(0) == ATC_POLICY_IN, "traffic_k == 0 is the ten-word policy");
 
 // KT = 0, 1, 2, 4 as k_rollout_policy_ends takes it.  The parameter list is k_rollout_policy_traffic's — out, action and logp are passed

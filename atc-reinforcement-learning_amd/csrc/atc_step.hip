@@ -1800,18 +1800,19 @@ static size_t lds_bytes(const atc_scenario*, bool pair_scan, bool step_kernel = 
 // the launch records (include/atc_step.h: the atc_*_launch_counts getters): launches made by the calling thread, every record's
 // counters in one table — plain thread-local counters that nothing in the library reads back.  REC_STEP has a slot for each k_step
 // instantiation and one for k_serve starts; a record of 7 slots counts by lane-group width (slot = log2(W)); a record of one slot
-// counts its entry point's launches; REC_POLICY_TRAFFIC counts by width and list length (slot = 3 log2(W) + log2(K)), REC_POLICY_ENDS
+// counts its entry point's launches; REC_POLICY_TRAFFIC and REC_POLICY_TERM count by width and list length (slot = 3 log2(W) + log2(K)), REC_POLICY_ENDS
 // and REC_POLICY_EVAL likewise with K = 0 in front (slot = 4 log2(W) + {0, 1, 2, 3}); REC_PPO_GRAD, REC_VALUE_FORWARD, REC_PPO_VALUE_GRAD and REC_POLICY_FORWARD count calls by K
 // (slot = {0, 1, 2, 3}); REC_ADV_NORMALISE counts calls in one slot and REC_ADAM_STEP by the number of tensors (slot = n_tensors - 1).  A call
 // moves its own record only.
-enum Record { REC_STEP, REC_SKIP, REC_TRAFFIC, REC_LOOKAHEAD, REC_PLAN, REC_PLAN_SAMPLED, REC_PLAN_DRAW, REC_PLAN_REFIT, REC_PLAN_SCORE, REC_BRANCH, REC_SELECT, REC_POLICY, REC_POLICY_TRAFFIC, REC_GAE, REC_POLICY_ENDS, REC_GAE_BOOT, REC_PPO_GRAD, REC_VALUE_FORWARD, REC_PPO_VALUE_GRAD, REC_POLICY_EVAL, REC_ADV_NORMALISE, REC_ADAM_STEP, REC_POLICY_FORWARD, REC_LOOKAHEAD_POLICY, REC_COUNT };
+enum Record { REC_STEP, REC_SKIP, REC_TRAFFIC, REC_LOOKAHEAD, REC_PLAN, REC_PLAN_SAMPLED, REC_PLAN_DRAW, REC_PLAN_REFIT, REC_PLAN_SCORE, REC_BRANCH, REC_SELECT, REC_POLICY, REC_POLICY_TRAFFIC, REC_GAE, REC_POLICY_ENDS, REC_GAE_BOOT, REC_PPO_GRAD, REC_VALUE_FORWARD, REC_PPO_VALUE_GRAD, REC_POLICY_EVAL, REC_ADV_NORMALISE, REC_ADAM_STEP, REC_POLICY_FORWARD, REC_LOOKAHEAD_POLICY, REC_POLICY_TERM, REC_COUNT };
 constexpr int kRecordSlots[REC_COUNT] = {ATC_LAUNCH_SLOTS, ATC_SKIP_LAUNCH_SLOTS, ATC_TRAFFIC_LAUNCH_SLOTS, ATC_LOOKAHEAD_LAUNCH_SLOTS, ATC_PLAN_LAUNCH_SLOTS,
                                          ATC_PLAN_SAMPLED_LAUNCH_SLOTS, ATC_PLAN_DRAW_LAUNCH_SLOTS, ATC_PLAN_REFIT_LAUNCH_SLOTS, ATC_PLAN_SCORE_LAUNCH_SLOTS,
                                          ATC_BRANCH_LAUNCH_SLOTS, ATC_SELECT_LAUNCH_SLOTS, ATC_ROLLOUT_POLICY_LAUNCH_SLOTS,
                                          ATC_ROLLOUT_POLICY_TRAFFIC_LAUNCH_SLOTS, ATC_GAE_LAUNCH_SLOTS, ATC_ROLLOUT_POLICY_ENDS_LAUNCH_SLOTS,
                                          ATC_GAE_BOOT_LAUNCH_SLOTS, ATC_PPO_GRAD_LAUNCH_SLOTS, ATC_VALUE_FORWARD_LAUNCH_SLOTS,
                                          ATC_PPO_VALUE_GRAD_LAUNCH_SLOTS, ATC_POLICY_EVAL_LAUNCH_SLOTS, ATC_ADV_NORMALISE_LAUNCH_SLOTS,
-                                         ATC_ADAM_STEP_LAUNCH_SLOTS, ATC_POLICY_FORWARD_LAUNCH_SLOTS, ATC_LOOKAHEAD_POLICY_LAUNCH_SLOTS};
+                                         ATC_ADAM_STEP_LAUNCH_SLOTS, ATC_POLICY_FORWARD_LAUNCH_SLOTS, ATC_LOOKAHEAD_POLICY_LAUNCH_SLOTS,
+                                         ATC_ROLLOUT_POLICY_TERM_LAUNCH_SLOTS};
 constexpr int record_offset(int id) {
     int o = 0;
     for (int i = 0; i < id; ++i) o += kRecordSlots[i];
@@ -2227,7 +2228,8 @@ static atc_out_t policy_out(const O* o) {
 // W lanes per env.  KT = 0: k_rollout_policy (P, O = atc_policy_t, atc_policy_out_t); KT = 1, 2, 4: k_rollout_policy_traffic<W, KT>, whose
 // selection borrows the pair-scan staging area between steps at W >= 32 (P, O = atc_policy_traffic_t, atc_policy_traffic_out_t).
 // ENDS: k_rollout_policy_ends<W, KT> for KT = 0, 1, 2, 4 (P, O = atc_policy_traffic_t, atc_policy_ends_out_t)
-template <int W, int KT, bool ENDS = false, typename P, typename O>
+// TERM (with ENDS): k_rollout_policy_term<W, KT> for KT = 1, 2, 4 (O = atc_policy_term_out_t)
+template <int W, int KT, bool ENDS = false, bool TERM = false, typename P, typename O>
 static int launch_policy(const atc_scenario* s, int B, int N, int T, int hold, const atc_state_t* st, const float* obs0, const P* pol, const O* o,
                          const atc_params_t* p, hipStream_t stream) {
     const size_t lds = lds_bytes(s, W >= 32, true);
@@ -2238,7 +2240,12 @@ static int launch_policy(const atc_scenario* s, int B, int N, int T, int hold, c
                            pol->decision0, pol->flags, o->action, o->logp, tail...);
     };
     uint64_t* rec;
-    if constexpr (ENDS) {
+    if constexpr (TERM) {
+        static_assert(ENDS && KT > 0, "the terminal records belong to the ends of a policy that sees traffic");
+        launch(k_rollout_policy_term<W, KT>, PolicyTrafficTail{traffic_common(s, p, KT), o->traffic}, PolicyEnds{o->term_obs, o->term_flags, o->control},
+               PolicyTerm{o->term_traffic});
+        rec = &record(REC_POLICY_TERM)[3 * __builtin_ctz(W) + __builtin_ctz(KT)];
+    } else if constexpr (ENDS) {
         launch(k_rollout_policy_ends<W, KT>, PolicyTrafficTail{KT ? traffic_common(s, p, KT) : TrafficArgs{}, o->traffic}, PolicyEnds{o->term_obs, o->term_flags, o->control});
         rec = &record(REC_POLICY_ENDS)[4 * __builtin_ctz(W) + (KT ? 1 + __builtin_ctz(KT) : 0)];
     } else if constexpr (KT == 0) {
@@ -2293,16 +2300,17 @@ static int policy_call_head(int T, int hold, const float* obs0, const P* pol, co
     if (!out) return fail_argf("null pointer: out (%s) is required", out_type);
     return ATC_OK;
 }
+// `dt`: false leaves the time increment, the one refusal that reads the sector, to the caller (atc_rollout_policy_term makes it last).
 template <typename P>
 static int policy_call_env(const atc_scenario_t* s, int B, int N, const atc_state_t* st, const P* pol, const atc_params_t* p, const char* out_type,
-                           const int32_t* traffic_k, const float* traffic, bool k0) {
+                           const int32_t* traffic_k, const float* traffic, bool k0, bool dt = true) {
     if (pol->n_hidden != ATC_POLICY_HIDDEN) return fail_arg("pol->n_hidden must be 64 (ATC_POLICY_HIDDEN)");
     if (traffic_k && !(k0 && *traffic_k == 0) && *traffic_k != 1 && *traffic_k != 2 && *traffic_k != 4)
         return fail_arg(k0 ? "pol->traffic_k must be 0, 1, 2 or 4 (the ten-word policy, or a compiled list length)" : "pol->traffic_k must be 1, 2 or 4 (the compiled list lengths)");
     if (pol->flags & ~ATC_POLICY_DETERMINISTIC) return fail_arg("pol->flags has unknown bits (ATC_POLICY_DETERMINISTIC or 0)");
     if (k0 && *traffic_k == 0 && traffic) return fail_argf("%s.traffic must be NULL where pol->traffic_k is 0 (no traffic query is evaluated)", out_type);
     if (const int rc = check_env_args(s, B, N, st, p)) return rc;
-    if (const int rc = check_dt(s, p)) return rc;
+    if (dt) if (const int rc = check_dt(s, p)) return rc;
     if (p->mode & ATC_M_DISCRETE) return fail_arg("ATC_M_DISCRETE: a Gaussian policy draws the continuous action space only");
     if (p->mode & ATC_M_ACTIONS_HELD) return fail_arg("ATC_M_ACTIONS_HELD is for atc_step only: every block's first step carries a fresh decision");
     return ATC_OK;
@@ -2316,15 +2324,16 @@ static int check_apart(const ByteRange& w, const ByteRange* others, int n, const
     return ATC_OK;
 }
 // the three rollouts.  `traffic` is atc_policy_traffic_out_t.traffic (its range joins the overlap rule); `ends`: the call is
-// atc_rollout_policy_ends, whose three arrays join the overlap rule.
+// atc_rollout_policy_ends, whose three arrays join the overlap rule.  `term`: the call is atc_rollout_policy_term — traffic_k == 0 is refused
+// as by atc_rollout_policy_traffic, and the time increment is left to check_policy_term_call.
 template <typename P, typename O>
 static int check_policy_call(const atc_scenario_t* s, int B, int N, int T, int hold, const atc_state_t* st, const float* obs0, const P* pol, const O* out,
                              const atc_params_t* p, const char* pol_type, const char* out_type, const int32_t* traffic_k, const float* traffic,
-                             const PolicyEnds* ends = nullptr) {
+                             const PolicyEnds* ends = nullptr, bool term = false) {
     if (const int rc = policy_call_head(T, hold, obs0, pol, out, pol_type, out_type)) return rc;
     if (!out->obs || !out->reward || !out->done || !out->flags) return fail_argf("null pointer: %s.obs, .reward, .done and .flags are required", out_type);
     if (!out->action) return fail_argf("null pointer: %s.action is required", out_type);
-    if (const int rc = policy_call_env(s, B, N, st, pol, p, out_type, traffic_k, traffic, ends != nullptr)) return rc;
+    if (const int rc = policy_call_env(s, B, N, st, pol, p, out_type, traffic_k, traffic, ends != nullptr && !term, !term)) return rc;
     const uintptr_t bn = (uintptr_t)B * (uintptr_t)N, row = bn * (ATC_OBS_DIM * 4u), n_dec = (uintptr_t)(T / hold);
     const ByteRange ranges[2] = {{obs0, row, "obs0"}, {out->obs, row * (uintptr_t)T, "out->obs"}};
     if (const int rc = check_disjoint(ranges, 2, {}, "decision 0 reads obs0 while the steps write out->obs")) return rc;
@@ -2345,6 +2354,29 @@ static int check_policy_call(const atc_scenario_t* s, int B, int N, int T, int h
             return rc;
     }
     return ATC_OK;
+}
+// atc_rollout_policy_term: atc_rollout_policy_ends' refusals in its order (traffic_k outside {1, 2, 4} refused where it refuses its own), then
+// term_traffic against the weights, obs0, every other output and the six state arrays, then the time increment — last, since it alone
+// reads the sector: everything in front of it follows no pointer but pol, out, st and p.
+static int check_policy_term_call(const atc_scenario_t* s, int B, int N, int T, int hold, const atc_state_t* st, const float* obs0, const atc_policy_traffic_t* pol,
+                                  const atc_policy_term_out_t* out, const atc_params_t* p) {
+    const PolicyEnds ends = {out ? out->term_obs : nullptr, out ? out->term_flags : nullptr, out ? out->control : nullptr};
+    if (const int rc = check_policy_call(s, B, N, T, hold, st, obs0, pol, out, p, "atc_policy_traffic_t", "atc_policy_term_out_t", pol ? &pol->traffic_k : nullptr,
+                                         out ? out->traffic : nullptr, &ends, true))
+        return rc;
+    if (out->term_traffic) {
+        const uintptr_t b = (uintptr_t)B, bn = b * (uintptr_t)N, row = bn * (ATC_OBS_DIM * 4u), t = (uintptr_t)T, n_dec = (uintptr_t)(T / hold), k = (uintptr_t)pol->traffic_k;
+        const ByteRange records = {out->term_traffic, n_dec * bn * k * (ATC_TRAFFIC_DIM * 4u), "out->term_traffic"};
+        const ByteRange others[18] = {{pol->w, (uintptr_t)ATC_POLICY_TRAFFIC_WORDS(pol->traffic_k) * 4u, "pol->w"}, {obs0, row, "obs0"}, {out->obs, row * t, "out->obs"},
+                                      {out->reward, t * b * 4u, "out->reward"}, {out->done, t * b, "out->done"}, {out->flags, t * bn * 2u, "out->flags"},
+                                      {out->action, n_dec * bn * 12u, "out->action"}, {out->logp, n_dec * bn * 4u, "out->logp"},
+                                      {out->traffic, n_dec * bn * k * (ATC_TRAFFIC_DIM * 4u), "out->traffic"}, {out->term_obs, n_dec * row, "out->term_obs"},
+                                      {out->term_flags, n_dec * b * 2u, "out->term_flags"}, {out->control, n_dec * bn, "out->control"},
+                                      {st->ac, bn * 16u, "st->ac"}, {st->alt, bn * 8u, "st->alt"}, {st->last_act, bn * 16u, "st->last_act"},
+                                      {st->env, b * (ATC_ENV_WORDS * 4u), "st->env"}, {st->stats, b * (ATC_STAT_WORDS * 4u), "st->stats"}, {st->phi_wide, bn * 32u, "st->phi_wide"}};
+        if (const int rc = check_apart(records, others, 18, "the terminal records are written while the launch reads and writes the other")) return rc;
+    }
+    return check_dt(s, p);
 }
 // atc_policy_eval: out->record stands where the rollouts' required outputs do; behind the mode's refusals its own two; record and obs_last
 // against obs0, the six state arrays and each other.

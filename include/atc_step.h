@@ -1156,6 +1156,46 @@ int atc_rollout_policy_ends(const atc_scenario_t* s, int B, int N, int T, int ho
 enum { ATC_ROLLOUT_POLICY_ENDS_LAUNCH_SLOTS = 28 };
 int atc_rollout_policy_ends_launch_counts(uint64_t* out, int n);
 
+/* POLICY ROLLOUT WITH TERMINAL TRAFFIC RECORDS (extension): atc_rollout_policy_ends for a policy that sees traffic (pol->traffic_k = K in
+ * {1, 2, 4}), with one more nullable per-decision output.  A critic over 10 + 7 K inputs bootstraps a time-limit end from the row
+ * [term_obs | words 0..6 of the K records of that state]; the auto-reset inside the ending step overwrites the state, so the records, like
+ * term_obs, can only be taken inside the launch.
+ *   - term_traffic[d], the env's N x K records: written only where block d has an ending step t* (ENDING STEP above) — bit for bit what
+ *     atc_observe_traffic(K) returns on the state step t* ENDED in, the state term_obs[d] describes: after that step's kinematics, with the
+ *     aircraft the step handed over taken out of the active mask (they are not under control: absent as intruders, all-ABSENT as
+ *     observers), ahead of the spawn.  Without ATC_M_AUTO_RESET it is atc_observe_traffic on the state step t* left.  The rows of an env
+ *     whose block has no ending step are NOT written and keep what they hold; a second episode end inside the same block writes nothing.
+ *   - WIDE headings: an aircraft whose terminal heading is WIDE (ABI 19) is rotated by its exact counts, as atc_observe_traffic reads them
+ *     from the side record — the reset writes no side record, and the launch reads the row before any later step can.
+ * EVERYTHING ELSE is atc_rollout_policy_ends' contract word for word: every other output and the state afterwards are bit-identical to that
+ * call's for the same arguments, with term_traffic given or NULL, and two launches of T / 2 equal one of T bit for bit, term_traffic
+ * included.  All stores are plain vector stores.
+ * ATC_ERR_ARG, in this order: T and hold; the pointers (pol, pol->w, obs0, out; obs / reward / done / flags; action); n_hidden; traffic_k
+ * outside {1, 2, 4} (0 is refused: the ten-word policy has no records — atc_rollout_policy_ends); the flag bits; the argument errors of
+ * atc_rollout_hold that need no sector (s, st, p, the batch shape, a null state field, the batch size); ATC_M_DISCRETE; ATC_M_ACTIONS_HELD;
+ * the overlap rule of atc_rollout_policy_ends; then term_traffic (T/hold * B*N*K*32 bytes) sharing memory with pol->w, obs0, any other
+ * output of the call or one of the six state arrays (ranges that only touch do not overlap); LAST the time increment (dt), the one refusal
+ * that reads the sector — everything in front of it looks at s for NULL only.
+ * Counted by atc_rollout_policy_term_launch_counts only: slot = 3 log2(W) + log2(K); a refused call moves no record. */
+typedef struct atc_policy_term_out {
+    float* obs;          /* [T][B*N*10]     required: atc_rollout's per-step outputs */
+    float* reward;       /* [T][B]          required */
+    uint8_t* done;       /* [T][B]          required */
+    uint16_t* flags;     /* [T][B*N]        required */
+    float* action;       /* [T/hold][B*N*3] required: the UNCLAMPED sample u */
+    float* logp;         /* [T/hold][B*N]   nullable */
+    float* traffic;      /* [T/hold][B*N*K*8] nullable: the records decision b saw */
+    float* term_obs;     /* [T/hold][B*N*10] nullable: rows of envs whose block ended, the others are left as they are */
+    uint16_t* term_flags;/* [T/hold][B]     nullable: 0, or ATC_TERM_ENDED | the OR of the env's flag words at the ending step */
+    uint8_t* control;    /* [T/hold][B*N]   nullable: 1 = under control when the decision was taken */
+    float* term_traffic; /* [T/hold][B*N*K*8] nullable: the records of the state term_obs describes, rows of envs whose block ended */
+} atc_policy_term_out_t;
+int atc_rollout_policy_term(const atc_scenario_t* s, int B, int N, int T, int hold, const atc_state_t* st,
+                            const float* obs0 /* [B*N*10] */, const atc_policy_traffic_t* pol, const atc_policy_term_out_t* out,
+                            const atc_params_t* p, void* stream);
+enum { ATC_ROLLOUT_POLICY_TERM_LAUNCH_SLOTS = 21 };
+int atc_rollout_policy_term_launch_counts(uint64_t* out, int n);
+
 /* POLICY EVALUATION (extension): how good is this policy?  The reference's trainer logs winning_ratio, the mean episode length and
  * Monitor's r / l after every update (learning/atc-gym-stable-baselines.py).  atc_policy_eval flies a packed policy for T steps exactly as
  * atc_rollout_policy_ends does — the decisions, the key, the draw, the clamp, ATC_POLICY_DETERMINISTIC, the traffic query for traffic_k > 0,
